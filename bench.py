@@ -17,9 +17,12 @@ Workloads (--config; the default c2 is the one BASELINE.json's metric is quoted 
 Multi-GPU: the distilled presets run ONE forward per step, so their denoise loop does not shard ("replicas only",
 SURVEY 8e): every rank generates its own video, no data-path collective, scaling weak.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
-`--gpus N` without a torchrun environment starts the N ranks itself (child process, before any GPU call)."""
+`--gpus N` without a torchrun environment starts the N ranks itself (child process, before any GPU call).
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the measurements beside the headline: the
+per-kernel event pass (`roofline`, `kernels`), two videos per call (c2, one GPU), the CPU baseline and, on N >= 3 ranks, the sharded forms.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as float32 .npy files, see dump_outputs()."""
 import argparse
 import json
 import math
@@ -321,6 +324,25 @@ def sharded_measurements(ltxhip, sharded, dist, dev, world, dit, vae, inputs, F,
     return res
 
 
+DUMP_VIDEO_ELEMS = 8 << 20          # 32 MiB of f32: the c2 video alone is 458 MB
+
+
+def dump_outputs(d, latents, video):
+    """--dump-outputs: what LtxPipeline.call returned in the last timed step - the final latents [B,S,C] in full as latents.npy,
+    the video [B,3,frames,H,W] as video.npy, or, when it has more than DUMP_VIDEO_ELEMS elements, as video_sample.npy: the
+    elements at sorted positions drawn from a fixed seed, so that the same config samples the same positions in every run."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "latents.npy"), latents.float().cpu().numpy())
+    if video is None:
+        return
+    if video.numel() <= DUMP_VIDEO_ELEMS:
+        np.save(os.path.join(d, "video.npy"), video.float().cpu().numpy())
+        return
+    idx = torch.randint(video.numel(), (DUMP_VIDEO_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+    np.save(os.path.join(d, "video_sample.npy"), video.float().reshape(-1)[idx.to(video.device)].cpu().numpy())
+
+
 def spawn_ranks(n, argv):
     """`--gpus N` outside torchrun: start the N ranks as a CHILD (torch.distributed.run) before this process touches the
     GPU, and leave with its exit code (never exec after GPU initialisation)."""
@@ -337,10 +359,15 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's latents and video (or a seeded sample of it) as .npy")
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline (per-kernel pass, two videos per call, "
+                                                        "CPU baseline, sharded forms); the --no-* options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="skip the per-kernel event timing pass")
     ap.add_argument("--no-batched", action="store_true", help="skip the untimed-region measurement of two videos per pipeline call (c2, one GPU)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(a.gpus, sys.argv[1:]))
@@ -421,17 +448,19 @@ def main():
     barrier()
     t0 = time.perf_counter()
     dit_ms = vae_ms = 0.0
-    video = None
+    latents = video = None
     for _ in range(a.steps):
         if plan["idle"]:
             continue
-        _, video = step()
+        latents, video = step()
         if plan["team_size"] == 1:
             dit_ms += pipe.last_timing_ms[0]; vae_ms += pipe.last_timing_ms[2]
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = reduce_elapsed(elapsed, dist, dev)
     assert plan["idle"] or torch.isfinite(video).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, latents, video)
 
     out = None
     if rank == 0:
@@ -452,7 +481,7 @@ def main():
         if plan["team_size"] == 1:
             out.update({"dit_step_ms": dit_ms / (n_steps * a.steps), "vae_decode_ms": vae_ms / a.steps,
                         "dit_tflops": fwd_per_step * fl_dit / (dit_ms / (n_steps * a.steps) * 1e-3) / 1e12, "vae_tflops": fl_vae / (vae_ms / a.steps * 1e-3) / 1e12})
-        if not a.no_prof and plan["team_size"] == 1:
+        if a.full and not a.no_prof and plan["team_size"] == 1:
             # separate, untimed pass with hipEvents around every launch of the heavy kernel classes (on their stream)
             ltxhip.prof_enable(True)
             step()
@@ -494,7 +523,7 @@ def main():
             out["gemm_plans"] = {"qkv": ltxhip.ops.gemm_plan(S, 3 * D, D), "attn_out/q2/out2": ltxhip.ops.gemm_plan(S, D, D),
                                  "ff1": ltxhip.ops.gemm_plan(S, 4 * D, D), "ff2": ltxhip.ops.gemm_plan(S, D, 4 * D),
                                  "vae_mid_1024": ltxhip.ops.gemm_plan(F * H * W, 1024, 1024, 1, 27, F, H, W)}
-        if not a.no_batched and world == 1 and a.config == "c2":
+        if a.full and not a.no_batched and world == 1 and a.config == "c2":
             # Beside the headline (ONE video per pipeline call, the reference CLI's form): the same videos two per call (B = 2).  Not
             # `value`; the extra rows turn one-round grids into two-round ones and the attention's 2.5 rounds into 5
             try:                                            # an extra: it must not be able to cost the job its bench line
@@ -514,7 +543,7 @@ def main():
                 del lat2, pe2, pm2, noise2
             except Exception as e:                          # noqa: BLE001
                 out["two_videos_per_call"] = {"error": repr(e)[:300]}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, fl_job)
     # N >= 3 on the headline workload: the sharded forms measured in the same job.  This path has never run on real multi-GPU
     # hardware (no node was available to any round), so it must not be able to cost the job its bench line: errors are
@@ -527,7 +556,7 @@ def main():
             print(json.dumps(out), flush=True)
 
     watchdog = None
-    if dist is not None and world >= 3 and a.config == "c2" and os.environ.get("LTX_BENCH_SHARDED", "1") != "0":
+    if a.full and dist is not None and world >= 3 and a.config == "c2" and os.environ.get("LTX_BENCH_SHARDED", "1") != "0":
         def bail():
             if out is not None:
                 out.setdefault("sharded", {"error": "timed out (a collective of the sharded section did not complete)"})

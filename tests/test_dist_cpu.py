@@ -60,3 +60,27 @@ def test_rank_plans_for_sharded_workloads():
     assert set(bench.CONFIGS) == {"c1", "c2", "c3", "c4", "c5"} and bench.CONFIGS["c2"]["num_frames"] == 97
     # algorithmic FLOPs of SURVEY 8d: 22.35 TFLOP per C2 forward, 48.4 per decode, 204.8 per video
     assert abs(bench.dit_flops(4992) / 1e12 - 22.35) < 0.05 and abs(bench.vae_flops(13, 16, 24) / 1e12 - 48.4) < 0.1
+
+
+def test_dump_outputs_writes_float32_and_samples_large_videos_at_fixed_positions(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the latents in full, a small video in full, a large one as a seeded sample that is the same
+    positions in every run and never more than DUMP_VIDEO_ELEMS elements."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    lat = torch.randn(1, 12, 8)
+    small = torch.rand(1, 3, 9, 4, 6) * 255
+    bench.dump_outputs(str(tmp_path / "s"), lat, small)
+    assert sorted(os.listdir(tmp_path / "s")) == ["latents.npy", "video.npy"]
+    got = np.load(tmp_path / "s" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, lat.numpy())
+    assert np.array_equal(np.load(tmp_path / "s" / "video.npy"), small.numpy())
+    monkeypatch.setattr(bench, "DUMP_VIDEO_ELEMS", 100)
+    big = torch.arange(3 * 9 * 8 * 12, dtype=torch.float32).reshape(1, 3, 9, 8, 12)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), lat, big)
+        assert sorted(os.listdir(tmp_path / d)) == ["latents.npy", "video_sample.npy"]
+    a, b = np.load(tmp_path / "a" / "video_sample.npy"), np.load(tmp_path / "b" / "video_sample.npy")
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and a.min() >= 0 and a.max() < big.numel()     # sorted positions of the flattened video

@@ -15,8 +15,8 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $B > $O/write.log 
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/sq -- $B > $O/sq.log 2>&1
 cd $R
 python3 tools/summarize_prof.py $O/stats $O/summary --pmc FETCH_SIZE=$O/fetch --pmc WRITE_SIZE=$O/write --sq $O/sq | tail -30
-python3 bench.py > $O/bench_n1.json 2> $O/bench.err; tail -c 400 $O/bench_n1.json
+python3 bench.py --full > $O/bench_n1.json 2> $O/bench.err; tail -c 400 $O/bench_n1.json
 : > $O/bench_modes.jsonl
-for c in c1 c2 c3 c4 c5; do python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline >> $O/bench_modes.jsonl 2>> $O/bench_modes.err; done
+for c in c1 c2 c3 c4 c5; do python3 bench.py --full --config $c --steps 2 --warmup 1 --no-cpu-baseline >> $O/bench_modes.jsonl 2>> $O/bench_modes.err; done
 cut -c1-260 $O/bench_modes.jsonl
 find $O -name "*.csv" -size +1M -delete; find $O -name "*.db" -delete; du -sh $O
