@@ -546,7 +546,48 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const GemmArg
     // of the lane's FN column groups, the depth-to-space residual's gathers - is issued FIRST and waited for once; inside the fm / fn
     // loops each fragment's load waited vmcnt(0), which on gfx950 also waits for the STORE of the fragment before it: FM x FN
     // store -> load round trips in a row on an epilogue nothing overlaps.  Same values added in the same order: same bits.
-    if constexpr (EPI == EPI_D2S || EPI == EPI_UNPATCH || EPI == EPI_BIAS) {
+    if constexpr (EPI == EPI_S2D) {
+        // the encoder's downsampler: per row of fragments, every gather of the grouped-mean residual is issued first (one wait), then
+        // the row's scattered stores; the first frame's tile runs a second pass for the repeated frame (kernels.h)
+        float bias4[FN][4];
+#pragma unroll
+        for (int fn = 0; fn < FN; ++fn) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) bias4[fn][i] = 0.f;
+        }
+        if (g.bias) {
+#pragma unroll
+            for (int fn = 0; fn < FN; ++fn) {
+                int nb = n0 + wn * WN + fn * 16 + 4 * fq; nb = nb < g.N ? nb : g.N - 4;
+                load4<bf16_t>(reinterpret_cast<const bf16_t*>(g.bias) + nb, bias4[fn]);
+            }
+        }
+        const int npass = (t == 0 && g.s2_st > 1) ? 2 : 1;
+        for (int pass = 0; pass < npass; ++pass) {
+#pragma unroll
+            for (int fm = 0; fm < FM; ++fm) {
+                int y = y0 + wm * FM + fm, x = x0 + frow;
+                const bool inside = y < g.H && x < g.Wd;
+                y = y < g.H ? y : g.H - 1; x = x < g.Wd ? x : g.Wd - 1;          // clamped: no condition in front of a load
+                float res[FN][4];
+#pragma unroll
+                for (int fn = 0; fn < FN; ++fn) {
+                    int nb = n0 + wn * WN + fn * 16 + 4 * fq; nb = nb < g.N ? nb : g.N - 4;
+                    s2d_residual<bf16_t>(g, b, t, y, x, nb, pass, res[fn]);
+                }
+                if (!inside) continue;
+#pragma unroll
+                for (int fn = 0; fn < FN; ++fn) {
+                    const int nb = n0 + wn * WN + fn * 16 + 4 * fq;
+                    if (nb >= g.N) continue;
+                    float v[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = acc[fm][fn][i] + bias4[fn][i];
+                    s2d_store<bf16_t>(g, b, t, y, x, nb, pass, v, res[fn]);
+                }
+            }
+        }
+    } else if constexpr (EPI == EPI_D2S || EPI == EPI_UNPATCH || EPI == EPI_BIAS) {
         float bias4[FN][4];
 #pragma unroll
         for (int fn = 0; fn < FN; ++fn) {
@@ -650,6 +691,7 @@ int launch_halo_epi(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_BIAS: return launch_halo<BN, WGM, WGN, EPI_BIAS, PIPE>(g, s);
         case EPI_RESID: return launch_halo<BN, WGM, WGN, EPI_RESID, PIPE>(g, s);
         case EPI_D2S: return launch_halo<BN, WGM, WGN, EPI_D2S, PIPE>(g, s);
+        case EPI_S2D: return launch_halo<BN, WGM, WGN, EPI_S2D, PIPE>(g, s);
     }
     LTX_FAIL(LTX_ERR_ARG, "conv_halo: unsupported epilogue");
 }
@@ -664,7 +706,7 @@ bool ltx_conv_halo_eligible(const GemmArgs& g, int epi, int bn) {
         if (epi != EPI_UNPATCH || g.N > 48 || g.N % 4 != 0) return false;
     } else {
         if (g.N % bn != 0) return false;
-        if (epi != EPI_BIAS && epi != EPI_RESID && epi != EPI_D2S) return false;
+        if (epi != EPI_BIAS && epi != EPI_RESID && epi != EPI_D2S && epi != EPI_S2D) return false;
     }
     if (g.c_seg_shift) return false;
     // a tile addresses the three frames around it: those (not the tensor) and the weights must stay below 2 GiB

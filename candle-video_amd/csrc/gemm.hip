@@ -170,6 +170,7 @@ int launch_t(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_RESID: hipLaunchKernelGGL((gemm_kernel<T, EPI_RESID, CONV>), grid, block, 0, s, g); break;
         case EPI_D2S: hipLaunchKernelGGL((gemm_kernel<T, EPI_D2S, CONV>), grid, block, 0, s, g); break;
         case EPI_UNPATCH: hipLaunchKernelGGL((gemm_kernel<T, EPI_UNPATCH, CONV>), grid, block, 0, s, g); break;
+        case EPI_S2D: hipLaunchKernelGGL((gemm_kernel<T, EPI_S2D, CONV>), grid, block, 0, s, g); break;
         default: LTX_FAIL(LTX_ERR_ARG, "gemm: bad epilogue");
     }
     LTX_CHECK_LAUNCH();
@@ -187,7 +188,8 @@ int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s) {
     if (g.K % ch != 0) LTX_FAIL(LTX_ERR_ARG, "gemm: K must be a multiple of the 16-byte chunk");
     if (g.N % 4 != 0) LTX_FAIL(LTX_ERR_ARG, "gemm: N must be a multiple of 4");
     if (!g.conv && g.lda % ch != 0) LTX_FAIL(LTX_ERR_ARG, "gemm: lda must be 16-byte aligned");
-    if ((epi == EPI_D2S || epi == EPI_UNPATCH) && !g.conv) LTX_FAIL(LTX_ERR_ARG, "gemm: d2s/unpatch need conv mode");
+    if ((epi == EPI_D2S || epi == EPI_UNPATCH || epi == EPI_S2D) && !g.conv) LTX_FAIL(LTX_ERR_ARG, "gemm: d2s/unpatch need conv mode");
+    if (epi == EPI_S2D && (!g.resid || g.s2_st * g.s2_sh * g.s2_sw < 2 || g.s2_group < 1)) LTX_FAIL(LTX_ERR_ARG, "gemm: the space-to-depth epilogue needs the input tensor and its strides");
     if (g.rowsq && (g.conv || g.c_seg_shift || epi == EPI_D2S || epi == EPI_UNPATCH)) LTX_FAIL(LTX_ERR_ARG, "gemm: rowsq needs a dense linear output");
     // K ranges left to the consumer are gemm_ring's (through gemm_big's plan dispatch); no other kernel honours the field
     if (g.defer_parts && (ltx_gemm_asm_eligible(g, dtype, epi) || !ltx_gemm_big_eligible(g, dtype)))

@@ -539,6 +539,7 @@ int launch_epi(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_RESID: return launch_one<BM, BN, WGM, WGN, EPI_RESID, CONV>(g, s);
         case EPI_D2S: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_D2S, CONV>(g, s); break;
         case EPI_UNPATCH: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_UNPATCH, CONV>(g, s); break;
+        case EPI_S2D: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_S2D, CONV>(g, s); break;
     }
     LTX_FAIL(LTX_ERR_ARG, "gemm_big: bad epilogue");
 }
@@ -656,6 +657,8 @@ bool plan_shape_ok(int plan, int N, int nk, bool split_shape) {
 bool plan_ok(const GemmArgs& g, int epi, int plan) {
     const int nk = (g.K + 63) / 64 * (g.conv ? g.ntaps : 1);
     if (!plan_shape_ok(plan, g.N, nk, ltx_gemm_split_factor(g) > 1)) return false;
+    // the encoder's space-to-depth epilogue lives in the gemm_big tiles and the halo-staged kernel; the other families fall back
+    if (epi == EPI_S2D && plan >= kPlanP8 && !(plan >= kPlanHalo && plan < kPlanAsm16)) return false;
     if (plan >= kPlanRing) return ltx_gemm_ring_tile_fits(g, epi, plan - kPlanRing);
     if (plan == kPlanAsm16Conv) return ltx_gemm_asm16_conv_fits(g, epi);
     if (plan >= kPlanAsm16) return ltx_gemm_asm16_fits(g, epi);

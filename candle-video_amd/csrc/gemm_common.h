@@ -56,6 +56,40 @@ __device__ __forceinline__ float ltx_rowsq_leaf(const f32x4& v) {
     return __builtin_fmaf(v[3], v[3], s);
 }
 
+// ---- EPI_S2D pieces (GemmArgs::s2_*): the residual's gathers and the placement, shared by every kernel that carries it ----
+// pass 0: conv frame t at padded frame t + st - 1; pass 1 (t == 0, st == 2 only): the repeated first frame, padded frame 0
+template <typename T>
+__device__ __forceinline__ void s2d_residual(const GemmArgs& g, int b, int t, int h, int w, int nb, int pass, float* res) {
+    const int st = g.s2_st, sh = g.s2_sh, sw = g.s2_sw, nsub = st * sh * sw, G = g.s2_group;
+    const int tp = pass ? 0 : t + st - 1, to = tp / st, it = tp - to * st;
+    const int ho = h / sh, ih = h - ho * sh, wo = w / sw, iw = w - wo * sw;
+    const int sub = (it * sh + ih) * sw + iw;
+    const T* X = reinterpret_cast<const T*>(g.resid);
+    const float inv = 1.0f / (float)G;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int co = (nb + i) * nsub + sub;
+        float acc = 0.f;
+        for (int gg = 0; gg < G; ++gg) {
+            const int pc = co * G + gg, cx = pc / nsub, s2 = pc - cx * nsub;
+            const int jt = s2 / (sh * sw), jh = (s2 / sw) % sh, jw = s2 % sw;
+            int tx = to * st + jt - (st - 1); tx = tx < 0 ? 0 : tx;
+            acc += to_f32(X[((((int64_t)b * g.T + tx) * g.H + ho * sh + jh) * g.Wd + wo * sw + jw) * (int64_t)g.Cin + cx]);
+        }
+        res[i] = to_f32(from_f32<T>(acc * inv));
+    }
+}
+template <typename T>
+__device__ __forceinline__ void s2d_store(const GemmArgs& g, int b, int t, int h, int w, int nb, int pass, const float* v, const float* res) {
+    const int st = g.s2_st, sh = g.s2_sh, sw = g.s2_sw, nsub = st * sh * sw;
+    const int tp = pass ? 0 : t + st - 1, to = tp / st, it = tp - to * st;
+    const int ho = h / sh, ih = h - ho * sh, wo = w / sw, iw = w - wo * sw;
+    const int sub = (it * sh + ih) * sw + iw;
+    T* out = reinterpret_cast<T*>(g.C) + ((((int64_t)b * g.To + to) * g.Ho + ho) * g.Wo + wo) * (int64_t)(g.N * nsub);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[(nb + i) * nsub + sub] = from_f32<T>(to_f32(from_f32<T>(v[i])) + res[i]);
+}
+
 template <typename T, int EPI>
 __device__ __forceinline__ void epilogue(const GemmArgs& g, int m, int nb, float* v) {
     T* C = reinterpret_cast<T*>(g.C);
@@ -104,6 +138,16 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, int m, int nb, float
         }
         int64_t o = ((((int64_t)b * g.To + to) * g.Ho + (2 * h + sh)) * g.Wo + (2 * w + sw)) * g.Cf + co;
         store4<T>(C + o, v);
+    } else if constexpr (EPI == EPI_S2D) {
+        int w = m % g.Wd; int t1 = m / g.Wd;
+        int h = t1 % g.H; int t2 = t1 / g.H;
+        int t = t2 % g.T; int b = t2 / g.T;
+        const int npass = (t == 0 && g.s2_st > 1) ? 2 : 1;
+        for (int pass = 0; pass < npass; ++pass) {
+            float res[4];
+            s2d_residual<T>(g, b, t, h, w, nb, pass, res);
+            s2d_store<T>(g, b, t, h, w, nb, pass, v, res);
+        }
     } else if constexpr (EPI == EPI_UNPATCH) {
         // conv_out + unpatchify (vae.rs:1626-1654); channels re-ordered at pack time to
         // n' = (c*4 + off_h)*4 + off_w.  Output is f32 NCTHW [B, N/16, T, 4H, 4W].

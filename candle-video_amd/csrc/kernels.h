@@ -27,7 +27,7 @@ bool ltx_prof_kernel_events(hipEvent_t* a, hipEvent_t* b);
     } while (0)
 
 // ---------------- GEMM / implicit-GEMM conv (gemm.hip) ----------------
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_GATE_RESID = 2, EPI_RESID = 3, EPI_D2S = 4, EPI_UNPATCH = 5 };
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_GATE_RESID = 2, EPI_RESID = 3, EPI_D2S = 4, EPI_UNPATCH = 5, EPI_S2D = 6 };
 
 struct GemmArgs {
     const void* A = nullptr;      // [M, lda] (linear) or channels-last activation [B,T,H,W,Cin] (conv)
@@ -46,6 +46,13 @@ struct GemmArgs {
     // D2S / UNPATCH
     int Cf = 0, Cr = 0, To = 0, Ho = 0, Wo = 0, post = 0;
     int d2s_sp = 0;                 // EPI_D2S: 1 = the spatial-only (1, 2, 2) depth-to-space of an up-block without temporal scaling (N = 4 Cf, To = T, no frame dropped; vae.rs:1225-1236)
+    // EPI_S2D (the encoder's pixel-unshuffle downsampler, vae.rs:534-581; the mirror of EPI_D2S): conv output channel c of voxel
+    // (t, h, w) goes to channel ((c*st + it)*sh + ih)*sw + iw of output voxel (to, h/sh, w/sw), where to*st + it = t + st - 1 - the
+    // reference convolves the input with st - 1 leading frames repeated, which for a causal conv is this conv's output with its
+    // first frame repeated: conv frame 0 is stored to the padded frames 0 .. st-1 - plus the residual: the mean of the s2_group
+    // consecutive packed channels of resid = x [B,T,H,W,Cin] re-arranged the same way (frame index clamped the same way).
+    // C [B,To,Ho,Wo,N*st*sh*sw]; the conv value and the mean are each rounded to T before they are added.
+    int s2_st = 1, s2_sh = 1, s2_sw = 1, s2_group = 1;
     // EPI_BIAS only: output split into column segments of width 1 << c_seg_shift, segment j a dense [M, ldc] matrix at
     // C + j * c_seg_stride elements (fused q|k|v projection -> three contiguous matrices); 0 = one [M, ldc] matrix
     int c_seg_shift = 0; int64_t c_seg_stride = 0;

@@ -1,6 +1,8 @@
-// AutoencoderKLLtxVideo::decode on MI355X (decoder side only; T2V never encodes).
+// AutoencoderKLLtxVideo on MI355X: decode (first part of the file) and encode (second part, "encode side" below).
 // Reference: src/models/ltx_video/vae.rs  (:1488-1727 decoder, :755-821 resnet, :1090-1169 upsampler,
-// :415-464 conv, :2037-2066 decode_z, :2225-2290 / :2358-2434 tiling, :1927-2006 blends).
+// :415-464 conv, :2037-2066 decode_z, :2225-2290 / :2358-2434 tiling, :1927-2006 blends;
+// :1316-1469 encoder, :469-582 downsampler, :841-948 down block, :117-145 posterior, :2017-2035 encode_z,
+// :2158-2223 / :2294-2357 tiled encodes).
 //
 // HBM layout: activations are CHANNELS-LAST [B,T,H,W,C] in the model dtype, so that
 //   * the conv3d is an implicit GEMM whose K dimension (C_in) is contiguous (16-B coalesced loads,
@@ -16,6 +18,8 @@
 #include "model_util.h"
 #include "options.h"
 #include "../../include/ltxhip_frames.h"
+#include "../../include/ltxhip_encoder.h"
+#include "../../include/ltxhip_ops.h"
 
 extern "C" int ltx_pcg32_randn(uint64_t seed, uint64_t inc, size_t n, float* out_host);   // host/pipeline.hip (utils/deterministic_rng.rs)
 
@@ -23,6 +27,7 @@ struct ConvW {
     void* w = nullptr;   // [27][N][Cin] model dtype (N possibly permuted)
     void* b = nullptr;   // [N]
     int cin = 0, cout = 0;
+    int st = 1, sh = 1, sw = 1, group = 1;   // EPI_S2D (encoder downsampler convs): strides and residual group size (vae.rs:516)
     int nsub = 8;        // depth-to-space convs: output channels per final channel, 8 = (2, 2, 2), 4 = (1, 2, 2)
 };
 struct TimeEmbW { LinearW l1, l2; int dim = 0; };
@@ -103,8 +108,8 @@ int ltx_pack_conv(const void* src_dev, int sdt, void* dst, int ddt, int O, int I
     return LTX_OK;
 }
 namespace {
-int load_conv(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int cin, int cout, int mode, int Cf, ConvW* c) {
-    const int dt = v->dtype; const size_t esz = ltx_dt_size(dt);
+int load_conv(int dt, std::vector<void*>& owned, const WeightMap& wm, const std::string& prefix, int cin, int cout, int mode, int Cf, ConvW* c) {
+    const size_t esz = ltx_dt_size(dt);
     c->cin = cin; c->cout = cout;
     const int nsub = (mode == PERM_D2S && Cf > 0) ? cout / Cf : 8;
     c->nsub = nsub;
@@ -114,8 +119,8 @@ int load_conv(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int ci
     if (!b) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight '" + prefix + ".conv.bias'");
     if (ltx_numel(w) != (int64_t)cout * cin * 27) LTX_FAIL(LTX_ERR_ARG, "weight '" + prefix + ".conv.weight': wrong size");
     if (ltx_numel(b) != cout) LTX_FAIL(LTX_ERR_ARG, "weight '" + prefix + ".conv.bias': wrong size");
-    HIP_TRY(hipMalloc(&c->w, (size_t)cout * cin * 27 * esz)); v->owned.push_back(c->w);
-    HIP_TRY(hipMalloc(&c->b, (size_t)cout * esz + 16)); v->owned.push_back(c->b);
+    HIP_TRY(hipMalloc(&c->w, (size_t)cout * cin * 27 * esz)); owned.push_back(c->w);
+    HIP_TRY(hipMalloc(&c->b, (size_t)cout * esz + 16)); owned.push_back(c->b);
     const void* src = nullptr; void* tmp = nullptr;
     LTX_TRY(ltx_stage_src(w, &src, &tmp));
     int64_t n = (int64_t)cout * cin * 27; int64_t blocks = cdiv64(n, 256); if (blocks > 16384) blocks = 16384;
@@ -129,6 +134,9 @@ int load_conv(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int ci
     e = hipDeviceSynchronize(); if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) { ltx_set_error(std::string("pack bias: ") + hipGetErrorString(e)); return LTX_ERR_HIP; }
     return LTX_OK;
+}
+int load_conv(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int cin, int cout, int mode, int Cf, ConvW* c) {
+    return load_conv(v->dtype, v->owned, wm, prefix, cin, cout, mode, Cf, c);
 }
 
 int load_temb(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int dim, TimeEmbW* t) {
@@ -240,52 +248,56 @@ struct Dims { int B, T, H, W; int64_t vox() const { return (int64_t)B * T * H * 
 
 struct PostNorm { int on = 0; float eps = 0.f; int act = 0; int mod_stride = 0; const float* scale = nullptr; const float* shift = nullptr; };
 
-GemmArgs conv_args(ltx_vae* v, const ConvW& cw, const Dims& d) {
+GemmArgs conv_args(int pad_t, const ConvW& cw, const Dims& d) {
     GemmArgs g;
     g.W = cw.w; g.bias = cw.b;
     g.M = (int)d.vox(); g.N = cw.cout; g.K = cw.cin; g.ldc = cw.cout; g.ldr = cw.cout;
     g.conv = 1; g.B = d.B; g.T = d.T; g.H = d.H; g.Wd = d.W; g.Cin = cw.cin;
     g.ntaps = 27; g.kh = 3; g.kw = 3;
-    g.pad_t = v->cfg.decoder_causal ? 2 : 1;
+    g.pad_t = pad_t;
     return g;
 }
+GemmArgs conv_args(ltx_vae* v, const ConvW& cw, const Dims& d) { return conv_args(v->cfg.decoder_causal ? 2 : 1, cw, d); }
 
 // Samples per conv launch: the fast conv kernels address their operands with 32-bit byte offsets (< 2 GiB per operand).
 // Samples never interact in a conv, so a batch whose activations pass that limit (the batched leaf tiles of a tiled decode
 // at the last stages) runs as sample groups that fit; a single sample beyond the limit goes to the launcher as it is.
-int conv_chunk(ltx_vae* v, const ConvW& cw, const Dims& d) {
+int conv_chunk(int dtype, const ConvW& cw, const Dims& d) {
     if (d.B <= 1) return d.B;
     {   // the large-tile conv kernels address a window around each tile, not the tensor: whole batch in one launch where they apply
         GemmArgs g; g.M = (int)std::min<int64_t>(d.vox(), 2147483647); g.N = cw.cout; g.K = cw.cin; g.conv = 1; g.B = d.B; g.T = d.T; g.H = d.H; g.Wd = d.W;
         g.Cin = cw.cin; g.ntaps = 27; g.kh = 3; g.kw = 3;
-        if (v->dtype == LTX_DT_BF16 && d.vox() < 2147483647 && ltx_gemm_big_eligible(g, v->dtype)) return d.B;
+        if (dtype == LTX_DT_BF16 && d.vox() < 2147483647 && ltx_gemm_big_eligible(g, dtype)) return d.B;
     }
     const int64_t per = (int64_t)d.T * d.H * d.W;
-    const int64_t lim = (2147483648LL - (1 << 20)) / (per * std::max(cw.cin, cw.cout) * (int64_t)ltx_dt_size(v->dtype));
+    const int64_t lim = (2147483648LL - (1 << 20)) / (per * std::max(cw.cin, cw.cout) * (int64_t)ltx_dt_size(dtype));
     return (lim >= 1 && lim < d.B) ? (int)lim : d.B;
 }
+int conv_chunk(ltx_vae* v, const ConvW& cw, const Dims& d) { return conv_chunk(v->dtype, cw, d); }
 
 // whether conv1 of a resnet can carry norm2 in its epilogue: bf16, the halo-staged kernel with BN == channels
-bool fuse_norm2(ltx_vae* v, const ConvW& cw, const Dims& d_all, int ch) {
-    Dims d = d_all; d.B = conv_chunk(v, cw, d_all);
+bool fuse_norm2(int dtype, int pad_t, const ConvW& cw, const Dims& d_all, int ch) {
+    Dims d = d_all; d.B = conv_chunk(dtype, cw, d_all);
     const LtxOptions& o = ltx_opt();
     if (!o.vae_fuse_norm || !o.gemm_wide_epi || (o.gemm_off & (LTX_FAM_HALO | LTX_FAM_BIG))) return false;
-    if (v->dtype != LTX_DT_BF16 || (ch != 128 && ch != 256) || cw.cout != ch) return false;
-    const GemmArgs g = conv_args(v, cw, d);
+    if (dtype != LTX_DT_BF16 || (ch != 128 && ch != 256) || cw.cout != ch) return false;
+    const GemmArgs g = conv_args(pad_t, cw, d);
     // the fused epilogue needs the whole channel row in one tile (BN == channels), i.e. a grid of M / 256 blocks: below about
     // one round of the chip the unfused conv on a plan with more, smaller tiles + the stand-alone norm is faster (C1's
     // 256-channel stage, 78 tiles: 168 us fused vs 108 + 13; decode 5.7 -> 5.45 ms, profiles/r5k_c1_vae_fused_norm_ab.jsonl)
     if ((g.M + 255) / 256 < 192 && o.vae_fuse_norm < 2) return false;
-    return ltx_gemm_big_eligible(g, v->dtype) && ltx_conv_halo_eligible(g, EPI_BIAS, ch);
+    return ltx_gemm_big_eligible(g, dtype) && ltx_conv_halo_eligible(g, EPI_BIAS, ch);
 }
+bool fuse_norm2(ltx_vae* v, const ConvW& cw, const Dims& d_all, int ch) { return fuse_norm2(v->dtype, v->cfg.decoder_causal ? 2 : 1, cw, d_all, ch); }
 
-int conv3d(ltx_vae* v, const ConvW& cw, const void* x, void* y, const Dims& d, int epi, const void* resid, int post, hipStream_t s, const PostNorm* pn = nullptr) {
-    const size_t esz = ltx_dt_size(v->dtype);
+int conv3d(int dtype, int pad_t, const ConvW& cw, const void* x, void* y, const Dims& d, int epi, const void* resid, int post, hipStream_t s, const PostNorm* pn = nullptr) {
+    const size_t esz = ltx_dt_size(dtype);
     const int64_t per = (int64_t)d.T * d.H * d.W;
-    const int nb = conv_chunk(v, cw, d);
+    const int nb = conv_chunk(dtype, cw, d);
     size_t out_b, res_b = 0;                              // bytes per sample of the output / residual tensor
     const int To = cw.nsub == 4 ? d.T : 2 * d.T - 1;      // frames a depth-to-space conv writes
     if (epi == EPI_D2S) { out_b = (size_t)To * (2 * d.H) * (2 * d.W) * (cw.cout / cw.nsub) * esz; res_b = (size_t)per * cw.cin * esz; }
+    else if (epi == EPI_S2D) { out_b = (size_t)((d.T + cw.st - 1) / cw.st) * (d.H / cw.sh) * (d.W / cw.sw) * cw.cout * cw.st * cw.sh * cw.sw * esz; res_b = (size_t)per * cw.cin * esz; }
     else if (epi == EPI_UNPATCH) out_b = (size_t)(cw.cout / 16) * d.T * (4 * d.H) * (4 * d.W) * sizeof(float);
     else { out_b = (size_t)per * cw.cout * esz; res_b = out_b; }
     for (int b0 = 0; b0 < d.B; b0 += nb) {
@@ -300,12 +312,16 @@ int conv3d(ltx_vae* v, const ConvW& cw, const void* x, void* y, const Dims& d, i
         g.M = (int)(bc * per); g.N = cw.cout; g.K = cw.cin; g.ldc = cw.cout; g.ldr = cw.cout;
         g.conv = 1; g.B = bc; g.T = d.T; g.H = d.H; g.Wd = d.W; g.Cin = cw.cin;
         g.ntaps = 27; g.kh = 3; g.kw = 3;
-        g.pad_t = v->cfg.decoder_causal ? 2 : 1;          // vae.rs:383-412
+        g.pad_t = pad_t;                                  // vae.rs:383-412
         g.post = post;
         if (epi == EPI_D2S) { g.Cf = cw.cout / cw.nsub; g.Cr = cw.cin / cw.nsub; g.To = To; g.Ho = 2 * d.H; g.Wo = 2 * d.W; g.d2s_sp = cw.nsub == 4; }
-        LTX_TRY(ltx_launch_gemm(g, v->dtype, epi, s));
+        if (epi == EPI_S2D) { g.s2_st = cw.st; g.s2_sh = cw.sh; g.s2_sw = cw.sw; g.s2_group = cw.group; g.To = (d.T + cw.st - 1) / cw.st; g.Ho = d.H / cw.sh; g.Wo = d.W / cw.sw; }
+        LTX_TRY(ltx_launch_gemm(g, dtype, epi, s));
     }
     return LTX_OK;
+}
+int conv3d(ltx_vae* v, const ConvW& cw, const void* x, void* y, const Dims& d, int epi, const void* resid, int post, hipStream_t s, const PostNorm* pn = nullptr) {
+    return conv3d(v->dtype, v->cfg.decoder_causal ? 2 : 1, cw, x, y, d, epi, resid, post, s, pn);
 }
 
 // CombinedTimestepEmbedder (vae.rs:236-265) + "+ scale_shift_table" -> f32 [B][rows][C]; *out points at the (cached) result
@@ -760,4 +776,566 @@ extern "C" int ltx_vae_prepare_latents(ltx_vae* v, const float* tokens, const fl
     TimeVec ns; ns.n = B; for (int i = 0; i < 8; ++i) ns.t[i] = (noise && i < B) ? noise_scale[i] : 0.f;
     return ltx_launch_denorm_mix(tokens, v->mean, v->std_, 1.0f / v->cfg.scaling_factor, noise, ns, out_tokens, LTX_DT_F32, B, S, C,
                                  (hipStream_t)stream);
+}
+
+// =====================================================================================================================
+// encode side: LtxVideoEncoder3d (vae.rs:1316-1469) + posterior + tiled encodes.  Same layout as the decoder: activations
+// channels-last in the model dtype, every 3x3x3 conv through ltx_launch_gemm (the measured conv kernels, pad_t = 2).
+//   patchify            one gather kernel, coalesced on the read side: [B,3,F,H,W] -> [B,F,H/4,W/4,48]
+//   resnet              the decoder's, without modulation / noise / timestep (norm2 in conv1's epilogue where that form applies)
+//   downsampler         one conv whose epilogue (EPI_S2D, kernels.h: the mirror of EPI_D2S) scatters to the space-to-depth
+//                       channel and adds the grouped-mean residual.  The reference convolves the input with st - 1 leading
+//                       frames repeated (vae.rs:539-544); with a causal conv that output is the conv of the un-repeated input
+//                       with ITS first frame repeated (frame t of the former reads input frames max(t-3,0), max(t-2,0),
+//                       max(t-1,0) = frame t-1 of the latter), so the repeat is an index clamp: the first frame's tiles store
+//                       twice, and no padded copy exists
+//   conv_out            129 output channels padded to 132 with zero weights; one kernel reads its rows and writes mean and the
+//                       broadcast logvar in f32 NCTHW (untiled), or the moments [B,129,F',h,w] the tiled paths blend; the
+//                       256-channel tensor of vae.rs:1463-1467 never exists
+// =====================================================================================================================
+struct DownBlockW { std::vector<ResnetW> res; ConvW down; int ch = 0, cout = 0, cc = 0, st = 1, sh = 1, sw = 1, group = 1; bool has_down = false; };
+
+struct ltx_vae_encoder {
+    ltx_vae_encoder_config cfg{};
+    int dtype = LTX_DT_BF16, device = 0;
+    ConvW conv_in, conv_out;
+    std::vector<DownBlockW> downs;
+    std::vector<ResnetW> mid;
+    int mid_ch = 0, nmom = 0, nmom_pad = 0, cin_p = 0;
+    std::vector<void*> owned;
+    DevBuf X, Y, N, C, mom, ttiles[2], scratch;
+    std::deque<DevBuf> tilebufs;
+    void free_all() {
+        for (void* p : owned) if (p) (void)hipFree(p);
+        owned.clear();
+        DevBuf* bs[] = {&X, &Y, &N, &C, &mom, &ttiles[0], &ttiles[1], &scratch};
+        for (DevBuf* b : bs) b->release();
+        for (auto& b : tilebufs) b.release();
+    }
+};
+
+namespace {
+
+// [B,C,F,H,W] window (t0.., h0.., w0.., extent nt x nh x nw) -> channels-last [B,nt,nh/p,nw/p,C*p*p], packed channel
+// (c*p + off_w)*p + off_h (vae.rs:1426-1444 with patch_size_t = 1).  One thread per input element: reads run along W.
+template <typename TI, typename TO>
+__global__ void patchify_kernel(const TI* __restrict__ x, TO* __restrict__ y, int B, int C, int F, int H, int W,
+                                int t0, int h0, int w0, int nt, int nh, int nw, int p) {
+    const int64_t n = (int64_t)B * C * nt * nh * nw;
+    const int hp = nh / p, wp = nw / p, cp = C * p * p;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        int w = (int)(idx % nw); int64_t r = idx / nw; int h = (int)(r % nh); r /= nh; int t = (int)(r % nt); r /= nt;
+        int c = (int)(r % C); int b = (int)(r / C);
+        const float v = to_f32(x[((((int64_t)b * C + c) * F + t0 + t) * H + h0 + h) * W + w0 + w]);
+        const int ch = (c * p + (w % p)) * p + (h % p);
+        y[((((int64_t)b * nt + t) * hp + h / p) * wp + w / p) * cp + ch] = from_f32<TO>(v);
+    }
+}
+
+// conv_out's channels-last result [B,S,ld] (first nmom channels) -> f32 NCTHW moments [B,nmom,S]
+template <typename T>
+__global__ void moments_kernel(const T* __restrict__ x, float* __restrict__ y, int B, int64_t S, int ld, int nmom) {
+    const int64_t n = (int64_t)B * nmom * S;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        int64_t sp = idx % S; int64_t r = idx / S; int c = (int)(r % nmom); int b = (int)(r / nmom);
+        y[idx] = to_f32(x[((int64_t)b * S + sp) * ld + c]);
+    }
+}
+
+// conv_out's channels-last result [B,S,ld] -> mean [B,L,S] f32 and (optional) logvar [B,L,S] = channel L replicated, in one pass
+// (the untiled encode: no moments tensor in between)
+template <typename T>
+__global__ void moments_out_kernel(const T* __restrict__ x, float* __restrict__ mean, float* __restrict__ logvar, int B, int64_t S, int ld, int L) {
+    const int64_t n = (int64_t)B * L * S;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        int64_t sp = idx % S; int64_t r = idx / S; int c = (int)(r % L); int b = (int)(r / L);
+        const T* row = x + ((int64_t)b * S + sp) * ld;
+        mean[idx] = to_f32(row[c]);
+        if (logvar) logvar[idx] = to_f32(row[L]);
+    }
+}
+
+// moments [B,L+1,S] -> mean [B,L,S] and (optional) logvar [B,L,S] = channel L replicated (vae.rs:1463-1467 + :122-131)
+__global__ void moments_split_kernel(const float* __restrict__ mom, float* __restrict__ mean, float* __restrict__ logvar, int B, int L, int64_t S) {
+    const int64_t n = (int64_t)B * L * S;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        int64_t sp = idx % S; int64_t r = idx / S; int c = (int)(r % L); int b = (int)(r / L);
+        mean[idx] = mom[((int64_t)b * (L + 1) + c) * S + sp];
+        if (logvar) logvar[idx] = mom[((int64_t)b * (L + 1) + L) * S + sp];
+    }
+}
+
+__global__ void posterior_sample_kernel(const float* __restrict__ mean, const float* __restrict__ logvar, const float* __restrict__ eps,
+                                        float* __restrict__ out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = mean[i] + expf(logvar[i] * 0.5f) * eps[i];                                  // vae.rs:139-143
+}
+
+// moments [B,L+1,S] (+ eps [B,L,S] or null = mode) -> tokens [B,S,L] = (z - mean[c]) * sf / std[c]  (t2v_pipeline.rs:552-571, 474-504)
+__global__ void moments_tokens_kernel(const float* __restrict__ mom, const float* __restrict__ eps, const float* __restrict__ lmean,
+                                      const float* __restrict__ lstd, float sf, float* __restrict__ tok, int B, int L, int64_t S) {
+    const int64_t n = (int64_t)B * S * L;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        int c = (int)(idx % L); int64_t r = idx / L; int64_t sp = r % S; int b = (int)(r / S);
+        float z = mom[((int64_t)b * (L + 1) + c) * S + sp];
+        if (eps) z = z + expf(mom[((int64_t)b * (L + 1) + L) * S + sp] * 0.5f) * eps[((int64_t)b * L + c) * S + sp];
+        tok[idx] = (z - lmean[c]) * sf / lstd[c];
+    }
+}
+
+inline dim3 enc_grid(int64_t n) { int64_t b = cdiv64(n, 256); if (b > 65536) b = 65536; if (b < 1) b = 1; return dim3((unsigned)b); }
+
+void down_stride(int type, int* st, int* sh, int* sw) {      // DownsampleType::stride, vae.rs:487-496
+    *st = type == LTX_DOWN_SPATIAL ? 1 : 2; *sh = type == LTX_DOWN_TEMPORAL ? 1 : 2; *sw = *sh;
+}
+
+int enc_load_resnet(ltx_vae_encoder* e, const WeightMap& wm, const std::string& prefix, int ch, ResnetW* r) {
+    LTX_TRY(load_conv(e->dtype, e->owned, wm, prefix + ".conv1", ch, ch, PERM_NONE, 0, &r->c1));
+    LTX_TRY(load_conv(e->dtype, e->owned, wm, prefix + ".conv2", ch, ch, PERM_NONE, 0, &r->c2));
+    return LTX_OK;
+}
+
+int enc_build(ltx_vae_encoder* e, const ltx_weight* weights, size_t n_weights) {
+    const ltx_vae_encoder_config& c = e->cfg;
+    std::vector<ltx_weight> renamed; std::vector<std::string> names;
+    names.reserve(n_weights); renamed.reserve(n_weights);
+    for (size_t i = 0; i < n_weights; ++i) {
+        std::string nm = weights[i].name ? weights[i].name : "";
+        if (nm.rfind("encoder.", 0) == 0) nm = nm.substr(8);
+        names.push_back(nm);
+    }
+    for (size_t i = 0; i < n_weights; ++i) { ltx_weight w = weights[i]; w.name = names[i].c_str(); renamed.push_back(w); }
+    WeightMap wm(renamed.data(), renamed.size());
+    // vae.rs:1388-1394 loads norm_out.weight when the checkpoint has one (no released checkpoint does; else ones): refused, not ignored
+    if (wm.find("norm_out.weight")) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder checkpoint carries 'norm_out.weight': a weighted norm_out is not implemented (the presets' RMS norm has no weight)");
+    const int nb = c.n_blocks;
+    e->cin_p = c.in_channels * c.patch_size * c.patch_size * c.patch_size_t;
+    LTX_TRY(load_conv(e->dtype, e->owned, wm, "conv_in", e->cin_p, c.block_out_channels[0], PERM_NONE, 0, &e->conv_in));
+    e->downs.resize(nb - 1);
+    int cur = c.block_out_channels[0];
+    for (int i = 0; i < nb - 1; ++i) {
+        DownBlockW& d = e->downs[i];
+        const std::string p = "down_blocks." + std::to_string(i);
+        d.ch = cur; d.cout = c.block_out_channels[i + 1];
+        d.res.resize(c.layers_per_block[i]);
+        for (int k = 0; k < c.layers_per_block[i]; ++k) LTX_TRY(enc_load_resnet(e, wm, p + ".resnets." + std::to_string(k), cur, &d.res[k]));
+        d.has_down = c.spatiotemporal_scaling[i] != 0;
+        if (d.has_down) {
+            down_stride(c.downsample_types[i], &d.st, &d.sh, &d.sw);
+            const int nsub = d.st * d.sh * d.sw;
+            if (d.cout % nsub != 0 || (cur * nsub) % d.cout != 0 || (d.cout / nsub) % 4 != 0)
+                LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder downsampler: channels must divide by the stride volume (and the conv's by 4)");
+            d.cc = d.cout / nsub; d.group = cur * nsub / d.cout;                       // vae.rs:516-517
+            LTX_TRY(load_conv(e->dtype, e->owned, wm, p + ".downsamplers.0.conv", cur, d.cc, PERM_NONE, 0, &d.down));
+            d.down.st = d.st; d.down.sh = d.sh; d.down.sw = d.sw; d.down.group = d.group;
+        } else if (d.cout != cur) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder down block without a downsampler cannot change the channel count");
+        cur = d.cout;
+    }
+    e->mid_ch = cur;
+    const int nmid = std::max(c.layers_per_block[nb - 1] - 1, 0);                      // vae.rs:1382-1386
+    e->mid.resize(nmid);
+    for (int k = 0; k < nmid; ++k) LTX_TRY(enc_load_resnet(e, wm, "mid_block.resnets." + std::to_string(k), cur, &e->mid[k]));
+    // conv_out: latent_channels + 1 outputs (vae.rs:1396-1405), padded with zero weights to the GEMM's multiple of 4
+    e->nmom = c.latent_channels + 1; e->nmom_pad = (e->nmom + 3) / 4 * 4;
+    {
+        const ltx_weight* w = wm.find("conv_out.conv.weight"); const ltx_weight* b = wm.find("conv_out.conv.bias");
+        if (!w) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight 'conv_out.conv.weight'");
+        if (!b) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight 'conv_out.conv.bias'");
+        if (ltx_numel(w) != (int64_t)e->nmom * cur * 27) LTX_FAIL(LTX_ERR_ARG, "weight 'conv_out.conv.weight': wrong size");
+        if (ltx_numel(b) != e->nmom) LTX_FAIL(LTX_ERR_ARG, "weight 'conv_out.conv.bias': wrong size");
+        const size_t wsz = ltx_dt_size(w->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32), bsz = ltx_dt_size(b->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32);
+        const size_t wrow = (size_t)cur * 27 * wsz;
+        DevBuf pw, pb;
+        int rc = pw.ensure((size_t)e->nmom_pad * wrow); if (rc == LTX_OK) rc = pb.ensure((size_t)e->nmom_pad * bsz);
+        if (rc == LTX_OK) {
+            hipError_t he = hipMemset(pw.p, 0, (size_t)e->nmom_pad * wrow);
+            if (he == hipSuccess) he = hipMemset(pb.p, 0, (size_t)e->nmom_pad * bsz);
+            if (he == hipSuccess) he = hipMemcpy(pw.p, w->data, (size_t)e->nmom * wrow, w->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+            if (he == hipSuccess) he = hipMemcpy(pb.p, b->data, (size_t)e->nmom * bsz, b->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+            if (he != hipSuccess) { ltx_set_error(std::string("conv_out padding: ") + hipGetErrorString(he)); rc = LTX_ERR_HIP; }
+        }
+        if (rc == LTX_OK) {
+            ltx_weight pad[2] = {*w, *b};
+            pad[0].name = "conv_out.conv.weight"; pad[0].data = pw.p; pad[0].on_device = 1; pad[0].shape[0] = e->nmom_pad;
+            pad[1].name = "conv_out.conv.bias"; pad[1].data = pb.p; pad[1].on_device = 1; pad[1].shape[0] = e->nmom_pad;
+            WeightMap wp(pad, 2);
+            rc = load_conv(e->dtype, e->owned, wp, "conv_out", cur, e->nmom_pad, PERM_NONE, 0, &e->conv_out);
+        }
+        pw.release(); pb.release();
+        if (rc != LTX_OK) return rc;
+    }
+    return LTX_OK;
+}
+
+int enc_resnet(ltx_vae_encoder* e, const ResnetW& r, int ch, const Dims& d, hipStream_t s) {
+    const int dt = e->dtype;
+    RowNormArgs rn; rn.x = e->X.p; rn.y = e->N.p; rn.rows = d.vox(); rn.D = ch; rn.ldx = ch; rn.ldy = ch;
+    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W; rn.mod_stride = 0;
+    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+    if (fuse_norm2(dt, 2, r.c1, d, ch)) {          // norm2 + SiLU in conv1's epilogue, no modulation tables (PostNorm scale / shift null)
+        PostNorm pn; pn.on = 1; pn.eps = rn.eps; pn.act = 1; pn.mod_stride = 0;
+        LTX_TRY(conv3d(dt, 2, r.c1, e->N.p, e->C.p, d, EPI_BIAS, nullptr, 0, s, &pn));
+        return conv3d(dt, 2, r.c2, e->C.p, e->X.p, d, EPI_RESID, e->X.p, 0, s);
+    }
+    LTX_TRY(conv3d(dt, 2, r.c1, e->N.p, e->C.p, d, EPI_BIAS, nullptr, 0, s));
+    rn.x = e->C.p;
+    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+    return conv3d(dt, 2, r.c2, e->N.p, e->X.p, d, EPI_RESID, e->X.p, 0, s);
+}
+
+// latent dims of an encoder call on nt x nh x nw samples, or LTX_ERR_ARG where the reference's reshapes fail
+int enc_out_dims(const ltx_vae_encoder* e, int nt, int nh, int nw, int* ot, int* oh, int* ow) {
+    const ltx_vae_encoder_config& c = e->cfg;
+    if (nt < 1 || nh < 1 || nw < 1 || nt % c.patch_size_t != 0 || nh % c.patch_size != 0 || nw % c.patch_size != 0)
+        LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes");                                     // vae.rs:1431-1433
+    int t = nt / c.patch_size_t, h = nh / c.patch_size, w = nw / c.patch_size;
+    for (const DownBlockW& d : e->downs) {
+        if (!d.has_down) continue;
+        if ((t + d.st - 1) % d.st != 0 || h % d.sh != 0 || w % d.sw != 0)
+            LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes (a downsampler cannot halve frames + 1, height or width evenly)");
+        t = (t + d.st - 1) / d.st; h /= d.sh; w /= d.sw;
+    }
+    *ot = t; *oh = h; *ow = w;
+    return LTX_OK;
+}
+
+// LtxVideoEncoder3d::forward (vae.rs:1446-1468) on a window of `video` [B,Cin,F,H,W]; moments f32 [B,L+1,t',h',w']
+int encoder_forward(ltx_vae_encoder* e, const void* video, int vdt, int B, int F, int H, int W,
+                    int t0, int nt, int h0, int nh, int w0, int nw, float* moments, hipStream_t s,
+                    float* mean_direct = nullptr, float* logvar_direct = nullptr) {
+    const ltx_vae_encoder_config& c = e->cfg;
+    const int dt = e->dtype; const size_t esz = ltx_dt_size(dt);
+    int ot, oh, ow;
+    LTX_TRY(enc_out_dims(e, nt, nh, nw, &ot, &oh, &ow));
+    Dims d{B, nt / c.patch_size_t, nh / c.patch_size, nw / c.patch_size};
+    int64_t max_elems = d.vox() * std::max(e->cin_p, c.block_out_channels[0]);
+    {
+        Dims q = d;
+        for (const DownBlockW& b : e->downs) {
+            max_elems = std::max(max_elems, q.vox() * std::max(b.ch, b.cc));
+            if (b.has_down) { q.T = (q.T + b.st - 1) / b.st; q.H /= b.sh; q.W /= b.sw; }
+            max_elems = std::max(max_elems, q.vox() * b.cout);
+        }
+        max_elems = std::max(max_elems, q.vox() * std::max(e->mid_ch, e->nmom_pad));
+    }
+    if (max_elems * (int64_t)esz >= 2147483648LL - (1 << 20) && B == 1)
+        LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_vae_encode: one sample's largest activation passes 2 GiB; use the tiled encode");
+    LTX_TRY(e->X.ensure(max_elems * esz)); LTX_TRY(e->Y.ensure(max_elems * esz));
+    LTX_TRY(e->N.ensure(max_elems * esz)); LTX_TRY(e->C.ensure(max_elems * esz));
+    {
+        const int64_t n = (int64_t)B * c.in_channels * nt * nh * nw;
+#define LTX_PATCHIFY(TI, TO) hipLaunchKernelGGL((patchify_kernel<TI, TO>), enc_grid(n), dim3(256), 0, s, (const TI*)video, (TO*)e->Y.p, \
+                                                B, c.in_channels, F, H, W, t0, h0, w0, nt, nh, nw, c.patch_size)
+        if (vdt == LTX_DT_BF16) { if (dt == LTX_DT_BF16) LTX_PATCHIFY(bf16_t, bf16_t); else LTX_PATCHIFY(bf16_t, float); }
+        else { if (dt == LTX_DT_BF16) LTX_PATCHIFY(float, bf16_t); else LTX_PATCHIFY(float, float); }
+#undef LTX_PATCHIFY
+        LTX_CHECK_LAUNCH();
+    }
+    LTX_TRY(conv3d(dt, 2, e->conv_in, e->Y.p, e->X.p, d, EPI_BIAS, nullptr, 0, s));
+    for (const DownBlockW& b : e->downs) {
+        for (const ResnetW& r : b.res) LTX_TRY(enc_resnet(e, r, b.ch, d, s));
+        if (!b.has_down) continue;
+        LTX_TRY(conv3d(dt, 2, b.down, e->X.p, e->Y.p, d, EPI_S2D, e->X.p, 0, s));      // conv + scatter + grouped-mean residual in the epilogue
+        std::swap(e->X, e->Y);
+        d.T = (d.T + b.st - 1) / b.st; d.H /= b.sh; d.W /= b.sw;
+    }
+    for (const ResnetW& r : e->mid) LTX_TRY(enc_resnet(e, r, e->mid_ch, d, s));
+    RowNormArgs rn; rn.x = e->X.p; rn.y = e->N.p; rn.rows = d.vox(); rn.D = e->mid_ch; rn.ldx = e->mid_ch; rn.ldy = e->mid_ch;
+    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W;
+    LTX_TRY(ltx_launch_rownorm(rn, dt, s));                                                               // norm_out + SiLU (vae.rs:1455-1459)
+    LTX_TRY(conv3d(dt, 2, e->conv_out, e->N.p, e->C.p, d, EPI_BIAS, nullptr, 0, s));
+    const int64_t S = (int64_t)d.T * d.H * d.W, n = (int64_t)B * e->nmom * S;
+    if (mean_direct) {
+        const int L = c.latent_channels;
+        if (dt == LTX_DT_BF16) hipLaunchKernelGGL(moments_out_kernel<bf16_t>, enc_grid((int64_t)B * L * S), dim3(256), 0, s, (const bf16_t*)e->C.p, mean_direct, logvar_direct, B, S, e->nmom_pad, L);
+        else hipLaunchKernelGGL(moments_out_kernel<float>, enc_grid((int64_t)B * L * S), dim3(256), 0, s, (const float*)e->C.p, mean_direct, logvar_direct, B, S, e->nmom_pad, L);
+        LTX_CHECK_LAUNCH();
+        return LTX_OK;
+    }
+    if (dt == LTX_DT_BF16) hipLaunchKernelGGL(moments_kernel<bf16_t>, enc_grid(n), dim3(256), 0, s, (const bf16_t*)e->C.p, moments, B, S, e->nmom_pad, e->nmom);
+    else hipLaunchKernelGGL(moments_kernel<float>, enc_grid(n), dim3(256), 0, s, (const float*)e->C.p, moments, B, S, e->nmom_pad, e->nmom);
+    LTX_CHECK_LAUNCH();
+    return LTX_OK;
+}
+
+// tiled_encode (vae.rs:2158-2223) of the frames [t0, t0+nt) of `video`: tiles in sample space, blends on the f32 moments
+int tiled_encode(ltx_vae_encoder* e, const void* video, int vdt, int B, int F, int H, int W, int t0, int nt,
+                 const ltx_tiling& tl, float* out, int oT, int oH, int oW, size_t& pool_used, hipStream_t s) {
+    const int r = e->cfg.spatial_compression_ratio;
+    const int BC = B * e->nmom;
+    if (tl.tile_sample_stride_height < r || tl.tile_sample_stride_width < r) LTX_FAIL(LTX_ERR_ARG, "tiling: stride must be >= one latent");
+    const int ls_h = tl.tile_sample_stride_height / r, ls_w = tl.tile_sample_stride_width / r;
+    const int blend_h = std::max(tl.tile_sample_min_height / r - ls_h, 0), blend_w = std::max(tl.tile_sample_min_width / r - ls_w, 0);
+    auto take = [&](size_t bytes, DevBuf** b) -> int {
+        if (pool_used >= e->tilebufs.size()) e->tilebufs.emplace_back();
+        *b = &e->tilebufs[pool_used++];
+        return (*b)->ensure(bytes);
+    };
+    std::vector<Tile> prev, cur;
+    int oy = 0;
+    for (int i = 0; i < H; i += tl.tile_sample_stride_height) {
+        cur.clear();
+        int ox = 0, row_h = 0;
+        for (int j = 0; j < W; j += tl.tile_sample_stride_width) {
+            const int h1 = std::min(i + tl.tile_sample_min_height, H), w1 = std::min(j + tl.tile_sample_min_width, W);
+            Tile t;
+            LTX_TRY(enc_out_dims(e, nt, h1 - i, w1 - j, &t.t, &t.h, &t.w));
+            DevBuf* tb = nullptr;
+            LTX_TRY(take((size_t)BC * t.t * t.h * t.w * sizeof(float), &tb));
+            t.p = tb->as<float>();
+            LTX_TRY(encoder_forward(e, video, vdt, B, F, H, W, t0, nt, i, h1 - i, j, w1 - j, t.p, s));
+            const size_t ci = cur.size();
+            if (!prev.empty()) {        // blend_v with the (already blended) tile above
+                BlendArgs ba; ba.a = prev[ci].p; ba.b = t.p; ba.dst = t.p; ba.BC = BC;
+                ba.at = prev[ci].t; ba.ah = prev[ci].h; ba.aw = prev[ci].w; ba.a_len = prev[ci].h;
+                ba.bt = ba.dt = t.t; ba.bh = ba.dh = t.h; ba.bw = ba.dw = t.w;
+                ba.dim = 3; ba.blend = std::min(blend_h, std::min(prev[ci].h, t.h));
+                ba.et = t.t; ba.eh = ba.blend; ba.ew = std::min(t.w, prev[ci].w);
+                LTX_TRY(ltx_launch_blend(ba, s));
+            }
+            if (ci > 0) {               // blend_h with the (already blended) tile to the left
+                BlendArgs ba; ba.a = cur[ci - 1].p; ba.b = t.p; ba.dst = t.p; ba.BC = BC;
+                ba.at = cur[ci - 1].t; ba.ah = cur[ci - 1].h; ba.aw = cur[ci - 1].w; ba.a_len = cur[ci - 1].w;
+                ba.bt = ba.dt = t.t; ba.bh = ba.dh = t.h; ba.bw = ba.dw = t.w;
+                ba.dim = 4; ba.blend = std::min(blend_w, std::min(cur[ci - 1].w, t.w));
+                ba.et = t.t; ba.eh = std::min(t.h, cur[ci - 1].h); ba.ew = ba.blend;
+                LTX_TRY(ltx_launch_blend(ba, s));
+            }
+            cur.push_back(t);
+            const int hs = std::min(ls_h, t.h), ws = std::min(ls_w, t.w);
+            const int ch = std::min(hs, oH - oy), cw_ = std::min(ws, oW - ox);
+            if (t.t != oT) LTX_FAIL(LTX_ERR_ARG, "tiled encode: tile frame count mismatch");
+            if (ch > 0 && cw_ > 0)
+                LTX_TRY(ltx_launch_copy_window(t.p, t.t, t.h, t.w, out, oT, oH, oW, BC, oT, ch, cw_, 0, oy, ox, s));
+            ox += ws; row_h = hs;
+        }
+        oy += row_h;
+        prev = cur;
+    }
+    return LTX_OK;
+}
+
+// encode_z (vae.rs:2017-2035) -> e->mom [B,L+1,F',H/r,W/r]; *oT/oH/oW = latent dims
+int encode_moments(ltx_vae_encoder* e, const void* video, int vdt, int B, int F, int H, int W, const ltx_tiling* tl,
+                   const ltx_encode_tiling* et, int* oT, int* oH, int* oW, hipStream_t s,
+                   float* mean_direct = nullptr, float* logvar_direct = nullptr, bool* direct_done = nullptr) {
+    const int r = e->cfg.spatial_compression_ratio, tr = e->cfg.temporal_compression_ratio;
+    const int BC = B * e->nmom;
+    const bool framewise = tl && et && et->use_framewise_encoding && F > tl->tile_sample_min_num_frames;
+    const bool spatial = tl && tl->use_tiling && (H > tl->tile_sample_min_height || W > tl->tile_sample_min_width);
+    if (!framewise && !spatial) {
+        LTX_TRY(enc_out_dims(e, F, H, W, oT, oH, oW));
+        if (mean_direct) {       // one encoder call: conv_out's rows go straight to the caller's mean / logvar
+            if (direct_done) *direct_done = true;
+            return encoder_forward(e, video, vdt, B, F, H, W, 0, F, 0, H, 0, W, nullptr, s, mean_direct, logvar_direct);
+        }
+        LTX_TRY(e->mom.ensure((size_t)BC * *oT * *oH * *oW * sizeof(float)));
+        return encoder_forward(e, video, vdt, B, F, H, W, 0, F, 0, H, 0, W, e->mom.as<float>(), s);
+    }
+    if (r < 1 || tr < 1 || H % r != 0 || W % r != 0) LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes (tiled encode: height and width must be multiples of the compression ratio)");
+    *oH = H / r; *oW = W / r; *oT = (F - 1) / tr + 1;                                             // vae.rs:2162-2163, 2298
+    LTX_TRY(e->mom.ensure((size_t)BC * *oT * *oH * *oW * sizeof(float)));
+    size_t pool_used = 0;
+    if (!framewise) {
+        int t, h, w; LTX_TRY(enc_out_dims(e, F, std::min(H, tl->tile_sample_min_height), std::min(W, tl->tile_sample_min_width), &t, &h, &w));
+        if (t != *oT) LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes (frame count)");
+        return tiled_encode(e, video, vdt, B, F, H, W, 0, F, *tl, e->mom.as<float>(), *oT, *oH, *oW, pool_used, s);
+    }
+    // temporal_tiled_encode (vae.rs:2294-2357)
+    if (tl->tile_sample_stride_num_frames < tr) LTX_FAIL(LTX_ERR_ARG, "tiling: temporal stride must be >= one latent frame");
+    const int ls_t = tl->tile_sample_stride_num_frames / tr;
+    const int blend_t = std::max(tl->tile_sample_min_num_frames / tr - ls_t, 0);
+    float* out = e->mom.as<float>();
+    const float* prev_p = nullptr; int prev_len = 0, prev_phys = 0;
+    int ot = 0, li = 0;
+    for (int i = 0; i < F; i += tl->tile_sample_stride_num_frames, ++li) {
+        const int t1 = std::min(i + tl->tile_sample_min_num_frames + 1, F), nf = t1 - i;
+        const bool sp = tl->use_tiling && (H > tl->tile_sample_min_height || W > tl->tile_sample_min_width);
+        int tt, th, tw;
+        LTX_TRY(enc_out_dims(e, nf, sp ? std::min(H, tl->tile_sample_min_height) : H, sp ? std::min(W, tl->tile_sample_min_width) : W, &tt, &th, &tw));
+        if (!sp && (th != *oH || tw != *oW)) LTX_FAIL(LTX_ERR_ARG, "temporal tiled encode: tile plane mismatch");
+        DevBuf& cur = e->ttiles[li & 1];
+        LTX_TRY(cur.ensure((size_t)BC * tt * *oH * *oW * sizeof(float)));
+        size_t pu = 0;
+        if (sp) LTX_TRY(tiled_encode(e, video, vdt, B, F, H, W, i, nf, *tl, cur.as<float>(), tt, *oH, *oW, pu, s));
+        else LTX_TRY(encoder_forward(e, video, vdt, B, F, H, W, i, nf, 0, H, 0, W, cur.as<float>(), s));
+        // "if i == 0: tile = tile[:, :, 1:]" (vae.rs:2322-2327): the logical tile starts one frame into the buffer
+        const float* cp = cur.as<float>(); int len = tt;
+        if (li == 0) { cp += (size_t)*oH * *oW; len -= 1; }
+        const int keep = li > 0 ? std::min(ls_t, len) : std::min(ls_t + 1, len);
+        const int n = std::min(keep, *oT - ot);
+        if (n > 0) {
+            LTX_TRY(ltx_launch_copy_window(cp, tt, *oH, *oW, out, *oT, *oH, *oW, BC, n, *oH, *oW, ot, 0, 0, s));
+            if (li > 0) {           // blend_t against the RAW previous tile (row[idx - 1], vae.rs:2338-2342), straight into `out`
+                BlendArgs ba; ba.a = prev_p; ba.b = cp; ba.dst = out; ba.BC = BC;
+                ba.at = prev_phys; ba.ah = *oH; ba.aw = *oW; ba.a_len = prev_len;
+                ba.bt = tt; ba.bh = *oH; ba.bw = *oW; ba.dt = *oT; ba.dh = *oH; ba.dw = *oW; ba.ot = ot;
+                ba.dim = 2; ba.blend = std::min(blend_t, std::min(prev_len, len));
+                ba.et = std::min(ba.blend, n); ba.eh = *oH; ba.ew = *oW;
+                if (ba.blend > 0) LTX_TRY(ltx_launch_blend(ba, s));
+            }
+        }
+        ot += std::max(keep, 0);
+        prev_p = cp; prev_len = len; prev_phys = tt;
+    }
+    if (ot < *oT) LTX_FAIL(LTX_ERR_ARG, "temporal tiled encode: the tiles do not cover the latent frames (frame count / tile parameters)");
+    return LTX_OK;
+}
+
+int check_encode_args(const char* fn, const ltx_vae_encoder* e, const void* video, int B, int F, int H, int W) {
+    if (!e) LTX_FAIL(LTX_ERR_ARG, std::string(fn) + ": null handle");
+    if (!video) LTX_FAIL(LTX_ERR_ARG, std::string(fn) + ": null tensor");
+    if (B < 1 || F < 1 || H < 1 || W < 1) LTX_FAIL(LTX_ERR_ARG, std::string(fn) + ": bad shape");
+    return LTX_OK;
+}
+
+}  // namespace
+
+extern "C" void ltx_vae_encoder_config_default(ltx_vae_encoder_config* c) {      // vae.rs:68-103
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->in_channels = 3; c->latent_channels = 128; c->n_blocks = 5;
+    const int boc[5] = {128, 256, 512, 1024, 2048}, lpb[5] = {4, 6, 6, 2, 2};
+    const int dst[4] = {LTX_DOWN_SPATIAL, LTX_DOWN_TEMPORAL, LTX_DOWN_SPATIOTEMPORAL, LTX_DOWN_SPATIOTEMPORAL};
+    for (int i = 0; i < 5; ++i) { c->block_out_channels[i] = boc[i]; c->layers_per_block[i] = lpb[i]; }
+    for (int i = 0; i < 4; ++i) { c->spatiotemporal_scaling[i] = 1; c->downsample_types[i] = dst[i]; }
+    c->patch_size = 4; c->patch_size_t = 1; c->is_causal = 1;
+    c->spatial_compression_ratio = 32; c->temporal_compression_ratio = 8;
+}
+extern "C" int ltx_vae_encoder_config_from_preset(const ltx_preset* p, ltx_vae_encoder_config* c) {
+    if (!p || !c) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_config_from_preset: null argument");
+    ltx_vae_encoder_config_default(c);
+    int n = 0;
+    while (n < 5 && p->vae_encoder_block_out_channels[n] > 0) ++n;
+    if (n < 2) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_config_from_preset: the preset carries no encoder channel list");
+    c->n_blocks = n;
+    for (int i = 0; i < 5; ++i) { c->block_out_channels[i] = i < n ? p->vae_encoder_block_out_channels[i] : 0; c->layers_per_block[i] = i < n ? p->vae_encoder_layers_per_block[i] : 0; }
+    c->latent_channels = p->vae.latent_channels; c->patch_size = p->vae.patch_size; c->patch_size_t = p->vae.patch_size_t;
+    c->spatial_compression_ratio = p->vae.spatial_compression_ratio; c->temporal_compression_ratio = p->vae.temporal_compression_ratio;
+    return LTX_OK;
+}
+
+extern "C" int ltx_vae_encoder_create(const ltx_vae_encoder_config* cfg, const ltx_weight* weights, size_t n_weights,
+                                      ltx_dtype model_dtype, int device, ltx_vae_encoder** out) {
+    if (!cfg || !weights || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_create: null argument");
+    *out = nullptr;
+    if (cfg->n_blocks < 2 || cfg->n_blocks > 5) LTX_FAIL(LTX_ERR_ARG, "encoder n_blocks must be 2..5");
+    if (cfg->patch_size < 1 || cfg->patch_size_t != 1) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder: only patch_size_t = 1 is supported");
+    if (!cfg->is_causal) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder: only the causal encoder (is_causal = 1) is supported");
+    if (cfg->in_channels < 1 || cfg->latent_channels < 1) LTX_FAIL(LTX_ERR_ARG, "encoder: bad channel counts");
+    if ((cfg->in_channels * cfg->patch_size * cfg->patch_size) % 8 != 0) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder: patchified channels must be a multiple of 8");
+    for (int i = 0; i < cfg->n_blocks; ++i) {
+        if (cfg->block_out_channels[i] < 8 || cfg->block_out_channels[i] % 8 != 0) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder block_out_channels must be multiples of 8");
+        if (cfg->layers_per_block[i] < 0) LTX_FAIL(LTX_ERR_ARG, "encoder layers_per_block must be >= 0");
+    }
+    for (int i = 0; i < cfg->n_blocks - 1; ++i) {
+        if (!cfg->spatiotemporal_scaling[i]) continue;
+        if (cfg->downsample_types[i] == LTX_DOWN_CONV)
+            LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder downsample_type 'conv' (strided conv + channel-changing conv_out resnet, vae.rs:888-934) is not implemented: no preset uses it");
+        if (cfg->downsample_types[i] < 0 || cfg->downsample_types[i] > LTX_DOWN_SPATIOTEMPORAL) LTX_FAIL(LTX_ERR_ARG, "encoder: bad downsample_type");
+    }
+    HIP_TRY(hipSetDevice(device));
+    ltx_vae_encoder* e = new ltx_vae_encoder();
+    e->cfg = *cfg; e->dtype = model_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32; e->device = device;
+    const int rc = enc_build(e, weights, n_weights);
+    if (rc != LTX_OK) { e->free_all(); delete e; return rc; }
+    *out = e;
+    return LTX_OK;
+}
+extern "C" void ltx_vae_encoder_destroy(ltx_vae_encoder* e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device); (void)hipDeviceSynchronize();
+    e->free_all(); delete e;
+}
+extern "C" int ltx_vae_encoder_get_config(const ltx_vae_encoder* e, ltx_vae_encoder_config* out) {
+    if (!e || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_get_config: null argument");
+    *out = e->cfg; return LTX_OK;
+}
+
+extern "C" int ltx_vae_encode(ltx_vae_encoder* e, const void* video, ltx_dtype video_dtype, int B, int F, int H, int W,
+                              const ltx_tiling* tiling, const ltx_encode_tiling* enc_tiling,
+                              float* mean_out, float* logvar_out, ltx_stream stream) {
+    LTX_TRY(check_encode_args("ltx_vae_encode", e, video, B, F, H, W));
+    if (!mean_out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode: null tensor");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    int oT, oH, oW;
+    bool direct = false;
+    LTX_TRY(encode_moments(e, video, video_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, F, H, W, tiling, enc_tiling, &oT, &oH, &oW, s,
+                           mean_out, logvar_out, &direct));
+    if (direct) return LTX_OK;
+    const int L = e->cfg.latent_channels; const int64_t S = (int64_t)oT * oH * oW;
+    hipLaunchKernelGGL(moments_split_kernel, enc_grid((int64_t)B * L * S), dim3(256), 0, s, e->mom.as<float>(), mean_out, logvar_out, B, L, S);
+    LTX_CHECK_LAUNCH();
+    return LTX_OK;
+}
+
+extern "C" int ltx_vae_posterior_sample(const float* mean, const float* logvar, const float* eps, size_t n, float* out, ltx_stream stream) {
+    if (!mean || !logvar || !eps || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_posterior_sample: null tensor");
+    if (n == 0) return LTX_OK;
+    hipLaunchKernelGGL(posterior_sample_kernel, enc_grid((int64_t)n), dim3(256), 0, (hipStream_t)stream, mean, logvar, eps, out, n);
+    LTX_CHECK_LAUNCH();
+    return LTX_OK;
+}
+
+extern "C" int ltx_vae_encode_tokens(ltx_vae_encoder* e, const ltx_vae* vae, const void* video, ltx_dtype video_dtype,
+                                     int B, int F, int H, int W, const ltx_tiling* tiling, const ltx_encode_tiling* enc_tiling,
+                                     const float* eps, float* tokens_out, ltx_stream stream) {
+    LTX_TRY(check_encode_args("ltx_vae_encode_tokens", e, video, B, F, H, W));
+    if (!vae || !tokens_out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode_tokens: null argument");
+    if (vae->cfg.latent_channels != e->cfg.latent_channels) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode_tokens: encoder and VAE disagree on latent_channels");
+    if (vae->device != e->device) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode_tokens: encoder and VAE live on different devices");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    int oT, oH, oW;
+    LTX_TRY(encode_moments(e, video, video_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, F, H, W, tiling, enc_tiling, &oT, &oH, &oW, s));
+    const int L = e->cfg.latent_channels; const int64_t S = (int64_t)oT * oH * oW;
+    hipLaunchKernelGGL(moments_tokens_kernel, enc_grid((int64_t)B * L * S), dim3(256), 0, s, e->mom.as<float>(), eps, vae->mean, vae->std_,
+                       vae->cfg.scaling_factor, tokens_out, B, L, S);
+    LTX_CHECK_LAUNCH();
+    return LTX_OK;
+}
+
+extern "C" int ltx_vae_encoder_warmup(ltx_vae_encoder* e, int B, int F, int H, int W, const ltx_tiling* tiling,
+                                      const ltx_encode_tiling* enc_tiling, ltx_stream stream) {
+    if (!e) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_warmup: null handle");
+    if (B < 1 || F < 1 || H < 1 || W < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_warmup: bad shape");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nb = (size_t)B * e->cfg.in_channels * F * H * W * ltx_dt_size(e->dtype);
+    LTX_TRY(e->scratch.ensure(nb));
+    HIP_TRY(hipMemsetAsync(e->scratch.p, 0, nb, s));
+    int oT, oH, oW;
+    const int rc = encode_moments(e, e->scratch.p, e->dtype, B, F, H, W, tiling, enc_tiling, &oT, &oH, &oW, s);
+    HIP_TRY(hipStreamSynchronize(s));
+    e->scratch.release();
+    return rc;
+}
+
+/* LtxVideoDownsampler3d::forward (vae.rs:534-581) alone: x [B,T,H,W,Cin] channels-last -> y [B,(T+st-1)/st,H/sh,W/sw,Cout] */
+extern "C" int ltx_op_downsample3d(const void* x, const void* w, const void* bias, int wdtype, void* y,
+                                   int B, int T, int H, int W, int Cin, int Cout, int down_type, int dtype, ltx_stream stream) {
+    if (!x || !w || !bias || !y) LTX_FAIL(LTX_ERR_ARG, "ltx_op_downsample3d: null tensor");
+    if (down_type == LTX_DOWN_CONV) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_op_downsample3d: downsample_type 'conv' is not implemented");
+    if (down_type < 0 || down_type > LTX_DOWN_SPATIOTEMPORAL) LTX_FAIL(LTX_ERR_ARG, "ltx_op_downsample3d: bad downsample_type");
+    int st, sh, sw; down_stride(down_type, &st, &sh, &sw);
+    const int nsub = st * sh * sw;
+    if (B < 1 || T < 1 || H < 1 || W < 1 || Cin < 8 || Cin % 8 != 0 || Cout < nsub || Cout % nsub != 0 || (Cout / nsub) % 4 != 0 || (Cin * nsub) % Cout != 0)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_op_downsample3d: bad shape");
+    if ((T + st - 1) % st != 0 || H % sh != 0 || W % sw != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_downsample3d: frames + 1, height and width must divide by the stride");
+    const int dt = dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32; const size_t esz = ltx_dt_size(dt);
+    hipStream_t s = (hipStream_t)stream;
+    const int cc = Cout / nsub;
+    ConvW cw; cw.cin = Cin; cw.cout = cc; cw.st = st; cw.sh = sh; cw.sw = sw; cw.group = Cin * nsub / Cout;
+    DevBuf wb, bb;
+    int rc = wb.ensure((size_t)cc * Cin * 27 * esz); if (rc == LTX_OK) rc = bb.ensure((size_t)cc * esz + 16);
+    const int wdt = wdtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
+    if (rc == LTX_OK) rc = ltx_pack_conv(w, wdt, wb.p, dt, cc, Cin, 27, PERM_NONE, 0, s);
+    if (rc == LTX_OK) rc = ltx_pack_conv(bias, wdt, bb.p, dt, cc, 1, 1, PERM_NONE, 0, s);
+    cw.w = wb.p; cw.b = bb.p;
+    Dims d{B, T, H, W};
+    if (rc == LTX_OK) rc = conv3d(dt, 2, cw, x, y, d, EPI_S2D, x, 0, s);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == LTX_OK) { ltx_set_error("ltx_op_downsample3d: stream failed"); rc = LTX_ERR_HIP; }
+    wb.release(); bb.release();
+    return rc;
 }

@@ -487,4 +487,11 @@ extern "C" int ltx_vae_create_from_files(const ltx_vae_config* cfg, const char* 
     LTX_TRY(gather(path, unified, 1, &L));
     return ltx_vae_create(&c, L.weights.data(), L.weights.size(), model_dtype, device, out);
 }
+extern "C" int ltx_vae_encoder_create_from_files(const ltx_vae_encoder_config* cfg, const char* path, int unified,
+                                                 ltx_dtype model_dtype, int device, ltx_vae_encoder** out) {
+    if (!cfg || !path) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_create_from_files: null argument");
+    Loaded L;
+    LTX_TRY(gather(path, unified, 1, &L));
+    return ltx_vae_encoder_create(cfg, L.weights.data(), L.weights.size(), model_dtype, device, out);
+}
 #endif

@@ -137,6 +137,7 @@ _SIGS = {
     "ltx_op_upsample3d": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_conv_out_unpatchify": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_blend": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ltx_op_downsample3d": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_gemm_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i],
     # include/ltxhip_t5.h
     "ltx_t5_config_default": [_vp], "ltx_t5_create": [_vp, _vp, _sz, _i, _i, _vp], "ltx_t5_destroy": [_vp],
@@ -161,7 +162,7 @@ _SIGS = {
     "ltx_safetensors_tensor": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "ltx_weights_resolve": [C.c_char_p, C.c_char_p, _sz, _vp],
     "ltx_dit_create_from_files": [_vp, C.c_char_p, _i, _i, _i, _vp], "ltx_vae_create_from_files": [_vp, C.c_char_p, _i, _i, _i, _vp],
-    "ltx_vae_config_from_json": [C.c_char_p, _vp],
+    "ltx_vae_config_from_json": [C.c_char_p, _vp], "ltx_vae_encoder_create_from_files": [_vp, C.c_char_p, _i, _i, _i, _vp],
     # ltxhip_team.h: RCCL behind the C ABI (dlopen'ed on first use)
     "ltx_team_unique_id": [_vp], "ltx_team_create": [_vp, _i, _i, _i, _vp], "ltx_team_destroy": [_vp], "ltx_team_size": [_vp], "ltx_team_rank": [_vp],
     "ltx_team_allgather_f32": [_vp, _vp, _vp, _sz, _vp], "ltx_team_exchange_f32": [_vp, _vp, _sz, _i, _vp, _sz, _i, _vp],
@@ -183,6 +184,34 @@ lib.ltx_safetensors_close.restype = None
 lib.ltx_safetensors_count.restype = C.c_size_t
 lib.ltx_gguf_close.restype = None
 lib.ltx_gguf_count.restype = C.c_size_t
+
+
+class VaeEncoderConfigC(C.Structure):            # ltx_vae_encoder_config (include/ltxhip_encoder.h)
+    _fields_ = [("in_channels", C.c_int), ("latent_channels", C.c_int), ("n_blocks", C.c_int),
+                ("block_out_channels", C.c_int * 5), ("layers_per_block", C.c_int * 5),
+                ("spatiotemporal_scaling", C.c_int * 4), ("downsample_types", C.c_int * 4),
+                ("patch_size", C.c_int), ("patch_size_t", C.c_int), ("is_causal", C.c_int),
+                ("spatial_compression_ratio", C.c_int), ("temporal_compression_ratio", C.c_int)]
+
+
+class EncodeTilingC(C.Structure):                # ltx_encode_tiling
+    _fields_ = [("use_framewise_encoding", C.c_int)]
+
+
+# include/ltxhip_encoder.h (kept apart from _SIGS: EXPORTED_SYMBOLS lists the headers that existed before it)
+_ENC_SIGS = {
+    "ltx_vae_encoder_config_default": [_vp], "ltx_vae_encoder_config_from_preset": [_vp, _vp],
+    "ltx_vae_encoder_create": [_vp, _vp, _sz, _i, _i, _vp], "ltx_vae_encoder_destroy": [_vp], "ltx_vae_encoder_get_config": [_vp, _vp],
+    "ltx_vae_encode": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ltx_vae_posterior_sample": [_vp, _vp, _vp, _sz, _vp, _vp],
+    "ltx_vae_encode_tokens": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ltx_vae_encoder_warmup": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
+}
+ENCODER_SYMBOLS = sorted(_ENC_SIGS)
+for _name, _sig in _ENC_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = None if _name in ("ltx_vae_encoder_config_default", "ltx_vae_encoder_destroy") else C.c_int
 
 
 def _dt(t: torch.dtype) -> int:
@@ -455,8 +484,169 @@ class AutoencoderKLLtxVideoConfig:               # vae.rs:32-103 (decoder side)
     resnet_eps: float = 1e-6                                                    # vae.rs:83 (norm3 only: unused by the decoder)
 
 
+DOWNSAMPLE_TYPES = {"conv": 0, "spatial": 1, "temporal": 2, "spatiotemporal": 3}      # DownsampleType::parse, vae.rs:477-485
+
+
+@dataclass
+class AutoencoderKLLtxVideoEncoderConfig:        # vae.rs:32-103 (encoder side)
+    in_channels: int = 3
+    latent_channels: int = 128
+    block_out_channels: Tuple[int, ...] = (128, 256, 512, 1024, 2048)
+    layers_per_block: Tuple[int, ...] = (4, 6, 6, 2, 2)
+    spatiotemporal_scaling: Tuple[bool, ...] = (True, True, True, True)
+    downsample_types: Tuple[str, ...] = ("spatial", "temporal", "spatiotemporal", "spatiotemporal")
+    patch_size: int = 4
+    patch_size_t: int = 1
+    is_causal: bool = True
+    spatial_compression_ratio: int = 32
+    temporal_compression_ratio: int = 8
+
+    def to_c(self) -> "VaeEncoderConfigC":
+        c = VaeEncoderConfigC()
+        c.in_channels, c.latent_channels, c.n_blocks = self.in_channels, self.latent_channels, len(self.block_out_channels)
+        for i, x in enumerate(self.block_out_channels[:5]): c.block_out_channels[i] = x
+        for i, x in enumerate(self.layers_per_block[:5]): c.layers_per_block[i] = x
+        for i, x in enumerate(self.spatiotemporal_scaling[:4]): c.spatiotemporal_scaling[i] = int(x)
+        for i, x in enumerate(self.downsample_types[:4]): c.downsample_types[i] = DOWNSAMPLE_TYPES.get(str(x).lower(), 0) if not isinstance(x, int) else x
+        c.patch_size, c.patch_size_t, c.is_causal = self.patch_size, self.patch_size_t, int(self.is_causal)
+        c.spatial_compression_ratio, c.temporal_compression_ratio = self.spatial_compression_ratio, self.temporal_compression_ratio
+        return c
+
+
+class DiagonalGaussianDistribution:
+    """vae.rs:117-145 over the two tensors ltx_vae_encode writes; sample() takes the noise (the reference draws it from the device RNG)."""
+
+    def __init__(self, mean: torch.Tensor, logvar: torch.Tensor):
+        self.mean, self.logvar = mean, logvar
+
+    def mode(self) -> torch.Tensor:
+        return self.mean.clone()
+
+    def sample(self, eps: torch.Tensor) -> torch.Tensor:
+        e = _dev(eps, torch.float32)
+        _expect("eps", e, self.mean.shape)
+        out = torch.empty_like(self.mean)
+        _check(lib.ltx_vae_posterior_sample(_ptr(self.mean), _ptr(self.logvar), _ptr(e), C.c_size_t(self.mean.numel()), _ptr(out), _stream()))
+        return out
+
+
+class LtxVideoEncoder3d:
+    """LtxVideoEncoder3d (vae.rs:1316-1469) over ltx_vae_encoder_*; weight names relative to `encoder.` (or carrying that prefix)."""
+
+    def __init__(self, config: AutoencoderKLLtxVideoEncoderConfig, weights: Dict[str, torch.Tensor],
+                 dtype: torch.dtype = torch.bfloat16, device: int = 0):
+        self.config, self.dtype = config, dtype
+        c = config.to_c()
+        arr, keep = _make_weights(weights)
+        self._h = C.c_void_p()
+        _check(lib.ltx_vae_encoder_create(C.byref(c), arr, C.c_size_t(len(weights)), _dt(dtype), device, C.byref(self._h)))
+        del keep
+
+    @classmethod
+    def from_files(cls, config: AutoencoderKLLtxVideoEncoderConfig, path: str, unified: bool = False,
+                   dtype: torch.dtype = torch.bfloat16, device: int = 0) -> "LtxVideoEncoder3d":
+        self = cls.__new__(cls)
+        self.config, self.dtype = config, dtype
+        c = config.to_c()
+        self._h = C.c_void_p()
+        _check(lib.ltx_vae_encoder_create_from_files(C.byref(c), path.encode(), int(unified), _dt(dtype), device, C.byref(self._h)))
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            lib.ltx_vae_encoder_destroy(h)
+            self._h = None
+
+    def get_config(self) -> "VaeEncoderConfigC":
+        c = VaeEncoderConfigC()
+        _check(lib.ltx_vae_encoder_get_config(self._h, C.byref(c)))
+        return c
+
+    def latent_shape(self, B: int, F: int, H: int, W: int):
+        r, tr = self.config.spatial_compression_ratio, self.config.temporal_compression_ratio
+        return (B, self.config.latent_channels, (F - 1) // tr + 1, H // r, W // r)
+
+    def _video(self, x: torch.Tensor):
+        io = x.dtype if x.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        v = _dev(x, io)
+        if v.dim() != 5 or v.shape[1] != self.config.in_channels:
+            raise LtxError("video must be [B, in_channels, F, H, W]")
+        return v, io
+
+    def encode(self, x: torch.Tensor, tiling: Optional[TilingC] = None, framewise: bool = False, want_logvar: bool = True):
+        v, io = self._video(x)
+        B, _, F, H, W = v.shape
+        shp = self.latent_shape(B, F, H, W)
+        mean = torch.empty(shp, dtype=torch.float32, device=v.device)
+        logvar = torch.empty(shp, dtype=torch.float32, device=v.device) if want_logvar else None
+        et = EncodeTilingC(int(framewise))
+        _check(lib.ltx_vae_encode(self._h, _ptr(v), _dt(io), B, F, H, W, C.byref(tiling) if tiling else None, C.byref(et),
+                                  _ptr(mean), _ptr(logvar), _stream()))
+        return mean, logvar
+
+    def encode_tokens(self, vae: "AutoencoderKLLtxVideo", x: torch.Tensor, eps: Optional[torch.Tensor] = None,
+                      tiling: Optional[TilingC] = None, framewise: bool = False) -> torch.Tensor:
+        v, io = self._video(x)
+        B, _, F, H, W = v.shape
+        shp = self.latent_shape(B, F, H, W)
+        e = None
+        if eps is not None:
+            e = _dev(eps, torch.float32)
+            _expect("eps", e, shp)
+        out = torch.empty(B, shp[2] * shp[3] * shp[4], shp[1], dtype=torch.float32, device=v.device)
+        et = EncodeTilingC(int(framewise))
+        _check(lib.ltx_vae_encode_tokens(self._h, vae._h, _ptr(v), _dt(io), B, F, H, W, C.byref(tiling) if tiling else None, C.byref(et),
+                                         _ptr(e), _ptr(out), _stream()))
+        return out
+
+    def warmup(self, B: int, F: int, H: int, W: int, tiling: Optional[TilingC] = None, framewise: bool = False):
+        et = EncodeTilingC(int(framewise))
+        _check(lib.ltx_vae_encoder_warmup(self._h, B, F, H, W, C.byref(tiling) if tiling else None, C.byref(et), _stream()))
+
+
 class AutoencoderKLLtxVideo:
-    """impl VaeLtxVideo (t2v_pipeline.rs:91-103) over ltx_vae_*; tiling fields as vae.rs:1744-1758."""
+    """impl VaeLtxVideo (t2v_pipeline.rs:91-103) over ltx_vae_*; tiling fields as vae.rs:1744-1758.
+    The encode side (encode / forward, vae.rs:2070-2156) exists once load_encoder() has been given the `encoder.*` weights."""
+
+    encoder: Optional["LtxVideoEncoder3d"] = None
+    use_framewise_encoding = False
+
+    def load_encoder(self, config: "AutoencoderKLLtxVideoEncoderConfig", weights: Dict[str, torch.Tensor], device: int = 0) -> None:
+        self.encoder = LtxVideoEncoder3d(config, weights, self.dtype, device)
+
+    def _encoder(self) -> "LtxVideoEncoder3d":
+        if self.encoder is None:
+            raise LtxError("this AutoencoderKLLtxVideo has no encoder: call load_encoder(config, weights) first")
+        return self.encoder
+
+    def _encode_tiling(self) -> Optional[TilingC]:
+        if not (self.use_tiling or self.use_framewise_encoding):
+            return None
+        return TilingC(int(self.use_tiling), int(self.use_framewise_decoding), self.tile_sample_min_height,
+                       self.tile_sample_min_width, self.tile_sample_min_num_frames, self.tile_sample_stride_height,
+                       self.tile_sample_stride_width, self.tile_sample_stride_num_frames)
+
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        """AutoencoderKLLtxVideo::encode (vae.rs:2070-2099): (AutoencoderKLOutput-like dict or None, posterior)."""
+        mean, logvar = self._encoder().encode(x, self._encode_tiling(), self.use_framewise_encoding)
+        post = DiagonalGaussianDistribution(mean, logvar)
+        return ({"latent_dist": post} if return_dict else None), post
+
+    def encode_tokens(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """encode -> mode / sample(eps) -> normalize_latents -> pack_latents: the `latents` of LtxPipeline.call"""
+        return self._encoder().encode_tokens(self, x, eps, self._encode_tiling(), self.use_framewise_encoding)
+
+    def forward(self, sample: torch.Tensor, temb=None, sample_posterior: bool = False, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """AutoencoderKLLtxVideo::forward (vae.rs:2139-2156): encode, mode or sample, decode.  `eps` is the draw of sample()."""
+        _, post = self.encode(sample, True)
+        if sample_posterior:
+            if eps is None:
+                raise LtxError("forward(sample_posterior=True) needs eps (the library draws no noise of its own)")
+            z = post.sample(eps)
+        else:
+            z = post.mode()
+        return self.decode(z, temb)
 
     @staticmethod
     def _config_c(config: "AutoencoderKLLtxVideoConfig") -> "VaeConfigC":
@@ -1212,6 +1402,17 @@ class ops:
         y = torch.empty(B, 2 * T - 1, 2 * H, 2 * W, Cout // 8, dtype=x_cl.dtype, device=x_cl.device)
         _check(lib.ltx_op_upsample3d(_ptr(x_cl.contiguous()), _ptr(w.contiguous()), _ptr(bias.to(w.dtype).contiguous()), _dt(w.dtype), _ptr(y),
                                      B, T, H, W, Cin, Cout, int(causal), int(residual), _dt(x_cl.dtype), _stream()))
+        return y
+
+    @staticmethod
+    def downsample3d(x_cl, w, bias, down_type):
+        """LtxVideoDownsampler3d (vae.rs:499-582) on a channels-last tensor; down_type 1 spatial, 2 temporal, 3 spatiotemporal; Cout = out channels"""
+        B, T, H, W, Cin = x_cl.shape
+        st, sh, sw = {1: (1, 2, 2), 2: (2, 1, 1), 3: (2, 2, 2)}.get(down_type, (2, 2, 2))
+        Cout = w.shape[0] * st * sh * sw
+        y = torch.empty(B, (T + st - 1) // st, H // sh, W // sw, Cout, dtype=x_cl.dtype, device=x_cl.device)
+        _check(lib.ltx_op_downsample3d(_ptr(x_cl.contiguous()), _ptr(w.contiguous()), _ptr(bias.to(w.dtype).contiguous()), _dt(w.dtype), _ptr(y),
+                                       B, T, H, W, Cin, Cout, down_type, _dt(x_cl.dtype), _stream()))
         return y
 
     @staticmethod

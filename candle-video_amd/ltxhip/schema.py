@@ -88,3 +88,33 @@ def vae_decoder_weight_shapes(cfg) -> Dict[str, Shape]:
         s["scale_shift_table"] = (2, cur)
         s["timestep_scale_multiplier"] = ()
     return s
+
+
+def vae_encoder_weight_shapes(cfg=None) -> Dict[str, Shape]:
+    """cfg: AutoencoderKLLtxVideoEncoderConfig (None: the reference's defaults, vae.rs:68-103); names carry the `encoder.`
+    prefix of the checkpoint (LtxVideoEncoder3d::new, vae.rs:1329-1423; down block :854-930; downsampler :508-532)."""
+    if cfg is None:
+        from . import AutoencoderKLLtxVideoEncoderConfig
+        cfg = AutoencoderKLLtxVideoEncoderConfig()
+    s: Dict[str, Shape] = {}
+    strides = {"spatial": 4, "temporal": 2, "spatiotemporal": 8}
+
+    def conv(name: str, cin: int, cout: int):
+        s["encoder." + name + ".conv.weight"] = (cout, cin, 3, 3, 3)
+        s["encoder." + name + ".conv.bias"] = (cout,)
+
+    boc = list(cfg.block_out_channels)
+    conv("conv_in", cfg.in_channels * cfg.patch_size * cfg.patch_size * cfg.patch_size_t, boc[0])
+    cur = boc[0]
+    for i in range(len(boc) - 1):
+        for k in range(cfg.layers_per_block[i]):
+            conv(f"down_blocks.{i}.resnets.{k}.conv1", cur, cur)
+            conv(f"down_blocks.{i}.resnets.{k}.conv2", cur, cur)
+        if cfg.spatiotemporal_scaling[i]:
+            conv(f"down_blocks.{i}.downsamplers.0.conv", cur, boc[i + 1] // strides[cfg.downsample_types[i]])   # vae.rs:517
+        cur = boc[i + 1]
+    for k in range(max(cfg.layers_per_block[-1] - 1, 0)):              # the mid block has one resnet less (vae.rs:1382-1386)
+        conv(f"mid_block.resnets.{k}.conv1", cur, cur)
+        conv(f"mid_block.resnets.{k}.conv2", cur, cur)
+    conv("conv_out", cur, cfg.latent_channels + 1)                     # vae.rs:1396-1405
+    return s

@@ -114,6 +114,14 @@ int ltx_op_conv3d(const void* x, const void* w, const void* bias, int wdtype, vo
 int ltx_op_upsample3d(const void* x, const void* w, const void* bias, int wdtype, void* y,
                       int B, int T, int H, int W, int Cin, int Cout, int causal, int residual, int dtype, ltx_stream stream);
 
+/* LtxVideoDownsampler3d (vae.rs:499-582), the encoder's pixel-unshuffle downsampler: causal conv Cin -> Cout/(st*sh*sw) on the
+ * input with st - 1 leading frames repeated, space-to-depth to channel ((c*st + it)*sh + ih)*sw + iw, plus the same
+ * re-arrangement of x averaged over groups of Cin*st*sh*sw/Cout consecutive channels.  down_type: 1 spatial (1,2,2),
+ * 2 temporal (2,1,1), 3 spatiotemporal (2,2,2) (LTX_DOWN_* of ltxhip_encoder.h; 0, the strided conv, is LTX_ERR_UNSUPPORTED).
+ * x [B,T,H,W,Cin] -> y [B,(T+st-1)/st,H/sh,W/sw,Cout] channels-last; w [Cout/(st*sh*sw),Cin,3,3,3]. */
+int ltx_op_downsample3d(const void* x, const void* w, const void* bias, int wdtype, void* y,
+                        int B, int T, int H, int W, int Cin, int Cout, int down_type, int dtype, ltx_stream stream);
+
 /* conv_out + unpatchify(4) (vae.rs:1626-1654, 1724-1725): x [B,T,H,W,Cin] -> f32 NCTHW [B,Cout/16,T,4H,4W]. */
 int ltx_op_conv_out_unpatchify(const void* x, const void* w, const void* bias, int wdtype, float* y,
                                int B, int T, int H, int W, int Cin, int Cout, int causal, int postprocess, int dtype, ltx_stream stream);

@@ -9,6 +9,7 @@
 #ifndef LTXHIP_WEIGHTS_H
 #define LTXHIP_WEIGHTS_H
 #include "ltxhip.h"
+#include "ltxhip_encoder.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -73,6 +74,10 @@ int ltx_dit_create_from_files(const ltx_dit_config* cfg, const char* path, int u
                               ltx_dtype model_dtype, int device, ltx_dit** out);
 int ltx_vae_create_from_files(const ltx_vae_config* cfg, const char* path, int unified,
                               ltx_dtype model_dtype, int device, ltx_vae** out);
+/* The encode side of the same checkpoint (ltxhip_encoder.h): the `encoder.*` tensors go through the same key remapper; *cfg is
+ * used as given (a config.json beside the weights is not read: ltx_vae_config_from_json covers the decoder-side fields only). */
+int ltx_vae_encoder_create_from_files(const ltx_vae_encoder_config* cfg, const char* path, int unified,
+                                      ltx_dtype model_dtype, int device, ltx_vae_encoder** out);
 
 /* ---- GGUF (the container of the reference's DEFAULT text encoder: examples/ltx-video/main.rs:261-296 picks
  * t5-v1_1-xxl-encoder-Q8_0.gguf / -Q5_K_M.gguf unless --use-bf16-t5; quantized_t5_encoder.rs:570-600 reads it through

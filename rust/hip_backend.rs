@@ -621,3 +621,79 @@ fn describe_weights(weights: &[(String, Tensor)]) -> Result<Described> {
     }
     Ok((names, datas, descs))
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Encode side (include/ltxhip_encoder.h): AutoencoderKLLtxVideo::encode, vae.rs:2070-2099
+// ------------------------------------------------------------------------------------------------------------------
+
+/// Replaces `LtxVideoEncoder3d` (vae.rs:1316-1469) + `encode_z`'s tiling dispatch (:2017-2035).
+pub struct HipVaeEncoder {
+    h: *mut sys::ltx_vae_encoder,
+    ccfg: sys::ltx_vae_encoder_config,
+    device: c_int,
+}
+
+impl HipVaeEncoder {
+    /// weights: the `encoder.*` keys (vae.rs:1329-1423); other keys of a VAE checkpoint are ignored
+    pub fn new_encoder(cfg: &sys::ltx_vae_encoder_config, weights: &[(String, Tensor)], dtype: DType, device: usize) -> Result<Self> {
+        let (names, datas, descs) = describe_weights(weights)?;
+        let mut h: *mut sys::ltx_vae_encoder = ptr::null_mut();
+        let rc = unsafe { sys::ltx_vae_encoder_create(cfg, descs.as_ptr(), descs.len(), model_dtype(dtype)?, device as c_int, &mut h) };
+        drop((names, datas));
+        check(rc)?;
+        Ok(Self { h, ccfg: *cfg, device: device as c_int })
+    }
+
+    pub fn encoder_from_files(cfg: &sys::ltx_vae_encoder_config, path: &Path, unified: bool, dtype: DType, device: usize) -> Result<Self> {
+        let cpath = CString::new(path.to_string_lossy().as_bytes()).map_err(candle_core::Error::wrap)?;
+        let mut h: *mut sys::ltx_vae_encoder = ptr::null_mut();
+        check(unsafe { sys::ltx_vae_encoder_create_from_files(cfg, cpath.as_ptr(), unified as c_int, model_dtype(dtype)?, device as c_int, &mut h) })?;
+        Ok(Self { h, ccfg: *cfg, device: device as c_int })
+    }
+
+    /// (mean, logvar) of the posterior, each [B, latent_channels, (F-1)/8+1, H/32, W/32] f32 (DiagonalGaussianDistribution, vae.rs:117-133)
+    pub fn encode_moments(&self, video: &Tensor, tiling: Option<&sys::ltx_tiling>, framewise: bool) -> Result<(Tensor, Tensor)> {
+        let (b, c, f, h, w) = video.dims5()?;
+        if c != self.ccfg.in_channels as usize {
+            bail!("video has {c} channels, the encoder takes {}", self.ccfg.in_channels);
+        }
+        let x = host_f32(video)?;
+        let (tr, sr) = (self.ccfg.temporal_compression_ratio as usize, self.ccfg.spatial_compression_ratio as usize);
+        let (fo, ho, wo) = ((f - 1) / tr + 1, h / sr, w / sr);
+        let n = b * self.ccfg.latent_channels as usize * fo * ho * wo;
+        let mut xin = DeviceBuf::new(self.device);
+        let mut mean_d = DeviceBuf::new(self.device);
+        let mut logvar_d = DeviceBuf::new(self.device);
+        let x_d = xin.upload(&x)?;
+        let m_d = mean_d.ensure(n * 4)?;
+        let l_d = logvar_d.ensure(n * 4)?;
+        let et = sys::ltx_encode_tiling { use_framewise_encoding: framewise as c_int };
+        check(unsafe {
+            sys::ltx_vae_encode(self.h, x_d, sys::LTX_F32, b as c_int, f as c_int, h as c_int, w as c_int,
+                                tiling.map_or(ptr::null(), |t| t as *const sys::ltx_tiling), &et, m_d as *mut f32, l_d as *mut f32, ptr::null_mut())
+        })?;
+        let mut mean = vec![0f32; n];
+        let mut logvar = vec![0f32; n];
+        check(unsafe { sys::ltx_memcpy_d2h(mean.as_mut_ptr() as *mut c_void, m_d as *const c_void, n * 4, ptr::null_mut()) })?;
+        check(unsafe { sys::ltx_memcpy_d2h(logvar.as_mut_ptr() as *mut c_void, l_d as *const c_void, n * 4, ptr::null_mut()) })?;
+        check(unsafe { sys::ltx_stream_synchronize(ptr::null_mut()) })?;
+        let shape = (b, self.ccfg.latent_channels as usize, fo, ho, wo);
+        Ok((Tensor::from_vec(mean, shape, &Device::Cpu)?, Tensor::from_vec(logvar, shape, &Device::Cpu)?))
+    }
+}
+
+impl Drop for HipVaeEncoder {
+    fn drop(&mut self) {
+        unsafe { sys::ltx_vae_encoder_destroy(self.h) }
+    }
+}
+
+impl HipVae {
+    /// AutoencoderKLLtxVideo::encode (vae.rs:2070-2099) with this VAE's tiling switches: the posterior's (mean, logvar)
+    pub fn encode(&self, encoder: &HipVaeEncoder, video: &Tensor, use_framewise_encoding: bool) -> Result<(Tensor, Tensor)> {
+        let mut tl = self.tiling;
+        tl.use_tiling = self.use_tiling as c_int;
+        let tiled = self.use_tiling || use_framewise_encoding;
+        encoder.encode_moments(video, if tiled { Some(&tl) } else { None }, use_framewise_encoding)
+    }
+}

@@ -208,3 +208,52 @@ extern "C" {
     pub fn ltx_pcg32_randn(seed: u64, inc: u64, n: usize, out_host: *mut c_float) -> c_int;
     pub fn ltx_pcg32_u32(seed: u64, inc: u64, n: usize, out_host: *mut u32) -> c_int;
 }
+
+// ---- include/ltxhip_encoder.h: the encode side of AutoencoderKLLtxVideo (vae.rs:1316-1469, 2017-2099, 2158-2223, 2294-2357) ----
+
+/// `ltx_vae_encoder_config`: encoder-side fields of AutoencoderKLLtxVideoConfig (vae.rs:32-103).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_vae_encoder_config {
+    pub in_channels: c_int,
+    pub latent_channels: c_int,
+    pub n_blocks: c_int,
+    pub block_out_channels: [c_int; 5],
+    pub layers_per_block: [c_int; 5],
+    pub spatiotemporal_scaling: [c_int; 4],
+    /// 0 conv (unsupported), 1 spatial, 2 temporal, 3 spatiotemporal
+    pub downsample_types: [c_int; 4],
+    pub patch_size: c_int,
+    pub patch_size_t: c_int,
+    pub is_causal: c_int,
+    pub spatial_compression_ratio: c_int,
+    pub temporal_compression_ratio: c_int,
+}
+
+/// `ltx_encode_tiling`: use_framewise_encoding (vae.rs:1851), the switch `ltx_tiling` lacks.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_encode_tiling {
+    pub use_framewise_encoding: c_int,
+}
+
+pub const ENCODER_LAYOUT_LTX_VAE_ENCODER_CONFIG: (usize, usize) = (104, 4);
+pub const ENCODER_LAYOUT_LTX_ENCODE_TILING: (usize, usize) = (4, 4);
+const _: () = assert!(size_of::<ltx_vae_encoder_config>() == ENCODER_LAYOUT_LTX_VAE_ENCODER_CONFIG.0 && align_of::<ltx_vae_encoder_config>() == ENCODER_LAYOUT_LTX_VAE_ENCODER_CONFIG.1);
+const _: () = assert!(size_of::<ltx_encode_tiling>() == ENCODER_LAYOUT_LTX_ENCODE_TILING.0 && align_of::<ltx_encode_tiling>() == ENCODER_LAYOUT_LTX_ENCODE_TILING.1);
+
+pub enum ltx_vae_encoder {}
+
+extern "C" {
+    pub fn ltx_vae_encoder_config_default(cfg: *mut ltx_vae_encoder_config);
+    pub fn ltx_vae_encoder_create(cfg: *const ltx_vae_encoder_config, weights: *const ltx_weight, n_weights: usize, model_dtype: c_int, device: c_int, out: *mut *mut ltx_vae_encoder) -> c_int;
+    pub fn ltx_vae_encoder_create_from_files(cfg: *const ltx_vae_encoder_config, path: *const c_char, unified: c_int, model_dtype: c_int, device: c_int, out: *mut *mut ltx_vae_encoder) -> c_int;
+    pub fn ltx_vae_encoder_destroy(e: *mut ltx_vae_encoder);
+    pub fn ltx_vae_encoder_get_config(e: *const ltx_vae_encoder, out: *mut ltx_vae_encoder_config) -> c_int;
+    pub fn ltx_vae_encode(e: *mut ltx_vae_encoder, video: *const c_void, video_dtype: c_int, b: c_int, f: c_int, h: c_int, w: c_int,
+                          tiling: *const ltx_tiling, enc_tiling: *const ltx_encode_tiling, mean_out: *mut c_float, logvar_out: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_vae_posterior_sample(mean: *const c_float, logvar: *const c_float, eps: *const c_float, n: usize, out: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_vae_encode_tokens(e: *mut ltx_vae_encoder, vae: *const ltx_vae, video: *const c_void, video_dtype: c_int, b: c_int, f: c_int, h: c_int, w: c_int,
+                                 tiling: *const ltx_tiling, enc_tiling: *const ltx_encode_tiling, eps: *const c_float, tokens_out: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_vae_encoder_warmup(e: *mut ltx_vae_encoder, b: c_int, f: c_int, h: c_int, w: c_int, tiling: *const ltx_tiling, enc_tiling: *const ltx_encode_tiling, stream: ltx_stream) -> c_int;
+}

@@ -21,6 +21,7 @@ import os
 import subprocess
 import sys
 import tempfile
+import time
 
 import numpy as np
 import torch
@@ -540,9 +541,36 @@ def c5dit_case():
                         "out_sub": "[:, ::16] of the [1,17556,128] output; bf16in = the same arithmetic on bf16-rounded weights / hidden / enc"})
 
 
+def vae_encode_full_case():
+    """tests/golden/oracle_vae_encode_full.safetensors: the VAE encoder (default config, synth_weights seed 31) on the seeded
+    full-size video [1,3,97,512,768] (seed 33), f32 mode of tests/vae_encoder_ref.py: the mean, stored as three files of at most 43
+    channels (each under the 1 MiB limit of a committed file) + the logvar channel, and the ref's own bf16-vs-f32 rel-L2 on the same input (the source of the test's bf16 bar)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import vae_encoder_ref as R
+    cfg = R.EncoderConfig()
+    w = O.synth_weights(R.encoder_weight_shapes(cfg), seed=31)
+    x = torch.rand(1, 3, 97, 512, 768, generator=torch.Generator().manual_seed(33)) * 2 - 1
+    t0 = time.time()
+    with torch.no_grad():
+        f = R.encoder_forward(w, cfg, x, torch.float32)[:, :129]
+        print(f"vae encode full f32: {time.time() - t0:.0f} s", flush=True)
+        b = R.encoder_forward(w, cfg, x, torch.bfloat16)[:, :129].float()
+    d = lambda a, r: float((a.double() - r.double()).norm() / r.double().norm())
+    dm, dl = d(b[:, :128], f[:, :128]), d(b[:, 128:], f[:, 128:])
+    print(f"vae encode full: {time.time() - t0:.0f} s; ref bf16 vs f32 rel-L2 mean {dm:.4e} logvar {dl:.4e}", flush=True)
+    save_file({"mean_0_43": f[:, 0:43].contiguous(), "logvar": f[:, 128:129].contiguous(),
+               "ref_bf16_rel_l2": torch.tensor([dm, dl], dtype=torch.float64)},
+              os.path.join(GOLD, "oracle_vae_encode_full.safetensors"))
+    save_file({"mean_43_86": f[:, 43:86].contiguous()}, os.path.join(GOLD, "oracle_vae_encode_full_b.safetensors"))
+    save_file({"mean_86_128": f[:, 86:128].contiguous()}, os.path.join(GOLD, "oracle_vae_encode_full_c.safetensors"))
+
+
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
+    if len(sys.argv) > 1 and sys.argv[1] == "vae_encode_full":
+        vae_encode_full_case()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "c1":
         c1_case()
         sys.exit(0)
