@@ -42,6 +42,63 @@ extern "C" int ltx_op_rowsq(const void* x, int64_t rows, int N, int ld, float* r
     return ltx_launch_rowsq(x, dtc(dtype), rows, N, ld, rowsq, (hipStream_t)stream);
 }
 
+// ---- norm fold (GemmArgs::C2 / ::rs_sq, kernels.h): the two epilogue sides and the three small launchers around them
+namespace {
+GemmArgs fold_out_args(const void* x, const void* w, const void* bias, void* y, void* y2, float* rowsq, const float* scale2, int scale2_stride,
+                       int M, int N, int K, const void* resid, const float* gate, int rows_per_batch) {
+    GemmArgs g; g.A = x; g.W = w; g.C = y; g.bias = bias; g.resid = resid; g.gate = gate; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N;
+    g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; g.gate_stride = N; g.rowsq = rowsq;
+    g.C2 = y2; g.scale2 = scale2; g.scale2_stride = scale2_stride;
+    return g;
+}
+GemmArgs fold_in_args(const void* x, const void* w, void* y, const float* rs_sq, int rs_n, int rs_D, float eps, const float* cvec, int cvec_stride,
+                      int M, int N, int K, int rows_per_batch) {
+    GemmArgs g; g.A = x; g.W = w; g.C = y; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
+    g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
+    g.rs_sq = rs_sq; g.rs_n = rs_n; g.rs_D = rs_D; g.rs_eps = eps; g.cvec = cvec; g.cvec_stride = cvec_stride;
+    return g;
+}
+}  // namespace
+
+extern "C" int ltx_op_linear_fold_out(const void* x, const void* w, const void* bias, void* y, void* y2, float* rowsq, const float* scale2, int scale2_stride,
+                                      int M, int N, int K, int epi, const void* resid, const float* gate, int rows_per_batch, ltx_stream stream) {
+    if (!x || !w || !y || !y2 || !rowsq || !scale2 || !resid) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_out: null tensor");
+    if (epi != 2 && epi != 3) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_out: epi must be 2 or 3 (the second output rides on the residual epilogues)");
+    if (epi == 2 && !gate) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_out: gated epilogue needs gate");
+    const GemmArgs g = fold_out_args(x, w, bias, y, y2, rowsq, scale2, scale2_stride, M, N, K, resid, gate, rows_per_batch);
+    if (!ltx_gemm_fold_ok(g, epi)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_out: not a call the norm fold serves (ltx_op_linear_fold_ok)");
+    return ltx_launch_gemm(g, LTX_DT_BF16, epi, (hipStream_t)stream);
+}
+
+extern "C" int ltx_op_linear_fold_in(const void* x, const void* w, void* y, const float* rs_sq, int rs_n, int rs_D, float eps, const float* cvec, int cvec_stride,
+                                     int M, int N, int K, int epi, int rows_per_batch, ltx_stream stream) {
+    if (!x || !w || !y || !rs_sq || !cvec) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_in: null tensor");
+    if (epi != 0 && epi != 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_in: epi must be 0 or 1 (the row scale rides on the bias / GELU epilogues)");
+    const GemmArgs g = fold_in_args(x, w, y, rs_sq, rs_n, rs_D, eps, cvec, cvec_stride, M, N, K, rows_per_batch);
+    if (!ltx_gemm_fold_ok(g, epi)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_fold_in: not a call the norm fold serves (ltx_op_linear_fold_ok)");
+    return ltx_launch_gemm(g, LTX_DT_BF16, epi, (hipStream_t)stream);
+}
+
+extern "C" int ltx_op_linear_fold_ok(int M, int N, int K, int epi, int consumer, int rs_n, int vec_stride, int rows_per_batch) {
+    if (M < 1 || N < 1 || K < 1) return 0;
+    // (aligned non-null pointers: a fit test, nothing is launched)
+    void* const p = reinterpret_cast<void*>((uintptr_t)4096); float* const f = reinterpret_cast<float*>(p);
+    if (consumer) return ltx_gemm_fold_ok(fold_in_args(p, p, p, f, rs_n, K, 1e-6f, f, vec_stride, M, N, K, rows_per_batch), epi) ? 1 : 0;
+    return ltx_gemm_fold_ok(fold_out_args(p, p, p, p, p, f, f, vec_stride, M, N, K, p, f, rows_per_batch), epi) ? 1 : 0;
+}
+
+extern "C" int ltx_op_shift_gemv(const void* w, const void* bias, const float* shift, int shift_stride, int B, int N, int K, float* cvec, int cvec_stride, ltx_stream stream) {
+    return ltx_launch_shift_gemv(w, bias, shift, shift_stride, B, N, K, cvec, cvec_stride, (hipStream_t)stream);
+}
+extern "C" int ltx_op_mod_scale(const void* h, const float* scale, int scale_stride, void* y, int B, int64_t rows_per_batch, int D, int dtype, ltx_stream stream) {
+    if (!h || !scale || !y || B < 1 || rows_per_batch < 1 || D < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_mod_scale: bad argument");
+    return ltx_launch_mod_scale(h, scale, scale_stride, y, B, rows_per_batch, D, dtc(dtype), (hipStream_t)stream);
+}
+extern "C" int ltx_op_scale_cols(const void* w, const float* scale, void* out, int64_t N, int K, int dtype, ltx_stream stream) {
+    if (!w || !scale || !out || N < 1 || K < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_scale_cols: bad argument");
+    return ltx_launch_scale_cols(w, scale, out, N, K, dtc(dtype), (hipStream_t)stream);
+}
+
 extern "C" int ltx_op_linear_segmented(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int seg_width,
                                        int dtype, ltx_stream stream) {
     if (!x || !w || !y) LTX_FAIL(LTX_ERR_ARG, "ltx_op_linear_segmented: null tensor");

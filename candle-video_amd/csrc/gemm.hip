@@ -194,6 +194,9 @@ int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s) {
     // K ranges left to the consumer are gemm_ring's (through gemm_big's plan dispatch); no other kernel honours the field
     if (g.defer_parts && (ltx_gemm_asm_eligible(g, dtype, epi) || !ltx_gemm_big_eligible(g, dtype)))
         LTX_FAIL(LTX_ERR_ARG, "gemm: defer_parts set on a call that is not routed to the ring tiles (ask ltx_gemm_defer_ok first)");
+    // the norm fold's second output / row scale are gemm_asm16's wide epilogue (again through gemm_big's dispatch): the same rule
+    if ((g.C2 || g.rs_sq) && (ltx_gemm_asm_eligible(g, dtype, epi) || !ltx_gemm_big_eligible(g, dtype)))
+        LTX_FAIL(LTX_ERR_ARG, "gemm: norm-fold arguments (C2 / rs_sq) on a call that is not routed to gemm_asm16 (ask ltx_gemm_fold_ok first)");
     t_rowsq_done = false;
     void* tok = nullptr;
     ltx_prof_begin(g.conv ? LTX_PROF_CONV : LTX_PROF_GEMM, 2.0 * g.M * (double)g.N * g.K * (g.conv ? g.ntaps : 1), s, &tok);

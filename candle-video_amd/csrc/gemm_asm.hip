@@ -898,6 +898,9 @@ bool ltx_gemm_asm16_fits(const GemmArgs& g, int epi) {
 // Norm fold (GemmArgs::C2 / ::rs_sq): what the wide epilogue needs on top of ltx_gemm_asm16_fits
 bool ltx_gemm_fold_ok(const GemmArgs& g, int epi) {
     if (!ltx_gemm_asm16_fits(g, epi) || (ltx_opt().gemm_off & LTX_FAM_ASM16) || !ltx_opt().gemm_wide_epi) return false;
+    // ... and ltx_launch_gemm must hand the call to gemm_big's plan dispatch, the only road to that epilogue: under gemm_off=big
+    // gemm.hip's 128 x 128 kernel serves it, under x_gemm_asm=1 (experiment builds) the 32x32x16 kernel - neither reads the fields
+    if (!ltx_gemm_big_eligible(g, LTX_DT_BF16) || ltx_gemm_asm_eligible(g, LTX_DT_BF16, epi)) return false;
     if (g.C2) {
         if ((epi != EPI_GATE_RESID && epi != EPI_RESID) || !g.rowsq || !g.scale2 || g.scale2_stride % 4 || ((uintptr_t)g.scale2 & 15) || ((uintptr_t)g.C2 & 7) || g.rows_per_batch < 320 || g.c_seg_shift) return false;
     }

@@ -123,6 +123,11 @@ _SIGS = {
     "ltx_op_linear_packed": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp],
     "ltx_op_rownorm_presum": [_vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _i64, _i, _i, _vp, _i, _i, _vp],
     "ltx_op_linear_rowsq": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp], "ltx_op_rowsq": [_vp, _i64, _i, _i, _vp, _i, _vp],
+    "ltx_op_linear_fold_out": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "ltx_op_linear_fold_in": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "ltx_op_linear_fold_ok": [_i, _i, _i, _i, _i, _i, _i, _i],
+    "ltx_op_shift_gemv": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp],
+    "ltx_op_mod_scale": [_vp, _vp, _i, _vp, _i, _i64, _i, _i, _vp], "ltx_op_scale_cols": [_vp, _vp, _vp, _i64, _i, _i, _vp],
     "ltx_op_linear_split_factor": [_i, _i, _i], "ltx_op_linear_deferred": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "ltx_op_rownorm_deferred": [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _i64, _i, _i, _vp],
     "ltx_op_attention_compact": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _i, _f, _vp, _vp],
@@ -1270,6 +1275,61 @@ class ops:
         rs = torch.empty(M, (N + 127) // 128, dtype=torch.float32, device=x.device)
         _check(lib.ltx_op_rowsq(_ptr(x.contiguous()), C.c_int64(M), N, N, _ptr(rs), _dt(x.dtype), _stream()))
         return rs
+
+    @staticmethod
+    def linear_fold_ok(M, N, K, epi, consumer, rs_n=0, vec_stride=None, rows_per_batch=None) -> bool:
+        """whether the norm fold serves the call (consumer False: linear_fold_out, True: linear_fold_in); nothing is launched"""
+        return bool(lib.ltx_op_linear_fold_ok(M, N, K, epi, int(bool(consumer)), rs_n, N if vec_stride is None else vec_stride,
+                                              M if rows_per_batch is None else rows_per_batch))
+
+    @staticmethod
+    def linear_fold_out(x, w, bias, scale2, epi, resid, gate=None, rows_per_batch=1):
+        """producer side of the norm fold (bf16): -> (y = the residual epilogue, y2 = y (.) (1 + scale2[b]), row partials of y).
+        scale2 f32 [batch, stride >= N]"""
+        M, K = x.shape
+        N = w.shape[0]
+        y = torch.empty(M, N, dtype=x.dtype, device=x.device); y2 = torch.empty_like(y)
+        rs = torch.empty(M, (N + 127) // 128, dtype=torch.float32, device=x.device)
+        _check(lib.ltx_op_linear_fold_out(_ptr(x.contiguous()), _ptr(w.contiguous()), _ptr(bias), _ptr(y), _ptr(y2), _ptr(rs), _ptr(scale2), scale2.shape[-1],
+                                          M, N, K, epi, _ptr(resid), _ptr(gate), rows_per_batch, _stream()))
+        return y, y2, rs
+
+    @staticmethod
+    def linear_fold_in(x, w, rs_sq, cvec, epi=0, rows_per_batch=1, rs_D=None, eps=1e-6):
+        """consumer side of the norm fold (bf16): epi(r_m * (x @ w^T) + cvec[b]) with r_m from the row partials rs_sq [M, rs_n] f32;
+        cvec f32 [batch, stride >= N]"""
+        M, K = x.shape
+        N = w.shape[0]
+        y = torch.empty(M, N, dtype=x.dtype, device=x.device)
+        _check(lib.ltx_op_linear_fold_in(_ptr(x.contiguous()), _ptr(w.contiguous()), _ptr(y), _ptr(rs_sq.contiguous()), rs_sq.shape[-1], K if rs_D is None else rs_D,
+                                         C.c_float(eps), _ptr(cvec), cvec.shape[-1], M, N, K, epi, rows_per_batch, _stream()))
+        return y
+
+    @staticmethod
+    def shift_gemv(w, bias, shift, K=None, out_stride=None):
+        """cvec [B, N] f32 = shift[:, :K] @ w^T + bias (bf16 w [N, K], bias or None; shift f32 [B, stride >= K])"""
+        N, Kw = w.shape
+        K = Kw if K is None else K
+        B = shift.shape[0]
+        out = torch.zeros(B, N if out_stride is None else out_stride, dtype=torch.float32, device=w.device)
+        _check(lib.ltx_op_shift_gemv(_ptr(w.contiguous()), _ptr(bias), _ptr(shift), shift.shape[-1], B, N, K, _ptr(out), out.shape[-1], _stream()))
+        return out
+
+    @staticmethod
+    def mod_scale(h, scale, rows_per_batch):
+        """h (.) (1 + scale[b]) in h's dtype: h [B * rows_per_batch, D], scale f32 [B, stride >= D]"""
+        rows, D = h.shape
+        y = torch.empty_like(h)
+        _check(lib.ltx_op_mod_scale(_ptr(h.contiguous()), _ptr(scale), scale.shape[-1], _ptr(y), rows // rows_per_batch, C.c_int64(rows_per_batch), D, _dt(h.dtype), _stream()))
+        return y
+
+    @staticmethod
+    def scale_cols(w, scale):
+        """w[n][k] * (1 + scale[k]) in w's dtype"""
+        N, K = w.shape
+        out = torch.empty_like(w)
+        _check(lib.ltx_op_scale_cols(_ptr(w.contiguous()), _ptr(scale), _ptr(out), C.c_int64(N), K, _dt(w.dtype), _stream()))
+        return out
 
     @staticmethod
     def attention_rowsq(q, k, v, heads, scale, key_bias, q_rowsq, eps=1e-5):

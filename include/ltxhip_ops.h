@@ -33,6 +33,27 @@ int ltx_op_linear_rowsq(const void* x, const void* w, const void* bias, void* y,
                         const void* resid, const float* gate, int rows_per_batch, ltx_stream stream);   /* epi 0, 2, 3 as ltx_op_linear */
 int ltx_op_rowsq(const void* x, int64_t rows, int N, int ld, float* rowsq, int dtype, ltx_stream stream);
 
+/* The norm fold of the DiT block (LtxVideoTransformerBlock::forward, ltx_transformer.rs:847-851, 905-909: y = h * r * (1 + sc) + sh
+ * in front of the q|k|v and ff1 projections, r = 1 / sqrt(mean(h^2) + eps)), as the two GEMM epilogue sides that replace the norm
+ * pass.  bf16, more than 512 rows, batch elements of at least 320 rows; LTX_ERR_ARG for a call the one-wave-per-SIMD kernels do
+ * not serve - ltx_op_linear_fold_ok answers that without launching (consumer 0: the producer side, vec_stride = scale2_stride;
+ * 1: the consumer side, vec_stride = cvec_stride, rs_n partials per row).  b(m) = m / rows_per_batch.
+ *   fold_out (epi 2 / 3 as ltx_op_linear): y = the residual epilogue, rowsq = its row partials (ltx_op_linear_rowsq), and
+ *     y2[m][n] = bf16(float(y[m][n] as stored) * (1.0f + scale2[b(m) * scale2_stride + n]))
+ *   fold_in (epi 0 / 1, no bias): y = epi(r_m * (x @ w^T) + cvec[b(m) * cvec_stride + n]),
+ *     r_m = 1 / sqrt(sum_g rs_sq[m * rs_n + g] / rs_D + eps); rs_n in {4, 8, 12, 16} */
+int ltx_op_linear_fold_out(const void* x, const void* w, const void* bias, void* y, void* y2, float* rowsq, const float* scale2, int scale2_stride,
+                           int M, int N, int K, int epi, const void* resid, const float* gate, int rows_per_batch, ltx_stream stream);
+int ltx_op_linear_fold_in(const void* x, const void* w, void* y, const float* rs_sq, int rs_n, int rs_D, float eps, const float* cvec, int cvec_stride,
+                          int M, int N, int K, int epi, int rows_per_batch, ltx_stream stream);
+int ltx_op_linear_fold_ok(int M, int N, int K, int epi, int consumer, int rs_n, int vec_stride, int rows_per_batch);
+/* cvec[b * cvec_stride + n] = sum_k shift[b * shift_stride + k] * w[n][k] + bias[n]: f32 from bf16 w [N, K] / bias (may be NULL), B <= 8 */
+int ltx_op_shift_gemv(const void* w, const void* bias, const float* shift, int shift_stride, int B, int N, int K, float* cvec, int cvec_stride, ltx_stream stream);
+/* y = h (.) (1 + scale[b]) on rows [B * rows_per_batch, D]: fold_out's second output as a stand-alone map (same bits) */
+int ltx_op_mod_scale(const void* h, const float* scale, int scale_stride, void* y, int B, int64_t rows_per_batch, int D, int dtype, ltx_stream stream);
+/* out[n][k] = w[n][k] * (1 + scale[k]): the factor of the fold moved into a copy of the consumer's weights */
+int ltx_op_scale_cols(const void* w, const float* scale, void* out, int64_t N, int K, int dtype, ltx_stream stream);
+
 /* The fused q|k|v projection of LtxAttention (ltx_transformer.rs:655-662: to_q, to_k, to_v on the same input) with the
  * output written as N/seg_width DENSE matrices: y[j][M][seg_width] = (x @ w^T + bias)[:, j*seg_width:(j+1)*seg_width].
  * seg_width a power of two dividing N. */

@@ -120,6 +120,45 @@ def test_weights_form_with_rows_at_one_timestep_and_a_cycling_schedule(hip):
     assert torch.equal(seq[896.0], y2)                          # still the scaled-weight form, rebuilt after its eviction: same bits
 
 
+def test_fold_stands_down_when_the_gemms_are_routed_past_its_epilogue(hip):
+    """gemm_off=big (the documented A/B arm: gemm.hip's 128 x 128 kernel for every GEMM) and, in experiment builds, x_gemm_asm=1
+    (round 1's 32x32x16 kernel on the large shapes): neither kernel reads GemmArgs::rs_sq / cvec / C2, so ltx_gemm_fold_ok must say
+    no and the forward run its norm passes - the bits of norm_fold=0 under the same routing, 2 * 3 + 1 norm launches - instead of
+    feeding un-normalised rows to q|k|v and ff1.  4992 tokens: the smallest size at which the K = N = 2048 layers take the fold."""
+    cfg = O.DitConfig(**CFGD)
+    w = O.synth_weights(O.dit_weight_shapes(cfg), seed=71)
+    B, F, H, W, K = 1, 13, 16, 24, 128
+    S = F * H * W
+    g = torch.Generator().manual_seed(72)
+    hidden = torch.randn(B, S, 128, generator=g); enc = torch.randn(B, K, 4096, generator=g)
+    mask = torch.zeros(B, K); mask[:, :40] = 1
+    t = torch.tensor([896.0])
+    coords = O.build_video_coords(B, F, H, W)
+    wr = {k: v.bfloat16().float() for k, v in w.items()}
+    want = O.dit_forward(wr, cfg, hidden.bfloat16().float(), enc.bfloat16().float(), t, mask, F, H, W, None, coords, None)
+    model = hip.LtxVideoTransformer3DModel(hip.LtxVideoTransformer3DModelConfig(**CFGD), {k: v.to(DEV) for k, v in w.items()}, torch.bfloat16)
+    args = (hidden.to(DEV), enc.to(DEV), t, mask.to(DEV), F, H, W, None, coords.to(DEV), None)
+    _, n_fold = run(hip, model, args, norm_fold="1")
+    assert n_fold == 2                                          # (the fold is what this size runs by default)
+    routings = [dict(gemm_off="big")] + ([dict(x_gemm_asm="1")] if hip.has_experiments() else [])
+    for route in routings:
+        y0, n0 = run(hip, model, args, norm_fold="0", **route)
+        for nf in ("1", "2"):
+            y, n = run(hip, model, args, norm_fold=nf, **route)
+            e = rel_l2(y, want)
+            print({"routing": route, "norm_fold": nf, "vs_oracle": round(e, 5), "norm_launches": n})
+            assert torch.isfinite(y).all() and e <= 2e-2, (route, nf, e)
+            assert torch.equal(y, y0), (route, nf, "the fold did not stand down")
+            assert n == 2 * 3 + 1 and n0 == n, (route, nf, n, n0)
+    # the op itself: an error, not numbers
+    M, N, D = 2200, 4096, 2048
+    z = lambda *s, dt=torch.bfloat16: torch.zeros(*s, dtype=dt, device=DEV)
+    with hip.options(gemm_off="big"):
+        with pytest.raises(hip.LtxError, match="rc=1"):
+            hip.ops.linear_fold_in(z(M, D), z(N, D), z(M, 16, dt=torch.float32), z(2, N, dt=torch.float32), rows_per_batch=1100)
+    assert torch.isfinite(hip.ops.linear_fold_in(z(M, D), z(N, D), z(M, 16, dt=torch.float32) + 1.0, z(2, N, dt=torch.float32), rows_per_batch=1100).float()).all()
+
+
 def test_guidance_rows_in_one_forward_keep_the_bits_of_separate_forwards(hip):
     """ltx_pipeline_call runs the guidance branches of a step as rows of one forward (pipeline.hip): a row that skips a layer must
     come out with the bits of a forward that never ran it - with the fold, the rows behind the blend take h (.) (1 + sc) from the
