@@ -320,3 +320,30 @@ extern "C" int ltx_op_gemm_plan(int M, int N, int K, int conv, int ntaps, int T,
     snprintf(name, (size_t)cap, "%s", n);
     return LTX_OK;
 }
+
+// Read-only probe of the GEMM dispatch: the described call with dense strides and aligned dummy pointers (never dereferenced)
+extern "C" int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B, int T, int H, int W, int epi, int dtype, int flags, char* name, int cap) {
+    if (!name || cap < 1 || M < 1 || N < 1 || K < 1 || epi < EPI_BIAS || epi > EPI_S2D) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_route: bad argument");
+    if (conv && (ntaps < 1 || B < 1 || T < 1 || H < 1 || W < 1 || (int64_t)B * T * H * W != M)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_route: conv calls need M = B T H W");
+    void* const p = reinterpret_cast<void*>((uintptr_t)4096); float* const f = reinterpret_cast<float*>(p);
+    const bool res = epi == EPI_GATE_RESID || epi == EPI_RESID;
+    GemmArgs g;
+    if (flags & LTX_ROUTE_FOLD_IN) g = fold_in_args(p, p, p, f, 16, K, 1e-6f, f, N, M, N, K, M);
+    else if (flags & LTX_ROUTE_FOLD_OUT) g = fold_out_args(p, p, p, p, p, f, f, N, M, N, K, p, epi == EPI_GATE_RESID ? f : nullptr, M);
+    else {
+        g.A = p; g.W = p; g.C = p; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N; g.rows_per_batch = M; g.gate_stride = N;
+        if (flags & LTX_ROUTE_DEFER) g.defer_parts = f;      // a bare launch: the consumer applies bias, gate and residual
+        else { g.bias = p; if (res || epi == EPI_S2D) g.resid = p; if (epi == EPI_GATE_RESID) g.gate = f; }
+    }
+    if (conv) {
+        g.conv = 1; g.B = B; g.T = T; g.H = H; g.Wd = W; g.Cin = K; g.ntaps = ntaps; g.kh = g.kw = ntaps == 27 ? 3 : 1; g.pad_t = 2;
+        if (epi == EPI_D2S) { g.Cf = N / 8; g.Cr = K / 8; g.To = 2 * T - 1; g.Ho = 2 * H; g.Wo = 2 * W; }
+        if (epi == EPI_S2D) { g.s2_st = g.s2_sh = g.s2_sw = 2; g.To = (T + 1) / 2; g.Ho = H / 2; g.Wo = W / 2; }
+        if (flags & LTX_ROUTE_PN) { g.pn_on = 1; g.pn_eps = 1e-6f; g.pn_act = 1; }
+    }
+    GemmRoute r;
+    LTX_TRY(ltx_gemm_route(g, dtc(dtype), epi, nullptr, false, &r));
+    if (const char* why = ltx_gemm_route_refusal(g, r)) LTX_FAIL(LTX_ERR_ARG, why);
+    snprintf(name, (size_t)cap, "%s", ltx_gemm_route_name(r));
+    return LTX_OK;
+}

@@ -191,22 +191,23 @@ int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s) {
     if ((epi == EPI_D2S || epi == EPI_UNPATCH || epi == EPI_S2D) && !g.conv) LTX_FAIL(LTX_ERR_ARG, "gemm: d2s/unpatch need conv mode");
     if (epi == EPI_S2D && (!g.resid || g.s2_st * g.s2_sh * g.s2_sw < 2 || g.s2_group < 1)) LTX_FAIL(LTX_ERR_ARG, "gemm: the space-to-depth epilogue needs the input tensor and its strides");
     if (g.rowsq && (g.conv || g.c_seg_shift || epi == EPI_D2S || epi == EPI_UNPATCH)) LTX_FAIL(LTX_ERR_ARG, "gemm: rowsq needs a dense linear output");
-    // K ranges left to the consumer are gemm_ring's (through gemm_big's plan dispatch); no other kernel honours the field
-    if (g.defer_parts && (ltx_gemm_asm_eligible(g, dtype, epi) || !ltx_gemm_big_eligible(g, dtype)))
-        LTX_FAIL(LTX_ERR_ARG, "gemm: defer_parts set on a call that is not routed to the ring tiles (ask ltx_gemm_defer_ok first)");
-    // the norm fold's second output / row scale are gemm_asm16's wide epilogue (again through gemm_big's dispatch): the same rule
-    if ((g.C2 || g.rs_sq) && (ltx_gemm_asm_eligible(g, dtype, epi) || !ltx_gemm_big_eligible(g, dtype)))
-        LTX_FAIL(LTX_ERR_ARG, "gemm: norm-fold arguments (C2 / rs_sq) on a call that is not routed to gemm_asm16 (ask ltx_gemm_fold_ok first)");
+    // route (gemm_big.hip: which kernel, which plan), refuse (operands that kernel does not read), launch
+    GemmRoute r;
+    LTX_TRY(ltx_gemm_route(g, dtype, epi, s, true, &r));
+    if (const char* why = ltx_gemm_route_refusal(g, r)) LTX_FAIL(LTX_ERR_ARG, why);
     t_rowsq_done = false;
     void* tok = nullptr;
     ltx_prof_begin(g.conv ? LTX_PROF_CONV : LTX_PROF_GEMM, 2.0 * g.M * (double)g.N * g.K * (g.conv ? g.ntaps : 1), s, &tok);
     int rc;
-    if (ltx_opt().gemm_trace && dtype == LTX_DT_BF16 && !ltx_gemm_asm_eligible(g, dtype, epi) && !ltx_gemm_big_eligible(g, dtype))     // debugging aid: bf16 shapes left to the 128 x 128 kernel
-        fprintf(stderr, "[ltx] gemm128 serves M=%d N=%d K=%d conv=%d ntaps=%d B=%d T=%d H=%d W=%d epi=%d fits=%d\n", g.M, g.N, g.K, g.conv, g.ntaps, g.B, g.T, g.H, g.Wd, epi, (int)ltx_gemm_big_fits(g));
-    if (ltx_gemm_asm_eligible(g, dtype, epi)) rc = ltx_launch_gemm_asm(g, epi, s);
-    else if (ltx_gemm_big_eligible(g, dtype)) rc = ltx_launch_gemm_big(g, epi, s);
-    else if (dtype == LTX_DT_BF16) rc = g.conv ? launch_t<bf16_t, true>(g, epi, s) : launch_t<bf16_t, false>(g, epi, s);
-    else rc = g.conv ? launch_t<float, true>(g, epi, s) : launch_t<float, false>(g, epi, s);
+    switch (r.kind) {
+        case LTX_ROUTE_PLAN: rc = ltx_launch_gemm_plan(g, epi, r.plan, s); break;
+        case LTX_ROUTE_ASM32: rc = ltx_launch_gemm_asm(g, epi, s); break;
+        default:
+            if (dtype != LTX_DT_BF16) { rc = g.conv ? launch_t<float, true>(g, epi, s) : launch_t<float, false>(g, epi, s); break; }
+            if (ltx_opt().gemm_trace)      // debugging aid: bf16 shapes left to the 128 x 128 kernel
+                fprintf(stderr, "[ltx] gemm128 serves M=%d N=%d K=%d conv=%d ntaps=%d B=%d T=%d H=%d W=%d epi=%d fits=%d\n", g.M, g.N, g.K, g.conv, g.ntaps, g.B, g.T, g.H, g.Wd, epi, (int)ltx_gemm_big_fits(g));
+            rc = g.conv ? launch_t<bf16_t, true>(g, epi, s) : launch_t<bf16_t, false>(g, epi, s);
+    }
     ltx_prof_end(tok, s);
     // by-product not written by the kernel that ran (every kernel but gemm_asm16): the stand-alone pass, same canonical order
     if (rc == LTX_OK && g.rowsq && !t_rowsq_done) rc = ltx_launch_rowsq(g.C, dtype, g.M, g.N, g.ldc, g.rowsq, s);

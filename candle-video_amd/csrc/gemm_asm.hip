@@ -808,6 +808,7 @@ __global__ __launch_bounds__(256, 1) void gemm_asm16_conv_kernel(const GemmArgs 
 }
 
 struct AsmTile { int bm, bn; const char* name; };
+// ONE tile order: ltx_gemm_asm_pick_tile, ltx_launch_gemm_asm16 / ltx_launch_gemm_asm and the asm16 entries of gemm_big.hip's plan table
 const AsmTile kAsmTiles[] = {{256, 256, "asm256x256"}, {320, 256, "asm320x256"}, {160, 256, "asm160x256"}};
 
 template <int BM, int BN, int WGM, int WGN, int EPI, bool MF16 = false>
@@ -898,9 +899,9 @@ bool ltx_gemm_asm16_fits(const GemmArgs& g, int epi) {
 // Norm fold (GemmArgs::C2 / ::rs_sq): what the wide epilogue needs on top of ltx_gemm_asm16_fits
 bool ltx_gemm_fold_ok(const GemmArgs& g, int epi) {
     if (!ltx_gemm_asm16_fits(g, epi) || (ltx_opt().gemm_off & LTX_FAM_ASM16) || !ltx_opt().gemm_wide_epi) return false;
-    // ... and ltx_launch_gemm must hand the call to gemm_big's plan dispatch, the only road to that epilogue: under gemm_off=big
-    // gemm.hip's 128 x 128 kernel serves it, under x_gemm_asm=1 (experiment builds) the 32x32x16 kernel - neither reads the fields
-    if (!ltx_gemm_big_eligible(g, LTX_DT_BF16) || ltx_gemm_asm_eligible(g, LTX_DT_BF16, epi)) return false;
+    // ... and the route must lead to the plan families, the only road to that epilogue: under gemm_off=big gemm.hip's 128 x 128
+    // kernel serves the call, under x_gemm_asm=1 (experiment builds) the 32x32x16 kernel - neither reads the fields
+    if (ltx_gemm_route_kind(g, LTX_DT_BF16, epi) != LTX_ROUTE_PLAN) return false;
     if (g.C2) {
         if ((epi != EPI_GATE_RESID && epi != EPI_RESID) || !g.rowsq || !g.scale2 || g.scale2_stride % 4 || ((uintptr_t)g.scale2 & 15) || ((uintptr_t)g.C2 & 7) || g.rows_per_batch < 320 || g.c_seg_shift) return false;
     }
@@ -944,10 +945,14 @@ extern "C" int ltx_dbg_gemm_asm16_trace(uint32_t* out, int n_words) {
 }
 #endif
 
-int ltx_launch_gemm_asm16(const GemmArgs& g, int epi, int tile, hipStream_t s) {     // tile 0: 256 x 256, 1: 160 x 256, 2: 320 x 256
+int ltx_launch_gemm_asm16(const GemmArgs& g, int epi, int tile, hipStream_t s) {     // tile: kAsmTiles order
     ltx_prof_kernel(LTX_PROFK_GEMM_ASM16);
-    if (tile == 0) return launch_asm_epi<256, 256, 2, 2, true>(g, epi, s);
-    return tile == 1 ? launch_asm_epi<160, 256, 1, 4, true>(g, epi, s) : launch_asm_epi<320, 256, 2, 2, true>(g, epi, s);
+    switch (tile) {
+        case 0: return launch_asm_epi<256, 256, 2, 2, true>(g, epi, s);
+        case 1: return launch_asm_epi<320, 256, 2, 2, true>(g, epi, s);
+        case 2: return launch_asm_epi<160, 256, 1, 4, true>(g, epi, s);
+    }
+    LTX_FAIL(LTX_ERR_ARG, "gemm_asm16: unsupported tile");
 }
 
 // What the conv-mode kernel needs of a call: bf16 3x3x3 conv with whole 64-channel slices, a plain / residual / depth-to-space

@@ -566,26 +566,53 @@ int launch_tile(const GemmArgs& g, int epi, int tile, hipStream_t s) {
     LTX_FAIL(LTX_ERR_ARG, "gemm_big: unsupported tile");
 }
 
-struct TileInfo { int bm, bn, threads; double rate; int per_cu; const char* name; };
+struct TileInfo { int bm, bn, threads; double rate; int per_cu; };
 // rate: per-CU sustained TFLOP/s of the tile at full occupancy (tools/microbench.py tiles, MI355X, random data);
-// per_cu: blocks that fit one CU (LDS 2*(BM+BN)*128 B of 160 KiB, <= 2048 threads)
+// per_cu: blocks that fit one CU (LDS 2*(BM+BN)*128 B of 160 KiB, <= 2048 threads).  Names: kGemmPlans, same order.
 const TileInfo kTiles[] = {
-    {256, 256, 512, 1160, 1, "256x256"}, {192, 256, 512, 1190, 1, "192x256"}, {128, 256, 512, 1023, 1, "128x256"},
-    {256, 128, 512, 989, 1, "256x128"},  {192, 128, 512, 1400, 2, "192x128"}, {128, 128, 512, 1032, 2, "128x128"},
-    {160, 128, 512, 1330, 2, "160x128"}, {192, 64, 512, 900, 2, "192x64"},
-    {160, 256, 1024, 1300, 1, "160x256w16"}, {192, 256, 1024, 1300, 1, "192x256w16"},
-    {320, 256, 1024, 1300, 1, "320x256w16"}, {256, 256, 1024, 1300, 1, "256x256w16"},
+    {256, 256, 512, 1160, 1}, {192, 256, 512, 1190, 1}, {128, 256, 512, 1023, 1},
+    {256, 128, 512, 989, 1},  {192, 128, 512, 1400, 2}, {128, 128, 512, 1032, 2},
+    {160, 128, 512, 1330, 2}, {192, 64, 512, 900, 2},
+    {160, 256, 1024, 1300, 1}, {192, 256, 1024, 1300, 1},
+    {320, 256, 1024, 1300, 1}, {256, 256, 1024, 1300, 1},
 };
 constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
 // a tile is a candidate for an N-wide output: 64-wide tiles only for narrow outputs, 256-wide only beyond 128 columns
 bool tile_fits(const TileInfo& t, int N) { return t.rate > 0 && !(t.bn > 128 && N <= 128) && !(t.bn == 64 && N > 64) && !(t.bn > 64 && N <= 64); }
 
+// Every plan, once, with the name the plan files and the gemm_plan option use.  The index inside a family is the family's own tile
+// index (kTiles, gemm_asm.hip's kAsmTiles, gemm_ring.hip's kRing); the order of the table is the order the tuner measures in.
+struct PlanInfo { GemmPlan p; const char* name; };
+const PlanInfo kGemmPlans[] = {
+    {{kPlanBig, 0}, "256x256"}, {{kPlanBig, 1}, "192x256"}, {{kPlanBig, 2}, "128x256"}, {{kPlanBig, 3}, "256x128"},
+    {{kPlanBig, 4}, "192x128"}, {{kPlanBig, 5}, "128x128"}, {{kPlanBig, 6}, "160x128"}, {{kPlanBig, 7}, "192x64"},
+    {{kPlanBig, 8}, "160x256w16"}, {{kPlanBig, 9}, "192x256w16"}, {{kPlanBig, 10}, "320x256w16"}, {{kPlanBig, 11}, "256x256w16"},
+    {{kPlanP8, 0}, "p8:256"}, {{kPlanP8, 1}, "p8:128"},                                  // gemm_p8.hip, BN = 256 / 128
+    {{kPlanHalo, 0}, "halo:128"}, {{kPlanHalo, 1}, "halo:256"},                          // conv_halo.hip, BN = 128 / 256 ...
+    {{kPlanHalo, 2}, "halo:64"},                                                         // ... and conv_out's 64-wide tile: the route's own choice, never measured, forced or loaded
+    {{kPlanAsm16, 0}, "asm16:256x256"}, {{kPlanAsm16, 1}, "asm16:320x256"}, {{kPlanAsm16, 2}, "asm16:160x256"},      // gemm_asm.hip, the 16x16x32 one-wave-per-SIMD kernel (linear layers)
+    {{kPlanAsm16Conv, 0}, "asm16c:256x256"},                                             // its loop in conv mode (3x3x3 convs of many channels)
+    {{kPlanRing, 0}, "ring:96x64"}, {{kPlanRing, 1}, "ring:96x96"}, {{kPlanRing, 2}, "ring:96x128"}, {{kPlanRing, 3}, "ring:64x64"},
+    {{kPlanRing, 4}, "ring:64x128"}, {{kPlanRing, 5}, "ring:128x64"}, {{kPlanRing, 6}, "ring:128x128"}, {{kPlanRing, 7}, "ring:128x96"},
+    {{kPlanRing, 8}, "ring:96x32"}, {{kPlanRing, 9}, "ring:128x32"}, {{kPlanRing, 10}, "ring:64x32"},        // gemm_ring.hip (small M)
+};
+static_assert(sizeof(kGemmPlans) / sizeof(kGemmPlans[0]) == kNumTiles + 2 + 3 + 3 + 1 + 11, "one entry per tile of every family");
+const char* plan_name(GemmPlan p) {
+    for (const PlanInfo& e : kGemmPlans) if (e.p.fam == p.fam && e.p.idx == p.idx) return e.name;
+    return "";
+}
+GemmPlan plan_from_name(const char* n) {
+    for (const PlanInfo& e : kGemmPlans) if (!strcmp(n, e.name)) return e.p;
+    return GemmPlan{};
+}
+constexpr int kHaloBn[] = {128, 256, 64}, kP8Bn[] = {256, 128};
+
 }  // namespace
 
 // Tile choice: minimise (rounds over the CUs) x (tile time); ties go to the larger tile (less operand re-reading).
 int ltx_gemm_big_pick_tile(int M, int N) {
-    const char* force = ltx_opt().gemm_plan;           // a gemm_big tile named by the gemm_plan option, e.g. "256x128" (tuning / test aid)
-    if (force[0]) for (int i = 0; i < kNumTiles; ++i) if (!strcmp(force, kTiles[i].name)) return i;
+    const GemmPlan force = plan_from_name(ltx_opt().gemm_plan);      // a gemm_big tile named by the gemm_plan option, e.g. "256x128" (tuning / test aid)
+    if (force.fam == kPlanBig) return force.idx;
     double best = 1e30; int bi = 4;
     for (int i = 0; i < kNumTiles; ++i) {
         const TileInfo& t = kTiles[i];
@@ -626,65 +653,100 @@ bool ltx_gemm_big_eligible(const GemmArgs& g, int dtype) {
 }
 
 // ---- plan selection --------------------------------------------------------------------------------------------
-// A plan is a gemm_big tile id (0 .. kNumTiles-1) or kPlanP8 + {0: BN=256, 1: BN=128} (gemm_p8.hip).  Every plan
-// accumulates K in the same order with the same MFMA, so the choice changes speed only, never a bit of the result.
-// Default: measure once per problem shape (first call: each candidate runs into a scratch output, best of the timed
-// launches wins, cached for the life of the process).  LTX_GEMM_TUNE=0 falls back to the static cost model;
-// LTX_GEMM_TILE / LTX_GEMM_P8 force a plan (tests, A/B runs).
+// A plan (GemmPlan, kernels.h) is a kernel family and a tile of it: an entry of kGemmPlans.  Every plan accumulates K in the same
+// order with the same MFMA, so the choice changes speed only, never a bit of the result.  Default: measure once per problem
+// shape (first call: each candidate runs into a scratch output, best of the timed launches wins, cached for the life of the
+// process; ltx_plan_save / ltx_plan_load carry the cache between processes).  Option gemm_tune=0 / ltx_set_autotune(0) fall back
+// to the static cost model; option gemm_plan forces a plan, option gemm_off leaves families out (tests, A/B runs).
 namespace {
-constexpr int kPlanP8 = 100;
-constexpr int kPlanHalo = 200;           // + {0: BN=128, 1: BN=256} (conv_halo.hip)
-constexpr int kPlanAsm16 = 300;          // + {0: 256 x 256, 1: 160 x 256, 2: 320 x 256} (gemm_asm.hip, the 16x16x32 one-wave-per-SIMD kernel; linear layers)
-constexpr int kPlanAsm16Conv = 350;      // gemm_asm.hip's loop in conv mode, tile 256 x 256 (3x3x3 convs of many channels: the VAE mid block; split shapes too: it keeps gemm_big's K partition)
-constexpr int kPlanRing = 400;           // + tile index of gemm_ring.hip (small-M linear layers; split shapes too: it keeps gemm_big's K partition)
 struct PlanKey {
-    int M, N, K, conv, ntaps, T, H, W;
+    int M, N, K, conv, ntaps, T, H, W;      // conv: 1 a conv, 2 a depth-to-space conv, 3 a linear layer with deferred K ranges (their own measurements)
     bool operator<(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }
 };
-std::map<PlanKey, int> g_plans;
+std::map<PlanKey, GemmPlan> g_plans;
 std::mutex g_plan_mu;
+std::atomic<int> g_autotune{1};      // ltx_set_autotune(0): never measure inside a call (cached / loaded plans, else the static model)
 
-// The predicates tune_plan applies before it measures a plan: a cached / loaded plan must pass them again for the shape
-// it is used on (a stale or hand-edited plan file, or one saved under other LTX_* settings).
-bool plan_shape_ok(int plan, int N, int nk, bool split_shape) {
-    if (plan >= kPlanRing) return plan < kPlanRing + ltx_gemm_ring_tiles() && N >= 32 && N % 4 == 0;
-    if (plan == kPlanAsm16Conv) return nk >= 2 && N >= 1024 && N % 8 == 0;
-    if (plan >= kPlanAsm16) return plan <= kPlanAsm16 + 2 && !split_shape && nk >= 2 && N >= 512 && N % 8 == 0;
-    if (plan >= kPlanHalo) return plan <= kPlanHalo + 1 && !split_shape;
-    if (plan >= kPlanP8) return plan <= kPlanP8 + 1 && !split_shape && nk >= 2 && N > 64 && !(plan == kPlanP8 && N <= 128);
-    return plan >= 0 && plan < kNumTiles && tile_fits(kTiles[plan], N);
+PlanKey plan_key(const GemmArgs& g, int epi) {
+    PlanKey key; memset(&key, 0, sizeof(key));
+    key.M = g.M; key.N = g.N; key.K = g.K; key.conv = g.conv ? (epi == EPI_D2S ? 2 : 1) : (g.defer_parts ? 3 : 0);
+    if (g.conv) { key.ntaps = g.ntaps; key.T = g.T; key.H = g.H; key.W = g.Wd; }
+    return key;
 }
-bool plan_ok(const GemmArgs& g, int epi, int plan) {
-    const int nk = (g.K + 63) / 64 * (g.conv ? g.ntaps : 1);
-    if (!plan_shape_ok(plan, g.N, nk, ltx_gemm_split_factor(g) > 1)) return false;
-    // the encoder's space-to-depth epilogue lives in the gemm_big tiles and the halo-staged kernel; the other families fall back
-    if (epi == EPI_S2D && plan >= kPlanP8 && !(plan >= kPlanHalo && plan < kPlanAsm16)) return false;
-    if (plan >= kPlanRing) return ltx_gemm_ring_tile_fits(g, epi, plan - kPlanRing);
-    if (plan == kPlanAsm16Conv) return ltx_gemm_asm16_conv_fits(g, epi);
-    if (plan >= kPlanAsm16) return ltx_gemm_asm16_fits(g, epi);
-    if (plan >= kPlanHalo) return true;                    // run_plan checks the halo kernel's own eligibility (epilogue-dependent)
-    if (plan >= kPlanP8) return ltx_gemm_p8_fits(g);
-    (void)epi;
+
+// May this plan serve this call?  ONE predicate for a forced plan, a cached or loaded one (a stale or hand-edited plan file, or
+// one saved under other options) and the tuner's candidates.  First the part the shape's key decides - all that
+// ltx_plan_load can check:
+bool plan_shape_valid(const PlanKey& k, GemmPlan p) {
+    const bool conv = k.conv == 1 || k.conv == 2;
+    if (k.M <= 0 || k.N <= 0 || k.K <= 0 || k.conv < 0 || k.conv > 3 || (conv && (k.ntaps <= 0 || k.T <= 0 || k.H <= 0 || k.W <= 0))) return false;
+    if (k.conv == 3 && p.fam != kPlanRing) return false;           // K ranges left to the consumer: gemm_ring.hip's tiles only
+    GemmArgs g; g.M = k.M; g.N = k.N; g.K = k.K; g.conv = conv; g.ntaps = conv ? k.ntaps : 1;
+    // split shapes run gemm_big tiles, ring tiles or the conv-mode asm16 tile: one K partition whatever the plan
+    const bool split = ltx_gemm_split_factor(g) > 1, conv27 = conv && k.ntaps == 27;
+    const int nk = (k.K + 63) / 64 * g.ntaps;
+    if (p.idx < 0) return false;
+    switch (p.fam) {
+        case kPlanBig: return p.idx < kNumTiles && tile_fits(kTiles[p.idx], k.N);
+        case kPlanP8: return p.idx < 2 && !split && nk >= 2 && k.N > kP8Bn[p.idx] / 2;
+        case kPlanHalo: return p.idx < 2 && !split && conv27 && k.K % 64 == 0 && k.N % kHaloBn[p.idx] == 0;
+        case kPlanAsm16: return p.idx < 3 && !split && !conv && nk >= 2 && k.N >= 512 && k.N % 8 == 0 && k.K % 64 == 0;
+        case kPlanAsm16Conv: return p.idx == 0 && conv27 && nk >= 2 && k.N >= 1024 && k.N % 8 == 0 && k.K % 64 == 0;
+        case kPlanRing: return p.idx < ltx_gemm_ring_tiles() && k.N >= 32 && k.N % 4 == 0 && k.K % 8 == 0 && k.M <= 2048 &&
+                               (!conv || (conv27 && k.conv != 2 && ltx_gemm_ring_tile_bn(p.idx) >= 64));
+    }
+    return false;
+}
+// ... then the family's own test of the call's operands (strides, pointers, epilogue)
+bool plan_valid(const GemmArgs& g, int epi, GemmPlan p) {
+    if (!plan_shape_valid(plan_key(g, epi), p)) return false;
+    // the encoder's space-to-depth epilogue lives in the gemm_big tiles and the halo-staged kernel
+    if (epi == EPI_S2D && p.fam != kPlanBig && p.fam != kPlanHalo) return false;
+    switch (p.fam) {
+        case kPlanBig: return true;
+        case kPlanP8: return ltx_gemm_p8_fits(g);
+        case kPlanHalo: return ltx_conv_halo_eligible(g, epi, kHaloBn[p.idx]);
+        case kPlanAsm16: return ltx_gemm_asm16_fits(g, epi);
+        case kPlanAsm16Conv: return ltx_gemm_asm16_conv_fits(g, epi);
+        case kPlanRing: return ltx_gemm_ring_tile_fits(g, epi, p.idx);
+    }
+    return false;
+}
+// What is worth measuring, among the valid plans: not a family that gemm_off leaves out (a forced or loaded plan of it still runs), and
+bool tune_candidate(const GemmArgs& g, GemmPlan p) {
+    const unsigned off = ltx_opt().gemm_off;
+    switch (p.fam) {
+        case kPlanP8: return !(off & LTX_FAM_P8);
+        case kPlanHalo: return !(off & LTX_FAM_HALO);
+        case kPlanAsm16: return !(off & LTX_FAM_ASM16);
+        // from 1024 input channels up only: at 512 / 256 it ties with / loses to the halo-staged kernel in the pipeline (1637-1675
+        // vs 1617-1623 us, 3572 vs 3365-3462) while back-to-back repeats of the measurement favour it
+        // (profiles/r5zz_bench_c2_kernel_stats.md, launches 22 and 33); gemm_plan=asm16c:256x256 still forces it
+        case kPlanAsm16Conv: return !(off & LTX_FAM_ASM16) && g.Cin >= 1024;
+        // a ring tile is built for grids of about one round: skip the ones that would need more than three
+        case kPlanRing: return (int64_t)cdiv(g.M, ltx_gemm_ring_tile_bm(p.idx)) * cdiv(g.N, ltx_gemm_ring_tile_bn(p.idx)) * ltx_gemm_split_factor(g) <= 768;
+    }
     return true;
 }
+}  // namespace
 
-int run_plan(const GemmArgs& g, int epi, int plan, hipStream_t s) {
-    if (!plan_ok(g, epi, plan)) plan = ltx_gemm_big_pick_tile(g.M, g.N);
-    if (plan >= kPlanRing) return ltx_launch_gemm_ring(g, epi, plan - kPlanRing, s);
-    if (plan == kPlanAsm16Conv) return ltx_launch_gemm_asm16_conv(g, epi, s);
-    if (plan >= kPlanAsm16) return ltx_launch_gemm_asm16(g, epi, plan - kPlanAsm16, s);
-    if (plan >= kPlanHalo) {
-        const int bn = plan == kPlanHalo ? 128 : 256;
-        if (ltx_conv_halo_eligible(g, epi, bn)) return ltx_launch_conv_halo(g, epi, bn, s);
-        plan = ltx_gemm_big_pick_tile(g.M, g.N);           // an epilogue the halo kernel does not carry
+// The launch of a route's plan: one switch over the family
+int ltx_launch_gemm_plan(const GemmArgs& g_in, int epi, GemmPlan p, hipStream_t s) {
+    GemmArgs g = g_in;
+    g.xcd_remap = ltx_exp("xcd_remap", 1);      // XCD-contiguous tile order (measured, tools/microbench.py xcd: linear +3..19 %, conv +5 %)
+    switch (p.fam) {
+        case kPlanBig: ltx_prof_kernel(LTX_PROFK_GEMM_BIG); return g.conv ? launch_tile<true>(g, epi, p.idx, s) : launch_tile<false>(g, epi, p.idx, s);
+        case kPlanP8: return ltx_launch_gemm_p8(g, epi, kP8Bn[p.idx & 1], s);
+        case kPlanHalo: return ltx_launch_conv_halo(g, epi, kHaloBn[p.idx % 3], s);
+        case kPlanAsm16: return ltx_launch_gemm_asm16(g, epi, p.idx, s);
+        case kPlanAsm16Conv: return ltx_launch_gemm_asm16_conv(g, epi, s);
+        case kPlanRing: return ltx_launch_gemm_ring(g, epi, p.idx, s);
     }
-    if (plan >= kPlanP8) return ltx_launch_gemm_p8(g, epi, plan == kPlanP8 ? 256 : 128, s);
-    ltx_prof_kernel(LTX_PROFK_GEMM_BIG);
-    return g.conv ? launch_tile<true>(g, epi, plan, s) : launch_tile<false>(g, epi, plan, s);
+    LTX_FAIL(LTX_ERR_ARG, "gemm: no such plan");
 }
 
-int tune_plan(const GemmArgs& g_in, int epi, hipStream_t s, int fallback, int* plan_out) {
-    *plan_out = fallback;
+namespace {
+int tune_plan(const GemmArgs& g_in, int epi, hipStream_t s, GemmPlan* best_plan) {
     // plain bias epilogue into a scratch [M, N] output - except the upsamplers' depth-to-space convs, measured with their own epilogue
     // (its scattered 8-byte stores cost the kernels differently; the output, (2T - 1) x 2H x 2W x N / 8 rows, fits the same scratch)
     const int tepi = (g_in.conv && epi == EPI_D2S) ? EPI_D2S : EPI_BIAS;
@@ -703,43 +765,20 @@ int tune_plan(const GemmArgs& g_in, int epi, hipStream_t s, int fallback, int* p
     } guard{scratch};
     HIP_TRY(hipEventCreate(&guard.e0)); HIP_TRY(hipEventCreate(&guard.e1));
     const hipEvent_t e0 = guard.e0, e1 = guard.e1;
-    const int nk = (g.K + 63) / 64 * (g.conv ? g.ntaps : 1);
     float best = 1e30f;
-    const bool p8_off = ltx_opt().gemm_off & LTX_FAM_P8, halo_off = ltx_opt().gemm_off & LTX_FAM_HALO;
-    const bool split_shape = ltx_gemm_split_factor(g) > 1;     // split shapes run gemm_big tiles only (same K partition in every plan)
-    const bool asm16_off = ltx_opt().gemm_off & LTX_FAM_ASM16;
-    for (int plan = defer ? kPlanRing : 0; plan < kPlanRing + ltx_gemm_ring_tiles(); ++plan) {
-        if (plan >= kPlanRing) {
-            if (!plan_ok(g, tepi, plan)) continue;
-            // a ring tile is built for grids of about one round: skip the ones that would need more than three
-            if ((int64_t)cdiv(g.M, ltx_gemm_ring_tile_bm(plan - kPlanRing)) * cdiv(g.N, ltx_gemm_ring_tile_bn(plan - kPlanRing)) * ltx_gemm_split_factor(g) > 768) continue;
-        } else if (plan > kPlanAsm16Conv) { plan = kPlanRing - 1; continue; }
-        else if (plan == kPlanAsm16Conv) {
-            // a candidate from 1024 input channels up only: at 512 / 256 it ties with / loses to the halo-staged kernel in the
-            // pipeline (1637-1675 vs 1617-1623 us, 3572 vs 3365-3462) while back-to-back repeats of the measurement favour it
-            // (profiles/r5zz_bench_c2_kernel_stats.md, launches 22 and 33); gemm_plan=asm16c:256x256 still forces it
-            if (asm16_off || g.Cin < 1024 || !plan_ok(g, tepi, plan)) continue;
-        } else if (plan >= kPlanAsm16 + 3) { plan = kPlanAsm16Conv - 1; continue; }
-        else if (plan >= kPlanAsm16) {
-            if (asm16_off || !plan_ok(g, tepi, plan)) continue;
-        } else if (plan >= kPlanHalo + 2) { plan = kPlanAsm16 - 1; continue; }
-        else if (plan < kPlanP8) {
-            if (plan >= kNumTiles) { plan = kPlanP8 - 1; continue; }
-            if (!tile_fits(kTiles[plan], g.N)) continue;
-        } else if (plan < kPlanHalo) {
-            if (plan >= kPlanP8 + 2) { plan = kPlanHalo - 1; continue; }
-            if (split_shape || p8_off || nk < 2 || g.N <= 64 || (plan == kPlanP8 && g.N <= 128) || !ltx_gemm_p8_fits(g)) continue;
-        } else if (split_shape || halo_off || !ltx_conv_halo_eligible(g, tepi, plan == kPlanHalo ? 128 : 256)) continue;
+    for (const PlanInfo& cand : kGemmPlans) {
+        const GemmPlan plan = cand.p;
+        if (!plan_valid(g, tepi, plan) || !tune_candidate(g, plan)) continue;
         // warm launch (code object load, caches), timed on its own to size the measurement: ~1.5 ms of launches,
         // 3..16 of them, best of three rounds
         HIP_TRY(hipEventRecord(e0, s));
-        int rc = run_plan(g, tepi, plan, s);
+        int rc = ltx_launch_gemm_plan(g, tepi, plan, s);
         if (rc != LTX_OK) continue;
         HIP_TRY(hipEventRecord(e1, s));
         HIP_TRY(hipEventSynchronize(e1));
         float ms = 0.f; HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         if (ms >= 10.f) {                                    // a launch this long (the 13B decode's last stages) is its own measurement
-            if (ms < best) { best = ms; *plan_out = plan; }
+            if (ms < best) { best = ms; *best_plan = plan; }
             continue;
         }
         int n = ms > 0.f ? (int)(1.5f / ms) : 16;
@@ -747,60 +786,103 @@ int tune_plan(const GemmArgs& g_in, int epi, hipStream_t s, int fallback, int* p
         for (int round = 0; round < 3; ++round) {
             HIP_TRY(hipEventRecord(e0, s));
             bool ok = true;
-            for (int i = 0; i < n; ++i) ok = ok && run_plan(g, tepi, plan, s) == LTX_OK;
+            for (int i = 0; i < n; ++i) ok = ok && ltx_launch_gemm_plan(g, tepi, plan, s) == LTX_OK;
             HIP_TRY(hipEventRecord(e1, s));
             HIP_TRY(hipEventSynchronize(e1));
             HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
             ms /= (float)n;
-            if (ok && ms < best) { best = ms; *plan_out = plan; }     // a plan whose launch failed is never the winner
+            if (ok && ms < best) { best = ms; *best_plan = plan; }     // a plan whose launch failed is never the winner
         }
     }
     return LTX_OK;
 }
-}  // namespace
 
-namespace {
-std::atomic<int> g_autotune{1};      // ltx_set_autotune(0): never measure inside a call (cached / loaded plans, else the static model)
-
-PlanKey plan_key(const GemmArgs& g, int epi) {
-    PlanKey key; memset(&key, 0, sizeof(key));
-    key.M = g.M; key.N = g.N; key.K = g.K; key.conv = g.conv ? (epi == EPI_D2S ? 2 : 1) : (g.defer_parts ? 3 : 0);      // 2: a depth-to-space conv, 3: a linear layer with deferred K ranges (their own measurements)
-    if (g.conv) { key.ntaps = g.ntaps; key.T = g.T; key.H = g.H; key.W = g.Wd; }
-    return key;
-}
-const char* plan_name(int plan) {
-    if (plan >= kPlanRing) return ltx_gemm_ring_tile_name(plan - kPlanRing);
-    if (plan == kPlanAsm16Conv) return "asm16c:256x256";
-    if (plan >= kPlanAsm16) return plan == kPlanAsm16 ? "asm16:256x256" : (plan == kPlanAsm16 + 1 ? "asm16:160x256" : "asm16:320x256");
-    if (plan >= kPlanHalo) return plan == kPlanHalo ? "halo:128" : "halo:256";
-    if (plan >= kPlanP8) return plan == kPlanP8 ? "p8:256" : "p8:128";
-    return plan >= 0 && plan < kNumTiles ? kTiles[plan].name : "";
-}
-int plan_from_name(const char* n) {
-    for (int i = 0; i < ltx_gemm_ring_tiles(); ++i) if (!strcmp(n, ltx_gemm_ring_tile_name(i))) return kPlanRing + i;
-    if (!strcmp(n, "asm16c:256x256")) return kPlanAsm16Conv;
-    if (!strcmp(n, "asm16:256x256")) return kPlanAsm16; if (!strcmp(n, "asm16:160x256")) return kPlanAsm16 + 1; if (!strcmp(n, "asm16:320x256")) return kPlanAsm16 + 2;
-    if (!strcmp(n, "halo:128")) return kPlanHalo; if (!strcmp(n, "halo:256")) return kPlanHalo + 1;
-    if (!strcmp(n, "p8:256")) return kPlanP8; if (!strcmp(n, "p8:128")) return kPlanP8 + 1;
-    for (int i = 0; i < kNumTiles; ++i) if (!strcmp(n, kTiles[i].name)) return i;
-    return -1;
-}
 // *plan holds the static model's choice on entry; replaced by the cached plan, or by a fresh measurement when allowed
-int cached_or_tuned_plan(const GemmArgs& g, int epi, hipStream_t s, int* plan) {
+int cached_or_tuned_plan(const GemmArgs& g, int epi, hipStream_t s, bool measure, GemmPlan* plan) {
     if (!ltx_opt().gemm_tune) return LTX_OK;
     const PlanKey key = plan_key(g, epi);
     std::lock_guard<std::mutex> lock(g_plan_mu);
     auto it = g_plans.find(key);
     if (it == g_plans.end()) {
-        if (!g_autotune.load()) return LTX_OK;
-        int tuned = *plan;
-        LTX_TRY(tune_plan(g, epi, s, *plan, &tuned));
+        if (!measure || !g_autotune.load()) return LTX_OK;
+        GemmPlan tuned = *plan;
+        LTX_TRY(tune_plan(g, epi, s, &tuned));
         it = g_plans.emplace(key, tuned).first;
     }
     *plan = it->second;
     return LTX_OK;
 }
+
+GemmPlan asm16_pick(const GemmArgs& g) { return GemmPlan{kPlanAsm16, ltx_gemm_asm_pick_tile(g.M, g.N)}; }
+GemmPlan ring_pick(const GemmArgs& g) { return GemmPlan{kPlanRing, ltx_gemm_ring_pick_tile(g)}; }
+
+// The plan of a call that ltx_gemm_route_kind leaves to the plan families: forced (option gemm_plan), else cached or measured,
+// else the static model - inside the families the call's operands admit.  An empty plan: no family honours those operands.
+int choose_plan(const GemmArgs& g, int epi, hipStream_t s, bool measure, GemmPlan* chosen) {
+    const LtxOptions& o = ltx_opt();
+    *chosen = GemmPlan{};
+    // fused output norm: only conv_halo's wide epilogue carries it, on the tile as wide as the output
+    if (g.pn_on) { const GemmPlan p{kPlanHalo, g.N == 256 ? 1 : 0}; if (g.N == kHaloBn[p.idx] && ltx_conv_halo_eligible(g, epi, g.N)) *chosen = p; return LTX_OK; }
+    const bool split = ltx_gemm_split_factor(g) > 1;
+    // conv_out (N = 48, unpatchify): the halo-staged kernel on its 64-wide tile - one staging of the 128-channel activation
+    // per nine taps instead of one per tap (the per-tap 192 x 64 tile moves 27 x 610 MB through L2 -> LDS at C2).  Same K order:
+    // same bits.  gemm_off=halo_out: the per-tap tile (A/B aid).
+    if (!split && g.conv && epi == EPI_UNPATCH && !(o.gemm_off & LTX_FAM_HALO_OUT) && ltx_conv_halo_eligible(g, epi, 64)) { *chosen = GemmPlan{kPlanHalo, 2}; return LTX_OK; }
+
+    // base: the choice that always serves the case; model: the static model's (no measured plan); only: the one family a call with special operands is held to
+    GemmPlan base{kPlanBig, ltx_gemm_big_pick_tile(g.M, g.N)}, model;
+    int only = -1;
+    if (g.defer_parts) {          // K-range sums left to the consumer: gemm_ring.hip's tiles only, a bare linear layer of at most 512 rows (ltx_gemm_defer_ok)
+        if (epi != EPI_BIAS || g.bias || g.conv || g.M > 512 || !ltx_gemm_ring_fits(g, EPI_BIAS)) return LTX_OK;
+        only = kPlanRing; model = base = ring_pick(g);
+    } else if (g.C2 || g.rs_sq) { // norm fold (kernels.h): only gemm_asm16's wide epilogue carries the second output / the row scale (ltx_gemm_fold_ok)
+        if (!ltx_gemm_fold_ok(g, epi)) return LTX_OK;
+        only = kPlanAsm16; model = base = asm16_pick(g);
+    } else {
+        model = base;
+        // convs over planes of at most 512 voxels (C1's mid block, an edge tile of the tiled decode), all of them split shapes, on the
+        // deep ring (72 -> 41 us at 384 voxels x 1024 channels, profiles/r5l_ring_conv_probe.jsonl); small-M linear layers that are
+        // not split (see ltx_gemm_split_factor: a gemm_big tile would leave most CUs idle): the ring tile whose grid wastes the least of a round
+        if (g.M <= 512 && (g.conv != 0) == split && ltx_gemm_ring_fits(g, epi)) model = ring_pick(g);
+        // the large linear layers take the one-wave-per-SIMD kernel, tile by whole rounds x tile area (it won every such shape that was measured)
+        if (!g.conv && !(o.gemm_off & LTX_FAM_ASM16) && g.M >= 2048 && g.N >= 1024 && ltx_gemm_asm16_fits(g, epi)) model = asm16_pick(g);
+    }
+    const auto usable = [&](GemmPlan p) { return p.ok() && (only < 0 || p.fam == only) && plan_valid(g, epi, p); };
+
+    // Option gemm_plan (tests, A/B): one plan forced wherever the call is eligible for it - a full plan name, or a family name
+    // ("asm16", "ring") for that family's own tile choice.  A gemm_big tile name is always honoured (ltx_gemm_big_pick_tile: base).
+    GemmPlan forced;
+    if (!strcmp(o.gemm_plan, "asm16")) { if (!g.conv && g.M >= 2048 && g.N >= 1024) forced = asm16_pick(g); }
+    else if (!strcmp(o.gemm_plan, "ring")) { if (ltx_gemm_ring_fits(g, epi)) forced = ring_pick(g); }
+    else if (o.gemm_plan[0]) forced = plan_from_name(o.gemm_plan);
+    if (forced.fam != kPlanBig && usable(forced)) { *chosen = forced; return LTX_OK; }
+    // (a call held to one family leaves the cache alone whenever gemm_plan is set; the others only under a forced gemm_big tile)
+    GemmPlan plan = forced.fam == kPlanBig ? base : model;
+    if (only < 0 ? forced.fam != kPlanBig : !o.gemm_plan[0]) LTX_TRY(cached_or_tuned_plan(g, epi, s, measure, &plan));
+    *chosen = usable(plan) ? plan : base;
+    return LTX_OK;
+}
 }  // namespace
+
+// ---- the route of a call (kernels.h) ---------------------------------------------------------------------------------
+int ltx_gemm_route_kind(const GemmArgs& g, int dtype, int epi) {
+    if (ltx_gemm_asm_eligible(g, dtype, epi)) return LTX_ROUTE_ASM32;
+    return ltx_gemm_big_eligible(g, dtype) ? LTX_ROUTE_PLAN : LTX_ROUTE_GEMM128;
+}
+int ltx_gemm_route(const GemmArgs& g, int dtype, int epi, hipStream_t s, bool measure, GemmRoute* r) {
+    r->kind = ltx_gemm_route_kind(g, dtype, epi); r->plan = GemmPlan{};
+    if (r->kind == LTX_ROUTE_PLAN) LTX_TRY(choose_plan(g, epi, s, measure, &r->plan));
+    return LTX_OK;
+}
+const char* ltx_gemm_route_name(const GemmRoute& r) { return r.kind == LTX_ROUTE_PLAN ? plan_name(r.plan) : (r.kind == LTX_ROUTE_ASM32 ? "asm32" : "gemm128"); }
+// Operands that only one family reads, on a route that is not that family's: the reason, else null
+const char* ltx_gemm_route_refusal(const GemmArgs& g, const GemmRoute& r) {
+    const int fam = r.kind == LTX_ROUTE_PLAN ? r.plan.fam : -1;
+    if (g.defer_parts && fam != kPlanRing) return "gemm: defer_parts set on a call that is not routed to the ring tiles (ask ltx_gemm_defer_ok first)";
+    if ((g.C2 || g.rs_sq) && fam != kPlanAsm16) return "gemm: norm-fold arguments (C2 / rs_sq) on a call that is not routed to gemm_asm16 (ask ltx_gemm_fold_ok first)";
+    if (g.pn_on && r.kind == LTX_ROUTE_PLAN && fam != kPlanHalo) return "gemm: the fused output norm needs conv_halo's tile as wide as the output (128 / 256 channels)";
+    return nullptr;
+}
 
 // ---- public plan control (include/ltxhip.h) ---------------------------------------------------------------------------
 extern "C" int ltx_set_autotune(int enabled) { g_autotune.store(enabled ? 1 : 0); return LTX_OK; }
@@ -820,123 +902,28 @@ extern "C" int ltx_plan_load(const char* path) {
     FILE* f = fopen(path, "r");
     if (!f) LTX_FAIL(LTX_ERR_ARG, std::string("ltx_plan_load: cannot read ") + path);
     char line[256], name[64];
+    std::string err;
     std::lock_guard<std::mutex> lock(g_plan_mu);
-    int n = 0;
-    while (fgets(line, sizeof(line), f)) {
+    while (err.empty() && fgets(line, sizeof(line), f)) {
         if (line[0] == '#' || line[0] == '\n') continue;
         PlanKey key; memset(&key, 0, sizeof(key));
-        if (sscanf(line, "%d %d %d %d %d %d %d %d %63s", &key.M, &key.N, &key.K, &key.conv, &key.ntaps, &key.T, &key.H, &key.W, name) != 9) { fclose(f); LTX_FAIL(LTX_ERR_ARG, std::string("ltx_plan_load: malformed line: ") + line); }
-        const int plan = plan_from_name(name);
-        if (plan < 0) { fclose(f); LTX_FAIL(LTX_ERR_ARG, std::string("ltx_plan_load: unknown plan name: ") + name); }
-        {   // the shape-level predicates of tune_plan (run_plan re-checks the call's own operands and falls back to the static model)
-            const bool kconv = key.conv == 1 || key.conv == 2;                                            // 2: a depth-to-space conv; 3: a linear layer with deferred K ranges
-            GemmArgs g; g.M = key.M; g.N = key.N; g.K = key.K; g.conv = kconv ? 1 : 0; g.ntaps = kconv ? key.ntaps : 1;
-            const int nk = (key.K + 63) / 64 * g.ntaps;
-            const bool dims_ok = key.M > 0 && key.N > 0 && key.K > 0 && key.conv >= 0 && key.conv <= 3 && (!kconv || (key.ntaps > 0 && key.T > 0 && key.H > 0 && key.W > 0)) && (key.conv != 3 || plan >= kPlanRing);
-            if (!dims_ok || !plan_shape_ok(plan, key.N, nk, ltx_gemm_split_factor(g) > 1) || (plan >= kPlanRing && ((kconv && (key.ntaps != 27 || key.conv == 2 || ltx_gemm_ring_tile_bn(plan - kPlanRing) < 64)) || key.K % 8 || key.M > 2048)) || (plan == kPlanAsm16Conv && (!kconv || key.ntaps != 27 || key.K % 64)) || (plan >= kPlanAsm16 && plan < kPlanAsm16Conv && (kconv || key.conv == 3 || key.K % 64)) || (plan >= kPlanHalo && plan < kPlanAsm16 && (!kconv || key.ntaps != 27 || key.K % 64 || key.N % (plan == kPlanHalo ? 128 : 256)))) {
-                fclose(f); LTX_FAIL(LTX_ERR_ARG, std::string("ltx_plan_load: plan not valid for its shape: ") + line);
-            }
-        }
-        g_plans[key] = plan; ++n;
+        if (sscanf(line, "%d %d %d %d %d %d %d %d %63s", &key.M, &key.N, &key.K, &key.conv, &key.ntaps, &key.T, &key.H, &key.W, name) != 9) { err = "malformed line: "; break; }
+        const GemmPlan plan = plan_from_name(name);
+        if (!plan.ok()) err = "unknown plan name: ";
+        // the shape-level part of plan_valid (a call checks its own operands too and falls back to the static model)
+        else if (!plan_shape_valid(key, plan)) err = "plan not valid for its shape: ";
+        else g_plans[key] = plan;
     }
     fclose(f);
+    if (!err.empty()) LTX_FAIL(LTX_ERR_ARG, "ltx_plan_load: " + err + line);
     return LTX_OK;
-}
-
-int ltx_launch_gemm_big(const GemmArgs& g_in, int epi, hipStream_t s) {
-    GemmArgs g = g_in;
-    ltx_prof_kernel(LTX_PROFK_GEMM_BIG);                   // the kernels this dispatcher hands over to overwrite it
-    // XCD-contiguous tile order (measured, tools/microbench.py xcd: linear +3..19 %, conv +5 %)
-    g.xcd_remap = ltx_exp("xcd_remap", 1);
-    if (g.pn_on) return ltx_launch_conv_halo(g, epi, g.N, s);      // fused output norm: only that kernel's wide epilogue carries it
-    if (g.defer_parts) {                                   // K-range sums left to the consumer: gemm_ring.hip's tiles only (the caller asked ltx_gemm_defer_ok)
-        if (epi != EPI_BIAS || g.bias || g.conv || g.M > 512 || !ltx_gemm_ring_fits(g, EPI_BIAS)) LTX_FAIL(LTX_ERR_ARG, "gemm: defer_parts needs a bare linear layer of at most 512 rows (ltx_gemm_defer_ok)");
-        int plan = kPlanRing + ltx_gemm_ring_pick_tile(g);
-        if (ltx_opt().gemm_plan[0]) { const int f = plan_from_name(ltx_opt().gemm_plan); if (f >= kPlanRing && plan_ok(g, epi, f)) plan = f; }
-        else {
-            int cached = plan;
-            (void)cached_or_tuned_plan(g, epi, s, &cached);
-            if (cached >= kPlanRing && plan_ok(g, epi, cached)) plan = cached;
-        }
-        return ltx_launch_gemm_ring(g, epi, plan - kPlanRing, s);
-    }
-    const LtxOptions& o = ltx_opt();
-    if (g.C2 || g.rs_sq) {
-        // Norm fold (kernels.h): only gemm_asm16's wide epilogue carries the second output / the row scale (the caller asked
-        // ltx_gemm_fold_ok).  Tile: the shape's measured plan where that is an asm16 tile (or a forced one), else the family's own choice.
-        if (!ltx_gemm_fold_ok(g, epi)) LTX_FAIL(LTX_ERR_ARG, "gemm: norm-fold arguments on a call gemm_asm16 does not serve (ltx_gemm_fold_ok)");
-        const int t = ltx_gemm_asm_pick_tile(g.M, g.N);                  // kAsmTiles order: 256 x 256, 320 x 256, 160 x 256
-        int plan = kPlanAsm16 + (t == 0 ? 0 : (t == 1 ? 2 : 1));
-        if (o.gemm_plan[0]) { const int f = plan_from_name(o.gemm_plan); if (f >= kPlanAsm16 && f < kPlanAsm16 + 3) plan = f; }
-        else {
-            int cached = plan;
-            (void)cached_or_tuned_plan(g, epi, s, &cached);
-            if (cached >= kPlanAsm16 && cached < kPlanAsm16 + 3) plan = cached;
-        }
-        return ltx_launch_gemm_asm16(g, epi, plan - kPlanAsm16, s);
-    }
-    const bool split_shape = ltx_gemm_split_factor(g) > 1;
-    const int nk = (g.K + 63) / 64 * (g.conv ? g.ntaps : 1);
-    // Option gemm_plan (tests, A/B): one plan forced wherever the call is eligible for it - a full plan name, or a family name
-    // ("asm16", "ring") for that family's own tile choice.  A gemm_big tile name is always honoured (ltx_gemm_big_pick_tile).
-    int forced = -1;
-    if (o.gemm_plan[0]) {
-        if (!strcmp(o.gemm_plan, "asm16")) {
-            if (!g.conv && g.M >= 2048 && g.N >= 1024) { const int t = ltx_gemm_asm_pick_tile(g.M, g.N); forced = kPlanAsm16 + (t == 0 ? 0 : (t == 1 ? 2 : 1)); }   // kAsmTiles order: 256 x 256, 320 x 256, 160 x 256
-        } else if (!strcmp(o.gemm_plan, "ring")) {
-            if (ltx_gemm_ring_fits(g, epi)) forced = kPlanRing + ltx_gemm_ring_pick_tile(g);
-        } else forced = plan_from_name(o.gemm_plan);
-        if (forced >= kNumTiles) {                          // not a gemm_big tile: the plan's own predicates for THIS call
-            bool ok = plan_ok(g, epi, forced);
-            if (forced >= kPlanHalo && forced < kPlanAsm16) ok = ok && g.conv && ltx_conv_halo_eligible(g, epi, forced == kPlanHalo ? 128 : 256);
-            if (forced >= kPlanP8 && forced < kPlanHalo) ok = ok && nk >= 2;
-            if (split_shape && forced < kPlanRing && forced != kPlanAsm16Conv) ok = false;      // split shapes: gemm_big tiles, ring tiles or the conv-mode asm16 tile (one K partition whatever the plan)
-            if (!ok) forced = -1;
-        }
-    }
-    const bool big_forced = forced >= 0 && forced < kNumTiles;
-    if (forced >= kPlanRing) return ltx_launch_gemm_ring(g, epi, forced - kPlanRing, s);
-    if (forced == kPlanAsm16Conv) return ltx_launch_gemm_asm16_conv(g, epi, s);
-    if (split_shape) {                                     // gemm_big tiles (or gemm_ring's, which keep their K partition): one partition whatever the plan
-        int plan = ltx_gemm_big_pick_tile(g.M, g.N);
-        if (!big_forced) {
-            // static model: convs over planes of at most 512 voxels (C1's mid block, an edge tile of the tiled decode) on the deep ring
-            // (72 -> 41 us at 384 voxels x 1024 channels, profiles/r5l_ring_conv_probe.jsonl)
-            if (g.conv && g.M <= 512 && ltx_gemm_ring_fits(g, epi)) plan = kPlanRing + ltx_gemm_ring_pick_tile(g);
-            (void)cached_or_tuned_plan(g, epi, s, &plan);
-        }
-        if (plan >= kPlanRing && plan_ok(g, epi, plan)) return ltx_launch_gemm_ring(g, epi, plan - kPlanRing, s);
-        if (plan == kPlanAsm16Conv && plan_ok(g, epi, plan)) return ltx_launch_gemm_asm16_conv(g, epi, s);
-        if (plan >= kPlanP8) plan = ltx_gemm_big_pick_tile(g.M, g.N);     // (includes the halo and asm16 families)
-        return g.conv ? launch_tile<true>(g, epi, plan, s) : launch_tile<false>(g, epi, plan, s);
-    }
-    // conv_out (N = 48, unpatchify): the halo-staged kernel on its 64-wide tile - one staging of the 128-channel activation
-    // per nine taps instead of one per tap (the per-tap 192 x 64 tile moves 27 x 610 MB through L2 -> LDS at C2).  Same K order:
-    // same bits.  gemm_off=halo_out: the per-tap tile (A/B aid).
-    if (g.conv && epi == EPI_UNPATCH && !(o.gemm_off & LTX_FAM_HALO_OUT) && ltx_conv_halo_eligible(g, epi, 64)) return ltx_launch_conv_halo(g, epi, 64, s);
-    if (forced >= kPlanP8) return run_plan(g, epi, forced, s);
-    int plan = ltx_gemm_big_pick_tile(g.M, g.N);
-    if (!big_forced) {
-        // static model, small M: the deep-ring tile whose grid wastes the least of a round (these shapes are never split, see
-        // ltx_gemm_split_factor: a gemm_big tile would leave most CUs idle)
-        if (!g.conv && g.M <= 512 && ltx_gemm_ring_fits(g, epi)) plan = kPlanRing + ltx_gemm_ring_pick_tile(g);
-        // static model (no measured plan: gemm_tune=0 / ltx_set_autotune(0) without a plan file): the large linear layers take
-        // the one-wave-per-SIMD kernel too, tile by whole rounds x tile area (it won every such shape that was measured)
-        if (!g.conv && !(o.gemm_off & LTX_FAM_ASM16) && g.M >= 2048 && g.N >= 1024 && ltx_gemm_asm16_fits(g, epi)) {
-            const int t = ltx_gemm_asm_pick_tile(g.M, g.N);              // 0: 256 x 256, 1: 320 x 256, 2: 160 x 256
-            plan = kPlanAsm16 + (t == 0 ? 0 : (t == 1 ? 2 : 1));
-        }
-        LTX_TRY(cached_or_tuned_plan(g, epi, s, &plan));
-    }
-    return run_plan(g, epi, plan, s);
 }
 
 // tuning/diagnostic aid: name of the plan cached for a shape ("" if none)
 const char* ltx_gemm_plan_name(int M, int N, int K, int conv, int ntaps, int T, int H, int W) {
-    if (!conv) {                                                   // shapes the asm family serves (by shape, not by plan)
-        GemmArgs g; g.M = M; g.N = N; g.K = K; g.lda = K;
-        if (ltx_gemm_asm_eligible(g, LTX_DT_BF16, EPI_BIAS)) return ltx_gemm_asm_tile_name(ltx_gemm_asm_pick_tile(M, N));
-    }
+    GemmArgs g; g.M = M; g.N = N; g.K = K; g.lda = K;
+    // shapes the 32x32x16 kernel serves (experiment builds; by shape, not by plan)
+    if (!conv && ltx_gemm_route_kind(g, LTX_DT_BF16, EPI_BIAS) == LTX_ROUTE_ASM32) return ltx_gemm_asm_tile_name(ltx_gemm_asm_pick_tile(M, N));
     PlanKey key; memset(&key, 0, sizeof(key));
     key.M = M; key.N = N; key.K = K; key.conv = conv;
     if (conv) { key.ntaps = ntaps; key.T = T; key.H = H; key.W = W; }

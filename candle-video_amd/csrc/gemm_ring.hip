@@ -380,12 +380,12 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void gemm_ring_kernel(const GemmA
 #endif
 }
 
-struct RingTile { int bm, bn, ns; const char* name; };
-// ns: stages that fit 160 KiB (at most 8: beyond that the ring holds more than any latency)
+struct RingTile { int bm, bn, ns; };
+// ns: stages that fit 160 KiB (at most 8: beyond that the ring holds more than any latency).  Plan names "ring:<bm>x<bn>":
+// gemm_big.hip's plan table, same order.
 const RingTile kRing[] = {
-    {96, 64, 8, "ring:96x64"}, {96, 96, 6, "ring:96x96"}, {96, 128, 5, "ring:96x128"}, {64, 64, 8, "ring:64x64"},
-    {64, 128, 6, "ring:64x128"}, {128, 64, 6, "ring:128x64"}, {128, 128, 5, "ring:128x128"}, {128, 96, 5, "ring:128x96"},
-    {96, 32, 8, "ring:96x32"}, {128, 32, 8, "ring:128x32"}, {64, 32, 8, "ring:64x32"},
+    {96, 64, 8}, {96, 96, 6}, {96, 128, 5}, {64, 64, 8}, {64, 128, 6}, {128, 64, 6}, {128, 128, 5}, {128, 96, 5},
+    {96, 32, 8}, {128, 32, 8}, {64, 32, 8},
 };
 constexpr int kNumRing = sizeof(kRing) / sizeof(kRing[0]);
 
@@ -459,7 +459,6 @@ int ltx_pack_ring_weights(const void* W, int N, int K, void* out, hipStream_t s)
     return LTX_OK;
 }
 int ltx_gemm_ring_tiles() { return kNumRing; }
-const char* ltx_gemm_ring_tile_name(int i) { return i >= 0 && i < kNumRing ? kRing[i].name : ""; }
 int ltx_gemm_ring_tile_bm(int i) { return i >= 0 && i < kNumRing ? kRing[i].bm : 1; }
 int ltx_gemm_ring_tile_bn(int i) { return i >= 0 && i < kNumRing ? kRing[i].bn : 1; }
 
@@ -492,9 +491,9 @@ bool ltx_gemm_ring_tile_fits(const GemmArgs& g, int epi, int tile) {
 bool ltx_gemm_defer_ok(const GemmArgs& g_in, int epi) {
     if (epi != EPI_GATE_RESID && epi != EPI_RESID) return false;
     GemmArgs g = g_in; g.bias = nullptr; g.resid = nullptr; g.gate = nullptr;
-    // the ring is reached through ltx_launch_gemm_big's plan dispatch only: with that family switched off (gemm_off=big) the call
-    // would fall to gemm.hip's kernel, which knows nothing of defer_parts
-    if (!ltx_gemm_big_eligible(g, LTX_DT_BF16)) return false;
+    // the ring is one of the plan families: where the route leads elsewhere (gemm_off=big: gemm.hip's kernel; experiment builds:
+    // the 32x32x16 kernel) nothing knows of defer_parts
+    if (ltx_gemm_route_kind(g, LTX_DT_BF16, EPI_BIAS) != LTX_ROUTE_PLAN) return false;
     return g.M <= 512 && g.N % 8 == 0 && !g.rowsq && !g.c_seg_shift && ltx_gemm_ring_fits(g, EPI_BIAS);
 }
 

@@ -94,22 +94,33 @@ struct GemmArgs {
     unsigned* sk_cnt = nullptr;   // arrival counters [tail tile], zeroed before the launch
 };
 int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s);
+// Where ltx_launch_gemm sends a call (gemm_big.hip, "the route of a call"): gemm.hip's 128 x 128 kernel, round 1's 32x32x16 kernel
+// (experiment builds) or a plan - a kernel family and a tile of it (gemm_big.hip's plan table).
+enum PlanFamily { kPlanBig, kPlanP8, kPlanHalo, kPlanAsm16, kPlanAsm16Conv, kPlanRing };
+struct GemmPlan { int fam = -1, idx = 0; bool ok() const { return fam >= 0; } };
+enum { LTX_ROUTE_GEMM128 = 0, LTX_ROUTE_ASM32 = 1, LTX_ROUTE_PLAN = 2 };
+struct GemmRoute { int kind = LTX_ROUTE_GEMM128; GemmPlan plan; };      // plan: empty where no family honours the call's operands
+int ltx_gemm_route_kind(const GemmArgs& g, int dtype, int epi);          // the static predicates alone: no plan is chosen
+// the whole decision; measure: a shape without a cached plan may be measured on s (otherwise s is not used)
+int ltx_gemm_route(const GemmArgs& g, int dtype, int epi, hipStream_t s, bool measure, GemmRoute* r);
+const char* ltx_gemm_route_name(const GemmRoute& r);                     // "gemm128", "asm32" or the plan's name
+const char* ltx_gemm_route_refusal(const GemmArgs& g, const GemmRoute& r);      // operands the route's kernel does not read: why, else null
+int ltx_launch_gemm_plan(const GemmArgs& g, int epi, GemmPlan p, hipStream_t s);
 // canonical per-row partial sums of squares of x [rows, N] (row stride ld elements): out[row * ceil(N / 128) + g] (rownorm.hip)
 int ltx_launch_rowsq(const void* x, int dtype, int64_t rows, int N, int ld, float* out, hipStream_t s);
 void ltx_gemm_rowsq_done();      // a GEMM kernel that wrote GemmArgs::rowsq itself tells ltx_launch_gemm so (thread-local)
-// large-tile LDS-DMA bf16 variant (gemm_big.hip); ltx_launch_gemm dispatches to it when eligible
+// large-tile LDS-DMA bf16 variant and the plan families around it (gemm_big.hip): a building block of the route
 bool ltx_gemm_big_eligible(const GemmArgs& g, int dtype);
-int ltx_launch_gemm_big(const GemmArgs& g, int epi, hipStream_t s);
 int ltx_gemm_split_factor(const GemmArgs& g);   // gemm_big.hip: K-ranges a small-output shape is cut into (shape only)
 bool ltx_gemm_defer_ok(const GemmArgs& g, int epi);   // gemm_ring.hip: the call can leave its K-range sums to the consumer (GemmArgs::defer_parts)
-// gemm_asm.hip: one-wave-per-SIMD kernels with a generated asm K loop; eligibility is a function of the shape only
+// gemm_asm.hip: one-wave-per-SIMD kernels with a generated asm K loop; eligibility is a function of the shape only (a building block of the route)
 bool ltx_gemm_asm_eligible(const GemmArgs& g, int dtype, int epi);
 int ltx_launch_gemm_asm(const GemmArgs& g, int epi, hipStream_t s);
 bool ltx_gemm_fold_ok(const GemmArgs& g, int epi);      // gemm_asm.hip: the call (with GemmArgs::C2 or ::rs_sq set) is one the wide epilogue serves
 // cvec[b][n] = sum_k shift[b * shift_stride + k] * W[n][k] + bias[n]   (f32 accumulation in ascending k; W, bias bf16; rownorm.hip)
 int ltx_launch_shift_gemv(const void* W, const void* bias, const float* shift, int shift_stride, int B, int N, int K, float* cvec, int cvec_stride, hipStream_t s);
 bool ltx_gemm_asm16_fits(const GemmArgs& g, int epi);                       // the 16x16x32 one-wave-per-SIMD kernel (plan family asm16:*)
-int ltx_launch_gemm_asm16(const GemmArgs& g, int epi, int tile, hipStream_t s);
+int ltx_launch_gemm_asm16(const GemmArgs& g, int epi, int tile, hipStream_t s);      // tile: ltx_gemm_asm_pick_tile's index
 bool ltx_gemm_asm16_conv_fits(const GemmArgs& g, int epi);                  // the same loop in conv mode (3x3x3, tile 256 x 256; plan "asm16c:256x256")
 int ltx_launch_gemm_asm16_conv(const GemmArgs& g, int epi, hipStream_t s);
 int ltx_gemm_asm_pick_tile(int M, int N);
@@ -123,7 +134,6 @@ bool ltx_gemm_ring_fits(const GemmArgs& g, int epi);
 bool ltx_gemm_ring_tile_fits(const GemmArgs& g, int epi, int tile);      // conv mode runs on the tiles of at least 64 columns
 int ltx_launch_gemm_ring(const GemmArgs& g, int epi, int tile, hipStream_t s);
 int ltx_gemm_ring_tiles();
-const char* ltx_gemm_ring_tile_name(int i);
 int ltx_gemm_ring_tile_bm(int i);
 int ltx_gemm_ring_tile_bn(int i);
 int ltx_gemm_ring_pick_tile(const GemmArgs& g);

@@ -267,7 +267,7 @@ int conv_chunk(int dtype, const ConvW& cw, const Dims& d) {
     {   // the large-tile conv kernels address a window around each tile, not the tensor: whole batch in one launch where they apply
         GemmArgs g; g.M = (int)std::min<int64_t>(d.vox(), 2147483647); g.N = cw.cout; g.K = cw.cin; g.conv = 1; g.B = d.B; g.T = d.T; g.H = d.H; g.Wd = d.W;
         g.Cin = cw.cin; g.ntaps = 27; g.kh = 3; g.kw = 3;
-        if (dtype == LTX_DT_BF16 && d.vox() < 2147483647 && ltx_gemm_big_eligible(g, dtype)) return d.B;
+        if (d.vox() < 2147483647 && ltx_gemm_route_kind(g, dtype, EPI_BIAS) == LTX_ROUTE_PLAN) return d.B;
     }
     const int64_t per = (int64_t)d.T * d.H * d.W;
     const int64_t lim = (2147483648LL - (1 << 20)) / (per * std::max(cw.cin, cw.cout) * (int64_t)ltx_dt_size(dtype));
@@ -281,12 +281,14 @@ bool fuse_norm2(int dtype, int pad_t, const ConvW& cw, const Dims& d_all, int ch
     const LtxOptions& o = ltx_opt();
     if (!o.vae_fuse_norm || !o.gemm_wide_epi || (o.gemm_off & (LTX_FAM_HALO | LTX_FAM_BIG))) return false;
     if (dtype != LTX_DT_BF16 || (ch != 128 && ch != 256) || cw.cout != ch) return false;
-    const GemmArgs g = conv_args(pad_t, cw, d);
+    GemmArgs g = conv_args(pad_t, cw, d);
     // the fused epilogue needs the whole channel row in one tile (BN == channels), i.e. a grid of M / 256 blocks: below about
     // one round of the chip the unfused conv on a plan with more, smaller tiles + the stand-alone norm is faster (C1's
     // 256-channel stage, 78 tiles: 168 us fused vs 108 + 13; decode 5.7 -> 5.45 ms, profiles/r5k_c1_vae_fused_norm_ab.jsonl)
     if ((g.M + 255) / 256 < 192 && o.vae_fuse_norm < 2) return false;
-    return ltx_gemm_big_eligible(g, dtype) && ltx_conv_halo_eligible(g, EPI_BIAS, ch);
+    g.pn_on = 1;                                            // ask the route: the fused call must land on the halo tile as wide as the output
+    GemmRoute r;
+    return ltx_gemm_route(g, dtype, EPI_BIAS, nullptr, false, &r) == LTX_OK && r.kind == LTX_ROUTE_PLAN && r.plan.fam == kPlanHalo;
 }
 bool fuse_norm2(ltx_vae* v, const ConvW& cw, const Dims& d_all, int ch) { return fuse_norm2(v->dtype, v->cfg.decoder_causal ? 2 : 1, cw, d_all, ch); }
 

@@ -144,6 +144,7 @@ _SIGS = {
     "ltx_op_blend": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_downsample3d": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_gemm_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i],
+    "ltx_op_gemm_route": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i],
     # include/ltxhip_t5.h
     "ltx_t5_config_default": [_vp], "ltx_t5_create": [_vp, _vp, _sz, _i, _i, _vp], "ltx_t5_destroy": [_vp],
     "ltx_t5_forward": [_vp, _vp, _i, _i, _i, _vp, _vp],
@@ -1480,6 +1481,15 @@ class ops:
         """name of the GEMM plan the dispatcher cached for this bf16 shape ("" before its first run)."""
         buf = C.create_string_buffer(32)
         _check(lib.ltx_op_gemm_plan(M, N, K, conv, ntaps, T, H, W, buf, 32))
+        return buf.value.decode()
+
+    @staticmethod
+    def gemm_route(M, N, K, conv=0, ntaps=1, B=1, T=1, H=1, W=1, epi=0, dtype=torch.bfloat16, pn=False, defer=False, fold_in=False, fold_out=False) -> str:
+        """where the GEMM dispatch sends the described call under the current options: "gemm128", "asm32" or a plan name.
+        Nothing is launched or measured; LtxError where the launch would refuse the call."""
+        buf = C.create_string_buffer(32)
+        flags = (1 if pn else 0) | (2 if defer else 0) | (4 if fold_in else 0) | (8 if fold_out else 0)
+        _check(lib.ltx_op_gemm_route(M, N, K, conv, ntaps, B, T, H, W, epi, _dt(dtype), flags, buf, 32))
         return buf.value.decode()
 
     @staticmethod

@@ -156,6 +156,18 @@ int ltx_op_blend(const float* a, float* b, int BC, int at, int ah, int aw, int b
  * ("192x128", "p8:256", ... or "" if the shape has not run yet) into name[cap]. */
 int ltx_op_gemm_plan(int M, int N, int K, int conv, int ntaps, int T, int H, int W, char* name, int cap);
 
+/* Diagnostic, read-only: where the GEMM dispatch sends a described call under the current options - "gemm128" (the 128 x 128
+ * kernel), "asm32" (experiment builds) or a plan name ("asm16:160x256", "ring:96x96", "halo:64", ...): the forced plan, else
+ * the cached one, else the static model's.  Nothing is launched or measured and no pointer is needed: dense operands are
+ * assumed.  conv = 1: K = Cin, M = B T H W, ntaps taps; epi 0 .. 6 (bias, GELU, gate + residual, residual, depth-to-space,
+ * unpatchify, space-to-depth); dtype as everywhere (1 = bf16).  flags describe the operand fields the dispatch reads.
+ * LTX_ERR_ARG where ltx_launch would refuse the call (deferred K ranges / norm-fold operands on a kernel without them). */
+enum { LTX_ROUTE_PN = 1,         /* conv with the fused output norm */
+       LTX_ROUTE_DEFER = 2,      /* K-range sums left to the consumer (ltx_op_linear_deferred) */
+       LTX_ROUTE_FOLD_IN = 4,    /* ltx_op_linear_fold_in's operands (16 row partials) */
+       LTX_ROUTE_FOLD_OUT = 8 }; /* ltx_op_linear_fold_out's operands */
+int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B, int T, int H, int W, int epi, int dtype, int flags, char* name, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,11 @@ def test_valid_plans_load_and_round_trip(hip, tmp_path):
     ("4992 6144 2048 0 0 0 0 0 halo:128", "plan not valid"),                  # a conv plan on a linear shape
     ("4992 6144 2048 0 0 0", "malformed line"),
     ("0 6144 2048 0 0 0 0 0 256x256", "plan not valid"),
+    ("4992 2048 2048 0 0 0 0 0 ring:96x96", "plan not valid"),                # the ring tiles serve at most 2048 rows
+    ("384 4096 1024 2 27 4 8 12 ring:96x128", "plan not valid"),              # ... and no depth-to-space conv (key conv = 2)
+    ("384 2048 8192 3 0 0 0 0 128x128", "plan not valid"),                    # deferred K ranges (key conv = 3) are the ring tiles' only
+    ("4992 2048 2048 0 0 0 0 0 asm16c:256x256", "plan not valid"),            # the conv-mode tile on a linear shape
+    ("2383872 128 128 1 27 97 128 192 halo:256", "plan not valid"),           # N not a multiple of the halo tile's width
 ])
 def test_invalid_plan_lines_are_refused(hip, tmp_path, line, msg):
     with pytest.raises(hip.LtxError, match=msg):
