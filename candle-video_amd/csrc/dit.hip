@@ -8,6 +8,7 @@
 #include <deque>
 #include "model_util.h"
 #include "options.h"
+#include "../../include/ltxhip_cond.h"
 
 struct DitBlock {
     LinearW qkv1, o1, q2, kv2, o2, ff1, ff2;
@@ -37,6 +38,16 @@ struct DitTimeEntry {
 // Keyed by the TIMESTEP alone (the modulation of a row depends on nothing else): forwards of any batch size at that timestep share the copy.
 struct DitWfold { float t = 0.f; hipStream_t stream = nullptr; bool valid = false; uint64_t used = 0; DevBuf w; };
 constexpr int kDitTimeEntries = 64;
+// Per-frame timesteps (ltx_dit_forward_frames): the modulation tables of one [B, G] timestep matrix, one row per (batch row, latent
+// frame) - the layouts of DitTimeEntry with B * G modulation groups in place of B batch rows.  Built by a gather from the entries of
+// the DISTINCT values (the MLP never runs twice for one value) and keyed on the whole matrix.  A sampler uses one matrix per step: a
+// schedule of at most kDitGroupEntries steps (the distilled presets' 7) finds every table again in its next call, a longer one
+// gathers its tables anew at every step - launches only (the values' entries stay cached), no wait for the device.
+struct DitGroupEntry {
+    std::vector<float> t; int B = 0, G = 0; hipStream_t stream = nullptr; bool valid = false; uint64_t used = 0;
+    DevBuf ada, adaf, cfold; bool cfold_valid = false;      // [L][B*G][6D], [2][B*G][D], per layer [B*G][3D] then [B*G][4D]
+};
+constexpr int kDitGroupEntries = 8;
 
 struct ltx_dit {
     ltx_dit_config cfg{};
@@ -54,6 +65,7 @@ struct ltx_dit {
     bool ctx_mode = false;
     std::deque<DitTimeEntry> tcache; uint64_t tclock = 0;
     std::deque<DitWfold> wcache;
+    std::deque<DitGroupEntry> gcache;
     bool wfold_off = false;          // norm_fold=2 gave up on this handle: more distinct timesteps in flight than scaled-weight copies (a schedule that would re-scale every step)
     // RoPE tables of the caching scope (ltx_dit_context_cache: the caller keeps coords / geometry constant inside it): what cosb / sinb hold
     struct { bool valid = false; const float* coords = nullptr; float rs[3] = {0, 0, 0}; bool has_rs = false; int B = 0, S = 0, F = 0, H = 0, W = 0; hipStream_t stream = nullptr; } rope_key;
@@ -70,6 +82,8 @@ struct ltx_dit {
         for (auto& e : tcache) { e.ada.release(); e.adaf.release(); e.cfold.release(); }
         for (auto& e : wcache) e.w.release();
         wcache.clear();
+        for (auto& e : gcache) { e.ada.release(); e.adaf.release(); e.cfold.release(); }
+        gcache.clear();
         tcache.clear();
     }
 };
@@ -206,8 +220,12 @@ extern "C" int ltx_dit_get_config(const ltx_dit* m, ltx_dit_config* out) {
     return LTX_OK;
 }
 
-// one forward of up to 8 batch rows (the per-batch scalars - timesteps, skip-mask rows - travel as kernel arguments)
-static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float* timestep,
+// one forward of up to 8 batch rows (the per-batch scalars - timesteps, skip-mask rows - travel as kernel arguments).
+// G: modulation groups per batch row - 1: one timestep per row (timestep [B]); num_frames: one per latent frame (timestep [B, G],
+// tokens in pack order, so a group is a run of S / G rows).  Only the AdaLN look-ups see the groups: they index their tables with
+// m / rows_per_batch, which becomes m / (S / G) over tables of B * G rows; attention, RoPE, the text context and the skip-layer
+// blend keep S.
+static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float* timestep, int G,
                           const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
                           const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
                           ltx_dtype io_dtype, void* out, ltx_stream stream) {
@@ -222,6 +240,8 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
     const size_t esz = ltx_dt_size(dt);
     const int D = m->D, L = c.num_layers, H = c.num_attention_heads, hd = c.attention_head_dim;
     const int64_t M = (int64_t)B * S, MK = (int64_t)B * K;
+    if (G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: the modulation groups must divide the sequence");
+    const int NB = B * G, Sg = S / G;                       // modulation groups of the call, rows of one group
 
     LTX_TRY(m->xin.ensure(M * c.in_channels * esz));
     LTX_TRY(m->encin.ensure(MK * c.caption_channels * esz));
@@ -229,9 +249,10 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
     LTX_TRY(m->qkv.ensure(M * 3 * D * esz)); LTX_TRY(m->attn.ensure(M * D * esz));
     LTX_TRY(m->ff.ensure(M * 4 * D * esz));
     LTX_TRY(m->c1.ensure(MK * D * esz)); LTX_TRY(m->encp.ensure(MK * D * esz)); LTX_TRY(m->kv2.ensure(MK * 2 * D * esz));
-    LTX_TRY(m->tproj.ensure((size_t)B * 256 * esz)); LTX_TRY(m->e1.ensure((size_t)B * D * esz));
-    LTX_TRY(m->emb.ensure((size_t)B * D * esz)); LTX_TRY(m->embs.ensure((size_t)B * D * esz));
-    LTX_TRY(m->temb.ensure((size_t)B * 6 * D * esz));
+    const size_t nte = G == 1 ? (size_t)B : 8;             // rows of one time-embedding launch: the batch rows, or eight distinct values of a per-frame call
+    LTX_TRY(m->tproj.ensure(nte * 256 * esz)); LTX_TRY(m->e1.ensure(nte * D * esz));
+    LTX_TRY(m->emb.ensure(nte * D * esz)); LTX_TRY(m->embs.ensure(nte * D * esz));
+    LTX_TRY(m->temb.ensure(nte * 6 * D * esz));
     LTX_TRY(m->cosb.ensure(M * (D / 2) * sizeof(float))); LTX_TRY(m->sinb.ensure(M * (D / 2) * sizeof(float)));
     LTX_TRY(m->bias.ensure(MK * sizeof(float)));
     LTX_TRY(m->outT.ensure(M * c.out_channels * esz));
@@ -261,7 +282,7 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
         GemmArgs gp; gp.A = m->attn.p; gp.W = m->blocks[0].o2.w; gp.C = m->h.p; gp.bias = m->blocks[0].o2.b; gp.resid = m->h.p;
         gp.M = (int)M; gp.N = m->blocks[0].o2.out; gp.K = m->blocks[0].o2.in; gp.lda = D; gp.ldc = D; gp.ldr = D;
         GemmArgs gf = gp; gf.A = m->ff.p; gf.W = m->blocks[0].ff2.w; gf.bias = m->blocks[0].ff2.b; gf.K = m->blocks[0].ff2.in; gf.lda = 4 * D;
-        gf.gate = reinterpret_cast<const float*>(m->h.p); gf.gate_stride = 6 * D; gf.rows_per_batch = S;      // (any aligned non-null pointer: a fit test, nothing is launched)
+        gf.gate = reinterpret_cast<const float*>(m->h.p); gf.gate_stride = 6 * D; gf.rows_per_batch = Sg;      // (any aligned non-null pointer: a fit test, nothing is launched)
         presum = (pe != 0 && ltx_gemm_asm16_fits(gp, EPI_RESID) && ltx_gemm_asm16_fits(gf, EPI_GATE_RESID)) || pe == 2;
     }
     if (presum) LTX_TRY(m->hsq.ensure(M * (D / 128) * sizeof(float)));
@@ -274,12 +295,12 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
     bool nfold = presum && ltx_opt().norm_fold != 0;
     if (nfold) {
         GemmArgs gp; gp.A = m->attn.p; gp.W = m->blocks[0].o2.w; gp.C = m->h.p; gp.bias = m->blocks[0].o2.b; gp.resid = m->h.p;
-        gp.M = (int)M; gp.N = D; gp.K = D; gp.lda = D; gp.ldc = D; gp.ldr = D; gp.rows_per_batch = S;
+        gp.M = (int)M; gp.N = D; gp.K = D; gp.lda = D; gp.ldc = D; gp.ldr = D; gp.rows_per_batch = Sg;
         gp.rowsq = m->hsq.as<float>(); gp.C2 = m->n.p; gp.scale2 = reinterpret_cast<const float*>(m->hsq.p); gp.scale2_stride = 6 * D;      // (aligned non-null pointers: a fit test)
         GemmArgs gf = gp; gf.A = m->ff.p; gf.W = m->blocks[0].ff2.w; gf.bias = m->blocks[0].ff2.b; gf.K = 4 * D; gf.lda = 4 * D;
         gf.gate = reinterpret_cast<const float*>(m->hsq.p); gf.gate_stride = 6 * D;
         GemmArgs gq; gq.A = m->n.p; gq.W = m->blocks[0].qkv1.w; gq.C = m->qkv.p; gq.M = (int)M; gq.N = 3 * D; gq.K = D; gq.lda = D; gq.ldc = D;
-        gq.c_seg_shift = __builtin_ctz((unsigned)D); gq.c_seg_stride = M * D; gq.rows_per_batch = S;
+        gq.c_seg_shift = __builtin_ctz((unsigned)D); gq.c_seg_stride = M * D; gq.rows_per_batch = Sg;
         gq.rs_sq = m->hsq.as<float>(); gq.rs_n = D / 128; gq.rs_D = D; gq.rs_eps = c.norm_eps; gq.cvec = m->hsq.as<float>(); gq.cvec_stride = 3 * D;
         GemmArgs g1 = gq; g1.W = m->blocks[0].ff1.w; g1.C = m->ff.p; g1.N = 4 * D; g1.ldc = 4 * D; g1.c_seg_shift = 0; g1.c_seg_stride = 0; g1.cvec_stride = 4 * D;
         nfold = ltx_opt().dense_qkv && m->blocks[0].qkv1.out == 3 * D && m->blocks[0].ff1.out == 4 * D &&
@@ -312,43 +333,96 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
     LTX_TRY(ltx_linear(m->proj_in, m->xin.p, c.in_channels, m->h.p, D, (int)M, dt, EPI_BIAS, s));
 
     // AdaLayerNormSingle (:262-267): sinusoid(256) -> Linear -> SiLU -> Linear = embedded_timestep ; SiLU -> Linear(6D) = temb
-    TimeVec tv; tv.n = B; for (int i = 0; i < 8; ++i) tv.t[i] = i < B ? timestep[i] : 0.f;
-    DitTimeEntry* te = nullptr;
-    for (auto& e : m->tcache) if (e.valid && e.B == B && e.stream == s && !memcmp(e.t, tv.t, sizeof(float) * B)) te = &e;
-    if (!te) {
-        if ((int)m->tcache.size() < kDitTimeEntries) { m->tcache.emplace_back(); te = &m->tcache.back(); }
-        else { te = &m->tcache.front(); for (auto& e : m->tcache) if (e.used < te->used) te = &e; }
-        te->valid = false; te->cfold_valid = false;
-        LTX_TRY(te->ada.ensure((size_t)L * B * 6 * D * sizeof(float))); LTX_TRY(te->adaf.ensure((size_t)2 * B * D * sizeof(float)));
-        LTX_TRY(ltx_launch_sinusoid(m->tproj.p, dt, tv, m->inv_freq, 128, /*round_t=*/dt == LTX_DT_BF16, 1.0f, s));
-        LTX_TRY(ltx_linear(m->te1, m->tproj.p, 256, m->e1.p, D, B, dt, EPI_BIAS, s));
-        LTX_TRY(ltx_launch_silu(m->e1.p, m->e1.p, (int64_t)B * D, dt, s));
-        LTX_TRY(ltx_linear(m->te2, m->e1.p, D, m->emb.p, D, B, dt, EPI_BIAS, s));
-        LTX_TRY(ltx_launch_silu(m->emb.p, m->embs.p, (int64_t)B * D, dt, s));
-        LTX_TRY(ltx_linear(m->te_lin, m->embs.p, D, m->temb.p, 6 * D, B, dt, EPI_BIAS, s));
-        LTX_TRY(ltx_launch_ada(te->ada.as<float>(), m->sst_blocks, m->temb.p, L, B, 6 * D, dt, s));
-        LTX_TRY(ltx_launch_ada(te->adaf.as<float>(), m->sst_final, m->emb.p, 2, B, D, dt, s));
-        memcpy(te->t, tv.t, sizeof(te->t)); te->B = B; te->stream = s; te->valid = true;
-    }
-    te->used = ++m->tclock;
-    const float* ada_all = te->ada.as<float>();
-    const float* adaf = te->adaf.as<float>();
-    if (nfold && !te->cfold_valid) {                        // once per distinct timestep vector: streams the q|k|v and ff1 weights of every layer once
-        LTX_TRY(te->cfold.ensure((size_t)L * B * 7 * D * sizeof(float)));
-        for (int l = 0; l < L; ++l) {
-            const float* ada = ada_all + (size_t)l * B * 6 * D;
-            float* cq = te->cfold.as<float>() + (size_t)l * B * 7 * D;
-            LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].qkv1.w, m->blocks[l].qkv1.b, ada, 6 * D, B, 3 * D, D, cq, 3 * D, s));
-            LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].ff1.w, m->blocks[l].ff1.b, ada + 3 * D, 6 * D, B, 4 * D, D, cq + (size_t)B * 3 * D, 4 * D, s));
+    // time_entry: the cached tables of up to 8 timestep values (computed on a miss); with_cfold: the norm fold's per-timestep vectors too
+    auto time_entry = [&](const float* vals, int nv, bool with_cfold, DitTimeEntry** out_e) -> int {
+        TimeVec tv; tv.n = nv; for (int i = 0; i < 8; ++i) tv.t[i] = i < nv ? vals[i] : 0.f;
+        DitTimeEntry* te = nullptr;
+        for (auto& e : m->tcache) if (e.valid && e.B == nv && e.stream == s && !memcmp(e.t, tv.t, sizeof(float) * nv)) te = &e;
+        if (!te) {
+            if ((int)m->tcache.size() < kDitTimeEntries) { m->tcache.emplace_back(); te = &m->tcache.back(); }
+            else { te = &m->tcache.front(); for (auto& e : m->tcache) if (e.used < te->used) te = &e; }
+            te->valid = false; te->cfold_valid = false;
+            LTX_TRY(te->ada.ensure((size_t)L * nv * 6 * D * sizeof(float))); LTX_TRY(te->adaf.ensure((size_t)2 * nv * D * sizeof(float)));
+            LTX_TRY(ltx_launch_sinusoid(m->tproj.p, dt, tv, m->inv_freq, 128, /*round_t=*/dt == LTX_DT_BF16, 1.0f, s));
+            LTX_TRY(ltx_linear(m->te1, m->tproj.p, 256, m->e1.p, D, nv, dt, EPI_BIAS, s));
+            LTX_TRY(ltx_launch_silu(m->e1.p, m->e1.p, (int64_t)nv * D, dt, s));
+            LTX_TRY(ltx_linear(m->te2, m->e1.p, D, m->emb.p, D, nv, dt, EPI_BIAS, s));
+            LTX_TRY(ltx_launch_silu(m->emb.p, m->embs.p, (int64_t)nv * D, dt, s));
+            LTX_TRY(ltx_linear(m->te_lin, m->embs.p, D, m->temb.p, 6 * D, nv, dt, EPI_BIAS, s));
+            LTX_TRY(ltx_launch_ada(te->ada.as<float>(), m->sst_blocks, m->temb.p, L, nv, 6 * D, dt, s));
+            LTX_TRY(ltx_launch_ada(te->adaf.as<float>(), m->sst_final, m->emb.p, 2, nv, D, dt, s));
+            memcpy(te->t, tv.t, sizeof(te->t)); te->B = nv; te->stream = s; te->valid = true;
         }
-        te->cfold_valid = true;
+        te->used = ++m->tclock;
+        if (with_cfold && !te->cfold_valid) {               // once per distinct timestep vector: streams the q|k|v and ff1 weights of every layer once
+            LTX_TRY(te->cfold.ensure((size_t)L * nv * 7 * D * sizeof(float)));
+            for (int l = 0; l < L; ++l) {
+                const float* ada = te->ada.as<float>() + (size_t)l * nv * 6 * D;
+                float* cq = te->cfold.as<float>() + (size_t)l * nv * 7 * D;
+                LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].qkv1.w, m->blocks[l].qkv1.b, ada, 6 * D, nv, 3 * D, D, cq, 3 * D, s));
+                LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].ff1.w, m->blocks[l].ff1.b, ada + 3 * D, 6 * D, nv, 4 * D, D, cq + (size_t)nv * 3 * D, 4 * D, s));
+            }
+            te->cfold_valid = true;
+        }
+        *out_e = te;
+        return LTX_OK;
+    };
+    TimeVec tv; tv.n = B; for (int i = 0; i < 8; ++i) tv.t[i] = i < B ? timestep[i] : 0.f;      // (G == 1: the rows' timesteps, read by norm_fold=2 below)
+    const float *ada_all = nullptr, *adaf = nullptr, *cfold_all = nullptr;
+    if (G == 1) {
+        DitTimeEntry* te = nullptr;
+        LTX_TRY(time_entry(timestep, B, nfold, &te));
+        ada_all = te->ada.as<float>(); adaf = te->adaf.as<float>(); cfold_all = nfold ? te->cfold.as<float>() : nullptr;
+    } else {
+        // One timestep per (batch row, latent frame).  The MLP runs once per DISTINCT value of the call, eight values a launch (each
+        // batch of eight is an ordinary cached entry above: the held frames' 0 and the step's t are two values however many frames
+        // there are), and a gather copies every group's rows out of them.
+        DitGroupEntry* ge = nullptr;
+        for (auto& e : m->gcache) if (e.valid && e.B == B && e.G == G && e.stream == s && !memcmp(e.t.data(), timestep, sizeof(float) * NB)) ge = &e;
+        if (!ge || (nfold && !ge->cfold_valid)) {
+            if (!ge) {
+                if ((int)m->gcache.size() < kDitGroupEntries) { m->gcache.emplace_back(); ge = &m->gcache.back(); }
+                else {
+                    ge = &m->gcache.front(); for (auto& e : m->gcache) if (e.used < ge->used) ge = &e;
+                    if (ge->valid && ge->stream != s) HIP_TRY(hipStreamSynchronize(ge->stream));      // (forwards on ITS stream may still read the tables)
+                }
+            }
+            ge->valid = false; ge->cfold_valid = false;
+            std::vector<float> distinct; std::vector<int> idx((size_t)NB);
+            for (int i = 0; i < NB; ++i) {
+                size_t j = 0;
+                while (j < distinct.size() && memcmp(&distinct[j], &timestep[i], sizeof(float)) != 0) ++j;
+                if (j == distinct.size()) distinct.push_back(timestep[i]);
+                idx[i] = (int)j;
+            }
+            LTX_TRY(ge->ada.ensure((size_t)L * NB * 6 * D * sizeof(float))); LTX_TRY(ge->adaf.ensure((size_t)2 * NB * D * sizeof(float)));
+            if (nfold) LTX_TRY(ge->cfold.ensure((size_t)L * NB * 7 * D * sizeof(float)));
+            const int nd = (int)distinct.size();
+            for (int c0 = 0; c0 < nd; c0 += 8) {
+                const int nc = nd - c0 < 8 ? nd - c0 : 8;
+                DitTimeEntry* te = nullptr;
+                LTX_TRY(time_entry(distinct.data() + c0, nc, nfold, &te));
+                const int* gi = idx.data();      // (read while the launches are enqueued: nothing of a miss waits for the device)
+                LTX_TRY(ltx_launch_group_gather(ge->ada.as<float>(), (int64_t)NB * 6 * D, te->ada.as<float>(), (int64_t)nc * 6 * D, gi, c0, nc, L, NB, 6 * D, s));
+                LTX_TRY(ltx_launch_group_gather(ge->adaf.as<float>(), (int64_t)NB * D, te->adaf.as<float>(), (int64_t)nc * D, gi, c0, nc, 2, NB, D, s));
+                if (nfold) {
+                    LTX_TRY(ltx_launch_group_gather(ge->cfold.as<float>(), (int64_t)NB * 7 * D, te->cfold.as<float>(), (int64_t)nc * 7 * D, gi, c0, nc, L, NB, 3 * D, s));
+                    LTX_TRY(ltx_launch_group_gather(ge->cfold.as<float>() + (size_t)NB * 3 * D, (int64_t)NB * 7 * D, te->cfold.as<float>() + (size_t)nc * 3 * D, (int64_t)nc * 7 * D,
+                                                    gi, c0, nc, L, NB, 4 * D, s));
+                }
+            }
+            ge->t.assign(timestep, timestep + NB); ge->B = B; ge->G = G; ge->stream = s; ge->valid = true; ge->cfold_valid = nfold;
+        }
+        ge->used = ++m->tclock;
+        ada_all = ge->ada.as<float>(); adaf = ge->adaf.as<float>(); cfold_all = nfold ? ge->cfold.as<float>() : nullptr;
     }
     // norm_fold=2: the (1 + scale) factor rides on the CONSUMER's weights instead of on a second output of the producer:
     // (h (.) (1 + sc)) W^T = h (W (.) (1 + sc))^T.  One scaled copy of the q|k|v and ff1 weights per distinct timestep (1.6 GB at 2B:
     // read + written once, then cached like the modulation they are made from - a distilled schedule has 7), all batch rows at one
     // timestep (what LtxPipeline::call passes, t2v_pipeline.rs:868); otherwise, or when the schedule has more distinct timesteps
     // than copies (norm_fold_copies; the 40-step presets), the second-output form serves.  bf16 rounding moves from h (1 + sc) to W (1 + sc).
-    bool wf = nfold && ltx_opt().norm_fold == 2 && !m->wfold_off;
+    // A per-frame call (G > 1: its groups are at different timesteps) never takes this form and never touches the copies or wfold_off.
+    bool wf = G == 1 && nfold && ltx_opt().norm_fold == 2 && !m->wfold_off;
     for (int i = 1; i < B; ++i) wf = wf && tv.t[i] == tv.t[0];
     DitWfold* we = nullptr;
     if (wf) {
@@ -377,7 +451,7 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
                 }
                 if (wf)
                 for (int l = 0; l < L; ++l) {
-                    const float* ada = ada_all + (size_t)l * B * 6 * D;
+                    const float* ada = ada_all + (size_t)l * NB * 6 * D;
                     char* wl = (char*)we->w.p + (size_t)l * per_layer;
                     LTX_TRY(ltx_launch_scale_cols(m->blocks[l].qkv1.w, ada + D, wl, 3 * D, D, dt, s));
                     LTX_TRY(ltx_launch_scale_cols(m->blocks[l].ff1.w, ada + 4 * D, wl + (size_t)3 * D * D * esz, 4 * D, D, dt, s));
@@ -482,13 +556,13 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
             }
         }
         const DitBlock& b = m->blocks[l];
-        const float* ada = ada_all + (size_t)l * B * 6 * D;
+        const float* ada = ada_all + (size_t)l * NB * 6 * D;
         // norm1 + AdaLN (shift_msa = row 0, scale_msa = row 1)
         RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = M; rn.D = D; rn.ldx = D; rn.ldy = D;
-        rn.kind = 0; rn.eps = c.norm_eps; rn.shift = ada; rn.scale = ada + D; rn.rows_per_batch = S; rn.mod_stride = 6 * D;
+        rn.kind = 0; rn.eps = c.norm_eps; rn.shift = ada; rn.scale = ada + D; rn.rows_per_batch = Sg; rn.mod_stride = 6 * D;
         if (presum && hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
         const bool fold1 = nfold && hsq_valid && (wf || hs_valid);      // the layer that wrote h left its row partials and h (.) (1 + scale_msa) in m->n (or the factor is in the weights): no pass
-        const float* cfold_l = nfold ? te->cfold.as<float>() + (size_t)l * B * 7 * D : nullptr;
+        const float* cfold_l = nfold ? cfold_all + (size_t)l * NB * 7 * D : nullptr;
         const char* wfold_l = wf ? (const char*)we->w.p + (size_t)l * 7 * D * D * esz : nullptr;
         if (!fold1) {
         take_pending(rn);
@@ -508,7 +582,7 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
             g.M = (int)M; g.N = b.qkv1.out; g.K = b.qkv1.in; g.lda = D; g.ldc = ldqkv;
             if (dense_qkv) { g.c_seg_shift = __builtin_ctz((unsigned)D); g.c_seg_stride = seg; }
             if (fold1) {
-                g.bias = nullptr; g.rows_per_batch = S; g.rs_sq = m->hsq.as<float>(); g.rs_n = D / 128; g.rs_D = D; g.rs_eps = c.norm_eps; g.cvec = cfold_l; g.cvec_stride = 3 * D;
+                g.bias = nullptr; g.rows_per_batch = Sg; g.rs_sq = m->hsq.as<float>(); g.rs_n = D / 128; g.rs_D = D; g.rs_eps = c.norm_eps; g.cvec = cfold_l; g.cvec_stride = 3 * D;
                 if (wf) { g.A = m->h.p; g.W = wfold_l; }
             }
             LTX_TRY(ltx_launch_gemm(g, dt, EPI_BIAS, s));
@@ -525,7 +599,7 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
         at.q_prescaled = fold_q ? 1 : 0;
         LTX_TRY(ltx_launch_attention(at, dt, s));
         // h = h + gate_msa * to_out(attn)     (gate_msa = row 2)
-        LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, S));
+        LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, Sg));
         hsq_valid = false;
         // cross attention (no pre-norm, no RoPE, q/k RMSNorm, additive key bias)
         const char* kvl = (const char*)(ctx->compact ? ctx->kvc.p : ctx->kv.p) + (size_t)l * MK * 2 * D * esz;
@@ -546,7 +620,7 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
         LTX_TRY(ltx_launch_attention(ax, dt, s));
         if (nfold && !wf) {                                    // + h (.) (1 + scale_mlp) into m->n for ff1
             GemmArgs g; g.A = m->attn.p; g.W = b.o2.w; g.C = m->h.p; g.bias = b.o2.b; g.resid = m->h.p; g.M = (int)M; g.N = b.o2.out; g.K = b.o2.in;
-            g.lda = D; g.ldc = D; g.ldr = D; g.rows_per_batch = S; g.rowsq = m->hsq.as<float>();
+            g.lda = D; g.ldc = D; g.ldr = D; g.rows_per_batch = Sg; g.rowsq = m->hsq.as<float>();
             g.C2 = m->n.p; g.scale2 = ada + 4 * D; g.scale2_stride = 6 * D;
             LTX_TRY(ltx_launch_gemm(g, dt, EPI_RESID, s));
             hs_valid = true;
@@ -558,8 +632,8 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
         rn.presum = nullptr; rn.presum_n = 0;
         if (presum && hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
         if (nfold && hsq_valid && (wf || hs_valid)) {
-            GemmArgs g; g.A = m->n.p; g.W = b.ff1.w; g.C = m->ff.p; g.M = (int)M; g.N = b.ff1.out; g.K = b.ff1.in; g.lda = D; g.ldc = 4 * D; g.rows_per_batch = S;
-            g.rs_sq = m->hsq.as<float>(); g.rs_n = D / 128; g.rs_D = D; g.rs_eps = c.norm_eps; g.cvec = cfold_l + (size_t)B * 3 * D; g.cvec_stride = 4 * D;
+            GemmArgs g; g.A = m->n.p; g.W = b.ff1.w; g.C = m->ff.p; g.M = (int)M; g.N = b.ff1.out; g.K = b.ff1.in; g.lda = D; g.ldc = 4 * D; g.rows_per_batch = Sg;
+            g.rs_sq = m->hsq.as<float>(); g.rs_n = D / 128; g.rs_D = D; g.rs_eps = c.norm_eps; g.cvec = cfold_l + (size_t)NB * 3 * D; g.cvec_stride = 4 * D;
             if (wf) { g.A = m->h.p; g.W = wfold_l + (size_t)3 * D * D * esz; }
             LTX_TRY(ltx_launch_gemm(g, dt, EPI_GELU, s));
         } else {
@@ -574,12 +648,12 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
             pending = true; pend_gate = ada + 5 * D; pend_bias = b.ff2.b;
         } else if (int ln = (nfold && !wf) ? next_block(l) : -1; ln >= 0) {      // + h (.) (1 + scale_msa of the next block that runs) into m->n for its q|k|v projection
             GemmArgs g; g.A = m->ff.p; g.W = b.ff2.w; g.C = m->h.p; g.bias = b.ff2.b; g.resid = m->h.p; g.M = (int)M; g.N = b.ff2.out; g.K = b.ff2.in;
-            g.lda = 4 * D; g.ldc = D; g.ldr = D; g.gate = ada + 5 * D; g.gate_stride = 6 * D; g.rows_per_batch = S; g.rowsq = m->hsq.as<float>();
-            g.C2 = m->n.p; g.scale2 = ada_all + (size_t)ln * B * 6 * D + D; g.scale2_stride = 6 * D;
+            g.lda = 4 * D; g.ldc = D; g.ldr = D; g.gate = ada + 5 * D; g.gate_stride = 6 * D; g.rows_per_batch = Sg; g.rowsq = m->hsq.as<float>();
+            g.C2 = m->n.p; g.scale2 = ada_all + (size_t)ln * NB * 6 * D + D; g.scale2_stride = 6 * D;
             LTX_TRY(ltx_launch_gemm(g, dt, EPI_GATE_RESID, s));
             hs_valid = true;
         } else
-        LTX_TRY(ltx_linear(b.ff2, m->ff.p, 4 * D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 5 * D, 6 * D, S, presum ? m->hsq.as<float>() : nullptr));
+        LTX_TRY(ltx_linear(b.ff2, m->ff.p, 4 * D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 5 * D, 6 * D, Sg, presum ? m->hsq.as<float>() : nullptr));
         hsq_valid = presum;
         if (skip_layer_mask && any) {
             LTX_TRY(ltx_launch_skip_blend(m->h.p, m->orig.p, mv, S, D, dt, s));
@@ -595,7 +669,7 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
             hs_valid = false;
             if (nfold && !wf && hsq_valid) {
                 if (const int ln = next_block(l); ln >= 0) {
-                    LTX_TRY(ltx_launch_mod_scale(m->h.p, ada_all + (size_t)ln * B * 6 * D + D, 6 * D, m->n.p, B, S, D, dt, s));
+                    LTX_TRY(ltx_launch_mod_scale(m->h.p, ada_all + (size_t)ln * NB * 6 * D + D, 6 * D, m->n.p, NB, Sg, D, dt, s));
                     hs_valid = true;
                 }
             }
@@ -605,8 +679,8 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
     // final LayerNorm (no affine) + modulation (:1126-1161), proj_out (:1163)
     {
         RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = M; rn.D = D; rn.ldx = D; rn.ldy = D;
-        rn.kind = 1; rn.eps = 1e-6f; rn.shift = adaf; rn.scale = adaf + (size_t)B * D;
-        rn.rows_per_batch = S; rn.mod_stride = D;
+        rn.kind = 1; rn.eps = 1e-6f; rn.shift = adaf; rn.scale = adaf + (size_t)NB * D;
+        rn.rows_per_batch = Sg; rn.mod_stride = D;
         take_pending(rn);
         LTX_TRY(ltx_launch_rownorm(rn, dt, s));
         void* dst = iodt == dt ? out : m->outT.p;
@@ -626,7 +700,7 @@ extern "C" int ltx_dit_forward(ltx_dit* m, const void* hidden, const void* enc, 
                                ltx_dtype io_dtype, void* out, ltx_stream stream) {
     if (!m || !hidden || !enc || !timestep || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: null argument");
     if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: batch must be at least 1");
-    if (B <= 8) return dit_forward_b8(m, hidden, enc, timestep, enc_mask, B, S, K, num_frames, height, width, rope_scale, video_coords, skip_layer_mask, io_dtype, out, stream);
+    if (B <= 8) return dit_forward_b8(m, hidden, enc, timestep, 1, enc_mask, B, S, K, num_frames, height, width, rope_scale, video_coords, skip_layer_mask, io_dtype, out, stream);
     const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
     const int L = m->cfg.num_layers;
     std::vector<float> mask_chunk;
@@ -639,7 +713,42 @@ extern "C" int ltx_dit_forward(ltx_dit* m, const void* hidden, const void* enc, 
             slm = mask_chunk.data();
         }
         LTX_TRY(dit_forward_b8(m, (const char*)hidden + (size_t)b0 * S * m->cfg.in_channels * esz, (const char*)enc + (size_t)b0 * K * m->cfg.caption_channels * esz,
-                               timestep + b0, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
+                               timestep + b0, 1, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
+                               video_coords ? video_coords + (size_t)b0 * S * 3 : nullptr, slm, io_dtype,
+                               (char*)out + (size_t)b0 * S * m->cfg.out_channels * esz, stream));
+    }
+    return LTX_OK;
+}
+
+// Per-frame timesteps (include/ltxhip_cond.h).  Rows whose frames all share one value need no groups: a call made of such rows IS
+// ltx_dit_forward (the same launches, the same bits, norm_fold=2's weight copies included).
+extern "C" int ltx_dit_forward_frames(ltx_dit* m, const void* hidden, const void* enc, const float* timestep,
+                                      const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
+                                      const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
+                                      ltx_dtype io_dtype, void* out, ltx_stream stream) {
+    if (!m || !hidden || !enc || !timestep || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: null argument");
+    if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: batch must be at least 1");
+    if (num_frames < 1 || height < 1 || width < 1 || (int64_t)num_frames * height * width != S)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: S must equal num_frames*height*width (tokens in pack order, with or without video_coords)");
+    const int F = num_frames;
+    const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
+    const int L = m->cfg.num_layers;
+    std::vector<float> mask_chunk, t_row;
+    for (int b0 = 0; b0 < B; b0 += 8) {
+        const int bc = B - b0 < 8 ? B - b0 : 8;
+        const float* slm = skip_layer_mask;
+        if (skip_layer_mask && bc != B) {                   // [L, B] -> [L, bc]
+            mask_chunk.resize((size_t)L * bc);
+            for (int l = 0; l < L; ++l) for (int b = 0; b < bc; ++b) mask_chunk[(size_t)l * bc + b] = skip_layer_mask[(size_t)l * B + b0 + b];
+            slm = mask_chunk.data();
+        }
+        const float* tc = timestep + (size_t)b0 * F;
+        bool uniform = true;
+        for (int b = 0; b < bc; ++b) for (int f = 1; f < F; ++f) uniform = uniform && memcmp(&tc[(size_t)b * F + f], &tc[(size_t)b * F], sizeof(float)) == 0;
+        t_row.resize(8);
+        for (int b = 0; b < bc; ++b) t_row[b] = tc[(size_t)b * F];
+        LTX_TRY(dit_forward_b8(m, (const char*)hidden + (size_t)b0 * S * m->cfg.in_channels * esz, (const char*)enc + (size_t)b0 * K * m->cfg.caption_channels * esz,
+                               uniform ? t_row.data() : tc, uniform ? 1 : F, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
                                video_coords ? video_coords + (size_t)b0 * S * 3 : nullptr, slm, io_dtype,
                                (char*)out + (size_t)b0 * S * m->cfg.out_channels * esz, stream));
     }

@@ -130,28 +130,120 @@ __global__ void guidance_stats_kernel(GuidanceArgs a) {
     }
     if (threadIdx.x < 4) atomicAdd(&a.stats[b * 4 + threadIdx.x], sh[threadIdx.x][0]);
 }
+// The combined prediction of one element and the scheduler update, ONE body for every kernel that finishes a step (the plain pass,
+// the held-frame passes): roundings spelled out - a fused multiply-add exactly where this file's apply kernel has always had one,
+// separate roundings elsewhere - so that the bits are a property of the text, not of what a compiler contracts in one kernel or
+// another.  ratio: the rescale factor of the element's batch row.
+__device__ __forceinline__ float step_pred(const GuidanceArgs& a, float t, float u, float p, float ratio, bool rescale) {
+#pragma clang fp contract(off)
+    float c = t;
+    if (a.uncond) c = __builtin_fmaf(a.guidance_scale, t - u, u);
+    if (rescale) {
+        const float keep = (1.0f - a.guidance_rescale) * c, resc = ratio * c;
+        c = __builtin_fmaf(a.guidance_rescale, resc, keep);
+    }
+    if (a.pert) c = __builtin_fmaf(a.stg_scale, t - p, c);
+    return c;
+}
+__device__ __forceinline__ float step_update(const GuidanceArgs& a, float x, float c, float noise) {
+#pragma clang fp contract(off)
+    if (a.step_noise) {
+        const float x0 = __builtin_fmaf(-a.sigma, c, x);
+        const float keep = (1.0f - a.sigma_next) * x0, fresh = a.sigma_next * noise;
+        return keep + fresh;
+    }
+    return __builtin_fmaf(a.dt, c, x);
+}
+__device__ __forceinline__ float step_ratio(const GuidanceArgs& a, int b) {
+    const double N = (double)a.n_per_batch;
+    const double* s = a.stats + b * 4;
+    double vt = (s[1] - s[0] * s[0] / N) / (N - 1.0), vc = (s[3] - s[2] * s[2] / N) / (N - 1.0);
+    return (float)sqrt(vt) / (float)sqrt(vc);
+}
+// one element per thread and step, any size and alignment.  a.hold (image-to-video conditioning, include/ltxhip_cond.h): the
+// latents of a held frame are left alone; the prediction (noise_out) covers every token.
 __global__ void guidance_apply_kernel(GuidanceArgs a) {
     const int64_t n = (int64_t)a.B * a.n_per_batch;
+    const bool rescale = a.uncond && a.guidance_rescale > 0.0f;
     GRID_STRIDE(i, n) {
-        float t; float c = cfg_of(a, i, t);
-        if (a.uncond && a.guidance_rescale > 0.0f) {
-            const int b = (int)(i / a.n_per_batch);
-            const double N = (double)a.n_per_batch;
-            const double* s = a.stats + b * 4;
-            double vt = (s[1] - s[0] * s[0] / N) / (N - 1.0), vc = (s[3] - s[2] * s[2] / N) / (N - 1.0);
-            float ratio = (float)sqrt(vt) / (float)sqrt(vc);
-            c = (c * ratio) * a.guidance_rescale + c * (1.0f - a.guidance_rescale);
-        }
-        if (a.pert) c = c + (t - ldd(a.pert, a.pred_dtype, i)) * a.stg_scale;
+        const int b = (rescale || a.hold) ? (int)(i / a.n_per_batch) : 0;
+        const bool held = a.hold && a.hold[(int64_t)b * a.num_frames + (int)((i - (int64_t)b * a.n_per_batch) / a.frame_elems)] != 0;
+        if (held && !a.noise_out) continue;
+        const float t = ldd(a.text, a.pred_dtype, i);
+        const float u = a.uncond ? ldd(a.uncond, a.pred_dtype, i) : 0.f, p = a.pert ? ldd(a.pert, a.pred_dtype, i) : 0.f;
+        const float c = step_pred(a, t, u, p, rescale ? step_ratio(a, b) : 1.0f, rescale);
         if (a.noise_out) a.noise_out[i] = c;
-        if (a.latents) {
-            if (a.step_noise) {
-                const float x0 = a.latents[i] - a.sigma * c;
-                a.latents[i] = (1.0f - a.sigma_next) * x0 + a.sigma_next * a.step_noise[i];
-            } else {
-                a.latents[i] = a.latents[i] + c * a.dt;
-            }
-        }
+        if (held || !a.latents) continue;
+        a.latents[i] = step_update(a, a.latents[i], c, a.step_noise ? a.step_noise[i] : 0.f);
+    }
+}
+
+template <typename P> __device__ __forceinline__ void ld4(const P* p, float* v);
+template <> __device__ __forceinline__ void ld4<float>(const float* p, float* v) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
+    v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
+}
+template <> __device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, float* v) {
+    const uint2 x = *reinterpret_cast<const uint2*>(p);
+    v[0] = __uint_as_float(x.x << 16); v[1] = __uint_as_float(x.x & 0xffff0000u);
+    v[2] = __uint_as_float(x.y << 16); v[3] = __uint_as_float(x.y & 0xffff0000u);
+}
+// Held frames, 16-byte chunks of four f32 (8 bytes of a bf16 prediction): n_per_batch and frame_elems are multiples of 4, so a chunk
+// lies in one frame of one batch row - one division pair per chunk, none per element.  A held chunk reads the predictions only if
+// noise_out wants them and never touches the latents.
+template <typename P>
+__global__ __launch_bounds__(256) void guidance_held_vec_kernel(GuidanceArgs a) {
+    const int64_t chunks_per_batch = a.n_per_batch >> 2, chunks_per_frame = a.frame_elems >> 2;
+    const int64_t nchunks = (int64_t)a.B * chunks_per_batch;
+    const bool rescale = a.uncond && a.guidance_rescale > 0.0f;
+    const P* tp = reinterpret_cast<const P*>(a.text); const P* up = reinterpret_cast<const P*>(a.uncond); const P* pp = reinterpret_cast<const P*>(a.pert);
+    GRID_STRIDE(ch, nchunks) {
+        const int b = (int)(ch / chunks_per_batch);
+        const int f = (int)((ch - (int64_t)b * chunks_per_batch) / chunks_per_frame);
+        const bool held = a.hold[(int64_t)b * a.num_frames + f] != 0;
+        if (held && !a.noise_out) continue;
+        const int64_t i = ch << 2;
+        float t[4], u[4] = {0.f, 0.f, 0.f, 0.f}, p[4] = {0.f, 0.f, 0.f, 0.f}, c[4];
+        ld4<P>(tp + i, t);
+        if (up) ld4<P>(up + i, u);
+        if (pp) ld4<P>(pp + i, p);
+        const float ratio = rescale ? step_ratio(a, b) : 1.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = step_pred(a, t[k], u[k], p[k], ratio, rescale);
+        if (a.noise_out) *reinterpret_cast<f32x4*>(a.noise_out + i) = (f32x4){c[0], c[1], c[2], c[3]};
+        if (held || !a.latents) continue;
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a.latents + i);
+        f32x4 nz = {0.f, 0.f, 0.f, 0.f};
+        if (a.step_noise) nz = *reinterpret_cast<const f32x4*>(a.step_noise + i);
+        f32x4 y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = step_update(a, x[k], c[k], nz[k]);
+        *reinterpret_cast<f32x4*>(a.latents + i) = y;
+    }
+}
+// one block row per (batch row, frame): a held frame is copied in 16-byte chunks (or element-wise when the frame is not a multiple of 4)
+__global__ __launch_bounds__(256) void cond_apply_kernel(float* latents, const float* cond, int Fc, const unsigned char* hold, int F, int64_t frame_elems, int vec) {
+    const int bf = blockIdx.y, b = bf / F, f = bf - b * F;
+    if (!hold[bf] || f >= Fc) return;
+    float* dst = latents + (int64_t)bf * frame_elems;
+    const float* src = cond + ((int64_t)b * Fc + f) * frame_elems;
+    if (vec) {
+        const int64_t nv = frame_elems >> 2;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x)
+            reinterpret_cast<f32x4*>(dst)[i] = reinterpret_cast<const f32x4*>(src)[i];
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < frame_elems; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
+    }
+}
+// the per-group modulation tables (kernels.h: ltx_launch_group_gather); one thread per 16-byte chunk of a destination row.  The value
+// indices of the launch's <= 128 groups travel by value (a kernel argument is copied when the launch is enqueued: no upload to wait for).
+__global__ __launch_bounds__(256) void group_gather_kernel(float* dst, int64_t dst_stride, const float* src, int64_t src_stride, GroupIdx idx, int g0, int ng, int c0, int nc, int nl, int width4) {
+    const int64_t n = (int64_t)nl * ng * width4;
+    GRID_STRIDE(i, n) {
+        const int j = (int)(i % width4); const int64_t r = i / width4; const int g = (int)(r % ng), l = (int)(r / ng);
+        const int v = idx.v[g] - c0;
+        if (v < 0 || v >= nc) continue;
+        reinterpret_cast<f32x4*>(dst + l * dst_stride + (int64_t)(g0 + g) * width4 * 4)[j] = reinterpret_cast<const f32x4*>(src + l * src_stride + (int64_t)v * width4 * 4)[j];
     }
 }
 
@@ -281,16 +373,52 @@ int ltx_launch_scale_cols(const void* W, const float* scale, void* out, int64_t 
 }
 int ltx_launch_guidance_step(const GuidanceArgs& a, hipStream_t s) {
     if (!a.text || a.B < 1 || a.n_per_batch < 1) LTX_FAIL(LTX_ERR_ARG, "guidance: text prediction required");
+    if (a.hold && (a.num_frames < 1 || a.frame_elems < 1 || (int64_t)a.num_frames * a.frame_elems != a.n_per_batch))
+        LTX_FAIL(LTX_ERR_ARG, "guidance (held): n must equal num_frames * frame_elems");
     const bool rescale = a.uncond && a.guidance_rescale > 0.0f;
-    if (rescale) {
+    if (rescale) {                                          // (the statistics of ALL tokens of a batch row, held or not)
         if (!a.stats) LTX_FAIL(LTX_ERR_ARG, "guidance: rescale needs a stats workspace");
         HIP_TRY(hipMemsetAsync(a.stats, 0, sizeof(double) * 4 * a.B, s));
         int64_t bx = cdiv64(a.n_per_batch, 256 * 8); if (bx > 1024) bx = 1024; if (bx < 1) bx = 1;
         hipLaunchKernelGGL(guidance_stats_kernel, dim3((unsigned)bx, (unsigned)a.B), dim3(256), 0, s, a);
         LTX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(guidance_apply_kernel, grid_for((int64_t)a.B * a.n_per_batch), dim3(256), 0, s, a);
+    // held frames: the 16-byte kernel where every chunk of four lies in one frame and every pointer is aligned for it
+    const bool bf = a.pred_dtype == LTX_DT_BF16;
+    const uintptr_t pa = bf ? 7 : 15;
+    const bool vec = a.hold && a.frame_elems % 4 == 0 && !((uintptr_t)a.text & pa) && !((uintptr_t)a.uncond & pa) && !((uintptr_t)a.pert & pa) &&
+                     !((uintptr_t)a.latents & 15) && !((uintptr_t)a.noise_out & 15) && !((uintptr_t)a.step_noise & 15);
+    if (vec) {
+        const dim3 grid = grid_for((int64_t)a.B * (a.n_per_batch >> 2));
+        if (bf) hipLaunchKernelGGL(guidance_held_vec_kernel<bf16_t>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(guidance_held_vec_kernel<float>, grid, dim3(256), 0, s, a);
+    } else hipLaunchKernelGGL(guidance_apply_kernel, grid_for((int64_t)a.B * a.n_per_batch), dim3(256), 0, s, a);
     LTX_CHECK_LAUNCH(); return LTX_OK;
+}
+int ltx_launch_guidance_step_held(const GuidanceArgs& a, hipStream_t s) {
+    if (!a.hold) LTX_FAIL(LTX_ERR_ARG, "guidance (held): hold is required");
+    return ltx_launch_guidance_step(a, s);
+}
+int ltx_launch_cond_apply(float* latents, const float* cond, int Fc, const unsigned char* hold_dev, int B, int F, int64_t frame_elems, hipStream_t s) {
+    if (!latents || !cond || !hold_dev || B < 1 || F < 1 || Fc < 1 || frame_elems < 1) LTX_FAIL(LTX_ERR_ARG, "cond_apply: bad argument");
+    if ((int64_t)B * F > 65535) LTX_FAIL(LTX_ERR_ARG, "cond_apply: too many frames");
+    const int vec = frame_elems % 4 == 0 && !((uintptr_t)latents & 15) && !((uintptr_t)cond & 15);
+    int64_t bx = cdiv64(vec ? frame_elems >> 2 : frame_elems, 256); if (bx > 256) bx = 256;
+    hipLaunchKernelGGL(cond_apply_kernel, dim3((unsigned)bx, (unsigned)(B * F)), dim3(256), 0, s, latents, cond, Fc, hold_dev, F, frame_elems, vec);
+    LTX_CHECK_LAUNCH(); return LTX_OK;
+}
+int ltx_launch_group_gather(float* dst, int64_t dst_stride, const float* src, int64_t src_stride, const int* idx_host, int c0, int nc, int nl, int ngroups, int width, hipStream_t s) {
+    if (!dst || !src || !idx_host || nc < 1 || nl < 1 || ngroups < 1 || width < 4 || width % 4 || dst_stride % 4 || src_stride % 4 || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15))
+        LTX_FAIL(LTX_ERR_ARG, "group_gather: bad argument");
+    for (int g0 = 0; g0 < ngroups; g0 += 128) {
+        GroupIdx gi; const int ng = ngroups - g0 < 128 ? ngroups - g0 : 128;
+        bool any = false;
+        for (int g = 0; g < 128; ++g) { gi.v[g] = g < ng ? idx_host[g0 + g] : -1; any = any || (g < ng && gi.v[g] >= c0 && gi.v[g] < c0 + nc); }
+        if (!any) continue;
+        hipLaunchKernelGGL(group_gather_kernel, grid_for((int64_t)nl * ng * (width / 4)), dim3(256), 0, s, dst, dst_stride, src, src_stride, gi, g0, ng, c0, nc, nl, width / 4);
+        LTX_CHECK_LAUNCH();
+    }
+    return LTX_OK;
 }
 int ltx_launch_denorm_mix(const float* lat, const float* mean, const float* std_dev, float inv_sf, const float* noise,
                           const TimeVec& nscale, void* out, int dtype, int B, int64_t S, int C, hipStream_t s) {

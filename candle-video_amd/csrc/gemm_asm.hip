@@ -946,6 +946,11 @@ extern "C" int ltx_dbg_gemm_asm16_trace(uint32_t* out, int n_words) {
 #endif
 
 int ltx_launch_gemm_asm16(const GemmArgs& g, int epi, int tile, hipStream_t s) {     // tile: kAsmTiles order
+    // The wide epilogue loads the per-group vectors (gate, 1 + scale2, cvec) of a tile's first and last row and chooses per row: right
+    // only while a tile meets at most one group boundary.  ltx_gemm_asm16_fits / ltx_gemm_fold_ok refuse shorter groups (the DiT's
+    // per-frame modulation at small latent planes); a call that got here past them would be modulated wrongly without a sign.
+    if (((epi == EPI_GATE_RESID && g.gate) || g.C2 || g.rs_sq) && g.rows_per_batch < 320)
+        LTX_FAIL(LTX_ERR_ARG, "gemm_asm16: per-group epilogue vectors need groups of at least 320 rows (a tile may meet one group boundary)");
     ltx_prof_kernel(LTX_PROFK_GEMM_ASM16);
     switch (tile) {
         case 0: return launch_asm_epi<256, 256, 2, 2, true>(g, epi, s);

@@ -253,6 +253,13 @@ int ltx_launch_skip_blend(void* h, const void* orig, const TimeVec& m, int64_t r
 int ltx_launch_scale_cols(const void* W, const float* scale, void* out, int64_t N, int K, int dtype, hipStream_t s);      // out[n][k] = W[n][k] * (1 + scale[k])
 int ltx_launch_mod_scale(const void* h, const float* scale, int scale_stride, void* y, int B, int64_t rows_per_batch, int D, int dtype, hipStream_t s);   // y = h (.) (1 + scale[b])
 
+// Per-group modulation tables from the tables of the distinct timesteps (dit.hip, DitGroupEntry): for every layer l < nl and group
+// g < ngroups whose value index idx_host[g] lies in [c0, c0 + nc):  dst[l * dst_stride + g * width + j] = src[l * src_stride + (idx_host[g] - c0) * width + j].
+// f32, width % 4 == 0, 16-byte aligned rows; the other groups of dst are left alone (another batch of values fills them).
+// idx_host is HOST memory, read before the call returns (it travels in the kernel arguments, 128 groups a launch).
+struct GroupIdx { int v[128]; };
+int ltx_launch_group_gather(float* dst, int64_t dst_stride, const float* src, int64_t src_stride, const int* idx_host, int c0, int nc, int nl, int ngroups, int width, hipStream_t s);
+
 struct GuidanceArgs {
     const void* text = nullptr; const void* uncond = nullptr; const void* pert = nullptr;  // model dtype (pred_dtype)
     int pred_dtype = LTX_DT_F32;
@@ -264,8 +271,15 @@ struct GuidanceArgs {
     // stochastic sampling (scheduler.rs:557-575): x = (1 - sigma_next) * (x - sigma * v) + sigma_next * noise
     const float* step_noise = nullptr;   // f32 [B, n_per_batch] or null (= deterministic Euler with dt)
     float sigma = 0.f, sigma_next = 0.f;
+    // Held frames (null: none): hold[b * num_frames + f] != 0 keeps the latents of frame f of batch row b -
+    // frame_elems consecutive values, n_per_batch = num_frames * frame_elems - bit for bit.  The mix, the rescale statistics and
+    // noise_out cover every token as without it.
+    const unsigned char* hold = nullptr; int num_frames = 1; int64_t frame_elems = 0;
 };
 int ltx_launch_guidance_step(const GuidanceArgs& a, hipStream_t s);
+int ltx_launch_guidance_step_held(const GuidanceArgs& a, hipStream_t s);
+// latents[b][f] = cond[b][f] for the frames with hold_dev[b * F + f] != 0 (f < Fc); latents f32 [B, F, frame_elems], cond f32 [B, Fc, frame_elems]
+int ltx_launch_cond_apply(float* latents, const float* cond, int Fc, const unsigned char* hold_dev, int B, int F, int64_t frame_elems, hipStream_t s);
 
 // tokens [B,S,C] f32 -> channels-last T:  y = (x*std/sf + mean)*(1-ns) + noise*ns ; noise is NCTHW f32 [B,C,S] or null
 int ltx_launch_denorm_mix(const float* lat, const float* mean, const float* std_, float inv_sf, const float* noise,

@@ -7,6 +7,7 @@
 #include <vector>
 #include "../csrc/model_util.h"
 #include "../csrc/options.h"
+#include "../../include/ltxhip_cond.h"
 
 // calculate_shift (t2v_pipeline.rs:159-169), f32 arithmetic
 extern "C" float ltx_calculate_shift(int seq_len, int base_seq_len, int max_seq_len, float base_shift, float max_shift) {
@@ -229,6 +230,62 @@ extern "C" int ltx_guidance_step_stochastic(const void* text, const void* uncond
     return ltx_launch_guidance_step(a, (hipStream_t)stream);
 }
 
+// ---- held frames (include/ltxhip_cond.h) ----
+extern "C" int ltx_guidance_step_held(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype,
+                                      float* latents, float* noise_pred_out, int B, int64_t n,
+                                      float guidance_scale, float guidance_rescale, float stg_scale, float dt,
+                                      void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems, ltx_stream stream) {
+    if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_held: hold is required");
+    GuidanceArgs a;
+    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
+    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
+    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale; a.dt = dt;
+    a.stats = reinterpret_cast<double*>(stats_ws);
+    a.hold = hold; a.num_frames = num_frames; a.frame_elems = frame_elems;
+    return ltx_launch_guidance_step_held(a, (hipStream_t)stream);
+}
+
+extern "C" int ltx_guidance_step_stochastic_held(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype,
+                                                 float* latents, float* noise_pred_out, int B, int64_t n,
+                                                 float guidance_scale, float guidance_rescale, float stg_scale,
+                                                 float sigma, float sigma_next, const float* step_noise,
+                                                 void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems, ltx_stream stream) {
+    if (!step_noise || !latents) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic_held: latents and step_noise are required");
+    if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic_held: hold is required");
+    GuidanceArgs a;
+    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
+    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
+    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale;
+    a.sigma = sigma; a.sigma_next = sigma_next; a.step_noise = step_noise;
+    a.stats = reinterpret_cast<double*>(stats_ws);
+    a.hold = hold; a.num_frames = num_frames; a.frame_elems = frame_elems;
+    return ltx_launch_guidance_step_held(a, (hipStream_t)stream);
+}
+
+extern "C" int ltx_cond_apply(float* latents, const float* cond_tokens, int cond_frames, const unsigned char* hold,
+                              int B, int num_frames, int tokens_per_frame, int channels, ltx_stream stream) {
+    if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_apply: hold is required");
+    if (!latents || !cond_tokens || B < 1 || num_frames < 1 || cond_frames < 1 || tokens_per_frame < 1 || channels < 1)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_cond_apply: bad argument");
+    bool any = false;
+    for (int b = 0; b < B; ++b)
+        for (int f = 0; f < num_frames; ++f)
+            if (hold[(size_t)b * num_frames + f]) {
+                if (f >= cond_frames) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_apply: held frame " + std::to_string(f) + " lies beyond the " + std::to_string(cond_frames) + " conditioning frame(s)");
+                any = true;
+            }
+    if (!any) return LTX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nh = (size_t)B * num_frames;
+    unsigned char* hd = nullptr;
+    HIP_TRY(hipMalloc((void**)&hd, nh));
+    struct Free { void* p; ~Free() { (void)hipFree(p); } } guard{hd};
+    HIP_TRY(hipMemcpyAsync(hd, hold, nh, hipMemcpyHostToDevice, s));
+    LTX_TRY(ltx_launch_cond_apply(latents, cond_tokens, cond_frames, hd, B, num_frames, (int64_t)tokens_per_frame * channels, s));
+    HIP_TRY(hipStreamSynchronize(s));                        // (hold is the caller's host memory and hd is freed here)
+    return LTX_OK;
+}
+
 // ---- LtxPipeline::call ----
 static thread_local float g_timing[4] = {0, 0, 0, 0};
 extern "C" int ltx_pipeline_last_timing(float ms[4]) {
@@ -248,7 +305,7 @@ namespace {
 // Device scratch of the denoise loop, kept per (thread, device) across calls: per-call hipMalloc/hipFree (an implicit
 // device sync each) and the coords rebuild + blocking upload cost ~1 ms per video for nothing.
 struct PipeCache {
-    DevBuf p_text, p_uncond, p_pert, stats, coords;
+    DevBuf p_text, p_uncond, p_pert, stats, coords, hold;
     DevBuf g_lat, g_emb, g_mask, g_pred, g_coords;      // the guidance branches of a step as one forward: inputs / predictions of all branches
     int coords_key[6] = {-1, -1, -1, -1, -1, -1};      // B, F, H, W, frame_rate, ratios packed
 };
@@ -274,10 +331,11 @@ struct PipeScratch {
 };
 }  // namespace
 
-extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p,
-                                 float* latents, const float* prompt_embeds, const float* prompt_mask,
-                                 const float* neg_embeds, const float* neg_mask, const float* decode_noise,
-                                 int B, int K, float* out_video, ltx_stream stream) {
+// hold: HOST u8 [B, F'] or null - the held latent frames of ltx_pipeline_call_cond (include/ltxhip_cond.h); null: ltx_pipeline_call
+static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const unsigned char* hold,
+                        float* latents, const float* prompt_embeds, const float* prompt_mask,
+                        const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                        int B, int K, float* out_video, ltx_stream stream) {
     if (!dit || !p || !latents || !prompt_embeds || !prompt_mask) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: null argument");
     if (!p->output_latent && (!vae || !out_video)) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: decode requested without vae/out_video");
     // check_inputs (:313-365)
@@ -316,6 +374,11 @@ extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_
     if (do_cfg) { LTX_TRY(pc.p_uncond.ensure(pred_bytes)); sc.p_uncond = pc.p_uncond.p; }
     if (do_stg) { LTX_TRY(pc.p_pert.ensure(pred_bytes)); sc.p_pert = pc.p_pert.p; }
     LTX_TRY(pc.stats.ensure(64 * B)); sc.stats = pc.stats.p;
+    if (hold) {                                      // device copy for the update kernels (the model's per-frame timesteps are built on the host)
+        LTX_TRY(pc.hold.ensure((size_t)B * F));
+        HIP_TRY(hipMemcpyAsync(pc.hold.p, hold, (size_t)B * F, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));            // (once per call, in front of the loop: `hold` is the caller's host memory)
+    }
     // video_coords [B,S,3] (:798-847): rebuilt only when the geometry changes
     {
         const int key[6] = {B, F, H, W, p->frame_rate, ts_ratio * 1000 + sp_ratio};
@@ -376,6 +439,7 @@ extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_
     // denoising loop (:860-994)
     const bool hooked = p->interrupt != nullptr || p->on_step != nullptr;
     bool stopped = false; int steps_run = 0;
+    std::vector<float> tframes;                             // held frames: the step's timesteps per (row of the forward, latent frame)
     std::vector<hipEvent_t> done_ev;                        // e2 of every executed step (owned by sc.step_ev)
     for (int i = 0; i < N; ++i) {
         // interrupt / per-step hook (:861-865).  The loop only ENQUEUES work: the host stays at most one step ahead of the device
@@ -390,25 +454,37 @@ extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_
         hipEvent_t e0, e1, e2;
         LTX_TRY(sc.new_event(&e0)); LTX_TRY(sc.new_event(&e1)); LTX_TRY(sc.new_event(&e2));
         HIP_TRY(hipEventRecord(e0, s));
+        // held frames: the model sees timestep 0 for their tokens and t_i for the rest, in every guidance branch
+        if (hold) {
+            tframes.resize((size_t)(gbatch ? nbr : 1) * B * F);
+            for (size_t r = 0; r < tframes.size() / ((size_t)B * F); ++r)
+                for (size_t j = 0; j < (size_t)B * F; ++j) tframes[r * B * F + j] = hold[j] ? 0.0f : (float)ts[i];
+        }
+        auto forward = [&](const void* x, const void* emb, const float* mk, int rows, const float* vc, const float* slm, void* pred) -> int {
+            if (hold) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
+            return ltx_dit_forward(dit, x, emb, tvals, mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
+        };
         if (gbatch) {
             for (int r = 0; r < nbr; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            LTX_TRY(ltx_dit_forward(dit, pc.g_lat.p, pc.g_emb.p, tvals, pc.g_mask.as<float>(), nbr * B, S, K, F, H, W, nullptr, pc.g_coords.as<float>(),
-                                    do_stg ? g_slm.data() : nullptr, LTX_F32, pc.g_pred.p, s));
+            LTX_TRY(forward(pc.g_lat.p, pc.g_emb.p, pc.g_mask.as<float>(), nbr * B, pc.g_coords.as<float>(), do_stg ? g_slm.data() : nullptr, pc.g_pred.p));
         } else {
-        if (do_cfg) LTX_TRY(ltx_dit_forward(dit, latents, neg_embeds, tvals, neg_mask, B, S, K, F, H, W, nullptr, coords, nullptr, LTX_F32, sc.p_uncond, s));
-        LTX_TRY(ltx_dit_forward(dit, latents, prompt_embeds, tvals, prompt_mask, B, S, K, F, H, W, nullptr, coords, nullptr, LTX_F32, sc.p_text, s));
-        if (do_stg) LTX_TRY(ltx_dit_forward(dit, latents, prompt_embeds, tvals, prompt_mask, B, S, K, F, H, W, nullptr, coords, stg_mask.data(), LTX_F32, sc.p_pert, s));
+            if (do_cfg) LTX_TRY(forward(latents, neg_embeds, neg_mask, B, coords, nullptr, sc.p_uncond));
+            LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, nullptr, sc.p_text));
+            if (do_stg) LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, stg_mask.data(), sc.p_pert));
         }
         HIP_TRY(hipEventRecord(e1, s));
         // guidance mix (:941-962) + scheduler.step (:987; scheduler.rs:544-581): dt = sigma_next - sigma
         const float dts = sig[i + 1] - sig[i];
-        if (p->stochastic_sampling)
-            LTX_TRY(ltx_guidance_step_stochastic(sc.p_text, do_cfg ? sc.p_uncond : nullptr, do_stg ? sc.p_pert : nullptr, LTX_F32, latents, nullptr, B, n,
-                                                 p->guidance_scale, p->guidance_rescale, p->stg_scale, sig[i], sig[i + 1],
-                                                 p->step_noise + (size_t)i * B * n, sc.stats, s));
-        else
-            LTX_TRY(ltx_guidance_step(sc.p_text, do_cfg ? sc.p_uncond : nullptr, do_stg ? sc.p_pert : nullptr, LTX_F32, latents, nullptr, B, n,
-                                      p->guidance_scale, p->guidance_rescale, p->stg_scale, dts, sc.stats, s));
+        {
+            GuidanceArgs ga;
+            ga.text = sc.p_text; ga.uncond = do_cfg ? sc.p_uncond : nullptr; ga.pert = do_stg ? sc.p_pert : nullptr; ga.pred_dtype = LTX_DT_F32;
+            ga.latents = latents; ga.B = B; ga.n_per_batch = n; ga.stats = reinterpret_cast<double*>(sc.stats);
+            ga.guidance_scale = p->guidance_scale; ga.guidance_rescale = p->guidance_rescale; ga.stg_scale = p->stg_scale;
+            if (p->stochastic_sampling) { ga.sigma = sig[i]; ga.sigma_next = sig[i + 1]; ga.step_noise = p->step_noise + (size_t)i * B * n; }
+            else ga.dt = dts;
+            if (hold) { ga.hold = pc.hold.as<unsigned char>(); ga.num_frames = F; ga.frame_elems = (int64_t)H * W * C; }      // held frames keep their bits
+            LTX_TRY(ltx_launch_guidance_step(ga, s));
+        }
         HIP_TRY(hipEventRecord(e2, s));
         done_ev.push_back(e2);
     }
@@ -433,6 +509,28 @@ extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_
     HIP_TRY(hipEventElapsedTime(&g_timing[2], sc.ev[1], sc.ev[2]));
     HIP_TRY(hipEventElapsedTime(&g_timing[3], sc.ev[0], sc.ev[2]));
     return LTX_OK;
+}
+
+extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p,
+                                 float* latents, const float* prompt_embeds, const float* prompt_mask,
+                                 const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                                 int B, int K, float* out_video, ltx_stream stream) {
+    return pipeline_run(dit, vae, p, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+}
+
+extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_conditioning* cond,
+                                      float* latents, const float* prompt_embeds, const float* prompt_mask,
+                                      const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                                      int B, int K, float* out_video, ltx_stream stream) {
+    if (!cond || !cond->hold) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cond: conditioning with a hold mask is required");
+    if (!p || B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cond: null argument");
+    int ts_ratio = 8;
+    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; }
+    const int F = (p->num_frames - 1) / ts_ratio + 1;
+    bool any = false;
+    for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) any = any || cond->hold[j] != 0;
+    // nothing held: ltx_pipeline_call itself
+    return pipeline_run(dit, vae, p, any ? cond->hold : nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
 }
 
 // ---- warm-up: everything a first call would otherwise do inside the caller's forward --------------------------------

@@ -220,6 +220,25 @@ for _name, _sig in _ENC_SIGS.items():
     _fn.restype = None if _name in ("ltx_vae_encoder_config_default", "ltx_vae_encoder_destroy") else C.c_int
 
 
+class ConditioningC(C.Structure):                # ltx_conditioning (include/ltxhip_cond.h)
+    _fields_ = [("hold", C.POINTER(C.c_ubyte))]
+
+
+# include/ltxhip_cond.h (kept apart like the encoder's: EXPORTED_SYMBOLS lists the headers that existed before both)
+_COND_SIGS = {
+    "ltx_dit_forward_frames": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
+    "ltx_guidance_step_held": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _f, _f, _f, _f, _vp, _vp, _i, _i64, _vp],
+    "ltx_guidance_step_stochastic_held": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _i64, _vp],
+    "ltx_cond_apply": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp],
+    "ltx_pipeline_call_cond": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+}
+COND_SYMBOLS = sorted(_COND_SIGS)
+for _name, _sig in _COND_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
+
+
 def _dt(t: torch.dtype) -> int:
     if t == torch.float32:
         return LTX_F32
@@ -271,6 +290,14 @@ def _make_weights(weights: Dict[str, torch.Tensor]):
 
 def _floats(vals) -> "C.Array":
     return (C.c_float * len(vals))(*[float(v) for v in vals])
+
+
+def _hold_host(hold, B: int, F: int) -> "C.Array":
+    """hold [B, F] (tensor or nested sequence, truthy = held) -> HOST u8 array in the order the C side reads"""
+    h = hold.detach().cpu().reshape(-1).tolist() if torch.is_tensor(hold) else [v for row in hold for v in (row if isinstance(row, (list, tuple)) else [row])]
+    if len(h) != B * F:
+        raise LtxError(f"hold must have {B} x {F} entries (batch rows x latent frames), got {len(h)}")
+    return (C.c_ubyte * (B * F))(*[1 if v else 0 for v in h])
 
 
 # ------------------------------------------------------------------ DiT
@@ -368,6 +395,39 @@ class LtxVideoTransformer3DModel:
                                    rs, _ptr(vc), slm, _dt(io), _ptr(out), _stream()))
         return out
 
+
+    def forward_frames(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor, timestep,
+                       encoder_attention_mask: Optional[torch.Tensor], num_frames: int, height: int, width: int,
+                       rope_interpolation_scale: Optional[Tuple[float, float, float]] = None,
+                       video_coords: Optional[torch.Tensor] = None,
+                       skip_layer_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """forward with one timestep per (batch row, latent frame): timestep [B, num_frames]; (num_frames, height, width) is the
+        latent grid and S must equal its product (ltx_dit_forward_frames, include/ltxhip_cond.h).  Inside context_cache(True) the
+        tensors must already be contiguous and of the call's dtype, as for forward."""
+        io = hidden_states.dtype if hidden_states.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        h = _dev(hidden_states, io)
+        e = _dev(encoder_hidden_states, io)
+        if h.dim() != 3 or e.dim() != 3:
+            raise LtxError("hidden_states must be [B,S,C] and encoder_hidden_states [B,K,C]")
+        B, S, _ = h.shape
+        K = e.shape[1]
+        t = torch.as_tensor(timestep, dtype=torch.float32).detach().flatten().cpu().tolist()
+        if len(t) != B * num_frames:
+            raise LtxError(f"timestep must have {B} x {num_frames} entries (batch rows x latent frames)")
+        if num_frames * height * width != S:
+            raise LtxError("forward_frames: S must equal num_frames*height*width (tokens in pack order, with or without video_coords)")
+        m = _dev(encoder_attention_mask, torch.float32) if encoder_attention_mask is not None else None
+        vc = _dev(video_coords, torch.float32) if video_coords is not None else None
+        if getattr(self, "_ctx_cache", False) and (e.data_ptr() != encoder_hidden_states.data_ptr() or (m is not None and m.data_ptr() != encoder_attention_mask.data_ptr())
+                                                   or (vc is not None and vc.data_ptr() != video_coords.data_ptr())):
+            raise LtxError("context_cache(True) needs encoder_hidden_states / encoder_attention_mask / video_coords that are already contiguous "
+                           "device tensors of the dtype the call uses: a temporary copy has no stable identity")
+        slm = _floats(skip_layer_mask.detach().float().cpu().flatten().tolist()) if skip_layer_mask is not None else None
+        rs = _floats(rope_interpolation_scale) if rope_interpolation_scale is not None else None
+        out = torch.empty(B, S, self.config.out_channels, dtype=io, device=h.device)
+        _check(lib.ltx_dit_forward_frames(self._h, _ptr(h), _ptr(e), _floats(t), _ptr(m), B, S, K, num_frames, height, width,
+                                          rs, _ptr(vc), slm, _dt(io), _ptr(out), _stream()))
+        return out
 
 # ------------------------------------------------------------------ T5 text encoder (include/ltxhip_t5.h)
 class T5ConfigC(C.Structure):
@@ -929,6 +989,22 @@ def pack_latents(x: torch.Tensor) -> torch.Tensor:
     return x.permute(0, 2, 3, 4, 1).reshape(b, f * h * w, c).contiguous()
 
 
+def cond_apply(latents: torch.Tensor, cond_tokens: torch.Tensor, hold, num_frames: int) -> torch.Tensor:
+    """latents[b, f] = cond_tokens[b, f] for the held latent frames (ltx_cond_apply), on a copy.  latents [B, num_frames*hw, C] f32,
+    cond_tokens [B, cond_frames*hw, C] f32 (encode_tokens of the image / clip), hold [B, num_frames] truthy = held."""
+    lat = _dev(latents, torch.float32).clone()
+    ct = _dev(cond_tokens, torch.float32)
+    if lat.dim() != 3 or ct.dim() != 3 or lat.shape[0] != ct.shape[0] or lat.shape[2] != ct.shape[2]:
+        raise LtxError("cond_apply: latents [B, F*hw, C] and cond_tokens [B, Fc*hw, C] must agree in B and C")
+    B, S, Cn = lat.shape
+    if num_frames < 1 or S % num_frames != 0 or ct.shape[1] % (S // num_frames) != 0 or ct.shape[1] == 0:
+        raise LtxError("cond_apply: token counts must be whole latent frames")
+    hw = S // num_frames
+    h = _hold_host(hold, B, num_frames)
+    _check(lib.ltx_cond_apply(_ptr(lat), _ptr(ct), ct.shape[1] // hw, h, B, num_frames, hw, Cn, _stream()))
+    return lat
+
+
 # ------------------------------------------------------------------ pipeline
 @dataclass
 class PipelineCall:
@@ -962,8 +1038,10 @@ class LtxPipeline:
     def call(self, args: PipelineCall, latents: torch.Tensor, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
              negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
              decode_noise: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
-             interrupt=None, on_step=None):
+             interrupt=None, on_step=None, hold=None):
         """Returns (final_latents [B,S,C] f32, video [B,3,frames,H,W] f32 or None).
+        hold [B, F'] (truthy = held): image-to-video / clip continuation (ltx_pipeline_call_cond) - `latents` carries the held
+        latent frames already (cond_apply); they see timestep 0 and leave the call unchanged.
         step_noise [steps,B,S,C] f32: the per-step draws of the stochastic-sampling scheduler (required iff enabled).
         interrupt: a ctypes.c_int the caller may set from another thread (LtxPipeline::interrupt, t2v_pipeline.rs:266, 861-863);
         on_step(step, num_steps, timestep) -> truthy to stop: the per-step hook.  self.last_steps = (executed, requested)."""
@@ -1037,9 +1115,16 @@ class LtxPipeline:
                 video = torch.empty(B, (F - 1) * tr + 1, H * sr, W * sr, 3, dtype=torch.uint8, device=lat.device)
             else:
                 video = torch.empty(B, 3, (F - 1) * tr + 1, H * sr, W * sr, dtype=torch.float32, device=lat.device)
-        _check(lib.ltx_pipeline_call(self.transformer._h, self.vae._h if self.vae is not None else None, C.byref(p),
-                                     _ptr(lat), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
-                                     _ptr(video), _stream()))
+        if hold is not None:
+            hh = _hold_host(hold, B, F); keep.append(hh)
+            cond = ConditioningC(C.cast(hh, C.POINTER(C.c_ubyte)))
+            _check(lib.ltx_pipeline_call_cond(self.transformer._h, self.vae._h if self.vae is not None else None, C.byref(p), C.byref(cond),
+                                              _ptr(lat), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                              _ptr(video), _stream()))
+        else:
+            _check(lib.ltx_pipeline_call(self.transformer._h, self.vae._h if self.vae is not None else None, C.byref(p),
+                                         _ptr(lat), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                         _ptr(video), _stream()))
         ms = (C.c_float * 4)()
         _check(lib.ltx_pipeline_last_timing(ms))
         self.last_timing_ms = tuple(ms)
@@ -1231,6 +1316,50 @@ def save_frames_png(video: torch.Tensor, out_dir: str) -> int:
 
 # ------------------------------------------------------------------ kernel-level ops (include/ltxhip_ops.h)
 class ops:
+    @staticmethod
+    def guidance_step(text, latents, uncond=None, perturbed=None, guidance_scale=1.0, guidance_rescale=0.0, stg_scale=0.0, dt=0.0,
+                      sigma=None, sigma_next=None, step_noise=None, hold=None, num_frames=None, want_noise_pred=False):
+        """One guidance mix + scheduler update on a copy of `latents` [B, ...] f32: Euler (x + dt * v), or with step_noise the
+        stochastic update (sigma, sigma_next).  hold [B, num_frames] (DEVICE u8 tensor or host values, truthy = held) selects the
+        held-frame kernels (ltx_guidance_step_held / _stochastic_held): those latent frames keep their bits.
+        Returns the new latents, or (latents, noise_pred f32) with want_noise_pred."""
+        t = _dev(text)
+        u = _dev(uncond, t.dtype) if uncond is not None else None
+        p = _dev(perturbed, t.dtype) if perturbed is not None else None
+        x = _dev(latents, torch.float32).clone()
+        B, n = x.shape[0], x[0].numel()
+        if t.shape[0] != B or t[0].numel() != n:
+            raise LtxError("guidance_step: predictions and latents must agree in shape")
+        nz = _dev(step_noise, torch.float32) if step_noise is not None else None
+        if nz is not None and (sigma is None or sigma_next is None or nz.numel() != B * n):
+            raise LtxError("guidance_step: the stochastic update needs sigma, sigma_next and step_noise of the latents' shape")
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_noise_pred else None
+        ws = torch.zeros(8 * B, dtype=torch.float64, device=x.device)
+        g = (C.c_float(guidance_scale), C.c_float(guidance_rescale), C.c_float(stg_scale))
+        if hold is None:
+            if nz is not None:
+                _check(lib.ltx_guidance_step_stochastic(_ptr(t), _ptr(u), _ptr(p), _dt(t.dtype), _ptr(x), _ptr(out), B, C.c_int64(n), *g,
+                                                        C.c_float(sigma), C.c_float(sigma_next), _ptr(nz), _ptr(ws), _stream()))
+            else:
+                _check(lib.ltx_guidance_step(_ptr(t), _ptr(u), _ptr(p), _dt(t.dtype), _ptr(x), _ptr(out), B, C.c_int64(n), *g, C.c_float(dt), _ptr(ws), _stream()))
+        else:
+            if num_frames is None or num_frames < 1 or n % num_frames != 0:
+                raise LtxError("guidance_step: hold needs num_frames dividing the per-row element count")
+            if torch.is_tensor(hold) and hold.is_cuda:
+                hd = hold.to(torch.uint8).contiguous()
+            else:
+                hd = torch.tensor(list(_hold_host(hold, B, num_frames)), dtype=torch.uint8).to(x.device)
+            if hd.numel() != B * num_frames:
+                raise LtxError(f"hold must have {B} x {num_frames} entries")
+            if nz is not None:
+                _check(lib.ltx_guidance_step_stochastic_held(_ptr(t), _ptr(u), _ptr(p), _dt(t.dtype), _ptr(x), _ptr(out), B, C.c_int64(n), *g,
+                                                             C.c_float(sigma), C.c_float(sigma_next), _ptr(nz), _ptr(ws), _ptr(hd), num_frames,
+                                                             C.c_int64(n // num_frames), _stream()))
+            else:
+                _check(lib.ltx_guidance_step_held(_ptr(t), _ptr(u), _ptr(p), _dt(t.dtype), _ptr(x), _ptr(out), B, C.c_int64(n), *g, C.c_float(dt),
+                                                  _ptr(ws), _ptr(hd), num_frames, C.c_int64(n // num_frames), _stream()))
+        return (x, out) if want_noise_pred else x
+
     @staticmethod
     def linear(x, w, bias=None, epi=0, resid=None, gate=None, rows_per_batch=1):
         M, K = x.shape

@@ -257,3 +257,33 @@ extern "C" {
                                  tiling: *const ltx_tiling, enc_tiling: *const ltx_encode_tiling, eps: *const c_float, tokens_out: *mut c_float, stream: ltx_stream) -> c_int;
     pub fn ltx_vae_encoder_warmup(e: *mut ltx_vae_encoder, b: c_int, f: c_int, h: c_int, w: c_int, tiling: *const ltx_tiling, enc_tiling: *const ltx_encode_tiling, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_cond.h: per-frame timesteps and held conditioning frames (image-to-video, clip continuation) ----
+
+/// `ltx_conditioning`: HOST u8 [B, F'] hold mask, 1 = the latent frame is given and held.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_conditioning {
+    pub hold: *const u8,
+}
+
+pub const COND_LAYOUT_LTX_CONDITIONING: (usize, usize) = (8, 8);
+const _: () = assert!(size_of::<ltx_conditioning>() == COND_LAYOUT_LTX_CONDITIONING.0 && align_of::<ltx_conditioning>() == COND_LAYOUT_LTX_CONDITIONING.1);
+
+extern "C" {
+    pub fn ltx_dit_forward_frames(m: *mut ltx_dit, hidden: *const c_void, enc: *const c_void, timestep: *const c_float, enc_mask: *const c_float,
+                                  b: c_int, s: c_int, k: c_int, num_frames: c_int, height: c_int, width: c_int, rope_scale: *const c_float,
+                                  video_coords: *const c_float, skip_layer_mask: *const c_float, io_dtype: c_int, out: *mut c_void, stream: ltx_stream) -> c_int;
+    pub fn ltx_guidance_step_held(text: *const c_void, uncond: *const c_void, perturbed: *const c_void, pred_dtype: c_int, latents: *mut c_float,
+                                  noise_pred_out: *mut c_float, b: c_int, n: i64, guidance_scale: c_float, guidance_rescale: c_float, stg_scale: c_float,
+                                  dt: c_float, stats_ws: *mut c_void, hold: *const u8, num_frames: c_int, frame_elems: i64, stream: ltx_stream) -> c_int;
+    pub fn ltx_guidance_step_stochastic_held(text: *const c_void, uncond: *const c_void, perturbed: *const c_void, pred_dtype: c_int, latents: *mut c_float,
+                                             noise_pred_out: *mut c_float, b: c_int, n: i64, guidance_scale: c_float, guidance_rescale: c_float,
+                                             stg_scale: c_float, sigma: c_float, sigma_next: c_float, step_noise: *const c_float, stats_ws: *mut c_void,
+                                             hold: *const u8, num_frames: c_int, frame_elems: i64, stream: ltx_stream) -> c_int;
+    pub fn ltx_cond_apply(latents: *mut c_float, cond_tokens: *const c_float, cond_frames: c_int, hold: *const u8, b: c_int, num_frames: c_int,
+                          tokens_per_frame: c_int, channels: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_call_cond(dit: *mut ltx_dit, vae: *mut ltx_vae, p: *const ltx_pipeline_params, cond: *const ltx_conditioning, latents: *mut c_float,
+                                  prompt_embeds: *const c_float, prompt_mask: *const c_float, neg_embeds: *const c_float, neg_mask: *const c_float,
+                                  decode_noise: *const c_float, b: c_int, k: c_int, out_video: *mut c_float, stream: ltx_stream) -> c_int;
+}
