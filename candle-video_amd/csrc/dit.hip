@@ -9,6 +9,7 @@
 #include "model_util.h"
 #include "options.h"
 #include "../../include/ltxhip_cond.h"
+#include "lora.h"
 
 struct DitBlock {
     LinearW qkv1, o1, q2, kv2, o2, ff1, ff2;
@@ -70,11 +71,19 @@ struct ltx_dit {
     // RoPE tables of the caching scope (ltx_dit_context_cache: the caller keeps coords / geometry constant inside it): what cosb / sinb hold
     struct { bool valid = false; const float* coords = nullptr; float rs[3] = {0, 0, 0}; bool has_rs = false; int B = 0, S = 0, F = 0, H = 0, W = 0; hipStream_t stream = nullptr; } rope_key;
     std::vector<void*> owned;        // every hipMalloc'd weight pointer
+    // LoRA (include/ltxhip_lora.h; ltx_dit_set_adapters below).  Per block and weight (qkv1, o1, q2, kv2, o2, ff1, ff2): the BASE
+    // pointer, never written after the upload, and the merged second buffer of a targeted weight (null: not targeted).  LinearW::w
+    // points at the merged buffer while adapters are active, so the forward reads one pointer either way.
+    struct LoraSlots { void* base[7] = {nullptr}; void* merged[7] = {nullptr}; };
+    std::vector<LoraSlots> lora_w;
+    int n_adapters = 0;
     // workspaces
     DevBuf xin, encin, h, n, qkv, attn, ff, c1, encp, kv2, tproj, e1, emb, embs, temb, ada, adaf, cosb, sinb, bias, orig, orig_hsq, outT, rsq, hsq, parts;
     void free_all() {
         for (void* p : owned) if (p) (void)hipFree(p);
         owned.clear();
+        for (auto& ls : lora_w) for (void*& p : ls.merged) if (p) { (void)hipFree(p); p = nullptr; }
+        lora_w.clear();
         DevBuf* bs[] = {&xin, &encin, &h, &n, &qkv, &attn, &ff, &c1, &encp, &kv2, &tproj, &e1, &emb, &embs, &temb, &ada, &adaf, &cosb, &sinb, &bias, &orig, &orig_hsq, &outT, &rsq, &hsq, &parts};
         for (DevBuf* b : bs) b->release();
         for (auto& e : ctxs) { e.kv.release(); e.bias.release(); e.kvc.release(); e.biasc.release(); e.kidx.release(); e.kcount.release(); }
@@ -177,6 +186,15 @@ int build(ltx_dit* m, const ltx_weight* weights, size_t n_weights) {
     return LTX_OK;
 }
 
+// the seven weights of a block in the order of ltx_dit::LoraSlots; the ten LoRA targets (ltxhip_lora.h's `which`) as
+// (weight, row part of a fused weight)
+LinearW* dit_slot(DitBlock& b, int slot) {
+    LinearW* const ws[7] = {&b.qkv1, &b.o1, &b.q2, &b.kv2, &b.o2, &b.ff1, &b.ff2};
+    return ws[slot];
+}
+constexpr int kLoraSlot[kLoraLinears] = {0, 0, 0, 1, 2, 3, 3, 4, 5, 6}, kLoraPart[kLoraLinears] = {0, 1, 2, 0, 0, 0, 1, 0, 0, 0};
+constexpr int kSlotParts[7] = {3, 1, 1, 2, 1, 1, 1}, kSlotFirst[7] = {0, 3, 4, 5, 7, 8, 9};
+
 }  // namespace
 
 extern "C" int ltx_dit_create(const ltx_dit_config* cfg, const ltx_weight* weights, size_t n_weights,
@@ -196,6 +214,9 @@ extern "C" int ltx_dit_create(const ltx_dit_config* cfg, const ltx_weight* weigh
     int rc = build(m, weights, n_weights);
     if (rc == LTX_OK && cfg->attention_head_dim == 128 && m->dtype == LTX_DT_BF16) rc = ltx_attention_q128_prepare();
     if (rc != LTX_OK) { m->free_all(); delete m; return rc; }
+    m->lora_w.resize(m->blocks.size());
+    for (size_t l = 0; l < m->blocks.size(); ++l)
+        for (int slot = 0; slot < 7; ++slot) m->lora_w[l].base[slot] = dit_slot(m->blocks[l], slot)->w;
     *out = m;
     return LTX_OK;
 }
@@ -760,5 +781,98 @@ extern "C" int ltx_dit_context_cache(ltx_dit* m, int enable) {
     for (auto& e : m->ctxs) e.valid = false;
     m->rope_key.valid = false;
     m->ctx_mode = enable != 0;
+    return LTX_OK;
+}
+
+// ---- LoRA adapters (include/ltxhip_lora.h) ----
+void ltx_dit_describe(const ltx_dit* m, ltx_dit_config* cfg, int* dtype, int* device) { *cfg = m->cfg; *dtype = m->dtype; *device = m->device; }
+
+extern "C" int ltx_dit_adapter_count(const ltx_dit* m) { return m ? m->n_adapters : 0; }
+
+extern "C" int ltx_dit_set_adapters(ltx_dit* m, const ltx_lora* const* loras, const float* scales, int n, ltx_stream stream) {
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_adapters: null handle");
+    if (n < 0 || n > kLoraMaxAdapters) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_adapters: " + std::to_string(n) + " adapters (0..8)");
+    if (n > 0 && (!loras || !scales)) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_adapters: null adapter list or scales");
+    const int L = m->cfg.num_layers;
+    for (int i = 0; i < n; ++i) {
+        const ltx_lora* l = loras[i];
+        if (!l) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_adapters: adapter " + std::to_string(i) + " is null");
+        if (l->cfg.num_attention_heads * l->cfg.attention_head_dim != m->D || l->cfg.num_layers != L || l->cfg.cross_attention_dim != m->cfg.cross_attention_dim ||
+            l->dtype != m->dtype || l->device != m->device)
+            LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_adapters: adapter " + std::to_string(i) + " was built for another configuration (inner dim " +
+                                  std::to_string(l->cfg.num_attention_heads * l->cfg.attention_head_dim) + ", " + std::to_string(l->cfg.num_layers) + " layers), dtype or device");
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t esz = ltx_dt_size(m->dtype);
+    // the merge of every target, operands in list order
+    std::vector<LoraMergeArgs> plan((size_t)L * kLoraLinears);
+    for (int i = 0; i < n; ++i)
+        for (const LoraEntry& e : loras[i]->entries) {
+            LoraMergeArgs& p = plan[(size_t)e.block * kLoraLinears + e.which];
+            p.At[p.n] = e.At; p.Bp[p.n] = e.Bp; p.r_pad[p.n] = e.r_pad; p.coef[p.n] = scales[i] * e.factor; ++p.n;
+        }
+    auto targeted = [&](int l, int slot) {
+        for (int part = 0; part < kSlotParts[slot]; ++part) if (plan[(size_t)l * kLoraLinears + kSlotFirst[slot] + part].n > 0) return true;
+        return false;
+    };
+    // second buffers first: nothing is launched and nothing changes before every one of them exists
+    std::vector<void**> fresh;
+    for (int l = 0; l < L; ++l)
+        for (int slot = 0; slot < 7; ++slot) {
+            if (!targeted(l, slot) || m->lora_w[l].merged[slot]) continue;
+            const LinearW* lw = dit_slot(m->blocks[l], slot);
+            void* p = nullptr;
+            const hipError_t e = hipMalloc(&p, (size_t)lw->out * lw->in * esz);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                for (void** q : fresh) { (void)hipFree(*q); *q = nullptr; }
+                LTX_FAIL(LTX_ERR_HIP, std::string("ltx_dit_set_adapters: hipMalloc of a merged weight: ") + hipGetErrorString(e) + " (the handle is unchanged)");
+            }
+            m->lora_w[l].merged[slot] = p; fresh.push_back(&m->lora_w[l].merged[slot]);
+        }
+    // every cache that is a function of the weights (wcache keeps its allocations; wfold_off and the GEMM plans are not touched)
+    for (auto& e : m->wcache) e.valid = false;
+    for (auto& e : m->tcache) e.cfold_valid = false;
+    for (auto& e : m->gcache) e.cfold_valid = false;
+    for (auto& e : m->ctxs) e.valid = false;
+    std::vector<void*> unused;
+    int rc = LTX_OK;
+    for (int l = 0; l < L; ++l)
+        for (int slot = 0; slot < 7; ++slot) {
+            LinearW* lw = dit_slot(m->blocks[l], slot);
+            auto& ls = m->lora_w[l];
+            if (!ls.merged[slot]) continue;                    // never targeted: w is the base
+            lw->wp.reset(); lw->wp_tried = false;                // (the packed copy, where one was made, is of the weights that go)
+            if (!targeted(l, slot)) { lw->w = ls.base[slot]; unused.push_back(ls.merged[slot]); ls.merged[slot] = nullptr; continue; }
+            const int parts = kSlotParts[slot], rows = lw->out / parts;
+            for (int part = 0; part < parts && rc == LTX_OK; ++part) {
+                const size_t off = (size_t)part * rows * lw->in * esz;
+                LoraMergeArgs a = plan[(size_t)l * kLoraLinears + kSlotFirst[slot] + part];
+                if (a.n > 0) {
+                    a.w0 = (const char*)ls.base[slot] + off; a.out = (char*)ls.merged[slot] + off; a.N = rows; a.K = lw->in;
+                    rc = ltx_launch_lora_merge(a, m->dtype, s);
+                } else if (hipMemcpyAsync((char*)ls.merged[slot] + off, (const char*)ls.base[slot] + off, (size_t)rows * lw->in * esz, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+                    ltx_set_error("ltx_dit_set_adapters: hipMemcpyAsync"); rc = LTX_ERR_HIP;
+                }
+            }
+            lw->w = ls.merged[slot];
+        }
+    m->n_adapters = n;
+    if (!unused.empty()) {                                       // forwards enqueued earlier may still read them
+        (void)hipDeviceSynchronize();
+        for (void* p : unused) (void)hipFree(p);
+    }
+    return rc;
+}
+
+extern "C" int ltx_dit_read_linear(const ltx_dit* m, int block, int which, void* out_dev, ltx_stream stream) {
+    if (!m || !out_dev) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_read_linear: null argument");
+    if (block < 0 || block >= m->cfg.num_layers || which < 0 || which >= kLoraLinears)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_read_linear: block 0.." + std::to_string(m->cfg.num_layers - 1) + ", which 0..9");
+    HIP_TRY(hipSetDevice(m->device));
+    const LinearW* lw = dit_slot(const_cast<DitBlock&>(m->blocks[block]), kLoraSlot[which]);
+    const size_t bytes = (size_t)(lw->out / kSlotParts[kLoraSlot[which]]) * lw->in * ltx_dt_size(m->dtype);
+    HIP_TRY(hipMemcpyAsync(out_dev, (const char*)lw->w + (size_t)kLoraPart[which] * bytes, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LTX_OK;
 }

@@ -239,6 +239,23 @@ for _name, _sig in _COND_SIGS.items():
     _fn.restype = C.c_int
 
 
+# include/ltxhip_lora.h (kept apart like the two above)
+_LORA_SIGS = {
+    "ltx_lora_parse_key": [C.c_char_p, C.c_char_p, _sz, C.POINTER(C.c_int)],
+    "ltx_lora_create": [_vp, _vp, _sz, _i, _vp, _vp], "ltx_lora_create_from_file": [_vp, C.c_char_p, _i, _vp, _vp], "ltx_lora_destroy": [_vp],
+    "ltx_dit_set_adapters": [_vp, _vp, _vp, _i, _vp], "ltx_dit_adapter_count": [_vp], "ltx_dit_read_linear": [_vp, _i, _i, _vp, _vp],
+    "ltx_op_lora_merge": [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
+}
+LORA_SYMBOLS = sorted(_LORA_SIGS)
+for _name, _sig in _LORA_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = None if _name == "ltx_lora_destroy" else C.c_int
+# the ten LoRA targets of a block, in the order of ltx_dit_read_linear's `which`
+LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0",
+                "ff.net.0.proj", "ff.net.2")
+
+
 def _dt(t: torch.dtype) -> int:
     if t == torch.float32:
         return LTX_F32
@@ -428,6 +445,76 @@ class LtxVideoTransformer3DModel:
         _check(lib.ltx_dit_forward_frames(self._h, _ptr(h), _ptr(e), _floats(t), _ptr(m), B, S, K, num_frames, height, width,
                                           rs, _ptr(vc), slm, _dt(io), _ptr(out), _stream()))
         return out
+
+    # ---- LoRA adapters (include/ltxhip_lora.h): handle state, so LtxPipeline.call runs on whatever is set
+    def set_adapters(self, loras: Sequence["LtxLora"] = (), scales: Optional[Sequence[float]] = None):
+        """effective weights = base + sum_i scales[i] * factor_i * (B_i A_i) on every linear the adapters target (no history: the list
+        replaces whatever was set; an empty list restores the base bit for bit).  Enqueued on the current stream."""
+        loras = list(loras)
+        scales = [1.0] * len(loras) if scales is None else [float(v) for v in scales]
+        if len(scales) != len(loras):
+            raise LtxError(f"set_adapters: {len(loras)} adapters but {len(scales)} scales")
+        arr = (C.c_void_p * max(len(loras), 1))(*[l._h for l in loras])
+        _check(lib.ltx_dit_set_adapters(self._h, arr, _floats(scales) if scales else None, len(loras), _stream()))
+        self._adapters = loras                  # (not needed by the library - merged weights do not refer to them - but cheap to show)
+
+    def adapter_count(self) -> int:
+        return int(lib.ltx_dit_adapter_count(self._h))
+
+    def linear_shape(self, which: int):
+        D = self.config.num_attention_heads * self.config.attention_head_dim
+        return (4 * D if which == 8 else D, 4 * D if which == 9 else self.config.cross_attention_dim if which in (5, 6) else D)
+
+    def read_linear(self, block: int, which: int, device="cuda") -> torch.Tensor:
+        """the current effective [out, in] matrix of linear `which` (index into LORA_TARGETS) of block `block`, model dtype"""
+        if not 0 <= which < 10:
+            raise LtxError("read_linear: which must be 0..9 (LORA_TARGETS)")
+        out = torch.empty(self.linear_shape(which), dtype=self.dtype, device=device)
+        _check(lib.ltx_dit_read_linear(self._h, block, which, _ptr(out), _stream()))
+        return out
+
+
+def lora_parse_key(key: str):
+    """(module name in Diffusers layout, role) of an adapter tensor name; role 0 = A / down, 1 = B / up, 2 = alpha (host only)"""
+    buf = C.create_string_buffer(1024)
+    role = C.c_int(0)
+    _check(lib.ltx_lora_parse_key(key.encode(), buf, C.c_size_t(len(buf)), C.byref(role)))
+    return buf.value.decode(), role.value
+
+
+class LtxLora:
+    """One LoRA adapter (ltx_lora): A / B pairs for block linears, uploaded once in the model dtype of `model`; usable with every
+    handle of the same configuration.  n_unmatched: adapter keys on modules that are not block linears."""
+
+    def __init__(self):
+        raise LtxError("use LtxLora.from_file or LtxLora.from_tensors")
+
+    @classmethod
+    def from_tensors(cls, model: LtxVideoTransformer3DModel, tensors: Dict[str, torch.Tensor], strict: bool = False) -> "LtxLora":
+        self = cls.__new__(cls)
+        arr, keep = _make_weights(tensors)
+        self._h = C.c_void_p()
+        nu = C.c_int(0)
+        _check(lib.ltx_lora_create(model._h, arr, C.c_size_t(len(tensors)), int(strict), C.byref(self._h), C.byref(nu)))
+        del keep
+        self.n_unmatched = nu.value
+        return self
+
+    @classmethod
+    def from_file(cls, model: LtxVideoTransformer3DModel, path: str, strict: bool = False) -> "LtxLora":
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        nu = C.c_int(0)
+        _check(lib.ltx_lora_create_from_file(model._h, path.encode(), int(strict), C.byref(self._h), C.byref(nu)))
+        self.n_unmatched = nu.value
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            lib.ltx_lora_destroy(h)
+            self._h = None
+
 
 # ------------------------------------------------------------------ T5 text encoder (include/ltxhip_t5.h)
 class T5ConfigC(C.Structure):
@@ -1459,6 +1546,20 @@ class ops:
         N, K = w.shape
         out = torch.empty_like(w)
         _check(lib.ltx_op_scale_cols(_ptr(w.contiguous()), _ptr(scale), _ptr(out), C.c_int64(N), K, _dt(w.dtype), _stream()))
+        return out
+
+    @staticmethod
+    def lora_merge(w0, adapters):
+        """out = round(f32(w0) + sum_i coef_i * (B_i A_i)): adapters = [(A [r, K], B [N, r], coef), ...] in w0's dtype (ltx_op_lora_merge)"""
+        w0 = _dev(w0); N, K = w0.shape
+        As = [_dev(a, w0.dtype) for a, _, _ in adapters]; Bs = [_dev(b, w0.dtype) for _, b, _ in adapters]
+        for a, b in zip(As, Bs):
+            _expect("A", a, (a.shape[0], K)); _expect("B", b, (N, a.shape[0]))
+        n = len(adapters)
+        out = torch.empty_like(w0)
+        pa = (C.c_void_p * max(n, 1))(*[a.data_ptr() for a in As]); pb = (C.c_void_p * max(n, 1))(*[b.data_ptr() for b in Bs])
+        rs = (C.c_int * max(n, 1))(*[a.shape[0] for a in As])
+        _check(lib.ltx_op_lora_merge(_ptr(w0), _ptr(out), N, K, n, pa, pb, rs, _floats([c for _, _, c in adapters]) if n else None, _dt(w0.dtype), _stream()))
         return out
 
     @staticmethod

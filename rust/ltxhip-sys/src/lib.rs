@@ -287,3 +287,23 @@ extern "C" {
                                   prompt_embeds: *const c_float, prompt_mask: *const c_float, neg_embeds: *const c_float, neg_mask: *const c_float,
                                   decode_noise: *const c_float, b: c_int, k: c_int, out_video: *mut c_float, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_lora.h: LoRA adapters merged into the DiT's weights on the device ----
+
+/// Opaque adapter object (`ltx_lora`): A / B pairs for block linears, bound to (dims, model dtype, device).
+#[repr(C)]
+pub struct ltx_lora {
+    _private: [u8; 0],
+}
+
+extern "C" {
+    pub fn ltx_lora_parse_key(key: *const c_char, module_out: *mut c_char, cap: usize, role: *mut c_int) -> c_int;
+    pub fn ltx_lora_create(like: *const ltx_dit, tensors: *const ltx_weight, n: usize, strict: c_int, out: *mut *mut ltx_lora, n_unmatched: *mut c_int) -> c_int;
+    pub fn ltx_lora_create_from_file(like: *const ltx_dit, path: *const c_char, strict: c_int, out: *mut *mut ltx_lora, n_unmatched: *mut c_int) -> c_int;
+    pub fn ltx_lora_destroy(l: *mut ltx_lora);
+    pub fn ltx_dit_set_adapters(m: *mut ltx_dit, loras: *const *const ltx_lora, scales: *const c_float, n: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_dit_adapter_count(m: *const ltx_dit) -> c_int;
+    pub fn ltx_dit_read_linear(m: *const ltx_dit, block: c_int, which: c_int, out_dev: *mut c_void, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_lora_merge(w0: *const c_void, out: *mut c_void, n_rows: i64, k: c_int, n: c_int, a: *const *const c_void, b: *const *const c_void,
+                             r: *const c_int, coef: *const c_float, dtype: c_int, stream: ltx_stream) -> c_int;
+}
