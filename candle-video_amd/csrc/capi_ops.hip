@@ -347,3 +347,14 @@ extern "C" int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B
     snprintf(name, (size_t)cap, "%s", ltx_gemm_route_name(r));
     return LTX_OK;
 }
+
+// Read-only probe of the DiT forward's decisions (dit.hip's ltx_dit_plan): no handle, no device, nothing launched
+extern "C" int ltx_op_dit_plan(int heads, int head_dim, int model_dtype, int io_dtype, int B, int S, int K, int G, int skip_mask, int64_t* out) {
+    if (!out || heads < 1 || head_dim < 1 || B < 1 || B > 8 || S < 1 || K < 1 || G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_dit_plan: bad argument");
+    ltx_dit_config c; ltx_dit_config_default(&c);
+    c.num_attention_heads = heads; c.attention_head_dim = head_dim; c.cross_attention_dim = heads * head_dim;
+    const DitPlan p = ltx_dit_plan(c, dtc(model_dtype), dtc(io_dtype), B, S, K, G, skip_mask != 0);
+    const int64_t v[LTX_DIT_PLAN_FIELDS] = {p.M, p.MK, p.NB, p.Sg, p.seg, p.ldqkv, p.fold_q2, p.presum, p.nfold, p.defer_ff2, p.ff2_parts, p.dense_qkv, p.fold_q};
+    for (int i = 0; i < LTX_DIT_PLAN_FIELDS; ++i) out[i] = v[i];
+    return LTX_OK;
+}

@@ -16,7 +16,7 @@ struct DitBlock {
     void *nq1 = nullptr, *nk1 = nullptr, *nq2 = nullptr, *nk2 = nullptr;
 };
 
-struct DitCtx {                      // cached text context (see ltx_dit_forward)
+struct DitCtx {                      // cached text context (text_context below)
     const void* enc = nullptr; const float* mask = nullptr;
     int B = 0, K = 0, iodt = 0; bool valid = false;
     bool fold_q2 = false;            // k additionally carries attn2.norm_q.weight (the q-norm folded into cross attention)
@@ -25,6 +25,7 @@ struct DitCtx {                      // cached text context (see ltx_dit_forward
     // multiplies ceil(count / 32) key blocks instead of ceil(K / 32) - BASELINE's prompts keep 32 of 128 text tokens
     bool compact = false;
     DevBuf kvc, biasc, kidx, kcount; // [L][B*K][2D], [B*K] f32, [B*K] int, [B] int
+    void release() { kv.release(); bias.release(); kvc.release(); biasc.release(); kidx.release(); kcount.release(); valid = false; }
 };
 
 // AdaLayerNormSingle's output for one set of timesteps (ltx_transformer.rs:262-309): a function of the timestep values and the
@@ -34,10 +35,14 @@ struct DitTimeEntry {
     float t[8] = {0}; int B = 0; hipStream_t stream = nullptr; bool valid = false; uint64_t used = 0;
     DevBuf ada, adaf;                // [L][B][6D] f32, [2][B][D] f32
     DevBuf cfold; bool cfold_valid = false;      // norm fold: per layer [B][3D] (shift_msa . W_qkv^T + b_qkv) then [B][4D] (shift_mlp . W_ff1^T + b_ff1), f32
+    void release() { ada.release(); adaf.release(); cfold.release(); valid = cfold_valid = false; }
 };
 // norm fold through the weights (norm_fold=2): per layer W_qkv (.) (1 + scale_msa) [3D, D] then W_ff1 (.) (1 + scale_mlp) [4D, D], model dtype.
 // Keyed by the TIMESTEP alone (the modulation of a row depends on nothing else): forwards of any batch size at that timestep share the copy.
-struct DitWfold { float t = 0.f; hipStream_t stream = nullptr; bool valid = false; uint64_t used = 0; DevBuf w; };
+struct DitWfold {
+    float t = 0.f; hipStream_t stream = nullptr; bool valid = false; uint64_t used = 0; DevBuf w;
+    void release() { w.release(); valid = false; }
+};
 constexpr int kDitTimeEntries = 64;
 // Per-frame timesteps (ltx_dit_forward_frames): the modulation tables of one [B, G] timestep matrix, one row per (batch row, latent
 // frame) - the layouts of DitTimeEntry with B * G modulation groups in place of B batch rows.  Built by a gather from the entries of
@@ -47,6 +52,7 @@ constexpr int kDitTimeEntries = 64;
 struct DitGroupEntry {
     std::vector<float> t; int B = 0, G = 0; hipStream_t stream = nullptr; bool valid = false; uint64_t used = 0;
     DevBuf ada, adaf, cfold; bool cfold_valid = false;      // [L][B*G][6D], [2][B*G][D], per layer [B*G][3D] then [B*G][4D]
+    void release() { ada.release(); adaf.release(); cfold.release(); valid = cfold_valid = false; }
 };
 constexpr int kDitGroupEntries = 8;
 
@@ -62,14 +68,26 @@ struct ltx_dit {
     float* rope_freqs = nullptr;     // [D/6]
     float* inv_freq = nullptr;       // [128]
     std::vector<int> skip_blocks;
+    // The five caches of the forward: text_context, time_tables, scaled_weights, group_tables, rope_tables (the last one is rope_key
+    // over cosb / sinb: a function of the geometry, not of the weights, and owns no memory).
     std::deque<DitCtx> ctxs;         // deque: entries must not move while `ctx` points at one
     bool ctx_mode = false;
     std::deque<DitTimeEntry> tcache; uint64_t tclock = 0;
     std::deque<DitWfold> wcache;
     std::deque<DitGroupEntry> gcache;
-    bool wfold_off = false;          // norm_fold=2 gave up on this handle: more distinct timesteps in flight than scaled-weight copies (a schedule that would re-scale every step)
+    bool wfold_off = false;          // norm_fold=2 gave up on this handle: more distinct timesteps in flight than scaled-weight copies (a schedule that would re-scale every step), or no memory for a copy
     // RoPE tables of the caching scope (ltx_dit_context_cache: the caller keeps coords / geometry constant inside it): what cosb / sinb hold
     struct { bool valid = false; const float* coords = nullptr; float rs[3] = {0, 0, 0}; bool has_rs = false; int B = 0, S = 0, F = 0, H = 0, W = 0; hipStream_t stream = nullptr; } rope_key;
+    // every cache that is a function of the weights (wcache keeps its allocations; wfold_off and the GEMM plans are not touched).
+    // A cache added to the forward is added HERE and to release_caches.
+    void invalidate_weight_derived() {
+        for (auto& e : wcache) e.valid = false;
+        for (auto& e : ctxs) e.valid = false;
+        for (auto& e : tcache) e.cfold_valid = false;
+        for (auto& e : gcache) e.cfold_valid = false;
+    }
+    void release_scaled_weights() { for (auto& e : wcache) e.release(); }      // norm_fold=2 gave up: the copies are never read again
+    void release_caches() { auto all = [](auto& c) { for (auto& e : c) e.release(); c.clear(); }; all(ctxs); all(tcache); all(wcache); all(gcache); }
     std::vector<void*> owned;        // every hipMalloc'd weight pointer
     // LoRA (include/ltxhip_lora.h; ltx_dit_set_adapters below).  Per block and weight (qkv1, o1, q2, kv2, o2, ff1, ff2): the BASE
     // pointer, never written after the upload, and the merged second buffer of a targeted weight (null: not targeted).  LinearW::w
@@ -86,14 +104,7 @@ struct ltx_dit {
         lora_w.clear();
         DevBuf* bs[] = {&xin, &encin, &h, &n, &qkv, &attn, &ff, &c1, &encp, &kv2, &tproj, &e1, &emb, &embs, &temb, &ada, &adaf, &cosb, &sinb, &bias, &orig, &orig_hsq, &outT, &rsq, &hsq, &parts};
         for (DevBuf* b : bs) b->release();
-        for (auto& e : ctxs) { e.kv.release(); e.bias.release(); e.kvc.release(); e.biasc.release(); e.kidx.release(); e.kcount.release(); }
-        ctxs.clear();
-        for (auto& e : tcache) { e.ada.release(); e.adaf.release(); e.cfold.release(); }
-        for (auto& e : wcache) e.w.release();
-        wcache.clear();
-        for (auto& e : gcache) { e.ada.release(); e.adaf.release(); e.cfold.release(); }
-        gcache.clear();
-        tcache.clear();
+        release_caches();
     }
 };
 
@@ -241,55 +252,93 @@ extern "C" int ltx_dit_get_config(const ltx_dit* m, ltx_dit_config* out) {
     return LTX_OK;
 }
 
-// one forward of up to 8 batch rows (the per-batch scalars - timesteps, skip-mask rows - travel as kernel arguments).
-// G: modulation groups per batch row - 1: one timestep per row (timestep [B]); num_frames: one per latent frame (timestep [B, G],
-// tokens in pack order, so a group is a run of S / G rows).  Only the AdaLN look-ups see the groups: they index their tables with
-// m / rows_per_batch, which becomes m / (S / G) over tables of B * G rows; attention, RoPE, the text context and the skip-layer
-// blend keep S.
-static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float* timestep, int G,
-                          const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
-                          const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
-                          ltx_dtype io_dtype, void* out, ltx_stream stream) {
-    if (B < 1 || B > 8) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: internal batch chunk must be 1..8");
-    if (S < 1 || K < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: empty sequence");
-    if (!video_coords && (int64_t)num_frames * height * width != S)
-        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: num_frames*height*width must equal S when video_coords is absent");
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    const ltx_dit_config& c = m->cfg;
-    const int dt = m->dtype, iodt = io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    const size_t esz = ltx_dt_size(dt);
-    const int D = m->D, L = c.num_layers, H = c.num_attention_heads, hd = c.attention_head_dim;
-    const int64_t M = (int64_t)B * S, MK = (int64_t)B * K;
-    if (G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: the modulation groups must divide the sequence");
-    const int NB = B * G, Sg = S / G;                       // modulation groups of the call, rows of one group
+// ---- the GEMMs of a block: one builder per call, used by the plan's fit tests (stand-in operands) and by dit_block (the real ones) ----
+namespace {
+enum DitForm { kPass,        // the plain call (the norm before it, where there is one, ran as a pass)
+               kFold1,       // norm fold: a producer (o2 / ff2) also stores h (.) (1 + scale) into n, a consumer (qkv1 / ff1) reads n and finishes with the row's 1 / rms and cvec
+               kFold2,       // norm_fold=2: the consumer reads h and the timestep's scaled weights (the producers run their pass form)
+               kDefer };     // ff2 alone: the K ranges are left in parts for the row norm that follows
+struct DitOperands {          // the handle's workspaces and one layer's table rows - or aligned non-null stand-ins: a fit test, nothing is launched
+    void *h, *n, *qkv, *attn, *ff; float *rsq, *hsq, *parts;
+    const float* ada;         // the layer's modulation [NB][6D]: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+    const float* ada_next;    // ... of the next block that runs (null: none)
+    const float* cfold;       // norm fold: the layer's [NB][3D] then [NB][4D]
+    const char* wfold;        // norm_fold=2: the layer's scaled q|k|v then ff1 weights
+    float eps;
+};
+GemmArgs gemm_base(const DitPlan& p, const LinearW& w, const void* A, int lda, void* C, int ldc) {
+    GemmArgs g; g.A = A; g.W = w.w; g.C = C; g.bias = w.b; g.M = (int)p.M; g.N = w.out; g.K = w.in; g.lda = lda; g.ldc = ldc;
+    return g;
+}
+// a consumer of the norm fold: out = epi(r_m * acc + cvec), r_m from the producer's row partials; form 2 reads h through the scaled weights
+void fold_in(GemmArgs& g, const DitPlan& p, DitForm f, const DitOperands& x, size_t cvec_at, size_t wfold_at) {
+    g.bias = nullptr; g.rows_per_batch = p.Sg; g.rs_sq = x.hsq; g.rs_n = p.D / 128; g.rs_D = p.D; g.rs_eps = x.eps; g.cvec = x.cfold + cvec_at; g.cvec_stride = g.N;
+    if (f == kFold2) { g.A = x.h; g.W = x.wfold + wfold_at; }
+}
+// q, k, v leave the fused projection as three DENSE [M, D] matrices (segmented GEMM output) when D is a power
+// of two: the attention kernel reads K/V rows of a dense matrix 7-11 % faster than column slices of [M, 3D]
+GemmArgs gemm_qkv1(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x) {
+    GemmArgs g = gemm_base(p, b.qkv1, x.n, p.D, x.qkv, p.ldqkv);
+    if (p.dense_qkv) { g.c_seg_shift = __builtin_ctz((unsigned)p.D); g.c_seg_stride = p.seg; }
+    if (f != kPass) fold_in(g, p, f, x, 0, 0);
+    return g;
+}
+GemmArgs gemm_q2(const DitPlan& p, const DitBlock& b, const DitOperands& x) {      // fold_q2: + the row partials of q for the attention kernel
+    GemmArgs g = gemm_base(p, b.q2, x.h, p.D, x.qkv, p.D);
+    if (p.fold_q2) g.rowsq = x.rsq;
+    return g;
+}
+GemmArgs gemm_o2(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x) {      // h += to_out(attn); fold 1: + h (.) (1 + scale_mlp) into n for ff1
+    GemmArgs g = gemm_base(p, b.o2, x.attn, p.D, x.h, p.D);
+    g.resid = x.h; g.ldr = p.D; g.rowsq = p.presum ? x.hsq : nullptr;
+    if (f == kFold1) { g.rows_per_batch = p.Sg; g.C2 = x.n; g.scale2 = x.ada + 4 * p.D; g.scale2_stride = 6 * p.D; }
+    return g;
+}
+GemmArgs gemm_ff1(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x) {
+    GemmArgs g = gemm_base(p, b.ff1, x.n, p.D, x.ff, 4 * p.D);
+    if (f != kPass) fold_in(g, p, f, x, (size_t)p.NB * 3 * p.D, (size_t)3 * p.D * p.D * ltx_dt_size(p.dt));
+    return g;
+}
+// h += gate_mlp * ff2(ff); fold 1: + h (.) (1 + scale_msa of the next block that runs) into n for its q|k|v projection; deferred: a bare
+// launch (no bias, gate or residual: RowNormArgs::parts finishes the rows)
+GemmArgs gemm_ff2(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x) {
+    GemmArgs g = gemm_base(p, b.ff2, x.ff, 4 * p.D, x.h, p.D);
+    if (f == kDefer) { g.bias = nullptr; g.defer_parts = x.parts; return g; }
+    g.resid = x.h; g.ldr = p.D; g.gate = x.ada + 5 * p.D; g.gate_stride = 6 * p.D; g.rows_per_batch = p.Sg; g.rowsq = p.presum ? x.hsq : nullptr;
+    if (f == kFold1) { g.C2 = x.n; g.scale2 = x.ada_next + p.D; g.scale2_stride = 6 * p.D; }
+    return g;
+}
+// a builder's plain form through ltx_linear, which writes the same fields from the same values
+int linear_of(const LinearW& l, const GemmArgs& g, int dt, int epi, hipStream_t s) {
+    return ltx_linear(l, g.A, g.lda, g.C, g.ldc, g.M, dt, epi, s, g.resid, g.ldr, g.gate, g.gate_stride, g.rows_per_batch, g.rowsq);
+}
+}  // namespace
 
-    LTX_TRY(m->xin.ensure(M * c.in_channels * esz));
-    LTX_TRY(m->encin.ensure(MK * c.caption_channels * esz));
-    LTX_TRY(m->h.ensure(M * D * esz)); LTX_TRY(m->n.ensure(M * D * esz));
-    LTX_TRY(m->qkv.ensure(M * 3 * D * esz)); LTX_TRY(m->attn.ensure(M * D * esz));
-    LTX_TRY(m->ff.ensure(M * 4 * D * esz));
-    LTX_TRY(m->c1.ensure(MK * D * esz)); LTX_TRY(m->encp.ensure(MK * D * esz)); LTX_TRY(m->kv2.ensure(MK * 2 * D * esz));
-    const size_t nte = G == 1 ? (size_t)B : 8;             // rows of one time-embedding launch: the batch rows, or eight distinct values of a per-frame call
-    LTX_TRY(m->tproj.ensure(nte * 256 * esz)); LTX_TRY(m->e1.ensure(nte * D * esz));
-    LTX_TRY(m->emb.ensure(nte * D * esz)); LTX_TRY(m->embs.ensure(nte * D * esz));
-    LTX_TRY(m->temb.ensure(nte * 6 * D * esz));
-    LTX_TRY(m->cosb.ensure(M * (D / 2) * sizeof(float))); LTX_TRY(m->sinb.ensure(M * (D / 2) * sizeof(float)));
-    LTX_TRY(m->bias.ensure(MK * sizeof(float)));
-    LTX_TRY(m->outT.ensure(M * c.out_channels * esz));
+// Which fusions a forward uses.  Each is decided by asking the kernel family that carries it whether it serves the call the block
+// loop WILL launch: the builders above with stand-in operands (the fit tests read the pointers' alignment alone, and hipMalloc
+// gives at least 256 bytes).  wf (norm_fold=2's scaled weights) is not here: it depends on the timestep values and the handle's state.
+DitPlan ltx_dit_plan(const ltx_dit_config& c, int dt, int iodt, int B, int S, int K, int G, bool skip_mask) {
+    DitPlan p; p.dt = dt; p.iodt = iodt; p.B = B; p.S = S; p.K = K;
+    const int D = c.num_attention_heads * c.attention_head_dim, hd = c.attention_head_dim;
+    p.D = D; p.M = (int64_t)B * S; p.MK = (int64_t)B * K; p.NB = B * G; p.Sg = S / G;
+    p.dense_qkv = (D & (D - 1)) == 0 && ltx_opt().dense_qkv;      // dense_qkv=0: column slices of [M, 3D] (A/B aid, and the path of a D that is not a power of two)
+    p.seg = p.dense_qkv ? p.M * D : D; p.ldqkv = p.dense_qkv ? D : 3 * D;
+    // bf16: q leaves the norm already multiplied by scale*log2(e) (ONE bf16 rounding, of the product), so the
+    // attention kernel's exponent is exp2(S - m) with no per-score multiply
+    p.fold_q = dt == LTX_DT_BF16 && ltx_attention_prescale_ok(hd);
+    const bool bf16 = dt == LTX_DT_BF16;
+    void* const a = reinterpret_cast<void*>((uintptr_t)4096); float* const f = reinterpret_cast<float*>(a);
+    auto lin = [&](int in, int out) { LinearW w; w.w = a; w.b = a; w.in = in; w.out = out; return w; };
+    DitBlock b; b.qkv1 = lin(D, 3 * D); b.q2 = lin(D, D); b.o2 = lin(D, D); b.ff1 = lin(D, 4 * D); b.ff2 = lin(4 * D, D);
+    const DitOperands x{a, a, a, a, a, f, f, f, f, f, f, (const char*)a, c.norm_eps};
     // Cross-attention q-norm folded into the attention kernel (bf16, head_dim 64, <= 128 text keys): scores are linear in q, so
     // rms_norm(q) . k = r_row * (q . (k * w_q)) - the q2 projection's epilogue leaves per-row partial sums of squares
     // (GemmArgs::rowsq), w_q = attn2.norm_q.weight rides on the cached k, and the stand-alone pass over q (read + write of
     // [M, D] per layer) disappears.  ltx_transformer.rs:671-678, 719-740.
     // Only where the projection can emit the partials from its own epilogue (a shape-only test: gemm_asm16's fit): behind any
     // other kernel they cost a stand-alone pass, which at small M (C1: 384 tokens) is dearer than the q-norm pass it replaces.
-    bool fold_q2 = dt == LTX_DT_BF16 && ltx_attention_rowsq_ok(hd, K, D);
-    if (fold_q2) {
-        GemmArgs gq; gq.A = m->h.p; gq.W = m->blocks[0].q2.w; gq.C = m->qkv.p; gq.bias = m->blocks[0].q2.b;
-        gq.M = (int)M; gq.N = m->blocks[0].q2.out; gq.K = m->blocks[0].q2.in; gq.lda = D; gq.ldc = D;
-        fold_q2 = ltx_gemm_asm16_fits(gq, EPI_BIAS) || ltx_opt().q2_fold == 2;       // q2_fold=2: fold whatever the shape (tests of the stand-alone partials)
-    }
-    if (fold_q2) LTX_TRY(m->rsq.ensure(M * (D / 128) * sizeof(float)));
+    p.fold_q2 = bf16 && ltx_attention_rowsq_ok(hd, K, D);
+    if (p.fold_q2) p.fold_q2 = ltx_gemm_asm16_fits(gemm_q2(p, b, x), EPI_BIAS) || ltx_opt().q2_fold == 2;       // q2_fold=2: fold whatever the shape (tests of the stand-alone partials)
     // The two RMS norms of a block take their rows' sums of squares from the epilogue of the GEMM that wrote h (ff2 of the block
     // before, attn2.to_out of this block: GemmArgs::rowsq) and run as a pure elementwise map; same shape-only condition as the
     // fold above (the partials must come from gemm_asm16's epilogue).  LTX_NORM_PRESUM=0: the row-reducing pass (A/B aid); "2" forces
@@ -297,464 +346,431 @@ static int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const
     // 13.5 us per launch) but operand re-use: with four rows per thread the 64 B of f32 modulation per 16-byte chunk are loaded once
     // per four chunks - 13.7 -> 11.0 us per launch, 7.3 -> 6.3 ms of norm passes per video against +0.5 ms in the two epilogues
     // (docs/lab_notes.md R4.4 / R4.7).
-    bool presum = dt == LTX_DT_BF16 && D % 512 == 0 && (D & (D - 1)) == 0 && D <= 2048;
-    if (presum) {
-        const int pe = ltx_opt().norm_presum;
-        GemmArgs gp; gp.A = m->attn.p; gp.W = m->blocks[0].o2.w; gp.C = m->h.p; gp.bias = m->blocks[0].o2.b; gp.resid = m->h.p;
-        gp.M = (int)M; gp.N = m->blocks[0].o2.out; gp.K = m->blocks[0].o2.in; gp.lda = D; gp.ldc = D; gp.ldr = D;
-        GemmArgs gf = gp; gf.A = m->ff.p; gf.W = m->blocks[0].ff2.w; gf.bias = m->blocks[0].ff2.b; gf.K = m->blocks[0].ff2.in; gf.lda = 4 * D;
-        gf.gate = reinterpret_cast<const float*>(m->h.p); gf.gate_stride = 6 * D; gf.rows_per_batch = Sg;      // (any aligned non-null pointer: a fit test, nothing is launched)
-        presum = (pe != 0 && ltx_gemm_asm16_fits(gp, EPI_RESID) && ltx_gemm_asm16_fits(gf, EPI_GATE_RESID)) || pe == 2;
-    }
-    if (presum) LTX_TRY(m->hsq.ensure(M * (D / 128) * sizeof(float)));
-    bool hsq_valid = false;                                 // m->hsq holds the partials of the CURRENT contents of h
+    p.presum = bf16 && D % 512 == 0 && (D & (D - 1)) == 0 && D <= 2048;
+    if (const int pe = ltx_opt().norm_presum; p.presum)
+        p.presum = (pe != 0 && ltx_gemm_asm16_fits(gemm_o2(p, kPass, b, x), EPI_RESID) && ltx_gemm_asm16_fits(gemm_ff2(p, kPass, b, x), EPI_GATE_RESID)) || pe == 2;
     // Norm fold (round 6; GemmArgs::C2 / ::rs_sq, kernels.h): with the partials in hand the norm pass between the layer that writes h
     // and the layer that reads the normalised rows is gone altogether - norm(h) * (1 + sc) + sh times W^T is
     // r_m * ((h (.) (1 + sc)) W^T) + (sh W^T + b): out2 / ff2 also store h (.) (1 + sc_next) into m->n, qkv / ff1 read it and finish
     // with the row's 1 / rms and the per-timestep vector sh W^T + b (cached with the timestep's modulation).  One rounding less than
     // the pass (bf16 of h (1 + sc) instead of bf16 of the modulated, normalised row); norm_fold=0: the pass (A/B arm).
-    bool nfold = presum && ltx_opt().norm_fold != 0;
-    if (nfold) {
-        GemmArgs gp; gp.A = m->attn.p; gp.W = m->blocks[0].o2.w; gp.C = m->h.p; gp.bias = m->blocks[0].o2.b; gp.resid = m->h.p;
-        gp.M = (int)M; gp.N = D; gp.K = D; gp.lda = D; gp.ldc = D; gp.ldr = D; gp.rows_per_batch = Sg;
-        gp.rowsq = m->hsq.as<float>(); gp.C2 = m->n.p; gp.scale2 = reinterpret_cast<const float*>(m->hsq.p); gp.scale2_stride = 6 * D;      // (aligned non-null pointers: a fit test)
-        GemmArgs gf = gp; gf.A = m->ff.p; gf.W = m->blocks[0].ff2.w; gf.bias = m->blocks[0].ff2.b; gf.K = 4 * D; gf.lda = 4 * D;
-        gf.gate = reinterpret_cast<const float*>(m->hsq.p); gf.gate_stride = 6 * D;
-        GemmArgs gq; gq.A = m->n.p; gq.W = m->blocks[0].qkv1.w; gq.C = m->qkv.p; gq.M = (int)M; gq.N = 3 * D; gq.K = D; gq.lda = D; gq.ldc = D;
-        gq.c_seg_shift = __builtin_ctz((unsigned)D); gq.c_seg_stride = M * D; gq.rows_per_batch = Sg;
-        gq.rs_sq = m->hsq.as<float>(); gq.rs_n = D / 128; gq.rs_D = D; gq.rs_eps = c.norm_eps; gq.cvec = m->hsq.as<float>(); gq.cvec_stride = 3 * D;
-        GemmArgs g1 = gq; g1.W = m->blocks[0].ff1.w; g1.C = m->ff.p; g1.N = 4 * D; g1.ldc = 4 * D; g1.c_seg_shift = 0; g1.c_seg_stride = 0; g1.cvec_stride = 4 * D;
-        nfold = ltx_opt().dense_qkv && m->blocks[0].qkv1.out == 3 * D && m->blocks[0].ff1.out == 4 * D &&
-                ltx_gemm_fold_ok(gp, EPI_RESID) && ltx_gemm_fold_ok(gf, EPI_GATE_RESID) && ltx_gemm_fold_ok(gq, EPI_BIAS) && ltx_gemm_fold_ok(g1, EPI_GELU);
-    }
-    bool hs_valid = false;                                  // m->n holds h (.) (1 + scale) of the norm that comes next (written by the layer that wrote h)
-    bool hsq_saved = false;                                 // m->orig_hsq holds the partials of m->orig (a layer some rows skip)
+    p.nfold = p.presum && ltx_opt().norm_fold != 0 && p.dense_qkv &&
+              ltx_gemm_fold_ok(gemm_o2(p, kFold1, b, x), EPI_RESID) && ltx_gemm_fold_ok(gemm_ff2(p, kFold1, b, x), EPI_GATE_RESID) &&
+              ltx_gemm_fold_ok(gemm_qkv1(p, kFold1, b, x), EPI_BIAS) && ltx_gemm_fold_ok(gemm_ff1(p, kFold1, b, x), EPI_GELU);
     // Few tokens (C1's 384: every linear layer is a latency-bound weight stream): ff2, the deepest one (K = 4 D), runs its K ranges as
     // separate blocks (the shape rule: four ranges from K = 8192 up) and leaves their f32 sums in m->parts; the row norm that follows
     // the block - the next block's norm1, or the final LayerNorm - adds them in part order, applies gate * y + h, writes h and goes on
     // normalising the row it has just finished (GemmArgs::defer_parts / RowNormArgs::parts).  Same K partition and order as the
     // in-launch reduction: the same bits.  ff2_defer=0: the in-launch reduction (A/B aid).
-    bool defer_ff2 = false; int ff2_parts = 1;
-    if (dt == LTX_DT_BF16 && !skip_layer_mask && ltx_opt().ff2_defer && !presum) {
-        GemmArgs gf; gf.A = m->ff.p; gf.W = m->blocks[0].ff2.w; gf.C = m->h.p; gf.M = (int)M; gf.N = m->blocks[0].ff2.out; gf.K = m->blocks[0].ff2.in; gf.lda = 4 * D; gf.ldc = D;
-        ff2_parts = ltx_gemm_split_factor(gf);
-        defer_ff2 = M <= 512 && ff2_parts > 1 && gf.N == D && ltx_gemm_defer_ok(gf, EPI_GATE_RESID);
+    if (bf16 && !skip_mask && ltx_opt().ff2_defer && !p.presum) {
+        const GemmArgs g = gemm_ff2(p, kDefer, b, x);
+        const int parts = ltx_gemm_split_factor(g);
+        if (p.M <= 512 && parts > 1 && ltx_gemm_defer_ok(g, EPI_GATE_RESID)) { p.defer_ff2 = true; p.ff2_parts = parts; }
     }
-    if (defer_ff2) LTX_TRY(m->parts.ensure((size_t)ff2_parts * M * D * sizeof(float)));
-    const float* pend_gate = nullptr; const void* pend_bias = nullptr; bool pending = false;      // h's rows are still K-range sums in m->parts
-    auto take_pending = [&](RowNormArgs& rn) {
-        if (!pending) return;
-        rn.parts = m->parts.as<float>(); rn.nparts = ff2_parts; rn.part_stride = M * D; rn.d_bias = pend_bias; rn.d_gate = pend_gate; rn.d_gate_stride = 6 * D;
-        rn.x_out = m->h.p; pending = false;
-    };
-    if (skip_layer_mask) LTX_TRY(m->orig.ensure(M * D * esz));
+    return p;
+}
 
-    // inputs -> model dtype (:1045-1047)
-    LTX_TRY(ltx_launch_cast(hidden, iodt, m->xin.p, dt, M * c.in_channels, s));
-    LTX_TRY(ltx_linear(m->proj_in, m->xin.p, c.in_channels, m->h.p, D, (int)M, dt, EPI_BIAS, s));
-
-    // AdaLayerNormSingle (:262-267): sinusoid(256) -> Linear -> SiLU -> Linear = embedded_timestep ; SiLU -> Linear(6D) = temb
-    // time_entry: the cached tables of up to 8 timestep values (computed on a miss); with_cfold: the norm fold's per-timestep vectors too
-    auto time_entry = [&](const float* vals, int nv, bool with_cfold, DitTimeEntry** out_e) -> int {
-        TimeVec tv; tv.n = nv; for (int i = 0; i < 8; ++i) tv.t[i] = i < nv ? vals[i] : 0.f;
-        DitTimeEntry* te = nullptr;
-        for (auto& e : m->tcache) if (e.valid && e.B == nv && e.stream == s && !memcmp(e.t, tv.t, sizeof(float) * nv)) te = &e;
-        if (!te) {
-            if ((int)m->tcache.size() < kDitTimeEntries) { m->tcache.emplace_back(); te = &m->tcache.back(); }
-            else { te = &m->tcache.front(); for (auto& e : m->tcache) if (e.used < te->used) te = &e; }
-            te->valid = false; te->cfold_valid = false;
-            LTX_TRY(te->ada.ensure((size_t)L * nv * 6 * D * sizeof(float))); LTX_TRY(te->adaf.ensure((size_t)2 * nv * D * sizeof(float)));
-            LTX_TRY(ltx_launch_sinusoid(m->tproj.p, dt, tv, m->inv_freq, 128, /*round_t=*/dt == LTX_DT_BF16, 1.0f, s));
-            LTX_TRY(ltx_linear(m->te1, m->tproj.p, 256, m->e1.p, D, nv, dt, EPI_BIAS, s));
-            LTX_TRY(ltx_launch_silu(m->e1.p, m->e1.p, (int64_t)nv * D, dt, s));
-            LTX_TRY(ltx_linear(m->te2, m->e1.p, D, m->emb.p, D, nv, dt, EPI_BIAS, s));
-            LTX_TRY(ltx_launch_silu(m->emb.p, m->embs.p, (int64_t)nv * D, dt, s));
-            LTX_TRY(ltx_linear(m->te_lin, m->embs.p, D, m->temb.p, 6 * D, nv, dt, EPI_BIAS, s));
-            LTX_TRY(ltx_launch_ada(te->ada.as<float>(), m->sst_blocks, m->temb.p, L, nv, 6 * D, dt, s));
-            LTX_TRY(ltx_launch_ada(te->adaf.as<float>(), m->sst_final, m->emb.p, 2, nv, D, dt, s));
-            memcpy(te->t, tv.t, sizeof(te->t)); te->B = nv; te->stream = s; te->valid = true;
-        }
-        te->used = ++m->tclock;
-        if (with_cfold && !te->cfold_valid) {               // once per distinct timestep vector: streams the q|k|v and ff1 weights of every layer once
-            LTX_TRY(te->cfold.ensure((size_t)L * nv * 7 * D * sizeof(float)));
-            for (int l = 0; l < L; ++l) {
-                const float* ada = te->ada.as<float>() + (size_t)l * nv * 6 * D;
-                float* cq = te->cfold.as<float>() + (size_t)l * nv * 7 * D;
-                LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].qkv1.w, m->blocks[l].qkv1.b, ada, 6 * D, nv, 3 * D, D, cq, 3 * D, s));
-                LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].ff1.w, m->blocks[l].ff1.b, ada + 3 * D, 6 * D, nv, 4 * D, D, cq + (size_t)nv * 3 * D, 4 * D, s));
-            }
-            te->cfold_valid = true;
-        }
-        *out_e = te;
-        return LTX_OK;
-    };
-    TimeVec tv; tv.n = B; for (int i = 0; i < 8; ++i) tv.t[i] = i < B ? timestep[i] : 0.f;      // (G == 1: the rows' timesteps, read by norm_fold=2 below)
-    const float *ada_all = nullptr, *adaf = nullptr, *cfold_all = nullptr;
-    if (G == 1) {
-        DitTimeEntry* te = nullptr;
-        LTX_TRY(time_entry(timestep, B, nfold, &te));
-        ada_all = te->ada.as<float>(); adaf = te->adaf.as<float>(); cfold_all = nfold ? te->cfold.as<float>() : nullptr;
-    } else {
-        // One timestep per (batch row, latent frame).  The MLP runs once per DISTINCT value of the call, eight values a launch (each
-        // batch of eight is an ordinary cached entry above: the held frames' 0 and the step's t are two values however many frames
-        // there are), and a gather copies every group's rows out of them.
-        DitGroupEntry* ge = nullptr;
-        for (auto& e : m->gcache) if (e.valid && e.B == B && e.G == G && e.stream == s && !memcmp(e.t.data(), timestep, sizeof(float) * NB)) ge = &e;
-        if (!ge || (nfold && !ge->cfold_valid)) {
-            if (!ge) {
-                if ((int)m->gcache.size() < kDitGroupEntries) { m->gcache.emplace_back(); ge = &m->gcache.back(); }
-                else {
-                    ge = &m->gcache.front(); for (auto& e : m->gcache) if (e.used < ge->used) ge = &e;
-                    if (ge->valid && ge->stream != s) HIP_TRY(hipStreamSynchronize(ge->stream));      // (forwards on ITS stream may still read the tables)
-                }
-            }
-            ge->valid = false; ge->cfold_valid = false;
-            std::vector<float> distinct; std::vector<int> idx((size_t)NB);
-            for (int i = 0; i < NB; ++i) {
-                size_t j = 0;
-                while (j < distinct.size() && memcmp(&distinct[j], &timestep[i], sizeof(float)) != 0) ++j;
-                if (j == distinct.size()) distinct.push_back(timestep[i]);
-                idx[i] = (int)j;
-            }
-            LTX_TRY(ge->ada.ensure((size_t)L * NB * 6 * D * sizeof(float))); LTX_TRY(ge->adaf.ensure((size_t)2 * NB * D * sizeof(float)));
-            if (nfold) LTX_TRY(ge->cfold.ensure((size_t)L * NB * 7 * D * sizeof(float)));
-            const int nd = (int)distinct.size();
-            for (int c0 = 0; c0 < nd; c0 += 8) {
-                const int nc = nd - c0 < 8 ? nd - c0 : 8;
-                DitTimeEntry* te = nullptr;
-                LTX_TRY(time_entry(distinct.data() + c0, nc, nfold, &te));
-                const int* gi = idx.data();      // (read while the launches are enqueued: nothing of a miss waits for the device)
-                LTX_TRY(ltx_launch_group_gather(ge->ada.as<float>(), (int64_t)NB * 6 * D, te->ada.as<float>(), (int64_t)nc * 6 * D, gi, c0, nc, L, NB, 6 * D, s));
-                LTX_TRY(ltx_launch_group_gather(ge->adaf.as<float>(), (int64_t)NB * D, te->adaf.as<float>(), (int64_t)nc * D, gi, c0, nc, 2, NB, D, s));
-                if (nfold) {
-                    LTX_TRY(ltx_launch_group_gather(ge->cfold.as<float>(), (int64_t)NB * 7 * D, te->cfold.as<float>(), (int64_t)nc * 7 * D, gi, c0, nc, L, NB, 3 * D, s));
-                    LTX_TRY(ltx_launch_group_gather(ge->cfold.as<float>() + (size_t)NB * 3 * D, (int64_t)NB * 7 * D, te->cfold.as<float>() + (size_t)nc * 3 * D, (int64_t)nc * 7 * D,
-                                                    gi, c0, nc, L, NB, 4 * D, s));
-                }
-            }
-            ge->t.assign(timestep, timestep + NB); ge->B = B; ge->G = G; ge->stream = s; ge->valid = true; ge->cfold_valid = nfold;
-        }
-        ge->used = ++m->tclock;
-        ada_all = ge->ada.as<float>(); adaf = ge->adaf.as<float>(); cfold_all = nfold ? ge->cfold.as<float>() : nullptr;
+namespace {
+// ---- the caches of a forward ----
+// One policy for the time, group and scaled-weight tables: a valid entry that matches (*hit), else an invalid slot, else a new one
+// while there are fewer than cap, else the least recently used.  What a miss does with the slot, and whether it first waits for
+// the stream of a victim that is still valid, is the caller's.
+template <class E, class Match>
+E* cache_slot(std::deque<E>& c, size_t cap, Match match, bool* hit) {
+    E *found = nullptr, *lru = nullptr;
+    for (auto& e : c) if (e.valid && match(e)) found = &e;
+    if ((*hit = found != nullptr)) return found;
+    for (auto& e : c) if (!e.valid) return &e;
+    if (c.size() < cap) { c.emplace_back(); return &c.back(); }
+    for (auto& e : c) if (!lru || e.used < lru->used) lru = &e;
+    return lru;
+}
+struct DitTables { const float *ada = nullptr, *adaf = nullptr, *cfold = nullptr; };      // [L][NB][6D], [2][NB][D], per layer [NB][3D] then [NB][4D] (norm fold; else null)
+// AdaLayerNormSingle (:262-267): sinusoid(256) -> Linear -> SiLU -> Linear = embedded_timestep ; SiLU -> Linear(6D) = temb.
+// The cached tables of up to 8 timestep values - the rows of a call with one timestep per row - computed on a miss, with the norm fold's per-timestep vectors where the plan folds.
+// Unlike the two caches below, a miss does NOT wait for the stream of the entry it overwrites.  On the stream of this call the stream
+// orders the writes behind the readers.  A victim of ANOTHER stream is safe only because two forwards of one handle share every
+// workspace (m->h, m->tproj, ...), so a caller with two streams has to order the forwards itself; read by the letter of
+// gcache / wcache, which do wait, this is the cache that would have to learn it (left as it was: a follow-up).
+int time_tables(ltx_dit* m, const DitPlan& p, const float* vals, int nv, hipStream_t s, DitTables* t) {
+    const int D = p.D, L = m->cfg.num_layers, dt = p.dt;
+    TimeVec tv; tv.n = nv; for (int i = 0; i < 8; ++i) tv.t[i] = i < nv ? vals[i] : 0.f;
+    bool hit;
+    DitTimeEntry* te = cache_slot(m->tcache, kDitTimeEntries, [&](const DitTimeEntry& e) { return e.B == nv && e.stream == s && !memcmp(e.t, tv.t, sizeof(float) * nv); }, &hit);
+    if (!hit) {
+        te->valid = false; te->cfold_valid = false;
+        LTX_TRY(te->ada.ensure((size_t)L * nv * 6 * D * sizeof(float))); LTX_TRY(te->adaf.ensure((size_t)2 * nv * D * sizeof(float)));
+        LTX_TRY(ltx_launch_sinusoid(m->tproj.p, dt, tv, m->inv_freq, 128, /*round_t=*/dt == LTX_DT_BF16, 1.0f, s));
+        LTX_TRY(ltx_linear(m->te1, m->tproj.p, 256, m->e1.p, D, nv, dt, EPI_BIAS, s));
+        LTX_TRY(ltx_launch_silu(m->e1.p, m->e1.p, (int64_t)nv * D, dt, s));
+        LTX_TRY(ltx_linear(m->te2, m->e1.p, D, m->emb.p, D, nv, dt, EPI_BIAS, s));
+        LTX_TRY(ltx_launch_silu(m->emb.p, m->embs.p, (int64_t)nv * D, dt, s));
+        LTX_TRY(ltx_linear(m->te_lin, m->embs.p, D, m->temb.p, 6 * D, nv, dt, EPI_BIAS, s));
+        LTX_TRY(ltx_launch_ada(te->ada.as<float>(), m->sst_blocks, m->temb.p, L, nv, 6 * D, dt, s));
+        LTX_TRY(ltx_launch_ada(te->adaf.as<float>(), m->sst_final, m->emb.p, 2, nv, D, dt, s));
+        memcpy(te->t, tv.t, sizeof(te->t)); te->B = nv; te->stream = s; te->valid = true;
     }
-    // norm_fold=2: the (1 + scale) factor rides on the CONSUMER's weights instead of on a second output of the producer:
-    // (h (.) (1 + sc)) W^T = h (W (.) (1 + sc))^T.  One scaled copy of the q|k|v and ff1 weights per distinct timestep (1.6 GB at 2B:
-    // read + written once, then cached like the modulation they are made from - a distilled schedule has 7), all batch rows at one
-    // timestep (what LtxPipeline::call passes, t2v_pipeline.rs:868); otherwise, or when the schedule has more distinct timesteps
-    // than copies (norm_fold_copies; the 40-step presets), the second-output form serves.  bf16 rounding moves from h (1 + sc) to W (1 + sc).
-    // A per-frame call (G > 1: its groups are at different timesteps) never takes this form and never touches the copies or wfold_off.
-    bool wf = G == 1 && nfold && ltx_opt().norm_fold == 2 && !m->wfold_off;
-    for (int i = 1; i < B; ++i) wf = wf && tv.t[i] == tv.t[0];
-    DitWfold* we = nullptr;
-    if (wf) {
-        for (auto& e : m->wcache) if (e.valid && e.t == tv.t[0] && e.stream == s) we = &e;
-        if (!we) {
-            const int cap = ltx_opt().norm_fold_copies > 0 ? ltx_opt().norm_fold_copies : 1;
-            int live = 0; DitWfold* victim = nullptr;
-            for (auto& e : m->wcache) if (e.valid) { ++live; if (!victim || e.used < victim->used) victim = &e; }
-            if (live >= cap) {
-                if (m->tclock - victim->used < (uint64_t)4 * cap) {      // its timestep ran a moment ago: the schedule cycles through more timesteps than copies
-                    m->wfold_off = true; wf = false;
-                    HIP_TRY(hipStreamSynchronize(s));               // (earlier forwards on this stream may still read the copies)
-                    for (auto& e : m->wcache) { e.w.release(); e.valid = false; }
-                } else {                                                // its buffer is re-used (same size)
-                    if (victim->stream != s) HIP_TRY(hipStreamSynchronize(victim->stream));      // (forwards on ITS stream may still read it)
-                    victim->valid = false; we = victim;
-                }
-            }
-            if (wf) {
-                if (!we) { for (auto& e : m->wcache) if (!e.valid) { we = &e; break; } }
-                if (!we) { m->wcache.emplace_back(); we = &m->wcache.back(); }
-                const size_t per_layer = (size_t)7 * D * D * esz;
-                if (we->w.ensure((size_t)L * per_layer) != LTX_OK) {      // no room for another copy: the second-output form from here on (speed only)
-                    (void)hipGetLastError();
-                    m->wfold_off = true; wf = false; we = nullptr;
-                }
-                if (wf)
-                for (int l = 0; l < L; ++l) {
-                    const float* ada = ada_all + (size_t)l * NB * 6 * D;
-                    char* wl = (char*)we->w.p + (size_t)l * per_layer;
-                    LTX_TRY(ltx_launch_scale_cols(m->blocks[l].qkv1.w, ada + D, wl, 3 * D, D, dt, s));
-                    LTX_TRY(ltx_launch_scale_cols(m->blocks[l].ff1.w, ada + 4 * D, wl + (size_t)3 * D * D * esz, 4 * D, D, dt, s));
-                }
-                if (wf) { we->t = tv.t[0]; we->stream = s; we->valid = true; }
-            }
-        }
-        if (wf) we->used = m->tclock;
-    }
-
-    // Text context: caption projection (:186-190), mask bias (:1059-1070) and, for every layer, the cross-attention
-    // K/V projections + k-RMSNorm (:667-672).  None of it depends on the timestep or the latents, so inside a
-    // caching scope (ltx_dit_context_cache) it is computed once per (enc, mask) pair instead of once per forward.
-    DitCtx* ctx = nullptr;
-    for (auto& e : m->ctxs) if (e.valid && e.enc == enc && e.mask == enc_mask && e.B == B && e.K == K && e.iodt == iodt && e.fold_q2 == fold_q2) ctx = &e;
-    if (!ctx) {
-        if (m->ctxs.size() >= 4 || !m->ctx_mode) { for (auto& e : m->ctxs) e.valid = false; }
-        for (auto& e : m->ctxs) if (!e.valid) { ctx = &e; break; }
-        if (!ctx) { m->ctxs.emplace_back(); ctx = &m->ctxs.back(); }
-        ctx->enc = enc; ctx->mask = enc_mask; ctx->B = B; ctx->K = K; ctx->iodt = iodt; ctx->fold_q2 = fold_q2;
-        LTX_TRY(ctx->kv.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->bias.ensure(MK * sizeof(float)));
-        LTX_TRY(ltx_launch_cast(enc, iodt, m->encin.p, dt, MK * c.caption_channels, s));
-        LTX_TRY(ltx_linear(m->cap1, m->encin.p, c.caption_channels, m->c1.p, D, (int)MK, dt, EPI_GELU, s));
-        LTX_TRY(ltx_linear(m->cap2, m->c1.p, D, m->encp.p, D, (int)MK, dt, EPI_BIAS, s));
-        if (enc_mask) LTX_TRY(ltx_launch_mask_bias(ctx->bias.as<float>(), enc_mask, MK, s));
+    te->used = ++m->tclock;
+    if (p.nfold && !te->cfold_valid) {                      // once per distinct timestep vector: streams the q|k|v and ff1 weights of every layer once
+        LTX_TRY(te->cfold.ensure((size_t)L * nv * 7 * D * sizeof(float)));
         for (int l = 0; l < L; ++l) {
-            void* kvl = (char*)ctx->kv.p + (size_t)l * MK * 2 * D * esz;
-            LTX_TRY(ltx_linear(m->blocks[l].kv2, m->encp.p, D, kvl, 2 * D, (int)MK, dt, EPI_BIAS, s));
-            QkNormRopeArgs k2; k2.x = kvl; k2.rows = MK; k2.D = D; k2.ld = 2 * D; k2.nseg = 1; k2.w0 = m->blocks[l].nk2; k2.eps = 1e-5f;
-            if (fold_q2) k2.w0b = m->blocks[l].nq2;
-            LTX_TRY(ltx_launch_qknorm_rope(k2, dt, s));
+            const float* ada = te->ada.as<float>() + (size_t)l * nv * 6 * D;
+            float* cq = te->cfold.as<float>() + (size_t)l * nv * 7 * D;
+            LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].qkv1.w, m->blocks[l].qkv1.b, ada, 6 * D, nv, 3 * D, D, cq, 3 * D, s));
+            LTX_TRY(ltx_launch_shift_gemv(m->blocks[l].ff1.w, m->blocks[l].ff1.b, ada + 3 * D, 6 * D, nv, 4 * D, D, cq + (size_t)nv * 3 * D, 4 * D, s));
         }
-        // Masked text tokens (bias -10000, :1059-1070) get softmax weight exp(s - 10000 - max) = +0.0f: exactly nothing.  Where the
-        // short-key-set kernel serves the layer, the keys that are left are moved to the front of their batch row once per context and
-        // the kernel sizes its work by their number (device-side count: no host synchronisation).
-        ctx->compact = enc_mask && dt == LTX_DT_BF16 && ltx_attention_cross64_ok(hd, K) && ltx_opt().xattn_compact;     // xattn_compact=0: every layer multiplies all K keys (A/B aid)
-        if (ctx->compact) {
-            LTX_TRY(ctx->kvc.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->biasc.ensure(MK * sizeof(float)));
-            LTX_TRY(ctx->kidx.ensure(MK * sizeof(int))); LTX_TRY(ctx->kcount.ensure((size_t)B * sizeof(int)));
-            LTX_TRY(ltx_launch_key_compact(ctx->bias.as<float>(), B, K, ctx->kidx.as<int>(), ctx->kcount.as<int>(), ctx->biasc.as<float>(), s));
-            LTX_TRY(ltx_launch_gather_rows(ctx->kv.p, ctx->kvc.p, ctx->kidx.as<int>(), ctx->kcount.as<int>(), L, B, K, (int)(2 * D * esz), s));
-        }
-        ctx->valid = true;     // outside a caching scope the entry is invalidated again at the end of this forward
+        te->cfold_valid = true;
     }
-    const float* bias = enc_mask ? ctx->bias.as<float>() : nullptr;
-
-    // RoPE tables (:436-524); inside a caching scope the tables of the previous forward are kept when coords / geometry are the same
-    {
-        auto& rk = m->rope_key;
-        const bool same = m->ctx_mode && rk.valid && rk.coords == video_coords && rk.B == B && rk.S == S && rk.F == num_frames && rk.H == height && rk.W == width &&
-                          rk.stream == s && rk.has_rs == (rope_scale != nullptr) && (!rope_scale || !memcmp(rk.rs, rope_scale, sizeof(rk.rs)));
-        if (!same) {
-            rk.valid = false;
-            RopeTableArgs r;
-            r.cos = m->cosb.as<float>(); r.sin = m->sinb.as<float>(); r.freqs = m->rope_freqs;
-            r.B = B; r.D = D;
-            if (video_coords) {
-                r.use_coords = 1; r.coords = video_coords; r.F = 1; r.H = 1; r.W = S;
-                r.gscale[0] = (float)(1.0 / 20.0); r.gscale[1] = (float)(1.0 / 2048.0); r.gscale[2] = (float)(1.0 / 2048.0);
-            } else {
-                r.F = num_frames; r.H = height; r.W = width;
-                if (rope_scale) {
-                    r.gscale[0] = (float)((double)rope_scale[0] * c.patch_size_t / 20.0);
-                    r.gscale[1] = (float)((double)rope_scale[1] * c.patch_size / 2048.0);
-                    r.gscale[2] = (float)((double)rope_scale[2] * c.patch_size / 2048.0);
-                }
+    *t = DitTables{te->ada.as<float>(), te->adaf.as<float>(), p.nfold ? te->cfold.as<float>() : nullptr};
+    return LTX_OK;
+}
+// One timestep per (batch row, latent frame) (timestep [B, G]).  The MLP runs once per DISTINCT value of the call, eight values a
+// launch (each batch of eight is an ordinary cached entry above: the held frames' 0 and the step's t are two values however many
+// frames there are), and a gather copies every group's rows out of them.
+int group_tables(ltx_dit* m, const DitPlan& p, const float* timestep, hipStream_t s, DitTables* t) {
+    const int D = p.D, L = m->cfg.num_layers, NB = p.NB, B = p.B, G = NB / B;
+    bool hit;
+    DitGroupEntry* ge = cache_slot(m->gcache, kDitGroupEntries, [&](const DitGroupEntry& e) { return e.B == B && e.G == G && e.stream == s && !memcmp(e.t.data(), timestep, sizeof(float) * NB); }, &hit);
+    if (!hit && ge->valid && ge->stream != s) HIP_TRY(hipStreamSynchronize(ge->stream));      // (forwards on ITS stream may still read the tables)
+    if (!hit || (p.nfold && !ge->cfold_valid)) {
+        ge->valid = false; ge->cfold_valid = false;
+        std::vector<float> distinct; std::vector<int> idx((size_t)NB);
+        for (int i = 0; i < NB; ++i) {
+            size_t j = 0;
+            while (j < distinct.size() && memcmp(&distinct[j], &timestep[i], sizeof(float)) != 0) ++j;
+            if (j == distinct.size()) distinct.push_back(timestep[i]);
+            idx[i] = (int)j;
+        }
+        LTX_TRY(ge->ada.ensure((size_t)L * NB * 6 * D * sizeof(float))); LTX_TRY(ge->adaf.ensure((size_t)2 * NB * D * sizeof(float)));
+        if (p.nfold) LTX_TRY(ge->cfold.ensure((size_t)L * NB * 7 * D * sizeof(float)));
+        const int nd = (int)distinct.size();
+        for (int c0 = 0; c0 < nd; c0 += 8) {
+            const int nc = nd - c0 < 8 ? nd - c0 : 8;
+            DitTables te;
+            LTX_TRY(time_tables(m, p, distinct.data() + c0, nc, s, &te));
+            const int* gi = idx.data();      // (read while the launches are enqueued: nothing of a miss waits for the device)
+            LTX_TRY(ltx_launch_group_gather(ge->ada.as<float>(), (int64_t)NB * 6 * D, te.ada, (int64_t)nc * 6 * D, gi, c0, nc, L, NB, 6 * D, s));
+            LTX_TRY(ltx_launch_group_gather(ge->adaf.as<float>(), (int64_t)NB * D, te.adaf, (int64_t)nc * D, gi, c0, nc, 2, NB, D, s));
+            if (p.nfold) {
+                LTX_TRY(ltx_launch_group_gather(ge->cfold.as<float>(), (int64_t)NB * 7 * D, te.cfold, (int64_t)nc * 7 * D, gi, c0, nc, L, NB, 3 * D, s));
+                LTX_TRY(ltx_launch_group_gather(ge->cfold.as<float>() + (size_t)NB * 3 * D, (int64_t)NB * 7 * D, te.cfold + (size_t)nc * 3 * D, (int64_t)nc * 7 * D, gi, c0, nc, L, NB, 4 * D, s));
             }
-            LTX_TRY(ltx_launch_rope_table(r, s));
-            rk.coords = video_coords; rk.B = B; rk.S = S; rk.F = num_frames; rk.H = height; rk.W = width; rk.stream = s;
-            rk.has_rs = rope_scale != nullptr; if (rope_scale) memcpy(rk.rs, rope_scale, sizeof(rk.rs));
-            rk.valid = m->ctx_mode;
         }
+        ge->t.assign(timestep, timestep + NB); ge->B = B; ge->G = G; ge->stream = s; ge->valid = true; ge->cfold_valid = p.nfold;
     }
-
-    const float attn_scale = 1.0f / std::sqrt((float)hd);
-    auto next_block = [&](int l) {                          // the next block that runs (not in the skip list, not skipped by every row), -1: none
-        for (int n = l + 1; n < L; ++n) {
-            bool skip = false;
-            for (int sb : m->skip_blocks) if (sb == n) skip = true;
-            if (skip) continue;
-            if (skip_layer_mask) { bool all = true; for (int bb = 0; bb < B; ++bb) all &= skip_layer_mask[(size_t)n * B + bb] == 1.f; if (all) continue; }
-            return n;
+    ge->used = ++m->tclock;
+    *t = DitTables{ge->ada.as<float>(), ge->adaf.as<float>(), p.nfold ? ge->cfold.as<float>() : nullptr};
+    return LTX_OK;
+}
+// norm_fold=2 stands down for the rest of the handle's life: the second-output form from here on (speed only), and the copies are
+// freed as include/ltxhip.h promises
+int give_up_scaled_weights(ltx_dit* m, hipStream_t s) {
+    m->wfold_off = true;
+    HIP_TRY(hipStreamSynchronize(s));                       // (earlier forwards on this stream may still read the copies)
+    m->release_scaled_weights();
+    return LTX_OK;
+}
+// norm_fold=2: the (1 + scale) factor rides on the CONSUMER's weights instead of on a second output of the producer:
+// (h (.) (1 + sc)) W^T = h (W (.) (1 + sc))^T.  One scaled copy of the q|k|v and ff1 weights per distinct timestep (1.6 GB at 2B:
+// read + written once, then cached like the modulation they are made from - a distilled schedule has 7), all batch rows at one
+// timestep (what LtxPipeline::call passes, t2v_pipeline.rs:868); otherwise, or when the schedule has more distinct timesteps
+// than copies (norm_fold_copies; the 40-step presets), the second-output form serves.  bf16 rounding moves from h (1 + sc) to W (1 + sc).
+// A per-frame call (G > 1: its groups are at different timesteps) never takes this form and never touches the copies or wfold_off.
+// *out: the copy this forward reads (null: the form is not taken - the run-time decision `wf` of the block loop).
+int scaled_weights(ltx_dit* m, const DitPlan& p, const float* timestep, const float* ada_all, hipStream_t s, const DitWfold** out) {
+    *out = nullptr;
+    bool wf = p.NB == p.B && p.nfold && ltx_opt().norm_fold == 2 && !m->wfold_off;
+    for (int i = 1; i < p.B; ++i) wf = wf && timestep[i] == timestep[0];
+    if (!wf) return LTX_OK;
+    const int D = p.D, L = m->cfg.num_layers, cap = ltx_opt().norm_fold_copies > 0 ? ltx_opt().norm_fold_copies : 1;
+    const size_t esz = ltx_dt_size(p.dt), per_layer = (size_t)7 * D * D * esz;
+    const float t0 = timestep[0];
+    bool hit;
+    DitWfold* we = cache_slot(m->wcache, (size_t)cap, [&](const DitWfold& e) { return e.t == t0 && e.stream == s; }, &hit);
+    if (!hit) {
+        if (we->valid) {                                    // every copy is in use: the least recently used one is the victim
+            // its timestep ran a moment ago: the schedule cycles through more timesteps than copies
+            if (m->tclock - we->used < (uint64_t)4 * cap) return give_up_scaled_weights(m, s);
+            if (we->stream != s) HIP_TRY(hipStreamSynchronize(we->stream));      // its buffer is re-used (same size); forwards on ITS stream may still read it
+            we->valid = false;
         }
-        return -1;
-    };
+        if (we->w.ensure((size_t)L * per_layer) != LTX_OK) {      // no room for another copy
+            (void)hipGetLastError();
+            return give_up_scaled_weights(m, s);
+        }
+        for (int l = 0; l < L; ++l) {
+            const float* ada = ada_all + (size_t)l * p.NB * 6 * D;
+            char* wl = (char*)we->w.p + (size_t)l * per_layer;
+            LTX_TRY(ltx_launch_scale_cols(m->blocks[l].qkv1.w, ada + D, wl, 3 * D, D, p.dt, s));
+            LTX_TRY(ltx_launch_scale_cols(m->blocks[l].ff1.w, ada + 4 * D, wl + (size_t)3 * D * D * esz, 4 * D, D, p.dt, s));
+        }
+        we->t = t0; we->stream = s; we->valid = true;
+    }
+    we->used = m->tclock;
+    *out = we;
+    return LTX_OK;
+}
+// Text context: caption projection (:186-190), mask bias (:1059-1070) and, for every layer, the cross-attention
+// K/V projections + k-RMSNorm (:667-672).  None of it depends on the timestep or the latents, so inside a
+// caching scope (ltx_dit_context_cache) it is computed once per (enc, mask) pair instead of once per forward.
+int text_context(ltx_dit* m, const DitPlan& p, const void* enc, const float* enc_mask, hipStream_t s, DitCtx** out) {
+    const ltx_dit_config& c = m->cfg;
+    const int D = p.D, L = c.num_layers, dt = p.dt, B = p.B, K = p.K;
+    const int64_t MK = p.MK; const size_t esz = ltx_dt_size(dt);
+    DitCtx* ctx = nullptr;
+    for (auto& e : m->ctxs) if (e.valid && e.enc == enc && e.mask == enc_mask && e.B == B && e.K == K && e.iodt == p.iodt && e.fold_q2 == p.fold_q2) ctx = &e;
+    *out = ctx;
+    if (ctx) return LTX_OK;
+    if (m->ctxs.size() >= 4 || !m->ctx_mode) { for (auto& e : m->ctxs) e.valid = false; }
+    for (auto& e : m->ctxs) if (!e.valid) { ctx = &e; break; }
+    if (!ctx) { m->ctxs.emplace_back(); ctx = &m->ctxs.back(); }
+    ctx->enc = enc; ctx->mask = enc_mask; ctx->B = B; ctx->K = K; ctx->iodt = p.iodt; ctx->fold_q2 = p.fold_q2;
+    LTX_TRY(ctx->kv.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->bias.ensure(MK * sizeof(float)));
+    LTX_TRY(ltx_launch_cast(enc, p.iodt, m->encin.p, dt, MK * c.caption_channels, s));
+    LTX_TRY(ltx_linear(m->cap1, m->encin.p, c.caption_channels, m->c1.p, D, (int)MK, dt, EPI_GELU, s));
+    LTX_TRY(ltx_linear(m->cap2, m->c1.p, D, m->encp.p, D, (int)MK, dt, EPI_BIAS, s));
+    if (enc_mask) LTX_TRY(ltx_launch_mask_bias(ctx->bias.as<float>(), enc_mask, MK, s));
     for (int l = 0; l < L; ++l) {
-        bool skip = false;
-        for (int sb : m->skip_blocks) if (sb == l) skip = true;
-        if (skip) continue;                                        // :1094-1096
-        // skip_layer_mask (:1098-1123): all-ones rows make the block an exact identity
-        TimeVec mv; mv.n = B; bool any = false, all = true;
-        for (int i = 0; i < 8; ++i) mv.t[i] = 0.f;
-        if (skip_layer_mask) {
-            for (int b = 0; b < B; ++b) { mv.t[b] = skip_layer_mask[(size_t)l * B + b]; any |= mv.t[b] != 0.f; all &= mv.t[b] == 1.f; }
-            if (all) continue;
-            if (any) {
-                HIP_TRY(hipMemcpyAsync(m->orig.p, m->h.p, M * D * esz, hipMemcpyDeviceToDevice, s));
-                // the row partials of the kept rows travel with them (restored after the blend): a batch whose rows skip different
-                // layers - the guidance branches of a step in one forward - then returns, row for row, the bits of separate forwards
-                hsq_saved = presum && hsq_valid;
-                if (hsq_saved) { LTX_TRY(m->orig_hsq.ensure(M * (D / 128) * sizeof(float))); HIP_TRY(hipMemcpyAsync(m->orig_hsq.p, m->hsq.p, M * (D / 128) * sizeof(float), hipMemcpyDeviceToDevice, s)); }
-            }
+        void* kvl = (char*)ctx->kv.p + (size_t)l * MK * 2 * D * esz;
+        LTX_TRY(ltx_linear(m->blocks[l].kv2, m->encp.p, D, kvl, 2 * D, (int)MK, dt, EPI_BIAS, s));
+        QkNormRopeArgs k2; k2.x = kvl; k2.rows = MK; k2.D = D; k2.ld = 2 * D; k2.nseg = 1; k2.w0 = m->blocks[l].nk2; k2.eps = 1e-5f;
+        if (p.fold_q2) k2.w0b = m->blocks[l].nq2;
+        LTX_TRY(ltx_launch_qknorm_rope(k2, dt, s));
+    }
+    // Masked text tokens (bias -10000, :1059-1070) get softmax weight exp(s - 10000 - max) = +0.0f: exactly nothing.  Where the
+    // short-key-set kernel serves the layer, the keys that are left are moved to the front of their batch row once per context and
+    // the kernel sizes its work by their number (device-side count: no host synchronisation).
+    ctx->compact = enc_mask && dt == LTX_DT_BF16 && ltx_attention_cross64_ok(c.attention_head_dim, K) && ltx_opt().xattn_compact;     // xattn_compact=0: every layer multiplies all K keys (A/B aid)
+    if (ctx->compact) {
+        LTX_TRY(ctx->kvc.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->biasc.ensure(MK * sizeof(float)));
+        LTX_TRY(ctx->kidx.ensure(MK * sizeof(int))); LTX_TRY(ctx->kcount.ensure((size_t)B * sizeof(int)));
+        LTX_TRY(ltx_launch_key_compact(ctx->bias.as<float>(), B, K, ctx->kidx.as<int>(), ctx->kcount.as<int>(), ctx->biasc.as<float>(), s));
+        LTX_TRY(ltx_launch_gather_rows(ctx->kv.p, ctx->kvc.p, ctx->kidx.as<int>(), ctx->kcount.as<int>(), L, B, K, (int)(2 * D * esz), s));
+    }
+    ctx->valid = true;     // outside a caching scope the entry is invalidated again at the end of this forward
+    *out = ctx;
+    return LTX_OK;
+}
+// RoPE tables (:436-524) in cosb / sinb; inside a caching scope the tables of the previous forward are kept when coords / geometry are the same
+int rope_tables(ltx_dit* m, const DitPlan& p, int num_frames, int height, int width, const float* rope_scale, const float* video_coords, hipStream_t s) {
+    const ltx_dit_config& c = m->cfg;
+    auto& rk = m->rope_key;
+    const bool same = m->ctx_mode && rk.valid && rk.coords == video_coords && rk.B == p.B && rk.S == p.S && rk.F == num_frames && rk.H == height && rk.W == width &&
+                      rk.stream == s && rk.has_rs == (rope_scale != nullptr) && (!rope_scale || !memcmp(rk.rs, rope_scale, sizeof(rk.rs)));
+    if (same) return LTX_OK;
+    rk.valid = false;
+    RopeTableArgs r;
+    r.cos = m->cosb.as<float>(); r.sin = m->sinb.as<float>(); r.freqs = m->rope_freqs;
+    r.B = p.B; r.D = p.D;
+    if (video_coords) {
+        r.use_coords = 1; r.coords = video_coords; r.F = 1; r.H = 1; r.W = p.S;
+        r.gscale[0] = (float)(1.0 / 20.0); r.gscale[1] = (float)(1.0 / 2048.0); r.gscale[2] = (float)(1.0 / 2048.0);
+    } else {
+        r.F = num_frames; r.H = height; r.W = width;
+        if (rope_scale) {
+            r.gscale[0] = (float)((double)rope_scale[0] * c.patch_size_t / 20.0);
+            r.gscale[1] = (float)((double)rope_scale[1] * c.patch_size / 2048.0);
+            r.gscale[2] = (float)((double)rope_scale[2] * c.patch_size / 2048.0);
         }
-        const DitBlock& b = m->blocks[l];
-        const float* ada = ada_all + (size_t)l * NB * 6 * D;
-        // norm1 + AdaLN (shift_msa = row 0, scale_msa = row 1)
-        RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = M; rn.D = D; rn.ldx = D; rn.ldy = D;
-        rn.kind = 0; rn.eps = c.norm_eps; rn.shift = ada; rn.scale = ada + D; rn.rows_per_batch = Sg; rn.mod_stride = 6 * D;
-        if (presum && hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
-        const bool fold1 = nfold && hsq_valid && (wf || hs_valid);      // the layer that wrote h left its row partials and h (.) (1 + scale_msa) in m->n (or the factor is in the weights): no pass
-        const float* cfold_l = nfold ? cfold_all + (size_t)l * NB * 7 * D : nullptr;
-        const char* wfold_l = wf ? (const char*)we->w.p + (size_t)l * 7 * D * D * esz : nullptr;
-        if (!fold1) {
-        take_pending(rn);
-        LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-        }
-        hs_valid = false;
-        rn.parts = nullptr; rn.nparts = 0; rn.x_out = nullptr; rn.d_bias = nullptr; rn.d_gate = nullptr;
-        // self attention
-        // q, k, v leave the fused projection as three DENSE [M, D] matrices (segmented GEMM output) when D is a power
-        // of two: the attention kernel reads K/V rows of a dense matrix 7-11 % faster than column slices of [M, 3D]
-        const bool dense_qkv = (D & (D - 1)) == 0 && ltx_opt().dense_qkv;      // dense_qkv=0: column slices of [M, 3D] (A/B aid, and the path of a D that is not a power of two)
-        const int64_t seg = dense_qkv ? M * D : D;           // elements from q to k to v
-        const int ldqkv = dense_qkv ? D : 3 * D;
-        {
-            GemmArgs g;
-            g.A = m->n.p; g.W = b.qkv1.w; g.C = m->qkv.p; g.bias = b.qkv1.b;
-            g.M = (int)M; g.N = b.qkv1.out; g.K = b.qkv1.in; g.lda = D; g.ldc = ldqkv;
-            if (dense_qkv) { g.c_seg_shift = __builtin_ctz((unsigned)D); g.c_seg_stride = seg; }
-            if (fold1) {
-                g.bias = nullptr; g.rows_per_batch = Sg; g.rs_sq = m->hsq.as<float>(); g.rs_n = D / 128; g.rs_D = D; g.rs_eps = c.norm_eps; g.cvec = cfold_l; g.cvec_stride = 3 * D;
-                if (wf) { g.A = m->h.p; g.W = wfold_l; }
-            }
-            LTX_TRY(ltx_launch_gemm(g, dt, EPI_BIAS, s));
-        }
-        QkNormRopeArgs qa; qa.x = m->qkv.p; qa.rows = M; qa.D = D; qa.ld = ldqkv; qa.seg_stride = seg; qa.nseg = 2; qa.w0 = b.nq1; qa.w1 = b.nk1;
-        qa.eps = 1e-5f; qa.cos = m->cosb.as<float>(); qa.sin = m->sinb.as<float>();
-        // bf16: q leaves the norm already multiplied by scale*log2(e) (ONE bf16 rounding, of the product), so the
-        // attention kernel's exponent is exp2(S - m) with no per-score multiply
-        const bool fold_q = dt == LTX_DT_BF16 && ltx_attention_prescale_ok(hd);
-        if (fold_q) qa.out_scale0 = attn_scale * 1.4426950408889634f;
-        LTX_TRY(ltx_launch_qknorm_rope(qa, dt, s));
-        AttnArgs at; at.q = m->qkv.p; at.k = (char*)m->qkv.p + (size_t)seg * esz; at.v = (char*)m->qkv.p + (size_t)2 * seg * esz; at.o = m->attn.p;
-        at.ldq = at.ldk = at.ldv = ldqkv; at.ldo = D; at.B = B; at.Sq = S; at.Sk = S; at.heads = H; at.hd = hd; at.scale = attn_scale;
-        at.q_prescaled = fold_q ? 1 : 0;
-        LTX_TRY(ltx_launch_attention(at, dt, s));
-        // h = h + gate_msa * to_out(attn)     (gate_msa = row 2)
-        LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, Sg));
-        hsq_valid = false;
-        // cross attention (no pre-norm, no RoPE, q/k RMSNorm, additive key bias)
-        const char* kvl = (const char*)(ctx->compact ? ctx->kvc.p : ctx->kv.p) + (size_t)l * MK * 2 * D * esz;
-        AttnArgs ax; ax.q = m->qkv.p; ax.k = kvl; ax.v = kvl + (size_t)D * esz; ax.o = m->attn.p;
-        ax.ldq = D; ax.ldk = ax.ldv = 2 * D; ax.ldo = D; ax.B = B; ax.Sq = S; ax.Sk = K; ax.heads = H; ax.hd = hd; ax.scale = attn_scale; ax.bias = bias;
-        if (ctx->compact) { ax.bias = ctx->biasc.as<float>(); ax.k_count = ctx->kcount.as<int>(); }
-        if (fold_q2) {
-            GemmArgs g;
-            g.A = m->h.p; g.W = b.q2.w; g.C = m->qkv.p; g.bias = b.q2.b; g.M = (int)M; g.N = b.q2.out; g.K = b.q2.in; g.lda = D; g.ldc = D;
-            g.rowsq = m->rsq.as<float>();
-            LTX_TRY(ltx_launch_gemm(g, dt, EPI_BIAS, s));
-            ax.q_rowsq = m->rsq.as<float>(); ax.q_rowsq_n = D / 128; ax.q_rowsq_D = D; ax.q_rowsq_eps = 1e-5f;
-        } else {
-            LTX_TRY(ltx_linear(b.q2, m->h.p, D, m->qkv.p, D, (int)M, dt, EPI_BIAS, s));
-            QkNormRopeArgs q2; q2.x = m->qkv.p; q2.rows = M; q2.D = D; q2.ld = D; q2.nseg = 1; q2.w0 = b.nq2; q2.eps = 1e-5f;
-            LTX_TRY(ltx_launch_qknorm_rope(q2, dt, s));
-        }
-        LTX_TRY(ltx_launch_attention(ax, dt, s));
-        if (nfold && !wf) {                                    // + h (.) (1 + scale_mlp) into m->n for ff1
-            GemmArgs g; g.A = m->attn.p; g.W = b.o2.w; g.C = m->h.p; g.bias = b.o2.b; g.resid = m->h.p; g.M = (int)M; g.N = b.o2.out; g.K = b.o2.in;
-            g.lda = D; g.ldc = D; g.ldr = D; g.rows_per_batch = Sg; g.rowsq = m->hsq.as<float>();
-            g.C2 = m->n.p; g.scale2 = ada + 4 * D; g.scale2_stride = 6 * D;
-            LTX_TRY(ltx_launch_gemm(g, dt, EPI_RESID, s));
-            hs_valid = true;
-        } else
-        LTX_TRY(ltx_linear(b.o2, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_RESID, s, m->h.p, D, nullptr, 0, 1, presum ? m->hsq.as<float>() : nullptr));
-        hsq_valid = presum;
-        // MLP (shift_mlp = row 3, scale_mlp = row 4, gate_mlp = row 5)
+    }
+    LTX_TRY(ltx_launch_rope_table(r, s));
+    rk.coords = video_coords; rk.B = p.B; rk.S = p.S; rk.F = num_frames; rk.H = height; rk.W = width; rk.stream = s;
+    rk.has_rs = rope_scale != nullptr; if (rope_scale) memcpy(rk.rs, rope_scale, sizeof(rk.rs));
+    rk.valid = m->ctx_mode;
+    return LTX_OK;
+}
+
+// ---- the block loop ----
+struct DitCarry {             // what a block leaves for the next one (and the last one for the final norm)
+    bool hsq_valid = false;   // m->hsq holds the partials of the CURRENT contents of h
+    bool hs_valid = false;    // m->n holds h (.) (1 + scale) of the norm that comes next (written by the layer that wrote h)
+    bool hsq_saved = false;   // m->orig_hsq holds the partials of m->orig (a layer some rows skip)
+    bool pending = false; const float* pend_gate = nullptr; const void* pend_bias = nullptr;      // h's rows are still ff2's K-range sums in m->parts
+    void take_pending(RowNormArgs& rn, const ltx_dit* m, const DitPlan& p) {      // the row norm that comes next finishes those rows first (RowNormArgs::parts)
+        if (!pending) return;
+        rn.parts = m->parts.as<float>(); rn.nparts = p.ff2_parts; rn.part_stride = p.M * p.D; rn.d_bias = pend_bias; rn.d_gate = pend_gate; rn.d_gate_stride = 6 * p.D;
+        rn.x_out = m->h.p; pending = false;
+    }
+};
+struct DitLayerIn { DitTables tab; const DitWfold* we = nullptr; const DitCtx* ctx = nullptr; const float* skip_layer_mask = nullptr; };      // what the forward hands every block
+// does block l run: not in the skip list (:1094-1096), not skipped by every row of the mask (all-ones rows make the block an exact identity, :1098-1123)
+bool block_runs(const ltx_dit* m, const float* skip_layer_mask, int B, int l) {
+    for (int sb : m->skip_blocks) if (sb == l) return false;
+    bool all = skip_layer_mask != nullptr;
+    for (int b = 0; all && b < B; ++b) all = skip_layer_mask[(size_t)l * B + b] == 1.f;
+    return !all;
+}
+int next_block(const ltx_dit* m, const float* skip_layer_mask, int B, int l) {      // the next block that runs, -1: none
+    for (int n = l + 1; n < m->cfg.num_layers; ++n) if (block_runs(m, skip_layer_mask, B, n)) return n;
+    return -1;
+}
+
+int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarry& st, hipStream_t s) {
+    const ltx_dit_config& c = m->cfg;
+    const int dt = p.dt, D = p.D, B = p.B, S = p.S, NB = p.NB, H = c.num_attention_heads, hd = c.attention_head_dim;
+    const int64_t M = p.M; const size_t esz = ltx_dt_size(dt);
+    const bool wf = in.we != nullptr, fold_out = p.nfold && !wf;      // fold_out: the producers write the second output
+    const DitBlock& b = m->blocks[l];
+    TimeVec mv; mv.n = B; bool any = false;
+    for (int i = 0; i < 8; ++i) mv.t[i] = 0.f;
+    if (in.skip_layer_mask) for (int bb = 0; bb < B; ++bb) { mv.t[bb] = in.skip_layer_mask[(size_t)l * B + bb]; any |= mv.t[bb] != 0.f; }
+    if (any) {
+        HIP_TRY(hipMemcpyAsync(m->orig.p, m->h.p, M * D * esz, hipMemcpyDeviceToDevice, s));
+        // the row partials of the kept rows travel with them (restored after the blend): a batch whose rows skip different
+        // layers - the guidance branches of a step in one forward - then returns, row for row, the bits of separate forwards
+        st.hsq_saved = p.presum && st.hsq_valid;
+        if (st.hsq_saved) { LTX_TRY(m->orig_hsq.ensure(M * (D / 128) * sizeof(float))); HIP_TRY(hipMemcpyAsync(m->orig_hsq.p, m->hsq.p, M * (D / 128) * sizeof(float), hipMemcpyDeviceToDevice, s)); }
+    }
+    const int ln = fold_out ? next_block(m, in.skip_layer_mask, B, l) : -1;
+    const float* ada = in.tab.ada + (size_t)l * NB * 6 * D;
+    DitOperands x{m->h.p, m->n.p, m->qkv.p, m->attn.p, m->ff.p, m->rsq.as<float>(), m->hsq.as<float>(), m->parts.as<float>(), ada,
+                  ln >= 0 ? in.tab.ada + (size_t)ln * NB * 6 * D : nullptr, p.nfold ? in.tab.cfold + (size_t)l * NB * 7 * D : nullptr,
+                  wf ? (const char*)in.we->w.p + (size_t)l * 7 * D * D * esz : nullptr, c.norm_eps};
+    const DitForm fold_in_form = wf ? kFold2 : kFold1;
+    // norm1 + AdaLN (shift_msa = row 0, scale_msa = row 1)
+    RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = M; rn.D = D; rn.ldx = D; rn.ldy = D;
+    rn.kind = 0; rn.eps = c.norm_eps; rn.shift = ada; rn.scale = ada + D; rn.rows_per_batch = p.Sg; rn.mod_stride = 6 * D;
+    if (p.presum && st.hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
+    const bool fold1 = p.nfold && st.hsq_valid && (wf || st.hs_valid);      // the layer that wrote h left its row partials and h (.) (1 + scale_msa) in m->n (or the factor is in the weights): no pass
+    if (!fold1) { st.take_pending(rn, m, p); LTX_TRY(ltx_launch_rownorm(rn, dt, s)); }
+    st.hs_valid = false;
+    rn.parts = nullptr; rn.nparts = 0; rn.x_out = nullptr; rn.d_bias = nullptr; rn.d_gate = nullptr;
+    // self attention
+    LTX_TRY(ltx_launch_gemm(gemm_qkv1(p, fold1 ? fold_in_form : kPass, b, x), dt, EPI_BIAS, s));
+    const float attn_scale = 1.0f / std::sqrt((float)hd);
+    QkNormRopeArgs qa; qa.x = m->qkv.p; qa.rows = M; qa.D = D; qa.ld = p.ldqkv; qa.seg_stride = p.seg; qa.nseg = 2; qa.w0 = b.nq1; qa.w1 = b.nk1;
+    qa.eps = 1e-5f; qa.cos = m->cosb.as<float>(); qa.sin = m->sinb.as<float>();
+    if (p.fold_q) qa.out_scale0 = attn_scale * 1.4426950408889634f;
+    LTX_TRY(ltx_launch_qknorm_rope(qa, dt, s));
+    AttnArgs at; at.q = m->qkv.p; at.k = (char*)m->qkv.p + (size_t)p.seg * esz; at.v = (char*)m->qkv.p + (size_t)2 * p.seg * esz; at.o = m->attn.p;
+    at.ldq = at.ldk = at.ldv = p.ldqkv; at.ldo = D; at.B = B; at.Sq = S; at.Sk = S; at.heads = H; at.hd = hd; at.scale = attn_scale;
+    at.q_prescaled = p.fold_q ? 1 : 0;
+    LTX_TRY(ltx_launch_attention(at, dt, s));
+    // h = h + gate_msa * to_out(attn)     (gate_msa = row 2)
+    LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, p.Sg));
+    st.hsq_valid = false;
+    // cross attention (no pre-norm, no RoPE, q/k RMSNorm, additive key bias)
+    const DitCtx* ctx = in.ctx;
+    const char* kvl = (const char*)(ctx->compact ? ctx->kvc.p : ctx->kv.p) + (size_t)l * p.MK * 2 * D * esz;
+    AttnArgs ax; ax.q = m->qkv.p; ax.k = kvl; ax.v = kvl + (size_t)D * esz; ax.o = m->attn.p;
+    ax.ldq = D; ax.ldk = ax.ldv = 2 * D; ax.ldo = D; ax.B = B; ax.Sq = S; ax.Sk = p.K; ax.heads = H; ax.hd = hd; ax.scale = attn_scale;
+    ax.bias = ctx->mask ? ctx->bias.as<float>() : nullptr;
+    if (ctx->compact) { ax.bias = ctx->biasc.as<float>(); ax.k_count = ctx->kcount.as<int>(); }
+    if (p.fold_q2) {
+        LTX_TRY(ltx_launch_gemm(gemm_q2(p, b, x), dt, EPI_BIAS, s));
+        ax.q_rowsq = m->rsq.as<float>(); ax.q_rowsq_n = D / 128; ax.q_rowsq_D = D; ax.q_rowsq_eps = 1e-5f;
+    } else {
+        LTX_TRY(linear_of(b.q2, gemm_q2(p, b, x), dt, EPI_BIAS, s));
+        QkNormRopeArgs q2; q2.x = m->qkv.p; q2.rows = M; q2.D = D; q2.ld = D; q2.nseg = 1; q2.w0 = b.nq2; q2.eps = 1e-5f;
+        LTX_TRY(ltx_launch_qknorm_rope(q2, dt, s));
+    }
+    LTX_TRY(ltx_launch_attention(ax, dt, s));
+    if (fold_out) { LTX_TRY(ltx_launch_gemm(gemm_o2(p, kFold1, b, x), dt, EPI_RESID, s)); st.hs_valid = true; }
+    else LTX_TRY(linear_of(b.o2, gemm_o2(p, kPass, b, x), dt, EPI_RESID, s));
+    st.hsq_valid = p.presum;
+    // MLP (shift_mlp = row 3, scale_mlp = row 4, gate_mlp = row 5)
+    if (p.nfold && st.hsq_valid && (wf || st.hs_valid)) LTX_TRY(ltx_launch_gemm(gemm_ff1(p, fold_in_form, b, x), dt, EPI_GELU, s));
+    else {
         rn.shift = ada + 3 * D; rn.scale = ada + 4 * D;
         rn.presum = nullptr; rn.presum_n = 0;
-        if (presum && hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
-        if (nfold && hsq_valid && (wf || hs_valid)) {
-            GemmArgs g; g.A = m->n.p; g.W = b.ff1.w; g.C = m->ff.p; g.M = (int)M; g.N = b.ff1.out; g.K = b.ff1.in; g.lda = D; g.ldc = 4 * D; g.rows_per_batch = Sg;
-            g.rs_sq = m->hsq.as<float>(); g.rs_n = D / 128; g.rs_D = D; g.rs_eps = c.norm_eps; g.cvec = cfold_l + (size_t)NB * 3 * D; g.cvec_stride = 4 * D;
-            if (wf) { g.A = m->h.p; g.W = wfold_l + (size_t)3 * D * D * esz; }
-            LTX_TRY(ltx_launch_gemm(g, dt, EPI_GELU, s));
-        } else {
+        if (p.presum && st.hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
         LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-        LTX_TRY(ltx_linear(b.ff1, m->n.p, D, m->ff.p, 4 * D, (int)M, dt, EPI_GELU, s));
-        }
-        hs_valid = false;
-        if (defer_ff2) {
-            GemmArgs g; g.A = m->ff.p; g.W = b.ff2.w; g.C = m->h.p; g.M = (int)M; g.N = b.ff2.out; g.K = b.ff2.in; g.lda = 4 * D; g.ldc = D;
-            g.defer_parts = m->parts.as<float>();
-            LTX_TRY(ltx_launch_gemm(g, dt, EPI_BIAS, s));
-            pending = true; pend_gate = ada + 5 * D; pend_bias = b.ff2.b;
-        } else if (int ln = (nfold && !wf) ? next_block(l) : -1; ln >= 0) {      // + h (.) (1 + scale_msa of the next block that runs) into m->n for its q|k|v projection
-            GemmArgs g; g.A = m->ff.p; g.W = b.ff2.w; g.C = m->h.p; g.bias = b.ff2.b; g.resid = m->h.p; g.M = (int)M; g.N = b.ff2.out; g.K = b.ff2.in;
-            g.lda = 4 * D; g.ldc = D; g.ldr = D; g.gate = ada + 5 * D; g.gate_stride = 6 * D; g.rows_per_batch = Sg; g.rowsq = m->hsq.as<float>();
-            g.C2 = m->n.p; g.scale2 = ada_all + (size_t)ln * NB * 6 * D + D; g.scale2_stride = 6 * D;
-            LTX_TRY(ltx_launch_gemm(g, dt, EPI_GATE_RESID, s));
-            hs_valid = true;
-        } else
-        LTX_TRY(ltx_linear(b.ff2, m->ff.p, 4 * D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 5 * D, 6 * D, Sg, presum ? m->hsq.as<float>() : nullptr));
-        hsq_valid = presum;
-        if (skip_layer_mask && any) {
-            LTX_TRY(ltx_launch_skip_blend(m->h.p, m->orig.p, mv, S, D, dt, s));
-            bool binary = true;
-            for (int bb = 0; bb < B; ++bb) binary &= mv.t[bb] == 0.f || mv.t[bb] == 1.f;
-            if (hsq_valid && hsq_saved && binary) {            // rows with mask 1 are the block's input again: so are their partials
-                const size_t rowb = (size_t)S * (D / 128) * sizeof(float);
-                for (int bb = 0; bb < B; ++bb)
-                    if (mv.t[bb] == 1.f) HIP_TRY(hipMemcpyAsync((char*)m->hsq.p + bb * rowb, (const char*)m->orig_hsq.p + bb * rowb, rowb, hipMemcpyDeviceToDevice, s));
-            } else hsq_valid = false;
-            // m->n was formed from the un-blended rows, for the block after this one; the restored rows need theirs: the producer's
-            // expression on the rows as they stand now (for the rows that kept the block: the bits the epilogue wrote)
-            hs_valid = false;
-            if (nfold && !wf && hsq_valid) {
-                if (const int ln = next_block(l); ln >= 0) {
-                    LTX_TRY(ltx_launch_mod_scale(m->h.p, ada_all + (size_t)ln * NB * 6 * D + D, 6 * D, m->n.p, NB, Sg, D, dt, s));
-                    hs_valid = true;
-                }
-            }
-        }
+        LTX_TRY(linear_of(b.ff1, gemm_ff1(p, kPass, b, x), dt, EPI_GELU, s));
     }
+    st.hs_valid = false;
+    if (p.defer_ff2) {
+        LTX_TRY(ltx_launch_gemm(gemm_ff2(p, kDefer, b, x), dt, EPI_BIAS, s));
+        st.pending = true; st.pend_gate = ada + 5 * D; st.pend_bias = b.ff2.b;
+    } else if (ln >= 0) { LTX_TRY(ltx_launch_gemm(gemm_ff2(p, kFold1, b, x), dt, EPI_GATE_RESID, s)); st.hs_valid = true; }
+    else LTX_TRY(linear_of(b.ff2, gemm_ff2(p, kPass, b, x), dt, EPI_GATE_RESID, s));
+    st.hsq_valid = p.presum;
+    if (!any) return LTX_OK;
+    LTX_TRY(ltx_launch_skip_blend(m->h.p, m->orig.p, mv, S, D, dt, s));
+    bool binary = true;
+    for (int bb = 0; bb < B; ++bb) binary &= mv.t[bb] == 0.f || mv.t[bb] == 1.f;
+    if (st.hsq_valid && st.hsq_saved && binary) {          // rows with mask 1 are the block's input again: so are their partials
+        const size_t rowb = (size_t)S * (D / 128) * sizeof(float);
+        for (int bb = 0; bb < B; ++bb)
+            if (mv.t[bb] == 1.f) HIP_TRY(hipMemcpyAsync((char*)m->hsq.p + bb * rowb, (const char*)m->orig_hsq.p + bb * rowb, rowb, hipMemcpyDeviceToDevice, s));
+    } else st.hsq_valid = false;
+    // m->n was formed from the un-blended rows, for the block after this one; the restored rows need theirs: the producer's
+    // expression on the rows as they stand now (for the rows that kept the block: the bits the epilogue wrote)
+    st.hs_valid = false;
+    if (fold_out && st.hsq_valid && ln >= 0) { LTX_TRY(ltx_launch_mod_scale(m->h.p, x.ada_next + D, 6 * D, m->n.p, NB, p.Sg, D, dt, s)); st.hs_valid = true; }
+    return LTX_OK;
+}
+
+// one forward of up to 8 batch rows (the per-batch scalars - timesteps, skip-mask rows - travel as kernel arguments).
+// G: modulation groups per batch row - 1: one timestep per row (timestep [B]); num_frames: one per latent frame (timestep [B, G],
+// tokens in pack order, so a group is a run of S / G rows).  Only the AdaLN look-ups see the groups: they index their tables with
+// m / rows_per_batch, which becomes m / (S / G) over tables of B * G rows; attention, RoPE, the text context and the skip-layer
+// blend keep S.
+int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float* timestep, int G,
+                   const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
+                   const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
+                   ltx_dtype io_dtype, void* out, ltx_stream stream) {
+    if (B < 1 || B > 8) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: internal batch chunk must be 1..8");
+    if (S < 1 || K < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: empty sequence");
+    if (!video_coords && (int64_t)num_frames * height * width != S)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: num_frames*height*width must equal S when video_coords is absent");
+    HIP_TRY(hipSetDevice(m->device));
+    if (G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: the modulation groups must divide the sequence");
+    hipStream_t s = (hipStream_t)stream;
+    const ltx_dit_config& c = m->cfg;
+    const DitPlan p = ltx_dit_plan(c, m->dtype, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, S, K, G, skip_layer_mask != nullptr);
+    const int dt = p.dt, D = p.D, L = c.num_layers;
+    const int64_t M = p.M, MK = p.MK; const size_t esz = ltx_dt_size(dt);
+    // the workspaces, sized for the plan; nothing is launched before every one of them exists
+    const size_t nte = p.NB == p.B ? (size_t)p.B : 8;      // rows of one time-embedding launch: the batch rows, or eight distinct values of a per-frame call
+    const size_t MD = M * D * esz, KD = MK * D * esz, part = M * (D / 128) * sizeof(float), rope = M * (D / 2) * sizeof(float);
+    const std::pair<DevBuf*, size_t> ws[] = {
+        {&m->xin, M * c.in_channels * esz}, {&m->encin, MK * c.caption_channels * esz}, {&m->h, MD}, {&m->n, MD}, {&m->qkv, 3 * MD}, {&m->attn, MD}, {&m->ff, 4 * MD},
+        {&m->c1, KD}, {&m->encp, KD}, {&m->kv2, 2 * KD}, {&m->tproj, nte * 256 * esz}, {&m->e1, nte * D * esz}, {&m->emb, nte * D * esz}, {&m->embs, nte * D * esz},
+        {&m->temb, nte * 6 * D * esz}, {&m->cosb, rope}, {&m->sinb, rope}, {&m->bias, MK * sizeof(float)}, {&m->outT, M * c.out_channels * esz},
+        {&m->rsq, p.fold_q2 ? part : 0}, {&m->hsq, p.presum ? part : 0}, {&m->parts, p.defer_ff2 ? (size_t)p.ff2_parts * M * D * sizeof(float) : 0}, {&m->orig, skip_layer_mask ? MD : 0}};
+    for (const auto& w : ws) LTX_TRY(w.first->ensure(w.second));
+
+    // inputs -> model dtype (:1045-1047)
+    LTX_TRY(ltx_launch_cast(hidden, p.iodt, m->xin.p, dt, p.M * c.in_channels, s));
+    LTX_TRY(ltx_linear(m->proj_in, m->xin.p, c.in_channels, m->h.p, D, (int)p.M, dt, EPI_BIAS, s));
+
+    DitLayerIn in; in.skip_layer_mask = skip_layer_mask;
+    LTX_TRY(G == 1 ? time_tables(m, p, timestep, B, s, &in.tab) : group_tables(m, p, timestep, s, &in.tab));
+    LTX_TRY(scaled_weights(m, p, timestep, in.tab.ada, s, &in.we));
+    DitCtx* ctx = nullptr;
+    LTX_TRY(text_context(m, p, enc, enc_mask, s, &ctx)); in.ctx = ctx;
+    LTX_TRY(rope_tables(m, p, num_frames, height, width, rope_scale, video_coords, s));
+
+    DitCarry st;
+    for (int l = 0; l < L; ++l)
+        if (block_runs(m, skip_layer_mask, B, l)) LTX_TRY(dit_block(m, p, l, in, st, s));
 
     // final LayerNorm (no affine) + modulation (:1126-1161), proj_out (:1163)
-    {
-        RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = M; rn.D = D; rn.ldx = D; rn.ldy = D;
-        rn.kind = 1; rn.eps = 1e-6f; rn.shift = adaf; rn.scale = adaf + (size_t)NB * D;
-        rn.rows_per_batch = Sg; rn.mod_stride = D;
-        take_pending(rn);
-        LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-        void* dst = iodt == dt ? out : m->outT.p;
-        LTX_TRY(ltx_linear(m->proj_out, m->n.p, D, dst, c.out_channels, (int)M, dt, EPI_BIAS, s));
-        if (iodt != dt) LTX_TRY(ltx_launch_cast(m->outT.p, dt, out, iodt, M * c.out_channels, s));
-    }
+    RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = p.M; rn.D = D; rn.ldx = D; rn.ldy = D;
+    rn.kind = 1; rn.eps = 1e-6f; rn.shift = in.tab.adaf; rn.scale = in.tab.adaf + (size_t)p.NB * D;
+    rn.rows_per_batch = p.Sg; rn.mod_stride = D;
+    st.take_pending(rn, m, p);
+    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+    void* dst = p.iodt == dt ? out : m->outT.p;
+    LTX_TRY(ltx_linear(m->proj_out, m->n.p, D, dst, c.out_channels, (int)p.M, dt, EPI_BIAS, s));
+    if (p.iodt != dt) LTX_TRY(ltx_launch_cast(m->outT.p, dt, out, p.iodt, p.M * c.out_channels, s));
     if (!m->ctx_mode) ctx->valid = false;
     return LTX_OK;
 }
 
 // The trait puts no bound on the batch (t2v_pipeline.rs:68-80).  Batch rows never interact in the forward
 // (ltx_transformer.rs:1029-1172: every op is per row or per (row, token)), so a larger batch runs as chunks of 8 rows with the
-// same results as one call would give.
-extern "C" int ltx_dit_forward(ltx_dit* m, const void* hidden, const void* enc, const float* timestep,
-                               const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
-                               const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
-                               ltx_dtype io_dtype, void* out, ltx_stream stream) {
-    if (!m || !hidden || !enc || !timestep || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: null argument");
-    if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: batch must be at least 1");
-    if (B <= 8) return dit_forward_b8(m, hidden, enc, timestep, 1, enc_mask, B, S, K, num_frames, height, width, rope_scale, video_coords, skip_layer_mask, io_dtype, out, stream);
+// same results as one call would give.  F: 0 - timestep [B], one per row; else timestep [B, F], one per latent frame: rows whose
+// frames all share one value need no groups, and a chunk made of such rows IS the plain forward (the same launches, the same bits,
+// norm_fold=2's weight copies included).
+int dit_forward_chunks(ltx_dit* m, const void* hidden, const void* enc, const float* timestep, int F,
+                       const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
+                       const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
+                       ltx_dtype io_dtype, void* out, ltx_stream stream) {
     const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
     const int L = m->cfg.num_layers;
     std::vector<float> mask_chunk;
-    for (int b0 = 0; b0 < B; b0 += 8) {
-        const int bc = B - b0 < 8 ? B - b0 : 8;
-        const float* slm = nullptr;
-        if (skip_layer_mask) {                              // [L, B] -> [L, bc]
-            mask_chunk.resize((size_t)L * bc);
-            for (int l = 0; l < L; ++l) for (int b = 0; b < bc; ++b) mask_chunk[(size_t)l * bc + b] = skip_layer_mask[(size_t)l * B + b0 + b];
-            slm = mask_chunk.data();
-        }
-        LTX_TRY(dit_forward_b8(m, (const char*)hidden + (size_t)b0 * S * m->cfg.in_channels * esz, (const char*)enc + (size_t)b0 * K * m->cfg.caption_channels * esz,
-                               timestep + b0, 1, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
-                               video_coords ? video_coords + (size_t)b0 * S * 3 : nullptr, slm, io_dtype,
-                               (char*)out + (size_t)b0 * S * m->cfg.out_channels * esz, stream));
-    }
-    return LTX_OK;
-}
-
-// Per-frame timesteps (include/ltxhip_cond.h).  Rows whose frames all share one value need no groups: a call made of such rows IS
-// ltx_dit_forward (the same launches, the same bits, norm_fold=2's weight copies included).
-extern "C" int ltx_dit_forward_frames(ltx_dit* m, const void* hidden, const void* enc, const float* timestep,
-                                      const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
-                                      const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
-                                      ltx_dtype io_dtype, void* out, ltx_stream stream) {
-    if (!m || !hidden || !enc || !timestep || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: null argument");
-    if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: batch must be at least 1");
-    if (num_frames < 1 || height < 1 || width < 1 || (int64_t)num_frames * height * width != S)
-        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: S must equal num_frames*height*width (tokens in pack order, with or without video_coords)");
-    const int F = num_frames;
-    const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
-    const int L = m->cfg.num_layers;
-    std::vector<float> mask_chunk, t_row;
+    float t_row[8];
     for (int b0 = 0; b0 < B; b0 += 8) {
         const int bc = B - b0 < 8 ? B - b0 : 8;
         const float* slm = skip_layer_mask;
@@ -763,17 +779,42 @@ extern "C" int ltx_dit_forward_frames(ltx_dit* m, const void* hidden, const void
             for (int l = 0; l < L; ++l) for (int b = 0; b < bc; ++b) mask_chunk[(size_t)l * bc + b] = skip_layer_mask[(size_t)l * B + b0 + b];
             slm = mask_chunk.data();
         }
-        const float* tc = timestep + (size_t)b0 * F;
-        bool uniform = true;
-        for (int b = 0; b < bc; ++b) for (int f = 1; f < F; ++f) uniform = uniform && memcmp(&tc[(size_t)b * F + f], &tc[(size_t)b * F], sizeof(float)) == 0;
-        t_row.resize(8);
-        for (int b = 0; b < bc; ++b) t_row[b] = tc[(size_t)b * F];
+        const float* tc = timestep + (size_t)b0 * (F ? F : 1);
+        int G = 1;
+        if (F) {
+            bool uniform = true;
+            for (int b = 0; b < bc; ++b) for (int f = 1; f < F; ++f) uniform = uniform && memcmp(&tc[(size_t)b * F + f], &tc[(size_t)b * F], sizeof(float)) == 0;
+            if (uniform) { for (int b = 0; b < bc; ++b) t_row[b] = tc[(size_t)b * F]; tc = t_row; } else G = F;
+        }
         LTX_TRY(dit_forward_b8(m, (const char*)hidden + (size_t)b0 * S * m->cfg.in_channels * esz, (const char*)enc + (size_t)b0 * K * m->cfg.caption_channels * esz,
-                               uniform ? t_row.data() : tc, uniform ? 1 : F, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
+                               tc, G, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
                                video_coords ? video_coords + (size_t)b0 * S * 3 : nullptr, slm, io_dtype,
                                (char*)out + (size_t)b0 * S * m->cfg.out_channels * esz, stream));
     }
     return LTX_OK;
+}
+
+}  // namespace
+
+extern "C" int ltx_dit_forward(ltx_dit* m, const void* hidden, const void* enc, const float* timestep,
+                               const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
+                               const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
+                               ltx_dtype io_dtype, void* out, ltx_stream stream) {
+    if (!m || !hidden || !enc || !timestep || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: null argument");
+    if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: batch must be at least 1");
+    return dit_forward_chunks(m, hidden, enc, timestep, 0, enc_mask, B, S, K, num_frames, height, width, rope_scale, video_coords, skip_layer_mask, io_dtype, out, stream);
+}
+
+// Per-frame timesteps (include/ltxhip_cond.h)
+extern "C" int ltx_dit_forward_frames(ltx_dit* m, const void* hidden, const void* enc, const float* timestep,
+                                      const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
+                                      const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
+                                      ltx_dtype io_dtype, void* out, ltx_stream stream) {
+    if (!m || !hidden || !enc || !timestep || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: null argument");
+    if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: batch must be at least 1");
+    if (num_frames < 1 || height < 1 || width < 1 || (int64_t)num_frames * height * width != S)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_frames: S must equal num_frames*height*width (tokens in pack order, with or without video_coords)");
+    return dit_forward_chunks(m, hidden, enc, timestep, num_frames, enc_mask, B, S, K, num_frames, height, width, rope_scale, video_coords, skip_layer_mask, io_dtype, out, stream);
 }
 
 extern "C" int ltx_dit_context_cache(ltx_dit* m, int enable) {
@@ -831,11 +872,7 @@ extern "C" int ltx_dit_set_adapters(ltx_dit* m, const ltx_lora* const* loras, co
             }
             m->lora_w[l].merged[slot] = p; fresh.push_back(&m->lora_w[l].merged[slot]);
         }
-    // every cache that is a function of the weights (wcache keeps its allocations; wfold_off and the GEMM plans are not touched)
-    for (auto& e : m->wcache) e.valid = false;
-    for (auto& e : m->tcache) e.cfold_valid = false;
-    for (auto& e : m->gcache) e.cfold_valid = false;
-    for (auto& e : m->ctxs) e.valid = false;
+    m->invalidate_weight_derived();
     std::vector<void*> unused;
     int rc = LTX_OK;
     for (int l = 0; l < L; ++l)

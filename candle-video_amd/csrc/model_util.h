@@ -79,6 +79,22 @@ int ltx_linear(const LinearW& l, const void* x, int lda, void* y, int ldc, int M
                const void* resid = nullptr, int ldr = 0, const float* gate = nullptr, int gate_stride = 0, int rows_per_batch = 1,
                float* rowsq = nullptr);
 
+// The decisions of one DiT forward of up to 8 batch rows (dit.hip): a function of the configuration, the dtypes, the shape, whether
+// a skip-layer mask is present and ltx_opt() - no handle, no device.  ltx_op_dit_plan reads it from outside.
+struct DitPlan {
+    int dt = 0, iodt = 0, D = 0, B = 0, S = 0, K = 0;
+    int64_t M = 0, MK = 0;        // latent rows B * S, text rows B * K
+    int NB = 0, Sg = 0;           // modulation groups of the call (B * G), rows of one group (S / G)
+    int64_t seg = 0; int ldqkv = 0;      // elements from q to k to v, leading dimension of each (dense_qkv)
+    bool fold_q2 = false;         // cross-attention q-norm folded into the attention kernel
+    bool presum = false;          // the block's RMS norms take their rows' sums of squares from the GEMM that wrote h
+    bool nfold = false;           // ... and the norm pass itself is folded into the GEMMs around it
+    bool defer_ff2 = false; int ff2_parts = 1;      // ff2 leaves its K ranges to the row norm that follows the block
+    bool dense_qkv = false;       // q, k, v as three dense [M, D] matrices
+    bool fold_q = false;          // self-attention q leaves its norm multiplied by scale * log2(e)
+};
+DitPlan ltx_dit_plan(const ltx_dit_config& c, int dt, int iodt, int B, int S, int K, int G, bool skip_mask);
+
 // conv weight repack [O,I,kt,kh,kw] -> [tap][n'][I] with output-channel permutation (vae.hip)
 enum { LTX_PERM_NONE = 0, LTX_PERM_D2S = 1, LTX_PERM_UNPATCH = 2 };
 int ltx_pack_conv(const void* src_dev, int sdt, void* dst, int ddt, int O, int I, int ntaps, int mode, int Cf, hipStream_t s);

@@ -145,6 +145,7 @@ _SIGS = {
     "ltx_op_downsample3d": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_gemm_plan": [_i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i],
     "ltx_op_gemm_route": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i],
+    "ltx_op_dit_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int64)],
     # include/ltxhip_t5.h
     "ltx_t5_config_default": [_vp], "ltx_t5_create": [_vp, _vp, _sz, _i, _i, _vp], "ltx_t5_destroy": [_vp],
     "ltx_t5_forward": [_vp, _vp, _i, _i, _i, _vp, _vp],
@@ -1721,6 +1722,16 @@ class ops:
         flags = (1 if pn else 0) | (2 if defer else 0) | (4 if fold_in else 0) | (8 if fold_out else 0)
         _check(lib.ltx_op_gemm_route(M, N, K, conv, ntaps, B, T, H, W, epi, _dt(dtype), flags, buf, 32))
         return buf.value.decode()
+
+    DIT_PLAN_FIELDS = ("M", "MK", "NB", "Sg", "seg", "ldqkv", "fold_q2", "presum", "nfold", "defer_ff2", "ff2_parts", "dense_qkv", "fold_q")
+
+    @staticmethod
+    def dit_plan(heads, head_dim, B, S, K, G=1, dtype=torch.bfloat16, io_dtype=torch.float32, skip_mask=False) -> dict:
+        """the decisions of one DiT forward (csrc/dit.hip's ltx_dit_plan) under the current options: sizes as ints, decisions as
+        bools (ff2_parts an int).  No handle, no device; nothing is launched."""
+        out = (C.c_int64 * len(ops.DIT_PLAN_FIELDS))()
+        _check(lib.ltx_op_dit_plan(heads, head_dim, _dt(dtype), _dt(io_dtype), B, S, K, G, int(bool(skip_mask)), out))
+        return {k: (int(v) if i < 6 or k == "ff2_parts" else bool(v)) for i, (k, v) in enumerate(zip(ops.DIT_PLAN_FIELDS, out))}
 
     @staticmethod
     def blend(a, b, dim, blend_extent):

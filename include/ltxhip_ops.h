@@ -168,6 +168,13 @@ enum { LTX_ROUTE_PN = 1,         /* conv with the fused output norm */
        LTX_ROUTE_FOLD_OUT = 8 }; /* ltx_op_linear_fold_out's operands */
 int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B, int T, int H, int W, int epi, int dtype, int flags, char* name, int cap);
 
+/* Diagnostic, read-only: the decisions of one DiT forward of B <= 8 batch rows under the current options, for a model of
+ * heads x head_dim channels, S latent tokens and K text tokens per row and G modulation groups per row (1, or the latent frames
+ * of ltx_dit_forward_frames; G divides S); skip_mask: a skip-layer mask is passed.  No handle and no device are needed.
+ * out[LTX_DIT_PLAN_FIELDS]: M, MK, NB, Sg, seg, ldqkv (sizes), then fold_q2, presum, nfold, defer_ff2, ff2_parts, dense_qkv, fold_q. */
+enum { LTX_DIT_PLAN_FIELDS = 13 };
+int ltx_op_dit_plan(int heads, int head_dim, int model_dtype, int io_dtype, int B, int S, int K, int G, int skip_mask, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif
