@@ -669,6 +669,12 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const GemmArg
     }
 }
 
+// whether a launch takes the wide epilogue (result tile through LDS, 16-byte row-contiguous stores; EPI_BIAS / EPI_RESID)
+bool halo_wide_epi(const GemmArgs& g) {
+    return ltx_opt().gemm_wide_epi && g.ldc % 8 == 0 && ((uintptr_t)g.C & 15) == 0 &&
+           (!g.resid || (g.ldr % 8 == 0 && ((uintptr_t)g.resid & 15) == 0 && (double)g.H * g.Wd * g.ldr * 2.0 < 2147483648.0));
+}
+
 template <int BN, int WGM, int WGN, int EPI, bool PIPE = false>
 int launch_halo(const GemmArgs& g, hipStream_t s) {
     constexpr int smem = PIPE ? 2 * 44 * 1024 + 3 * BN * ROWB : 2 * A_STAGE + 2 * BN * ROWB;
@@ -677,9 +683,9 @@ int launch_halo(const GemmArgs& g, hipStream_t s) {
     LTX_TRY(ltx_set_max_dyn_smem(attr_devs, reinterpret_cast<const void*>(kern), smem));
     const int tiles = g.B * g.T * cdiv(g.H, PH) * cdiv(g.Wd, PW) * cdiv(g.N, BN);
     GemmArgs ga = g;
-    ga.wide_epi = ltx_opt().gemm_wide_epi && g.ldc % 8 == 0 && ((uintptr_t)g.C & 15) == 0 &&
-                  (!g.resid || (g.ldr % 8 == 0 && ((uintptr_t)g.resid & 15) == 0 && (double)g.H * g.Wd * g.ldr * 2.0 < 2147483648.0));
-    if (g.pn_on && (!ga.wide_epi || EPI != EPI_BIAS || BN != g.N || !HALO_WIDE_EPI)) LTX_FAIL(LTX_ERR_ARG, "conv_halo: the fused output norm needs the wide bias epilogue and BN == N");
+    ga.wide_epi = halo_wide_epi(g);
+    // (the route asks the same question before it sends a fused call here: ltx_conv_halo_norm_ok)
+    if (g.pn_on && (!ga.wide_epi || BN != g.N || !ltx_conv_halo_norm_ok(g, EPI))) LTX_FAIL(LTX_ERR_ARG, "conv_halo: the fused output norm needs the wide bias epilogue and BN == N");
     LTX_LAUNCH_TIMED(kern, dim3((unsigned)tiles), dim3(WGM * WGN * 64), smem, s, ga);
     LTX_CHECK_LAUNCH();
     return LTX_OK;
@@ -712,6 +718,16 @@ bool ltx_conv_halo_eligible(const GemmArgs& g, int epi, int bn) {
     // a tile addresses the three frames around it: those (not the tensor) and the weights must stay below 2 GiB
     const double frame_bytes = (double)g.H * g.Wd * g.Cin * 2.0, w_bytes = 27.0 * g.N * g.K * 2.0;
     return 3.0 * frame_bytes < 2147483648.0 && w_bytes < 2147483648.0 && (double)g.B * g.T * g.H * g.Wd < 2147483648.0;
+}
+
+// whether the halo-staged kernel can finish this conv with the fused output norm (GemmArgs::pn_on): only the wide bias epilogue of
+// the tile as wide as the output carries it, and its modulation rows are read as 16-byte vectors.  ONE predicate for the route
+// (gemm_big.hip's choose_plan, so that the probe and the launch agree) and for launch_halo.
+bool ltx_conv_halo_norm_ok(const GemmArgs& g, int epi) {
+    if (!HALO_WIDE_EPI || epi != EPI_BIAS || (g.N != 128 && g.N != 256) || !halo_wide_epi(g)) return false;
+    if ((g.pn_scale == nullptr) != (g.pn_shift == nullptr)) return false;
+    if (g.pn_scale && (g.pn_mod_stride % 4 != 0 || (((uintptr_t)g.pn_scale | (uintptr_t)g.pn_shift) & 15))) return false;
+    return ltx_conv_halo_eligible(g, epi, g.N);
 }
 
 int ltx_launch_conv_halo(const GemmArgs& g, int epi, int bn, hipStream_t s) {

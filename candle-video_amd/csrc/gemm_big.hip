@@ -821,8 +821,13 @@ GemmPlan ring_pick(const GemmArgs& g) { return GemmPlan{kPlanRing, ltx_gemm_ring
 int choose_plan(const GemmArgs& g, int epi, hipStream_t s, bool measure, GemmPlan* chosen) {
     const LtxOptions& o = ltx_opt();
     *chosen = GemmPlan{};
-    // fused output norm: only conv_halo's wide epilogue carries it, on the tile as wide as the output
-    if (g.pn_on) { const GemmPlan p{kPlanHalo, g.N == 256 ? 1 : 0}; if (g.N == kHaloBn[p.idx] && ltx_conv_halo_eligible(g, epi, g.N)) *chosen = p; return LTX_OK; }
+    // fused output norm: only conv_halo's wide bias epilogue carries it, on the tile as wide as the output - an empty plan (a refusal,
+    // ltx_gemm_route_refusal) for any other epilogue, under gemm_wide_epi=0 and under gemm_off=halo, where the launch would not apply it
+    if (g.pn_on) {
+        const GemmPlan p{kPlanHalo, g.N == 256 ? 1 : 0};
+        if (g.N == kHaloBn[p.idx] && !(o.gemm_off & LTX_FAM_HALO) && ltx_conv_halo_norm_ok(g, epi)) *chosen = p;
+        return LTX_OK;
+    }
     const bool split = ltx_gemm_split_factor(g) > 1;
     // conv_out (N = 48, unpatchify): the halo-staged kernel on its 64-wide tile - one staging of the 128-channel activation
     // per nine taps instead of one per tap (the per-tap 192 x 64 tile moves 27 x 610 MB through L2 -> LDS at C2).  Same K order:
@@ -880,7 +885,8 @@ const char* ltx_gemm_route_refusal(const GemmArgs& g, const GemmRoute& r) {
     const int fam = r.kind == LTX_ROUTE_PLAN ? r.plan.fam : -1;
     if (g.defer_parts && fam != kPlanRing) return "gemm: defer_parts set on a call that is not routed to the ring tiles (ask ltx_gemm_defer_ok first)";
     if ((g.C2 || g.rs_sq) && fam != kPlanAsm16) return "gemm: norm-fold arguments (C2 / rs_sq) on a call that is not routed to gemm_asm16 (ask ltx_gemm_fold_ok first)";
-    if (g.pn_on && r.kind == LTX_ROUTE_PLAN && fam != kPlanHalo) return "gemm: the fused output norm needs conv_halo's tile as wide as the output (128 / 256 channels)";
+    // (any route: gemm.hip's 128 x 128 kernel - f32, convs below 16 voxels, gemm_off=big - and the 32x32x16 kernel do not read pn_on either)
+    if (g.pn_on && fam != kPlanHalo) return "gemm: the fused output norm (pn_on) on a call that is not routed to conv_halo's wide bias epilogue on the tile as wide as the output (bf16, 128 / 256 channels, EPI_BIAS, gemm_wide_epi on, the halo family on)";
     return nullptr;
 }
 

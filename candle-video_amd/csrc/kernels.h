@@ -143,6 +143,7 @@ int ltx_pack_ring_weights(const void* W, int N, int K, void* out, hipStream_t s)
 bool ltx_gemm_big_fits(const GemmArgs& g);   // gemm_big.hip: every span its 32-bit buffer offsets address stays below 2 GiB
 // conv_halo.hip: 3x3x3 conv with the activation patch + rim staged once per nine in-plane taps; bn = 128 / 256
 bool ltx_conv_halo_eligible(const GemmArgs& g, int epi, int bn);
+bool ltx_conv_halo_norm_ok(const GemmArgs& g, int epi);      // ... and can finish it with the fused output norm (GemmArgs::pn_on) under the current options
 int ltx_launch_conv_halo(const GemmArgs& g, int epi, int bn, hipStream_t s);   // operands addressable with the kernel's 32-bit buffer offsets
 
 // ---------------- row norms (rownorm.hip) ----------------

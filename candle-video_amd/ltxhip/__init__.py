@@ -139,6 +139,7 @@ _SIGS = {
     "ltx_op_attention": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp],
     "ltx_op_attention_prescaled": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_conv3d": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ltx_op_conv3d_norm": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_upsample3d": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_conv_out_unpatchify": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "ltx_op_blend": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -1685,6 +1686,29 @@ class ops:
         y = torch.empty(B, T, H, W, Cout, dtype=x_cl.dtype, device=x_cl.device)
         _check(lib.ltx_op_conv3d(_ptr(x_cl.contiguous()), _ptr(w.contiguous()), _ptr(bias.to(w.dtype).contiguous()), _dt(w.dtype), _ptr(y), _ptr(resid),
                                  B, T, H, W, Cin, Cout, int(causal), _dt(x_cl.dtype), _stream()))
+        return y
+
+    @staticmethod
+    def conv3d_norm(x_cl, w, bias, causal=False, eps=1e-6, act=1, scale=None, shift=None):
+        """ops.conv3d finished inside the conv's epilogue with the per-voxel RMS norm over all output channels, (1 + scale[b]) and
+        shift[b], and SiLU (act=1): conv1 + norm2 of the VAE's resnet.  scale / shift: f32 [B, Cout], dense or column slices of one
+        wider table (the decoder's [B, 4 * Cout] modulation table) - the row stride is taken from the tensors; both None: no
+        modulation.  LtxError for a call the halo-staged kernel does not serve (f32, widths other than 128 / 256, under 16 voxels)."""
+        B, T, H, W, Cin = x_cl.shape
+        Cout = w.shape[0]
+        if (scale is None) != (shift is None):
+            raise LtxError("conv3d_norm: scale and shift come together")
+        ms = 0
+        if scale is not None:
+            for t in (scale, shift):
+                if t.dtype != torch.float32 or tuple(t.shape) != (B, Cout) or t.stride(1) != 1:
+                    raise LtxError(f"conv3d_norm: scale / shift must be f32 [{B}, {Cout}] with dense rows")
+            ms = scale.stride(0) if B > 1 else max(scale.stride(0), Cout)
+            if B > 1 and shift.stride(0) != ms:
+                raise LtxError("conv3d_norm: scale and shift must share one row stride")
+        y = torch.empty(B, T, H, W, Cout, dtype=x_cl.dtype, device=x_cl.device)
+        _check(lib.ltx_op_conv3d_norm(_ptr(x_cl.contiguous()), _ptr(w.contiguous()), _ptr(bias.to(w.dtype).contiguous()), _dt(w.dtype), _ptr(y),
+                                      _ptr(scale), _ptr(shift), ms, C.c_float(eps), act, B, T, H, W, Cin, Cout, int(causal), _dt(x_cl.dtype), _stream()))
         return y
 
     @staticmethod

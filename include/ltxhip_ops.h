@@ -130,6 +130,17 @@ int ltx_op_attention_prescaled(const void* q, const void* k, const void* v, void
 int ltx_op_conv3d(const void* x, const void* w, const void* bias, int wdtype, void* y, const void* resid,
                   int B, int T, int H, int W, int Cin, int Cout, int causal, int dtype, ltx_stream stream);
 
+/* ltx_op_conv3d (no residual) finished with the consumer's per-voxel RMS norm, modulation and activation inside the conv's epilogue
+ * (LtxVideoResnetBlock3d: conv1 + norm2, vae.rs:779-801; the encoder's calls pass eps = 1e-8 and no modulation):
+ *   y[b,t,h,w,:] = act(r * c * (1 + scale[b*mod_stride + :]) + shift[b*mod_stride + :]),  c = the conv's output row as ltx_op_conv3d
+ *   stores it (rounded to bf16), r = 1 / sqrt(mean_n(c^2) + eps); act 0: none, 1: SiLU.
+ * scale / shift: f32 DEVICE rows of Cout values, mod_stride floats apart (column slices of one table: mod_stride >= Cout, a
+ * multiple of 4, 16-byte aligned pointers), or both NULL: no modulation.  Served by the halo-staged kernel alone: bf16, Cout 128 or
+ * 256, Cin a multiple of 64, at least 16 voxels, options gemm_wide_epi on and gemm_off without halo / big; LTX_ERR_ARG for any
+ * other call (ltx_op_gemm_route with LTX_ROUTE_PN answers the same question) - never a conv without the norm. */
+int ltx_op_conv3d_norm(const void* x, const void* w, const void* bias, int wdtype, void* y, const float* scale, const float* shift, int mod_stride,
+                       float eps, int act, int B, int T, int H, int W, int Cin, int Cout, int causal, int dtype, ltx_stream stream);
+
 /* LtxVideoUpsampler3d (vae.rs:1090-1169): conv + depth-to-space(2,2,2) + drop first frame + tiled residual.
  * x [B,T,H,W,Cin] -> y [B,2T-1,2H,2W,Cout/8] channels-last. */
 int ltx_op_upsample3d(const void* x, const void* w, const void* bias, int wdtype, void* y,
@@ -161,7 +172,8 @@ int ltx_op_gemm_plan(int M, int N, int K, int conv, int ntaps, int T, int H, int
  * the cached one, else the static model's.  Nothing is launched or measured and no pointer is needed: dense operands are
  * assumed.  conv = 1: K = Cin, M = B T H W, ntaps taps; epi 0 .. 6 (bias, GELU, gate + residual, residual, depth-to-space,
  * unpatchify, space-to-depth); dtype as everywhere (1 = bf16).  flags describe the operand fields the dispatch reads.
- * LTX_ERR_ARG where ltx_launch would refuse the call (deferred K ranges / norm-fold operands on a kernel without them). */
+ * LTX_ERR_ARG where ltx_launch would refuse the call (deferred K ranges / norm-fold operands / the fused output norm on a kernel
+ * without them). */
 enum { LTX_ROUTE_PN = 1,         /* conv with the fused output norm */
        LTX_ROUTE_DEFER = 2,      /* K-range sums left to the consumer (ltx_op_linear_deferred) */
        LTX_ROUTE_FOLD_IN = 4,    /* ltx_op_linear_fold_in's operands (16 row partials) */

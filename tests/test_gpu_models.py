@@ -140,6 +140,45 @@ def test_vae_resnet_norm_fused_into_conv_epilogue(hip, monkeypatch, blocks, laye
     assert rel_l2(outs[torch.bfloat16], outs[torch.float32]) <= 3e-2
 
 
+def test_vae_fused_norm_batch_of_two_with_per_row_timesteps(hip):
+    """The fused norm2 with two batch rows and a modulation row each (timesteps 0.05 and 0.6): the (256, 512) decoder of the test
+    above, fused against the separate norm pass under the same 5e-3 bar, and each row decoded alone equal to its row of the batched
+    decode bit for bit - nothing in a conv tile crosses batch rows, so a slip in the modulation row index (b * pn_mod_stride)
+    shows in both.
+
+    Two things outside the norm make the bits of a decode depend on the batch size, and the bit comparison is set up so that neither
+    does here.  The shape rule cuts K by the size of the WHOLE output (the 128-channel stage of a 3 x 10 x 12 latent: seven ranges
+    for one row, three for two): the comparison runs under gemm_splitk=0.  And the stand-alone row norm sums a row in another order
+    from rows_total >= 64 / lanes_per_row * 2048 up (2048 / 4096 / 8192 rows at 512 / 256 / 128 channels; measured on the 3 x 10 x 12
+    latent: the 256-channel stage has 2400 rows for one batch row and 4800 for two, and that alone moved a single-row decode 1.1e-3
+    rel-L2 away from its batched row, fused or not): the latent is 3 x 12 x 18, whose stages have 648 / 4320 / 31104 rows per batch
+    row - the same side of each threshold for one row and for two."""
+    cfgd = dict(latent_channels=16, decoder_block_out_channels=(256, 512), decoder_layers_per_block=(1, 1, 1))
+    w = O.synth_weights(O.vae_decoder_weight_shapes(O.VaeConfig(**cfgd)), seed=11)
+    # (two up blocks: 4 x 4 x the patch in the plane, 4 in time - the ratios size the output tensor, so that out[b] is batch row b)
+    model = hip.AutoencoderKLLtxVideo(hip.AutoencoderKLLtxVideoConfig(spatial_compression_ratio=16, temporal_compression_ratio=4, **cfgd),
+                                      {"decoder." + k: v.to(DEV) for k, v in w.items()}, torch.bfloat16)
+    z = torch.randn(2, 16, 3, 12, 18, generator=torch.Generator().manual_seed(4)).to(DEV)
+    t = torch.tensor([0.05, 0.6])
+    hip.set_option("vae_fuse_norm", "2")             # these planes are far below one round of the chip: the default would not fuse
+    fused = model.decode(z, t).cpu()
+    assert fused.shape == (2, 3, 9, 192, 288) and torch.isfinite(fused).all()
+    with hip.options(vae_fuse_norm="0"):
+        sep = model.decode(z, t).cpu()
+    e = rel_l2(fused, sep)
+    print(f"batch of two, fused vs separate norm: rel-L2 {e:.3e}")
+    assert e <= 5e-3, e
+    assert not torch.equal(fused, sep)               # (the fused arm really ran the other algorithm)
+    assert rel_l2(fused[1], fused[0]) > 0.1          # the two rows are different videos
+    hip.set_option("gemm_splitk", "0")
+    both = model.decode(z, t).cpu()
+    assert rel_l2(both, sep) <= 5e-3
+    for b in (1, 0):
+        assert torch.equal(model.decode(z[b:b + 1], t[b:b + 1]).cpu()[0], both[b]), b
+    # ... and the row's own timestep matters: row 1 decoded with row 0's timestep is another video
+    assert not torch.equal(model.decode(z[1:2], t[0:1]).cpu()[0], both[1])
+
+
 def test_vae_decode_f32_fixture(hip, golden):
     g = golden("oracle_vae.safetensors")
     _, _, model = _vae(hip, torch.float32)
