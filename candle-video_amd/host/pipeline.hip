@@ -331,6 +331,20 @@ struct PipeScratch {
 };
 }  // namespace
 
+// The schedule of one call at S latent tokens (t2v_pipeline.rs:750-791): N + 1 sigmas and N truncated timesteps.  The one place that
+// builds it: the denoise loop below and ltx_pipeline_first_sigma (the re-noise in front of a second pass, csrc/upsampler.hip) both ask here.
+int ltx_pipeline_schedule(const ltx_pipeline_params* p, int S, std::vector<float>* sig, std::vector<int64_t>* ts) {
+    const int N = p->num_inference_steps;
+    if (N < 1) LTX_FAIL(LTX_ERR_ARG, "num_inference_steps must be >= 1");
+    std::vector<float> sig_in(N);
+    sig->assign(N + 1, 0.0f); ts->assign(N, 0);
+    const bool custom = p->sigmas != nullptr;
+    for (int i = 0; i < N; ++i)
+        sig_in[i] = custom ? p->sigmas[i] : (N == 1 ? 1.0f : 1.0f + (1.0f / (float)N - 1.0f) * (float)i / (float)(N - 1));
+    const float mu = custom ? 0.0f : ltx_calculate_shift(S, 256, 4096, 0.5f, 1.15f);      // static default cfg (scheduler.rs:638-639)
+    return ltx_sched_set_timesteps(sig_in.data(), N, mu, 1, 1.0f, p->shift_terminal, p->use_shift_terminal, sig->data(), ts->data());
+}
+
 // hold: HOST u8 [B, F'] or null - the held latent frames of ltx_pipeline_call_cond (include/ltxhip_cond.h); null: ltx_pipeline_call
 static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const unsigned char* hold,
                         float* latents, const float* prompt_embeds, const float* prompt_mask,
@@ -359,12 +373,8 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     }
     // sigmas / mu / timesteps (:750-791)
     const int N = p->num_inference_steps;
-    std::vector<float> sig_in(N), sig(N + 1); std::vector<int64_t> ts(N);
-    const bool custom = p->sigmas != nullptr;
-    for (int i = 0; i < N; ++i)
-        sig_in[i] = custom ? p->sigmas[i] : (N == 1 ? 1.0f : 1.0f + (1.0f / (float)N - 1.0f) * (float)i / (float)(N - 1));
-    const float mu = custom ? 0.0f : ltx_calculate_shift(S, 256, 4096, 0.5f, 1.15f);      // static default cfg (scheduler.rs:638-639)
-    LTX_TRY(ltx_sched_set_timesteps(sig_in.data(), N, mu, 1, 1.0f, p->shift_terminal, p->use_shift_terminal, sig.data(), ts.data()));
+    std::vector<float> sig; std::vector<int64_t> ts;
+    LTX_TRY(ltx_pipeline_schedule(p, S, &sig, &ts));
 
     PipeScratch sc;
     int cur_dev = 0; HIP_TRY(hipGetDevice(&cur_dev));

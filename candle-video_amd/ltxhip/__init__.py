@@ -253,6 +253,28 @@ for _name, _sig in _LORA_SIGS.items():
     _fn = getattr(lib, _name)
     _fn.argtypes = _sig
     _fn.restype = None if _name == "ltx_lora_destroy" else C.c_int
+class UpsamplerConfigC(C.Structure):             # ltx_upsampler_config (include/ltxhip_upsampler.h)
+    _fields_ = [("in_channels", C.c_int), ("mid_channels", C.c_int), ("num_blocks_per_stage", C.c_int)]
+
+
+# include/ltxhip_upsampler.h (kept apart like the three above)
+_UP_SIGS = {
+    "ltx_upsampler_config_default": [_vp], "ltx_upsampler_create": [_vp, _vp, _sz, _i, _i, _vp],
+    "ltx_upsampler_create_from_file": [_vp, C.c_char_p, _i, _i, _vp], "ltx_upsampler_destroy": [_vp], "ltx_upsampler_get_config": [_vp, _vp],
+    "ltx_upsampler_forward": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "ltx_latent_upsample_tokens": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "ltx_latent_adain": [_vp, _vp, _i, _i, _i, _i, _f, _vp], "ltx_latent_renoise": [_vp, _vp, _f, _sz, _vp],
+    "ltx_pipeline_first_sigma": [_vp, _i, _vp], "ltx_upsampler_warmup": [_vp, _i, _i, _i, _i, _vp],
+    "ltx_pipeline_call_multiscale": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "ltx_pipeline_multiscale_last_timing": [_vp],
+    "ltx_op_groupnorm": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp],
+}
+UPSAMPLER_SYMBOLS = sorted(_UP_SIGS)
+for _name, _sig in _UP_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = None if _name in ("ltx_upsampler_config_default", "ltx_upsampler_destroy") else C.c_int
+LTX_GN_SILU, LTX_GN_GUARDS = 1, 2
 # the ten LoRA targets of a block, in the order of ltx_dit_read_linear's `which`
 LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0",
                 "ff.net.0.proj", "ff.net.2")
@@ -1225,6 +1247,196 @@ class LtxPipeline:
         return lat, video
 
 
+# ------------------------------------------------------------------ latent upsampler + two-pass call (include/ltxhip_upsampler.h)
+@dataclass
+class LatentUpsamplerConfig:
+    in_channels: int = 128
+    mid_channels: int = 512
+    num_blocks_per_stage: int = 4
+
+    def to_c(self) -> "UpsamplerConfigC":
+        return UpsamplerConfigC(self.in_channels, self.mid_channels, self.num_blocks_per_stage)
+
+
+class LatentUpsampler:
+    """The latent upsampler (spatial x2 in latent space) over ltx_upsampler_*; weight names as in the header."""
+
+    def __init__(self, config: LatentUpsamplerConfig, weights: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16, device: int = 0):
+        self.config, self.dtype = config, dtype
+        c = config.to_c()
+        arr, keep = _make_weights(weights)
+        self._h = C.c_void_p()
+        _check(lib.ltx_upsampler_create(C.byref(c), arr, C.c_size_t(len(weights)), _dt(dtype), device, C.byref(self._h)))
+        del keep
+
+    @classmethod
+    def from_file(cls, config: LatentUpsamplerConfig, path: str, dtype: torch.dtype = torch.bfloat16, device: int = 0) -> "LatentUpsampler":
+        self = cls.__new__(cls)
+        self.config, self.dtype = config, dtype
+        c = config.to_c()
+        self._h = C.c_void_p()
+        _check(lib.ltx_upsampler_create_from_file(C.byref(c), path.encode(), _dt(dtype), device, C.byref(self._h)))
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            lib.ltx_upsampler_destroy(h)
+            self._h = None
+
+    def get_config(self) -> "UpsamplerConfigC":
+        c = UpsamplerConfigC()
+        _check(lib.ltx_upsampler_get_config(self._h, C.byref(c)))
+        return c
+
+    def forward(self, latents: torch.Tensor) -> torch.Tensor:
+        """[B, in_channels, F, H, W] (f32 or bf16, un-normalised) -> [B, in_channels, F, 2H, 2W] of the same dtype"""
+        io = latents.dtype if latents.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        z = _dev(latents, io)
+        if z.dim() != 5 or z.shape[1] != self.config.in_channels:
+            raise LtxError("latents must be [B, in_channels, F, H, W]")
+        B, Cn, F, H, W = z.shape
+        out = torch.empty(B, Cn, F, 2 * H, 2 * W, dtype=io, device=z.device)
+        _check(lib.ltx_upsampler_forward(self._h, _ptr(z), _dt(io), B, F, H, W, _ptr(out), _stream()))
+        return out
+
+    def upsample_tokens(self, vae: "AutoencoderKLLtxVideo", tokens: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
+        """packed normalised tokens [B, F*H*W, C] f32 -> [B, F*2H*2W, C] f32 (un-normalise, forward, normalise)"""
+        t = _dev(tokens, torch.float32)
+        B = t.shape[0]
+        _expect("tokens", t, (B, F * H * W, self.config.in_channels))
+        out = torch.empty(B, F * 4 * H * W, self.config.in_channels, dtype=torch.float32, device=t.device)
+        _check(lib.ltx_latent_upsample_tokens(self._h, vae._h, _ptr(t), B, F, H, W, _ptr(out), _stream()))
+        return out
+
+    def warmup(self, B: int, F: int, H: int, W: int):
+        _check(lib.ltx_upsampler_warmup(self._h, B, F, H, W, _stream()))
+
+
+def latent_adain(tokens: torch.Tensor, ref_tokens: torch.Tensor, factor: float = 1.0) -> torch.Tensor:
+    """AdaIN of tokens [B,S,C] against ref_tokens [B,S_ref,C] (ltx_latent_adain); returns a new tensor"""
+    t = _dev(tokens, torch.float32).clone()
+    r = _dev(ref_tokens, torch.float32)
+    if t.dim() != 3 or r.dim() != 3 or t.shape[0] != r.shape[0] or t.shape[2] != r.shape[2]:
+        raise LtxError("tokens [B,S,C] and ref_tokens [B,S_ref,C] must agree on B and C")
+    _check(lib.ltx_latent_adain(_ptr(t), _ptr(r), t.shape[0], t.shape[1], r.shape[1], t.shape[2], float(factor), _stream()))
+    return t
+
+
+def latent_renoise(tokens: torch.Tensor, noise: torch.Tensor, sigma: float) -> torch.Tensor:
+    """(1 - sigma) * tokens + sigma * noise (ltx_latent_renoise); returns a new tensor"""
+    t = _dev(tokens, torch.float32).clone()
+    n = _dev(noise, torch.float32)
+    _expect("noise", n, t.shape)
+    _check(lib.ltx_latent_renoise(_ptr(t), _ptr(n), float(sigma), C.c_size_t(t.numel()), _stream()))
+    return t
+
+
+def _params_c(args: "PipelineCall", vae, keep: list) -> "PipelineParamsC":
+    """PipelineCall -> ltx_pipeline_params (deterministic scheduler; the buffers it points at are appended to `keep`)"""
+    if args.stochastic_sampling:
+        raise LtxError("the multi-scale call runs the deterministic scheduler")
+    p = PipelineParamsC()
+    lib.ltx_pipeline_params_default(C.byref(p))
+    p.height, p.width, p.num_frames, p.frame_rate = args.height, args.width, args.num_frames, args.frame_rate
+    p.num_inference_steps = args.num_inference_steps
+    if args.sigmas is not None:
+        s = _floats(args.sigmas); keep.append(s)
+        p.sigmas = C.cast(s, C.POINTER(C.c_float))
+    p.guidance_scale, p.guidance_rescale, p.stg_scale = args.guidance_scale, args.guidance_rescale, args.stg_scale
+    if args.skip_block_list is not None:
+        sb = (C.c_int * max(len(args.skip_block_list), 1))(*args.skip_block_list); keep.append(sb)
+        p.skip_block_list = C.cast(sb, C.POINTER(C.c_int))
+        p.n_skip_blocks = len(args.skip_block_list)
+    p.decode_timestep, p.decode_noise_scale = args.decode_timestep, args.decode_noise_scale
+    p.output_latent, p.postprocess = int(args.output_latent), (2 if args.output_rgb8 else int(args.postprocess))
+    p.shift_terminal = args.shift_terminal if args.shift_terminal is not None else 0.0
+    p.use_shift_terminal = int(args.shift_terminal is not None)
+    tl = vae._tiling() if vae is not None else None
+    if tl is not None:
+        keep.append(tl)
+        p.tiling = C.pointer(tl)
+    return p
+
+
+def pipeline_first_sigma(args: "PipelineCall", S: int) -> float:
+    """the first sigma LtxPipeline.call(args) runs at S latent tokens (ltx_pipeline_first_sigma)"""
+    keep = []
+    p = _params_c(args, None, keep)
+    out = C.c_float(0.0)
+    _check(lib.ltx_pipeline_first_sigma(C.byref(p), int(S), C.byref(out)))
+    return out.value
+
+
+class LtxMultiScalePipeline:
+    """first pass -> latent upsampler -> AdaIN -> re-noise -> second pass (ltx_pipeline_call_multiscale)"""
+
+    def __init__(self, transformer: LtxVideoTransformer3DModel, vae: AutoencoderKLLtxVideo, upsampler: LatentUpsampler):
+        self.transformer, self.vae, self.upsampler = transformer, vae, upsampler
+        self.last_timing_ms = (0.0,) * 9
+
+    def call(self, first: PipelineCall, second: PipelineCall, latents_lo: torch.Tensor, noise_hi: torch.Tensor,
+             prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
+             negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
+             decode_noise: Optional[torch.Tensor] = None, adain_factor: float = 1.0, interrupt=None, on_step=None):
+        """Returns (first-pass latents [B,S,C], second-pass latents [B,4S,C], video or None).  interrupt / on_step as LtxPipeline.call;
+        both passes see them."""
+        lo = _dev(latents_lo, torch.float32).clone()
+        nh = _dev(noise_hi, torch.float32)
+        pe = _dev(prompt_embeds, torch.float32)
+        pm = _dev(prompt_attention_mask, torch.float32)
+        ne = _dev(negative_prompt_embeds, torch.float32) if negative_prompt_embeds is not None else None
+        nm = _dev(negative_prompt_attention_mask, torch.float32) if negative_prompt_attention_mask is not None else None
+        dn = _dev(decode_noise, torch.float32) if decode_noise is not None else None
+        if pe.dim() != 3 or lo.dim() != 3:
+            raise LtxError("latents must be [B, F*H*W, in_channels] and prompt_embeds [B, K, caption_channels]")
+        B, K = pe.shape[0], pe.shape[1]
+        tr, sr = self.vae.config.temporal_compression_ratio, self.vae.config.spatial_compression_ratio
+        F, H, W = (first.num_frames - 1) // tr + 1, first.height // sr, first.width // sr
+        Cin = self.transformer.config.in_channels
+        S = F * H * W
+        # the C entry takes raw pointers: every tensor is checked against the geometry first
+        _expect("latents_lo", lo, (B, S, Cin))
+        _expect("noise_hi", nh, (B, 4 * S, Cin))
+        _expect("prompt_embeds", pe, (B, K, self.transformer.config.caption_channels))
+        _expect("prompt_attention_mask", pm, (B, K))
+        if ne is not None: _expect("negative_prompt_embeds", ne, (B, K, self.transformer.config.caption_channels))
+        if nm is not None: _expect("negative_prompt_attention_mask", nm, (B, K))
+        if dn is not None: _expect("decode_noise", dn, (B, Cin, F, 2 * H, 2 * W))
+        keep = []
+        p1, p2 = _params_c(first, self.vae, keep), _params_c(second, self.vae, keep)
+        hook_exc = []
+        for p in (p1, p2):
+            if interrupt is not None:
+                p.interrupt = C.pointer(interrupt)
+        if on_step is not None:
+            def _hook(_user, step, num_steps, timestep):
+                try:
+                    return 1 if on_step(step, num_steps, timestep) else 0
+                except BaseException as exc:                  # never unwind through the C frame
+                    hook_exc.append(exc)
+                    return 1
+            cb = StepFn(_hook); keep.append(cb)
+            p1.on_step = C.cast(cb, C.c_void_p)
+            p2.on_step = C.cast(cb, C.c_void_p)
+        hi = torch.empty(B, 4 * S, Cin, dtype=torch.float32, device=lo.device)
+        video = None
+        if not second.output_latent:
+            if second.output_rgb8:
+                video = torch.empty(B, (F - 1) * tr + 1, 2 * H * sr, 2 * W * sr, 3, dtype=torch.uint8, device=lo.device)
+            else:
+                video = torch.empty(B, 3, (F - 1) * tr + 1, 2 * H * sr, 2 * W * sr, dtype=torch.float32, device=lo.device)
+        _check(lib.ltx_pipeline_call_multiscale(self.transformer._h, self.vae._h, self.upsampler._h, C.byref(p1), C.byref(p2), float(adain_factor),
+                                                _ptr(lo), _ptr(nh), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                                _ptr(hi), _ptr(video), _stream()))
+        ms = (C.c_float * 9)()
+        _check(lib.ltx_pipeline_multiscale_last_timing(ms))
+        self.last_timing_ms = tuple(ms)
+        if hook_exc:
+            raise hook_exc[0]
+        return lo, hi, video
+
+
 # ------------------------------------------------------------------ version presets (include/ltxhip_presets.h; configs.rs:50-283)
 class PresetC(C.Structure):
     _fields_ = [("version", C.c_char_p), ("guidance_scale", C.c_float), ("num_inference_steps", C.c_int), ("stg_scale", C.c_float),
@@ -1756,6 +1968,21 @@ class ops:
         out = (C.c_int64 * len(ops.DIT_PLAN_FIELDS))()
         _check(lib.ltx_op_dit_plan(heads, head_dim, _dt(dtype), _dt(io_dtype), B, S, K, G, int(bool(skip_mask)), out))
         return {k: (int(v) if i < 6 or k == "ff2_parts" else bool(v)) for i, (k, v) in enumerate(zip(ops.DIT_PLAN_FIELDS, out))}
+
+    @staticmethod
+    def groupnorm(x_cl, weight, bias, groups=32, eps=1e-5, resid=None, silu=False, guards=False):
+        """x_cl [B, F (+ 2 guard frames), H, W, C] channels-last; returns a new tensor (ltx_op_groupnorm)"""
+        x = _dev(x_cl)
+        B, Ft, H, W, Cn = x.shape
+        F = Ft - 2 if guards else Ft
+        y = torch.empty_like(x)
+        w, b = _dev(weight, x.dtype), _dev(bias, x.dtype)
+        r = _dev(resid, x.dtype) if resid is not None else None
+        if r is not None:
+            _expect("resid", r, x.shape)
+        _check(lib.ltx_op_groupnorm(_ptr(x), _ptr(y), _ptr(r), _ptr(w), _ptr(b), B, F, H, W, Cn, groups, float(eps),
+                                    (LTX_GN_SILU if silu else 0) | (LTX_GN_GUARDS if guards else 0), _dt(x.dtype), _stream()))
+        return y
 
     @staticmethod
     def blend(a, b, dim, blend_extent):

@@ -697,3 +697,55 @@ impl HipVae {
         encoder.encode_moments(video, if tiled { Some(&tl) } else { None }, use_framewise_encoding)
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Latent upsampler (include/ltxhip_upsampler.h): the step between the two passes of the multi-scale recipe
+// ------------------------------------------------------------------------------------------------------------------
+
+/// The latent upsampler (Conv3d + GroupNorm network, spatial x2 in latent space); no counterpart in the reference.
+pub struct HipLatentUpsampler {
+    h: *mut sys::ltx_upsampler,
+    ccfg: sys::ltx_upsampler_config,
+    device: c_int,
+}
+
+impl HipLatentUpsampler {
+    pub fn from_file(cfg: &sys::ltx_upsampler_config, path: &Path, dtype: DType, device: usize) -> Result<Self> {
+        let cpath = CString::new(path.to_string_lossy().as_bytes()).map_err(candle_core::Error::wrap)?;
+        let mut h: *mut sys::ltx_upsampler = ptr::null_mut();
+        check(unsafe { sys::ltx_upsampler_create_from_file(cfg, cpath.as_ptr(), model_dtype(dtype)?, device as c_int, &mut h) })?;
+        Ok(Self { h, ccfg: *cfg, device: device as c_int })
+    }
+
+    /// packed normalised tokens [B, F*H*W, C] f32 -> [B, F*2H*2W, C] f32 with `vae`'s latent statistics (ltx_latent_upsample_tokens)
+    pub fn upsample_tokens(&self, vae: &HipVae, tokens: &Tensor, f: usize, h: usize, w: usize) -> Result<Tensor> {
+        let (b, s, c) = tokens.dims3()?;
+        if s != f * h * w || c != self.ccfg.in_channels as usize {
+            bail!("ltxhip: tokens must be [B, F*H*W, in_channels]");
+        }
+        let x = host_f32(tokens)?;
+        let mut xin = DeviceBuf::new(self.device);
+        let mut out_d = DeviceBuf::new(self.device);
+        let x_d = xin.upload(&x)?;
+        let n = b * 4 * s * c;
+        let o_d = out_d.ensure(n * 4)?;
+        check(unsafe {
+            sys::ltx_latent_upsample_tokens(self.h, vae.h as *const sys::ltx_vae, x_d as *const f32, b as c_int, f as c_int, h as c_int, w as c_int,
+                                            o_d as *mut f32, ptr::null_mut())
+        })?;
+        let mut out = vec![0f32; n];
+        check(unsafe { sys::ltx_memcpy_d2h(out.as_mut_ptr() as *mut c_void, o_d as *const c_void, n * 4, ptr::null_mut()) })?;
+        check(unsafe { sys::ltx_stream_synchronize(ptr::null_mut()) })?;
+        Tensor::from_vec(out, (b, 4 * s, c), &Device::Cpu)
+    }
+
+    pub fn raw(&self) -> *mut sys::ltx_upsampler {
+        self.h
+    }
+}
+
+impl Drop for HipLatentUpsampler {
+    fn drop(&mut self) {
+        unsafe { sys::ltx_upsampler_destroy(self.h) }
+    }
+}

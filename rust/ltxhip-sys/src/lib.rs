@@ -307,3 +307,51 @@ extern "C" {
     pub fn ltx_op_lora_merge(w0: *const c_void, out: *mut c_void, n_rows: i64, k: c_int, n: c_int, a: *const *const c_void, b: *const *const c_void,
                              r: *const c_int, coef: *const c_float, dtype: c_int, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_upsampler.h: the latent upsampler and the two-pass (multi-scale) pipeline call ----
+
+/// Opaque latent upsampler handle (`ltx_upsampler`).
+#[repr(C)]
+pub struct ltx_upsampler {
+    _private: [u8; 0],
+}
+
+/// `ltx_upsampler_config`: widths and block count of the upsampler network.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_upsampler_config {
+    pub in_channels: c_int,
+    pub mid_channels: c_int,
+    pub num_blocks_per_stage: c_int,
+}
+
+pub const UPSAMPLER_LAYOUT_LTX_UPSAMPLER_CONFIG: (usize, usize) = (12, 4);
+const _: () = assert!(size_of::<ltx_upsampler_config>() == UPSAMPLER_LAYOUT_LTX_UPSAMPLER_CONFIG.0 && align_of::<ltx_upsampler_config>() == UPSAMPLER_LAYOUT_LTX_UPSAMPLER_CONFIG.1);
+
+pub const LTX_GN_SILU: c_int = 1;
+pub const LTX_GN_GUARDS: c_int = 2;
+
+extern "C" {
+    pub fn ltx_upsampler_config_default(cfg: *mut ltx_upsampler_config);
+    pub fn ltx_upsampler_create(cfg: *const ltx_upsampler_config, weights: *const ltx_weight, n_weights: usize, model_dtype: c_int, device: c_int,
+                                out: *mut *mut ltx_upsampler) -> c_int;
+    pub fn ltx_upsampler_create_from_file(cfg: *const ltx_upsampler_config, path: *const c_char, model_dtype: c_int, device: c_int, out: *mut *mut ltx_upsampler) -> c_int;
+    pub fn ltx_upsampler_destroy(up: *mut ltx_upsampler);
+    pub fn ltx_upsampler_get_config(up: *const ltx_upsampler, out: *mut ltx_upsampler_config) -> c_int;
+    pub fn ltx_upsampler_forward(up: *mut ltx_upsampler, latents: *const c_void, io_dtype: c_int, b: c_int, f: c_int, h: c_int, w: c_int, out: *mut c_void,
+                                 stream: ltx_stream) -> c_int;
+    pub fn ltx_latent_upsample_tokens(up: *mut ltx_upsampler, vae: *const ltx_vae, tokens_lo: *const c_float, b: c_int, f: c_int, h: c_int, w: c_int,
+                                      tokens_hi: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_latent_adain(tokens: *mut c_float, ref_tokens: *const c_float, b: c_int, s: c_int, s_ref: c_int, c: c_int, factor: c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_latent_renoise(tokens: *mut c_float, noise: *const c_float, sigma: c_float, n: usize, stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_first_sigma(p: *const ltx_pipeline_params, s: c_int, sigma0: *mut c_float) -> c_int;
+    pub fn ltx_upsampler_warmup(up: *mut ltx_upsampler, b: c_int, f: c_int, h: c_int, w: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_call_multiscale(dit: *mut ltx_dit, vae: *mut ltx_vae, up: *mut ltx_upsampler, p_first: *const ltx_pipeline_params,
+                                        p_second: *const ltx_pipeline_params, adain_factor: c_float, latents_lo: *mut c_float, noise_hi: *const c_float,
+                                        prompt_embeds: *const c_float, prompt_mask: *const c_float, neg_embeds: *const c_float, neg_mask: *const c_float,
+                                        decode_noise: *const c_float, b: c_int, k: c_int, latents_hi_out: *mut c_float, out_video: *mut c_float,
+                                        stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_multiscale_last_timing(ms: *mut c_float) -> c_int;
+    pub fn ltx_op_groupnorm(x: *const c_void, y: *mut c_void, resid: *const c_void, weight: *const c_void, bias: *const c_void, b: c_int, f: c_int, h: c_int,
+                            w: c_int, c: c_int, groups: c_int, eps: c_float, flags: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
+}
