@@ -1,5 +1,5 @@
 // Kernel-level C entry points (include/ltxhip_ops.h) — thin argument marshalling only.
-#include "model_util.h"
+#include "conv3d.h"
 #include "../../include/ltxhip_ops.h"
 
 static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
@@ -261,41 +261,24 @@ extern "C" int ltx_op_attention_prescaled(const void* q, const void* k, const vo
 }
 
 namespace {
-struct ConvNorm { float eps; int act; const float* scale; const float* shift; int mod_stride; };      // GemmArgs::pn_* of ltx_op_conv3d_norm
-
+// (depth-to-space: ConvW's default nsub = 8, the (2, 2, 2) upsampler)
 int conv_common(const void* x, const void* w, const void* bias, int wdtype, void* y, const void* resid,
-                int B, int T, int H, int W, int Cin, int Cout, int causal, int dtype, int epi, int mode, int post, hipStream_t s, const ConvNorm* pn = nullptr) {
+                int B, int T, int H, int W, int Cin, int Cout, int causal, int dtype, int epi, int mode, int post, hipStream_t s, const PostNorm* pn = nullptr) {
     if (!x || !w || !bias || !y) LTX_FAIL(LTX_ERR_ARG, "conv: null tensor");
-    const int dt = dtc(dtype); const size_t esz = ltx_dt_size(dt);
-    const int Cf = Cout / 8;
-    GemmArgs g; g.A = x; g.C = y; g.resid = resid;
-    g.M = B * T * H * W; g.N = Cout; g.K = Cin; g.ldc = Cout; g.ldr = Cout;
-    g.conv = 1; g.B = B; g.T = T; g.H = H; g.Wd = W; g.Cin = Cin; g.ntaps = 27; g.kh = 3; g.kw = 3; g.pad_t = causal ? 2 : 1; g.post = post;
-    if (epi == EPI_D2S) { g.Cf = Cf; g.Cr = Cin / 8; g.To = 2 * T - 1; g.Ho = 2 * H; g.Wo = 2 * W; }
+    const int dt = dtc(dtype), pad_t = causal ? 2 : 1;
+    const Dims d{B, T, H, W};
+    ConvW cw; cw.cin = Cin; cw.cout = Cout;
     if (pn) {
-        g.pn_on = 1; g.pn_eps = pn->eps; g.pn_act = pn->act; g.pn_mod_stride = pn->mod_stride; g.pn_scale = pn->scale; g.pn_shift = pn->shift;
         // a fused call that the dispatch does not serve is refused before anything is allocated or packed: the route and the
         // refusal that ltx_launch_gemm repeats below (the packed weights and bias are hipMalloc'ed: aligned like w and bias)
         if (B < 1 || T < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) LTX_FAIL(LTX_ERR_ARG, "conv: empty problem");
-        g.W = w; g.bias = bias;
+        ConvW raw = cw; raw.w = const_cast<void*>(w); raw.b = const_cast<void*>(bias);
+        GemmArgs g = conv_args(raw, d, pad_t, epi, pn); g.A = x; g.C = y;
         GemmRoute r;
         LTX_TRY(ltx_gemm_route(g, dt, epi, nullptr, false, &r));
         if (const char* why = ltx_gemm_route_refusal(g, r)) LTX_FAIL(LTX_ERR_ARG, why);
     }
-    void *pw = nullptr, *pb = nullptr;
-    HIP_TRY(hipMalloc(&pw, (size_t)Cout * Cin * 27 * esz));
-    if (hipMalloc(&pb, (size_t)Cout * esz + 16) != hipSuccess) { (void)hipFree(pw); LTX_FAIL(LTX_ERR_HIP, "hipMalloc"); }
-    int rc = ltx_pack_conv(w, dtc(wdtype), pw, dt, Cout, Cin, 27, mode, Cf, s);
-    if (rc == LTX_OK) rc = ltx_pack_conv(bias, dtc(wdtype), pb, dt, Cout, 1, 1, mode, Cf, s);
-    if (rc == LTX_OK) {
-        g.W = pw; g.bias = pb;
-        rc = ltx_launch_gemm(g, dt, epi, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(pw); (void)hipFree(pb);
-    if (rc != LTX_OK) return rc;
-    if (e != hipSuccess) { ltx_set_error(hipGetErrorString(e)); return LTX_ERR_HIP; }
-    return LTX_OK;
+    return conv3d_unpacked(dt, pad_t, cw, w, bias, dtc(wdtype), mode, x, y, d, epi, resid, post, s, pn);
 }
 }  // namespace
 
@@ -309,7 +292,7 @@ extern "C" int ltx_op_conv3d_norm(const void* x, const void* w, const void* bias
     if (scale && mod_stride < Cout) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_norm: mod_stride is the row stride of scale / shift, at least Cout");
     if (act != 0 && act != 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_norm: act must be 0 (none) or 1 (SiLU)");
     if (!(eps >= 0.f)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_norm: eps must not be negative");
-    const ConvNorm pn{eps, act, scale, shift, scale ? mod_stride : 0};
+    PostNorm pn; pn.on = 1; pn.eps = eps; pn.act = act; pn.scale = scale; pn.shift = shift; pn.mod_stride = scale ? mod_stride : 0;
     return conv_common(x, w, bias, wdtype, y, nullptr, B, T, H, W, Cin, Cout, causal, dtype, EPI_BIAS, LTX_PERM_NONE, 0, (hipStream_t)stream, &pn);
 }
 extern "C" int ltx_op_upsample3d(const void* x, const void* w, const void* bias, int wdtype, void* y,

@@ -96,3 +96,5 @@ __device__ __forceinline__ void gelu_tanh4(float* v) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of 256 threads for a grid-stride loop over n elements: at least 1, at most cap
+static inline unsigned ltx_grid1d(int64_t n, int64_t cap) { const int64_t b = cdiv64(n, 256); return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b)); }

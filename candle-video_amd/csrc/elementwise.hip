@@ -314,7 +314,7 @@ __global__ void noise_inject_kernel(const T* __restrict__ x, T* __restrict__ y, 
     }
 }
 
-inline dim3 grid_for(int64_t n) { int64_t b = cdiv64(n, 256); if (b > 16384) b = 16384; if (b < 1) b = 1; return dim3((unsigned)b); }
+inline dim3 grid_for(int64_t n) { return dim3(ltx_grid1d(n, 16384)); }
 
 }  // namespace
 

@@ -175,7 +175,7 @@ __global__ void lora_pack_kernel(const void* src, int sdt, TD* dst, int64_t rows
     }
 }
 
-inline unsigned blocks_for(int64_t n) { int64_t b = cdiv64(n, 256); if (b > 16384) b = 16384; if (b < 1) b = 1; return (unsigned)b; }
+inline unsigned blocks_for(int64_t n) { return ltx_grid1d(n, 16384); }
 
 }  // namespace
 

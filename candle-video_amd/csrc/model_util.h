@@ -1,4 +1,5 @@
-// Host-side helpers shared by dit.hip / vae.hip / pipeline.hip: device buffers, weight lookup/upload.
+// Host-side helpers shared by dit.hip / vae.hip / upsampler.hip / pipeline.hip: device buffers, weight lookup/upload
+// (the model convs' own: conv3d.h).
 #pragma once
 #include <map>
 #include <memory>
@@ -94,10 +95,6 @@ struct DitPlan {
     bool fold_q = false;          // self-attention q leaves its norm multiplied by scale * log2(e)
 };
 DitPlan ltx_dit_plan(const ltx_dit_config& c, int dt, int iodt, int B, int S, int K, int G, bool skip_mask);
-
-// conv weight repack [O,I,kt,kh,kw] -> [tap][n'][I] with output-channel permutation (vae.hip)
-enum { LTX_PERM_NONE = 0, LTX_PERM_D2S = 1, LTX_PERM_UNPATCH = 2 };
-int ltx_pack_conv(const void* src_dev, int sdt, void* dst, int ddt, int O, int I, int ntaps, int mode, int Cf, hipStream_t s);
 
 // sigmas [N + 1] and truncated timesteps [N] of ltx_pipeline_call(p) at S latent tokens (host/pipeline.hip)
 int ltx_pipeline_schedule(const ltx_pipeline_params* p, int S, std::vector<float>* sig, std::vector<int64_t>* ts);

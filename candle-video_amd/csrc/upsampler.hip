@@ -18,7 +18,8 @@
 #include <algorithm>
 #include <cstring>
 #include <set>
-#include "model_util.h"
+#include "conv3d.h"
+#include "../host/weight_list.h"
 #include "../../include/ltxhip_upsampler.h"
 #include "../../include/ltxhip_weights.h"
 
@@ -44,7 +45,7 @@ __device__ __forceinline__ Stat stat_from_shifted(float cnt, float k, float s1, 
 __device__ __forceinline__ float ld_el(const void* p, int dt, int64_t i) { return dt == LTX_DT_BF16 ? (float)reinterpret_cast<const bf16_t*>(p)[i] : reinterpret_cast<const float*>(p)[i]; }
 __device__ __forceinline__ void st_el(void* p, int dt, int64_t i, float v) { if (dt == LTX_DT_BF16) reinterpret_cast<bf16_t*>(p)[i] = (bf16_t)v; else reinterpret_cast<float*>(p)[i] = v; }
 
-inline dim3 up_grid(int64_t n) { int64_t b = cdiv64(n, 256); if (b > 65536) b = 65536; if (b < 1) b = 1; return dim3((unsigned)b); }
+inline dim3 up_grid(int64_t n) { return dim3(ltx_grid1d(n, 65536)); }
 #define UP_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 // ------------------------------------------------------------------------------------------------ GroupNorm
@@ -383,9 +384,8 @@ __global__ void renoise_kernel(float* __restrict__ x, const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ the model
-struct UpConv { void* w = nullptr; void* b = nullptr; int cin = 0, cout = 0; };
 struct UpNorm { void* w = nullptr; void* b = nullptr; };
-struct UpRes { UpConv c1, c2; UpNorm n1, n2; };
+struct UpRes { ConvW c1, c2; UpNorm n1, n2; };
 
 std::vector<std::string> up_keys(const ltx_upsampler_config& c) {
     std::vector<std::string> k;
@@ -411,7 +411,7 @@ int check_cfg(const ltx_upsampler_config* c, const char* who) {
 struct ltx_upsampler {
     ltx_upsampler_config cfg{};
     int dtype = LTX_DT_BF16, device = 0;
-    UpConv initial_conv, up, final_conv;
+    ConvW initial_conv, up, final_conv;
     UpNorm initial_norm;
     std::vector<UpRes> res, post;
     std::vector<void*> owned;
@@ -446,36 +446,20 @@ const ltx_weight* find_shaped(const WeightMap& wm, const std::string& name, std:
     return w;
 }
 
-int sync_free(void* tmp, const char* what) {
-    const hipError_t e = hipDeviceSynchronize();
-    if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) { ltx_set_error(std::string(what) + ": " + hipGetErrorString(e)); return LTX_ERR_HIP; }
+int pack_conv2d(const void* src, int sdt, void* dst, int ddt, int cout, int cin) {      // conv_upload's pack step for upsampler.0
+    hipLaunchKernelGGL(pack_conv2d_kernel, up_grid((int64_t)27 * cout * cin), dim3(256), 0, 0, src, sdt, dst, ddt, cout, cin, cout / 4);
     return LTX_OK;
 }
 
 // conv2d != 0: upsampler.0, [cout, cin, 3, 3] -> the 27-tap form with the sub-pixel permutation (Cf = cout / 4)
-int load_conv(ltx_upsampler* u, const WeightMap& wm, const std::string& prefix, int cin, int cout, int conv2d, UpConv* c) {
-    const int dt = u->dtype; const size_t esz = ltx_dt_size(dt);
+int load_conv(ltx_upsampler* u, const WeightMap& wm, const std::string& prefix, int cin, int cout, int conv2d, ConvW* c) {
     int rc = LTX_OK;
     const ltx_weight* w = conv2d ? find_shaped(wm, prefix + ".weight", {cout, cin, 3, 3}, &rc) : find_shaped(wm, prefix + ".weight", {cout, cin, 3, 3, 3}, &rc);
     if (!w) return rc;
     const ltx_weight* b = find_shaped(wm, prefix + ".bias", {cout}, &rc);
     if (!b) return rc;
-    c->cin = cin; c->cout = cout;
-    HIP_TRY(hipMalloc(&c->w, (size_t)cout * cin * 27 * esz)); u->owned.push_back(c->w);
-    HIP_TRY(hipMalloc(&c->b, (size_t)cout * esz + 16)); u->owned.push_back(c->b);
-    const void* src = nullptr; void* tmp = nullptr;
-    LTX_TRY(ltx_stage_src(w, &src, &tmp));
-    const int wdt = w->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    if (conv2d) { hipLaunchKernelGGL(pack_conv2d_kernel, up_grid((int64_t)27 * cout * cin), dim3(256), 0, 0, src, wdt, c->w, dt, cout, cin, cout / 4); rc = LTX_OK; }
-    else rc = ltx_pack_conv(src, wdt, c->w, dt, cout, cin, 27, LTX_PERM_NONE, 0, 0);
-    const int rs = sync_free(tmp, "pack conv");
-    if (rc != LTX_OK) return rc;
-    if (rs != LTX_OK) return rs;
-    LTX_TRY(ltx_stage_src(b, &src, &tmp));
-    rc = ltx_pack_conv(src, b->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, c->b, dt, cout, 1, 1, conv2d ? LTX_PERM_D2S : LTX_PERM_NONE, conv2d ? cout / 4 : 0, 0);
-    const int rs2 = sync_free(tmp, "pack bias");
-    return rc != LTX_OK ? rc : rs2;
+    if (conv2d) return conv_upload(u->dtype, u->owned, w, b, cin, cout, LTX_PERM_D2S, cout / 4, c, pack_conv2d);
+    return conv_upload(u->dtype, u->owned, w, b, cin, cout, LTX_PERM_NONE, 0, c);
 }
 int load_norm(ltx_upsampler* u, const WeightMap& wm, const std::string& prefix, int ch, UpNorm* n) {
     int rc = LTX_OK;
@@ -503,39 +487,17 @@ int up_build(ltx_upsampler* u, const ltx_weight* weights, size_t n) {
     return LTX_OK;
 }
 
-struct GDims { int B, Ft, H, W; int64_t vox() const { return (int64_t)B * Ft * H * W; } };      // Ft = F + 2: the guard frames are frames to the conv
-
-// a 3x3x3 conv over the guarded tensor through the GEMM dispatch; samples never interact, so a batch whose operands pass the
-// conv kernels' 2 GiB of 32-bit byte offsets runs as sample groups that fit (as the VAE's convs do)
-int up_conv(ltx_upsampler* u, const UpConv& cw, const void* x, void* y, const GDims& d, hipStream_t s) {
-    const int dt = u->dtype; const size_t esz = ltx_dt_size(dt);
-    const int64_t per = (int64_t)d.Ft * d.H * d.W;
-    if (per > 2147483647LL) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler: more than 2^31 voxels per sample");
-    int nb = d.B;
-    const int64_t lim = (2147483648LL - (1 << 20)) / (per * std::max(cw.cin, cw.cout) * (int64_t)esz);
-    if (lim >= 1 && lim < nb) nb = (int)lim;
-    if ((int64_t)nb * per > 2147483647LL) nb = (int)(2147483647LL / per);
-    for (int b0 = 0; b0 < d.B; b0 += nb) {
-        const int bc = std::min(nb, d.B - b0);
-        GemmArgs g;
-        g.A = (const char*)x + (size_t)b0 * per * cw.cin * esz; g.W = cw.w; g.C = (char*)y + (size_t)b0 * per * cw.cout * esz; g.bias = cw.b;
-        g.M = (int)(bc * per); g.N = cw.cout; g.K = cw.cin; g.ldc = cw.cout; g.ldr = cw.cout;
-        g.conv = 1; g.B = bc; g.T = d.Ft; g.H = d.H; g.Wd = d.W; g.Cin = cw.cin;
-        g.ntaps = 27; g.kh = 3; g.kw = 3; g.pad_t = 1;
-        LTX_TRY(ltx_launch_gemm(g, dt, EPI_BIAS, s));
-    }
-    return LTX_OK;
-}
-int up_gn(ltx_upsampler* u, const UpNorm& n, const void* x, void* y, const void* resid, const GDims& d, int ch, hipStream_t s) {
+// (Dims::T of the calls below is F + 2: the guard frames are frames to the conv, which runs with pad_t = 1)
+int up_gn(ltx_upsampler* u, const UpNorm& n, const void* x, void* y, const void* resid, const Dims& d, int ch, hipStream_t s) {
     GnGeom q;
-    if (!gn_geom(d.B, d.Ft - 2, d.H, d.W, ch, kGroups, 1, &q)) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler: bad GroupNorm geometry");
+    if (!gn_geom(d.B, d.T - 2, d.H, d.W, ch, kGroups, 1, &q)) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler: bad GroupNorm geometry");
     return gn_launch(u->dtype, x, y, resid, n.w, n.b, q, kGnEps, 1, u->part.as<float>(), s);
 }
 // norm2 has no activation of its own: silu(norm2(h) + r) is the kernel's residual form
-int up_res(ltx_upsampler* u, const UpRes& r, const GDims& d, int ch, hipStream_t s) {
-    LTX_TRY(up_conv(u, r.c1, u->X.p, u->Cb.p, d, s));
+int up_res(ltx_upsampler* u, const UpRes& r, const Dims& d, int ch, hipStream_t s) {
+    LTX_TRY(conv3d(u->dtype, 1, r.c1, u->X.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s));
     LTX_TRY(up_gn(u, r.n1, u->Cb.p, u->Cb.p, nullptr, d, ch, s));
-    LTX_TRY(up_conv(u, r.c2, u->Cb.p, u->Nb.p, d, s));
+    LTX_TRY(conv3d(u->dtype, 1, r.c2, u->Cb.p, u->Nb.p, d, EPI_BIAS, nullptr, 0, s));
     return up_gn(u, r.n2, u->Nb.p, u->X.p, u->X.p, d, ch, s);
 }
 
@@ -557,20 +519,20 @@ int up_ensure(ltx_upsampler* u, int B, int F, int H, int W) {
 int up_forward_cl(ltx_upsampler* u, int B, int F, int H, int W, hipStream_t s) {
     const ltx_upsampler_config& c = u->cfg;
     const int mid = c.mid_channels;
-    GDims d{B, F + 2, H, W};
-    LTX_TRY(up_conv(u, u->initial_conv, u->zin.p, u->Cb.p, d, s));
+    Dims d{B, F + 2, H, W};
+    LTX_TRY(conv3d(u->dtype, 1, u->initial_conv, u->zin.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s));
     LTX_TRY(up_gn(u, u->initial_norm, u->Cb.p, u->X.p, nullptr, d, mid, s));
     for (auto& r : u->res) LTX_TRY(up_res(u, r, d, mid, s));
-    LTX_TRY(up_conv(u, u->up, u->X.p, u->Cb.p, d, s));
+    LTX_TRY(conv3d(u->dtype, 1, u->up, u->X.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s));
     {
         const int64_t n = d.vox() * 4 * (mid / (u->dtype == LTX_DT_BF16 ? 8 : 4));
-        if (u->dtype == LTX_DT_BF16) hipLaunchKernelGGL(pixel_shuffle_kernel<bf16_t>, up_grid(n), dim3(256), 0, s, (const bf16_t*)u->Cb.p, (bf16_t*)u->X.p, B, d.Ft, H, W, mid);
-        else hipLaunchKernelGGL(pixel_shuffle_kernel<float>, up_grid(n), dim3(256), 0, s, (const float*)u->Cb.p, (float*)u->X.p, B, d.Ft, H, W, mid);
+        if (u->dtype == LTX_DT_BF16) hipLaunchKernelGGL(pixel_shuffle_kernel<bf16_t>, up_grid(n), dim3(256), 0, s, (const bf16_t*)u->Cb.p, (bf16_t*)u->X.p, B, d.T, H, W, mid);
+        else hipLaunchKernelGGL(pixel_shuffle_kernel<float>, up_grid(n), dim3(256), 0, s, (const float*)u->Cb.p, (float*)u->X.p, B, d.T, H, W, mid);
         LTX_CHECK_LAUNCH();
     }
     d.H *= 2; d.W *= 2;
     for (auto& r : u->post) LTX_TRY(up_res(u, r, d, mid, s));
-    return up_conv(u, u->final_conv, u->X.p, u->Cb.p, d, s);
+    return conv3d(u->dtype, 1, u->final_conv, u->X.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s);
 }
 
 int check_shape(const char* who, const ltx_upsampler* u, int B, int F, int H, int W) {
@@ -613,26 +575,8 @@ extern "C" int ltx_upsampler_create_from_file(const ltx_upsampler_config* cfg, c
     const std::set<std::string> wanted(keys.begin(), keys.end());
     ltx_safetensors* st = nullptr;
     LTX_TRY(ltx_safetensors_open(path, &st));
-    const size_t count = ltx_safetensors_count(st);
-    std::vector<ltx_weight> ws;
-    ws.reserve(count);
-    int rc = LTX_OK;
-    for (size_t i = 0; i < count && rc == LTX_OK; ++i) {
-        const char *name = nullptr, *dtype = nullptr; int ndim = 0; const int64_t* shape = nullptr; const void* data = nullptr; size_t nbytes = 0;
-        rc = ltx_safetensors_tensor(st, i, &name, &dtype, &ndim, &shape, &data, &nbytes);
-        if (rc != LTX_OK) break;
-        if (!name || !wanted.count(name)) continue;      // not one of the model's tensors: ignored, as ltx_upsampler_create does
-        ltx_weight w; memset(&w, 0, sizeof(w));
-        if (!strcmp(dtype, "F32")) w.dtype = LTX_F32;
-        else if (!strcmp(dtype, "BF16")) w.dtype = LTX_BF16;
-        else { ltx_set_error(std::string("ltx_upsampler_create_from_file: tensor '") + name + "' is " + dtype + " (F32 and BF16 are read)"); rc = LTX_ERR_UNSUPPORTED; break; }
-        if (ndim > 5) { ltx_set_error(std::string("ltx_upsampler_create_from_file: tensor '") + name + "' has more than 5 dimensions"); rc = LTX_ERR_ARG; break; }
-        int64_t numel = 1;
-        for (int d = 0; d < ndim; ++d) { w.shape[d] = shape[d]; numel *= shape[d]; }
-        if ((size_t)numel * (w.dtype == LTX_BF16 ? 2 : 4) != nbytes) { ltx_set_error(std::string("ltx_upsampler_create_from_file: tensor '") + name + "': byte count does not match its shape"); rc = LTX_ERR_ARG; break; }
-        w.name = name; w.data = data; w.ndim = ndim; w.on_device = 0;      // (name and data point into the mapping, alive until close)
-        ws.push_back(w);
-    }
+    std::vector<ltx_weight> ws;      // not one of the model's tensors: ignored, as ltx_upsampler_create does
+    int rc = ltx_safetensors_weight_list(st, "ltx_upsampler_create_from_file", [&](const char* name) { return wanted.count(name) != 0; }, &ws);
     if (rc == LTX_OK) rc = ltx_upsampler_create(cfg, ws.data(), ws.size(), model_dtype, device, out);
     ltx_safetensors_close(st);
     return rc;

@@ -15,7 +15,7 @@
 // unpack_latents is free on this path.
 #include <cstring>
 #include <deque>
-#include "model_util.h"
+#include "conv3d.h"
 #include "options.h"
 #include "../../include/ltxhip_frames.h"
 #include "../../include/ltxhip_encoder.h"
@@ -23,13 +23,6 @@
 
 extern "C" int ltx_pcg32_randn(uint64_t seed, uint64_t inc, size_t n, float* out_host);   // host/pipeline.hip (utils/deterministic_rng.rs)
 
-struct ConvW {
-    void* w = nullptr;   // [27][N][Cin] model dtype (N possibly permuted)
-    void* b = nullptr;   // [N]
-    int cin = 0, cout = 0;
-    int st = 1, sh = 1, sw = 1, group = 1;   // EPI_S2D (encoder downsampler convs): strides and residual group size (vae.rs:516)
-    int nsub = 8;        // depth-to-space convs: output channels per final channel, 8 = (2, 2, 2), 4 = (1, 2, 2)
-};
 struct TimeEmbW { LinearW l1, l2; int dim = 0; };
 struct ResnetW { ConvW c1, c2; void* sst = nullptr; void *pcs1 = nullptr, *pcs2 = nullptr; };   // pcs: per_channel_scale{1,2} [C] where the block injects noise (vae.rs:676-689)
 struct UpBlockW { ConvW up; TimeEmbW te; std::vector<ResnetW> res; int ch = 0, cin = 0; bool residual = true, temporal = true; };
@@ -70,22 +63,6 @@ struct ltx_vae {
 
 namespace {
 
-enum { PERM_NONE = LTX_PERM_NONE, PERM_D2S = LTX_PERM_D2S, PERM_UNPATCH = LTX_PERM_UNPATCH };
-
-// dst[tap][n'][i] = src[o][i][tap] ; bias'[n'] = bias[o]
-__global__ void pack_conv_kernel(const void* src, int sdt, void* dst, int ddt, int O, int I, int ntaps, int mode, int Cf, int nsub) {
-    const int64_t n = (int64_t)O * I * ntaps;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
-        int i = (int)(idx % I); int64_t r = idx / I; int np = (int)(r % O); int tap = (int)(r / O);
-        int o = np;
-        if (mode == PERM_D2S) { int s = np / Cf, c = np - s * Cf; o = c * nsub + s; }                 // n' = s*Cf + c' (nsub = 8: (2,2,2), 4: (1,2,2))
-        else if (mode == PERM_UNPATCH) { int c = np >> 4, oh = (np >> 2) & 3, ow = np & 3; o = (c * 4 + ow) * 4 + oh; }  // n' = (c*4+oh)*4+ow
-        float v = sdt == LTX_DT_BF16 ? (float)reinterpret_cast<const bf16_t*>(src)[((int64_t)o * I + i) * ntaps + tap]
-                                     : reinterpret_cast<const float*>(src)[((int64_t)o * I + i) * ntaps + tap];
-        if (ddt == LTX_DT_BF16) reinterpret_cast<bf16_t*>(dst)[idx] = (bf16_t)v; else reinterpret_cast<float*>(dst)[idx] = v;
-    }
-}
-
 // crop a [t0:t1, h0:h1, w0:w1] window of a channels-last tensor (elements of esz bytes)
 __global__ void cl_window_kernel(const unsigned char* src, unsigned char* dst, int esz, int B, int T, int H, int W, int C,
                                  int t0, int t1, int h0, int h1, int w0, int w1) {
@@ -99,44 +76,32 @@ __global__ void cl_window_kernel(const unsigned char* src, unsigned char* dst, i
     }
 }
 
-}  // namespace
-int ltx_pack_conv(const void* src_dev, int sdt, void* dst, int ddt, int O, int I, int ntaps, int mode, int Cf, hipStream_t s) {
-    const int nsub = (mode == PERM_D2S && Cf > 0) ? O / Cf : 8;
-    int64_t n = (int64_t)O * I * ntaps; int64_t blocks = cdiv64(n, 256); if (blocks > 16384) blocks = 16384; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src_dev, sdt, dst, ddt, O, I, ntaps, mode, Cf, nsub);
-    LTX_CHECK_LAUNCH();
-    return LTX_OK;
-}
-namespace {
+// the model's tensors under their bare names: "<prefix>xxx" and "xxx" are both accepted
+struct BareNames {
+    std::vector<std::string> names; std::vector<ltx_weight> w;
+    BareNames(const ltx_weight* weights, size_t n, const std::string& prefix) : w(weights, weights + n) {
+        names.reserve(n);
+        for (size_t i = 0; i < n; ++i) {
+            const std::string nm = w[i].name ? w[i].name : "";
+            names.push_back(nm.rfind(prefix, 0) == 0 ? nm.substr(prefix.size()) : nm);
+            w[i].name = names[i].c_str();
+        }
+    }
+};
+
 int load_conv(int dt, std::vector<void*>& owned, const WeightMap& wm, const std::string& prefix, int cin, int cout, int mode, int Cf, ConvW* c) {
-    const size_t esz = ltx_dt_size(dt);
-    c->cin = cin; c->cout = cout;
-    const int nsub = (mode == PERM_D2S && Cf > 0) ? cout / Cf : 8;
-    c->nsub = nsub;
     const ltx_weight* w = wm.find(prefix + ".conv.weight");
     const ltx_weight* b = wm.find(prefix + ".conv.bias");
     if (!w) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight '" + prefix + ".conv.weight'");
     if (!b) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight '" + prefix + ".conv.bias'");
     if (ltx_numel(w) != (int64_t)cout * cin * 27) LTX_FAIL(LTX_ERR_ARG, "weight '" + prefix + ".conv.weight': wrong size");
     if (ltx_numel(b) != cout) LTX_FAIL(LTX_ERR_ARG, "weight '" + prefix + ".conv.bias': wrong size");
-    HIP_TRY(hipMalloc(&c->w, (size_t)cout * cin * 27 * esz)); owned.push_back(c->w);
-    HIP_TRY(hipMalloc(&c->b, (size_t)cout * esz + 16)); owned.push_back(c->b);
-    const void* src = nullptr; void* tmp = nullptr;
-    LTX_TRY(ltx_stage_src(w, &src, &tmp));
-    int64_t n = (int64_t)cout * cin * 27; int64_t blocks = cdiv64(n, 256); if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)blocks), dim3(256), 0, 0, src, w->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32,
-                       c->w, dt, cout, cin, 27, mode, Cf, nsub);
-    hipError_t e = hipDeviceSynchronize(); if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) { ltx_set_error(std::string("pack conv: ") + hipGetErrorString(e)); return LTX_ERR_HIP; }
-    LTX_TRY(ltx_stage_src(b, &src, &tmp));
-    hipLaunchKernelGGL(pack_conv_kernel, dim3((unsigned)cdiv(cout, 256)), dim3(256), 0, 0, src, b->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32,
-                       c->b, dt, cout, 1, 1, mode, Cf, nsub);
-    e = hipDeviceSynchronize(); if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) { ltx_set_error(std::string("pack bias: ") + hipGetErrorString(e)); return LTX_ERR_HIP; }
-    return LTX_OK;
+    return conv_upload(dt, owned, w, b, cin, cout, mode, Cf, c);
 }
-int load_conv(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int cin, int cout, int mode, int Cf, ConvW* c) {
-    return load_conv(v->dtype, v->owned, wm, prefix, cin, cout, mode, Cf, c);
+
+int load_resnet_convs(int dt, std::vector<void*>& owned, const WeightMap& wm, const std::string& prefix, int ch, ResnetW* r) {
+    LTX_TRY(load_conv(dt, owned, wm, prefix + ".conv1", ch, ch, LTX_PERM_NONE, 0, &r->c1));
+    return load_conv(dt, owned, wm, prefix + ".conv2", ch, ch, LTX_PERM_NONE, 0, &r->c2);
 }
 
 int load_temb(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int dim, TimeEmbW* t) {
@@ -149,8 +114,7 @@ int load_temb(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int di
 }
 
 int load_resnet(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int ch, bool inject, ResnetW* r) {
-    LTX_TRY(load_conv(v, wm, prefix + ".conv1", ch, ch, PERM_NONE, 0, &r->c1));
-    LTX_TRY(load_conv(v, wm, prefix + ".conv2", ch, ch, PERM_NONE, 0, &r->c2));
+    LTX_TRY(load_resnet_convs(v->dtype, v->owned, wm, prefix, ch, r));
     if (inject) {
         // vae.rs:676-689: vb.pp("per_channel_scaleN").get((C, 1, 1), "weight").ok() - a scale that is absent from the checkpoint
         // under exactly that name is no injection, not an error
@@ -172,23 +136,15 @@ int load_resnet(ltx_vae* v, const WeightMap& wm, const std::string& prefix, int 
 int build(ltx_vae* v, const ltx_weight* weights, size_t n_weights) {
     const ltx_vae_config& c = v->cfg;
     WeightMap wm0(weights, n_weights);
-    // accept both "decoder.xxx" and bare "xxx" names
-    std::vector<ltx_weight> renamed; std::vector<std::string> names;
-    names.reserve(n_weights); renamed.reserve(n_weights);
-    for (size_t i = 0; i < n_weights; ++i) {
-        std::string nm = weights[i].name ? weights[i].name : "";
-        if (nm.rfind("decoder.", 0) == 0) nm = nm.substr(8);
-        names.push_back(nm);
-    }
-    for (size_t i = 0; i < n_weights; ++i) { ltx_weight w = weights[i]; w.name = names[i].c_str(); renamed.push_back(w); }
-    WeightMap wm(renamed.data(), renamed.size());
+    const BareNames bare(weights, n_weights, "decoder.");
+    WeightMap wm(bare.w.data(), bare.w.size());
 
     const int nb = c.n_blocks;
     std::vector<int> boc(nb), upf(nb), lpb(nb + 1);
     for (int i = 0; i < nb; ++i) { boc[i] = c.decoder_block_out_channels[nb - 1 - i]; upf[i] = c.decoder_upsample_factor[nb - 1 - i]; }
     for (int i = 0; i <= nb; ++i) lpb[i] = c.decoder_layers_per_block[nb - i];
     v->mid_ch = boc[0];
-    LTX_TRY(load_conv(v, wm, "conv_in", c.latent_channels, v->mid_ch, PERM_NONE, 0, &v->conv_in));
+    LTX_TRY(load_conv(v->dtype, v->owned, wm, "conv_in", c.latent_channels, v->mid_ch, LTX_PERM_NONE, 0, &v->conv_in));
     if (c.timestep_conditioning) LTX_TRY(load_temb(v, wm, "mid_block.time_embedder", 4 * v->mid_ch, &v->mid_te));
     v->mid.resize(lpb[0]);
     for (int i = 0; i < lpb[0]; ++i) LTX_TRY(load_resnet(v, wm, "mid_block.resnets." + std::to_string(i), v->mid_ch, c.decoder_inject_noise[nb] != 0, &v->mid[i]));   // inject list reversed: entry nb is the mid block (vae.rs:1514-1515, 1541)
@@ -204,7 +160,7 @@ int build(ltx_vae* v, const ltx_weight* weights, size_t n_weights) {
         u.temporal = c.decoder_spatiotemporal_scaling[nb - 1 - bi] != 0;   // reversed too (vae.rs:1509-1510); false: the (1, 2, 2) upsampler (:1225-1236)
         const int nsub = u.temporal ? 8 : 4;
         if ((u.ch * nsub) % u.cin != 0 || u.cin % nsub != 0) LTX_FAIL(LTX_ERR_UNSUPPORTED, "upsampler residual repeat must be integral");
-        LTX_TRY(load_conv(v, wm, p + ".upsamplers.0.conv", u.cin, u.ch * nsub, PERM_D2S, u.ch, &u.up));
+        LTX_TRY(load_conv(v->dtype, v->owned, wm, p + ".upsamplers.0.conv", u.cin, u.ch * nsub, LTX_PERM_D2S, u.ch, &u.up));
         if (c.timestep_conditioning) LTX_TRY(load_temb(v, wm, p + ".time_embedder", 4 * u.ch, &u.te));
         u.res.resize(lpb[bi + 1]);
         for (int i = 0; i < lpb[bi + 1]; ++i) LTX_TRY(load_resnet(v, wm, p + ".resnets." + std::to_string(i), u.ch, c.decoder_inject_noise[nb - 1 - bi] != 0, &u.res[i]));   // inj[bi + 1] of the reversed list (vae.rs:1561)
@@ -212,7 +168,7 @@ int build(ltx_vae* v, const ltx_weight* weights, size_t n_weights) {
     }
     v->last_ch = cur;
     const int nout = c.out_channels * c.patch_size * c.patch_size;
-    LTX_TRY(load_conv(v, wm, "conv_out", cur, nout, PERM_UNPATCH, 0, &v->conv_out));
+    LTX_TRY(load_conv(v->dtype, v->owned, wm, "conv_out", cur, nout, LTX_PERM_UNPATCH, 0, &v->conv_out));
     if (c.timestep_conditioning) {
         LTX_TRY(load_temb(v, wm, "time_embedder", 2 * cur, &v->out_te));
         LTX_TRY(ltx_load_tensor(wm, "scale_shift_table", 2 * (int64_t)cur, v->dtype, &v->sst_out)); v->owned.push_back(v->sst_out);
@@ -242,88 +198,6 @@ int build(ltx_vae* v, const ltx_weight* weights, size_t n_weights) {
         HIP_TRY(hipMemcpy(v->vtab, tab.data(), sizeof(float) * 128, hipMemcpyHostToDevice));
     }
     return LTX_OK;
-}
-
-struct Dims { int B, T, H, W; int64_t vox() const { return (int64_t)B * T * H * W; } };
-
-struct PostNorm { int on = 0; float eps = 0.f; int act = 0; int mod_stride = 0; const float* scale = nullptr; const float* shift = nullptr; };
-
-GemmArgs conv_args(int pad_t, const ConvW& cw, const Dims& d) {
-    GemmArgs g;
-    g.W = cw.w; g.bias = cw.b;
-    g.M = (int)d.vox(); g.N = cw.cout; g.K = cw.cin; g.ldc = cw.cout; g.ldr = cw.cout;
-    g.conv = 1; g.B = d.B; g.T = d.T; g.H = d.H; g.Wd = d.W; g.Cin = cw.cin;
-    g.ntaps = 27; g.kh = 3; g.kw = 3;
-    g.pad_t = pad_t;
-    return g;
-}
-GemmArgs conv_args(ltx_vae* v, const ConvW& cw, const Dims& d) { return conv_args(v->cfg.decoder_causal ? 2 : 1, cw, d); }
-
-// Samples per conv launch: the fast conv kernels address their operands with 32-bit byte offsets (< 2 GiB per operand).
-// Samples never interact in a conv, so a batch whose activations pass that limit (the batched leaf tiles of a tiled decode
-// at the last stages) runs as sample groups that fit; a single sample beyond the limit goes to the launcher as it is.
-int conv_chunk(int dtype, const ConvW& cw, const Dims& d) {
-    if (d.B <= 1) return d.B;
-    {   // the large-tile conv kernels address a window around each tile, not the tensor: whole batch in one launch where they apply
-        GemmArgs g; g.M = (int)std::min<int64_t>(d.vox(), 2147483647); g.N = cw.cout; g.K = cw.cin; g.conv = 1; g.B = d.B; g.T = d.T; g.H = d.H; g.Wd = d.W;
-        g.Cin = cw.cin; g.ntaps = 27; g.kh = 3; g.kw = 3;
-        if (d.vox() < 2147483647 && ltx_gemm_route_kind(g, dtype, EPI_BIAS) == LTX_ROUTE_PLAN) return d.B;
-    }
-    const int64_t per = (int64_t)d.T * d.H * d.W;
-    const int64_t lim = (2147483648LL - (1 << 20)) / (per * std::max(cw.cin, cw.cout) * (int64_t)ltx_dt_size(dtype));
-    return (lim >= 1 && lim < d.B) ? (int)lim : d.B;
-}
-int conv_chunk(ltx_vae* v, const ConvW& cw, const Dims& d) { return conv_chunk(v->dtype, cw, d); }
-
-// whether conv1 of a resnet can carry norm2 in its epilogue: bf16, the halo-staged kernel with BN == channels
-bool fuse_norm2(int dtype, int pad_t, const ConvW& cw, const Dims& d_all, int ch) {
-    Dims d = d_all; d.B = conv_chunk(dtype, cw, d_all);
-    const LtxOptions& o = ltx_opt();
-    if (!o.vae_fuse_norm || !o.gemm_wide_epi || (o.gemm_off & (LTX_FAM_HALO | LTX_FAM_BIG))) return false;
-    if (dtype != LTX_DT_BF16 || (ch != 128 && ch != 256) || cw.cout != ch) return false;
-    GemmArgs g = conv_args(pad_t, cw, d);
-    // the fused epilogue needs the whole channel row in one tile (BN == channels), i.e. a grid of M / 256 blocks: below about
-    // one round of the chip the unfused conv on a plan with more, smaller tiles + the stand-alone norm is faster (C1's
-    // 256-channel stage, 78 tiles: 168 us fused vs 108 + 13; decode 5.7 -> 5.45 ms, profiles/r5k_c1_vae_fused_norm_ab.jsonl)
-    if ((g.M + 255) / 256 < 192 && o.vae_fuse_norm < 2) return false;
-    g.pn_on = 1;                                            // ask the route: the fused call must land on the halo tile as wide as the output
-    GemmRoute r;
-    return ltx_gemm_route(g, dtype, EPI_BIAS, nullptr, false, &r) == LTX_OK && r.kind == LTX_ROUTE_PLAN && r.plan.fam == kPlanHalo;
-}
-bool fuse_norm2(ltx_vae* v, const ConvW& cw, const Dims& d_all, int ch) { return fuse_norm2(v->dtype, v->cfg.decoder_causal ? 2 : 1, cw, d_all, ch); }
-
-int conv3d(int dtype, int pad_t, const ConvW& cw, const void* x, void* y, const Dims& d, int epi, const void* resid, int post, hipStream_t s, const PostNorm* pn = nullptr) {
-    const size_t esz = ltx_dt_size(dtype);
-    const int64_t per = (int64_t)d.T * d.H * d.W;
-    const int nb = conv_chunk(dtype, cw, d);
-    size_t out_b, res_b = 0;                              // bytes per sample of the output / residual tensor
-    const int To = cw.nsub == 4 ? d.T : 2 * d.T - 1;      // frames a depth-to-space conv writes
-    if (epi == EPI_D2S) { out_b = (size_t)To * (2 * d.H) * (2 * d.W) * (cw.cout / cw.nsub) * esz; res_b = (size_t)per * cw.cin * esz; }
-    else if (epi == EPI_S2D) { out_b = (size_t)((d.T + cw.st - 1) / cw.st) * (d.H / cw.sh) * (d.W / cw.sw) * cw.cout * cw.st * cw.sh * cw.sw * esz; res_b = (size_t)per * cw.cin * esz; }
-    else if (epi == EPI_UNPATCH) out_b = (size_t)(cw.cout / 16) * d.T * (4 * d.H) * (4 * d.W) * sizeof(float);
-    else { out_b = (size_t)per * cw.cout * esz; res_b = out_b; }
-    for (int b0 = 0; b0 < d.B; b0 += nb) {
-        const int bc = std::min(nb, d.B - b0);
-        GemmArgs g;
-        if (pn && pn->on) {
-            g.pn_on = 1; g.pn_eps = pn->eps; g.pn_act = pn->act; g.pn_mod_stride = pn->mod_stride;
-            g.pn_scale = pn->scale ? pn->scale + (size_t)b0 * pn->mod_stride : nullptr; g.pn_shift = pn->shift ? pn->shift + (size_t)b0 * pn->mod_stride : nullptr;
-        }
-        g.A = (const char*)x + (size_t)b0 * per * cw.cin * esz; g.W = cw.w; g.C = (char*)y + (size_t)b0 * out_b; g.bias = cw.b;
-        g.resid = resid ? (const char*)resid + (size_t)b0 * res_b : nullptr;
-        g.M = (int)(bc * per); g.N = cw.cout; g.K = cw.cin; g.ldc = cw.cout; g.ldr = cw.cout;
-        g.conv = 1; g.B = bc; g.T = d.T; g.H = d.H; g.Wd = d.W; g.Cin = cw.cin;
-        g.ntaps = 27; g.kh = 3; g.kw = 3;
-        g.pad_t = pad_t;                                  // vae.rs:383-412
-        g.post = post;
-        if (epi == EPI_D2S) { g.Cf = cw.cout / cw.nsub; g.Cr = cw.cin / cw.nsub; g.To = To; g.Ho = 2 * d.H; g.Wo = 2 * d.W; g.d2s_sp = cw.nsub == 4; }
-        if (epi == EPI_S2D) { g.s2_st = cw.st; g.s2_sh = cw.sh; g.s2_sw = cw.sw; g.s2_group = cw.group; g.To = (d.T + cw.st - 1) / cw.st; g.Ho = d.H / cw.sh; g.Wo = d.W / cw.sw; }
-        LTX_TRY(ltx_launch_gemm(g, dtype, epi, s));
-    }
-    return LTX_OK;
-}
-int conv3d(ltx_vae* v, const ConvW& cw, const void* x, void* y, const Dims& d, int epi, const void* resid, int post, hipStream_t s, const PostNorm* pn = nullptr) {
-    return conv3d(v->dtype, v->cfg.decoder_causal ? 2 : 1, cw, x, y, d, epi, resid, post, s, pn);
 }
 
 // CombinedTimestepEmbedder (vae.rs:236-265) + "+ scale_shift_table" -> f32 [B][rows][C]; *out points at the (cached) result
@@ -360,40 +234,51 @@ int inject_noise(ltx_vae* v, const void* x, void* y, const void* scale, const vo
     return ltx_launch_noise_inject(x, y, v->noise_plane.as<float>(), scale, shortcut, d.vox(), ch, hw, v->dtype, s);
 }
 
-int resnet(ltx_vae* v, const ResnetW& r, const TimeEmbW& te, int ch, const Dims& d, const TimeVec* tv, hipStream_t s) {
-    const int dt = v->dtype;
-    const float* mod = nullptr;
-    if (tv && r.sst) LTX_TRY(time_mod(v, te, r.sst, *tv, &mod, s));
-    RowNormArgs rn; rn.x = v->X.p; rn.y = v->N.p; rn.rows = d.vox(); rn.D = ch; rn.ldx = ch; rn.ldy = ch;
-    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W; rn.mod_stride = 4 * ch;
-    if (mod) { rn.shift = mod; rn.scale = mod + ch; }
-    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+// the per-voxel RMS norm + modulation + SiLU of the resnets and of norm_out; shift: f32 [B][mod_stride] rows, the scale ch after it (null: none)
+RowNormArgs norm_silu(const void* x, void* y, const Dims& d, int ch, int mod_stride, const float* shift) {
+    RowNormArgs rn; rn.x = x; rn.y = y; rn.rows = d.vox(); rn.D = ch; rn.ldx = ch; rn.ldy = ch;
+    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W; rn.mod_stride = mod_stride;
+    if (shift) { rn.shift = shift; rn.scale = shift + ch; }
+    return rn;
+}
+
+// LtxVideoResnetBlock3d without noise injection (vae.rs:755-821), in place on X with N and C as scratch.
+// mod: f32 [B][mod_stride] rows of shift1, scale1, shift2, scale2 (null: no modulation)
+int resnet_plain(int dt, int pad_t, const ResnetW& r, int ch, const Dims& d, const float* mod, int mod_stride, void* X, void* N, void* C, hipStream_t s) {
+    LTX_TRY(ltx_launch_rownorm(norm_silu(X, N, d, ch, mod_stride, mod), dt, s));
     // norm2 + modulation + SiLU inside conv1's epilogue where one conv tile spans all channels (128 / 256): no pass of
     // its own over the stage's largest tensor
-    if (!r.pcs1 && !r.pcs2 && fuse_norm2(v, r.c1, d, ch)) {
-        PostNorm pn; pn.on = 1; pn.eps = rn.eps; pn.act = 1; pn.mod_stride = 4 * ch;
+    if (fuse_norm2(dt, pad_t, r.c1, d, ch)) {
+        PostNorm pn; pn.on = 1; pn.eps = 1e-8f; pn.act = 1; pn.mod_stride = mod_stride;
         if (mod) { pn.shift = mod + 2 * ch; pn.scale = mod + 3 * ch; }
-        LTX_TRY(conv3d(v, r.c1, v->N.p, v->C.p, d, EPI_BIAS, nullptr, 0, s, &pn));
-        LTX_TRY(conv3d(v, r.c2, v->C.p, v->X.p, d, EPI_RESID, v->X.p, 0, s));   // X = conv2(..) + X, in place
-        return LTX_OK;
+        LTX_TRY(conv3d(dt, pad_t, r.c1, N, C, d, EPI_BIAS, nullptr, 0, s, &pn));
+        return conv3d(dt, pad_t, r.c2, C, X, d, EPI_RESID, X, 0, s);   // X = conv2(..) + X, in place
     }
-    LTX_TRY(conv3d(v, r.c1, v->N.p, v->C.p, d, EPI_BIAS, nullptr, 0, s));
+    LTX_TRY(conv3d(dt, pad_t, r.c1, N, C, d, EPI_BIAS, nullptr, 0, s));
+    LTX_TRY(ltx_launch_rownorm(norm_silu(C, N, d, ch, mod_stride, mod ? mod + 2 * ch : nullptr), dt, s));
+    return conv3d(dt, pad_t, r.c2, N, X, d, EPI_RESID, X, 0, s);       // X = conv2(..) + X, in place
+}
+
+int resnet(ltx_vae* v, const ResnetW& r, const TimeEmbW& te, int ch, const Dims& d, const TimeVec* tv, hipStream_t s) {
+    const int dt = v->dtype, pad_t = v->cfg.decoder_causal ? 2 : 1;
+    const float* mod = nullptr;
+    if (tv && r.sst) LTX_TRY(time_mod(v, te, r.sst, *tv, &mod, s));
+    if (!r.pcs1 && !r.pcs2) return resnet_plain(dt, pad_t, r, ch, d, mod, 4 * ch, v->X.p, v->N.p, v->C.p, s);
+    LTX_TRY(ltx_launch_rownorm(norm_silu(v->X.p, v->N.p, d, ch, 4 * ch, mod), dt, s));
+    LTX_TRY(conv3d(dt, pad_t, r.c1, v->N.p, v->C.p, d, EPI_BIAS, nullptr, 0, s));
     if (r.pcs1) LTX_TRY(inject_noise(v, v->C.p, v->C.p, r.pcs1, nullptr, d, ch, s));        // vae.rs:784
-    rn.x = v->C.p;
-    if (mod) { rn.shift = mod + 2 * ch; rn.scale = mod + 3 * ch; }
-    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+    LTX_TRY(ltx_launch_rownorm(norm_silu(v->C.p, v->N.p, d, ch, 4 * ch, mod ? mod + 2 * ch : nullptr), dt, s));
     if (r.pcs2) {                                                                           // vae.rs:807-819: h = conv2(h); h += noise * scale; h + x
-        LTX_TRY(conv3d(v, r.c2, v->N.p, v->C.p, d, EPI_BIAS, nullptr, 0, s));
+        LTX_TRY(conv3d(dt, pad_t, r.c2, v->N.p, v->C.p, d, EPI_BIAS, nullptr, 0, s));
         return inject_noise(v, v->C.p, v->X.p, r.pcs2, v->X.p, d, ch, s);
     }
-    LTX_TRY(conv3d(v, r.c2, v->N.p, v->X.p, d, EPI_RESID, v->X.p, 0, s));   // X = conv2(..) + X, in place
-    return LTX_OK;
+    return conv3d(dt, pad_t, r.c2, v->N.p, v->X.p, d, EPI_RESID, v->X.p, 0, s);             // X = conv2(..) + X, in place
 }
 
 // LtxVideoDecoder3d::forward on a channels-last latent `z` [B,F,H,W,Clat] (model dtype) -> f32 NCTHW
 int decoder_forward(ltx_vae* v, const void* z, int B, int F, int H, int W, const TimeVec* tv, int post, float* out, hipStream_t s) {
     const ltx_vae_config& c = v->cfg;
-    const int dt = v->dtype; const size_t esz = ltx_dt_size(dt);
+    const int dt = v->dtype, pad_t = c.decoder_causal ? 2 : 1; const size_t esz = ltx_dt_size(dt);
     // workspace sizing: the largest activation is the last stage
     Dims d{B, F, H, W};
     int64_t max_elems = d.vox() * v->mid_ch;
@@ -408,10 +293,10 @@ int decoder_forward(ltx_vae* v, const void* z, int B, int F, int H, int W, const
     LTX_TRY(v->te.ensure((size_t)B * maxdim * esz)); LTX_TRY(v->mod.ensure((size_t)B * maxdim * sizeof(float)));
     const TimeVec* tvc = (tv && c.timestep_conditioning) ? tv : nullptr;
 
-    LTX_TRY(conv3d(v, v->conv_in, z, v->X.p, d, EPI_BIAS, nullptr, 0, s));
+    LTX_TRY(conv3d(dt, pad_t, v->conv_in, z, v->X.p, d, EPI_BIAS, nullptr, 0, s));
     for (auto& r : v->mid) LTX_TRY(resnet(v, r, v->mid_te, v->mid_ch, d, tvc, s));
     for (auto& u : v->ups) {
-        LTX_TRY(conv3d(v, u.up, v->X.p, v->Y.p, d, EPI_D2S, u.residual ? v->X.p : nullptr, 0, s));   // vae.rs:1164-1168
+        LTX_TRY(conv3d(dt, pad_t, u.up, v->X.p, v->Y.p, d, EPI_D2S, u.residual ? v->X.p : nullptr, 0, s));   // vae.rs:1164-1168
         std::swap(v->X, v->Y);
         if (u.temporal) d.T = 2 * d.T - 1;
         d.H *= 2; d.W *= 2;
@@ -421,18 +306,13 @@ int decoder_forward(ltx_vae* v, const void* z, int B, int F, int H, int W, const
     const int ch = v->last_ch;
     const float* mod = nullptr;
     if (tvc && v->sst_out) LTX_TRY(time_mod(v, v->out_te, v->sst_out, *tvc, &mod, s));
-    RowNormArgs rn; rn.x = v->X.p; rn.y = v->N.p; rn.rows = d.vox(); rn.D = ch; rn.ldx = ch; rn.ldy = ch;
-    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W; rn.mod_stride = 2 * ch;
-    if (mod) { rn.shift = mod; rn.scale = mod + ch; }
-    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-    LTX_TRY(conv3d(v, v->conv_out, v->N.p, out, d, EPI_UNPATCH, nullptr, post, s));
-    return LTX_OK;
+    LTX_TRY(ltx_launch_rownorm(norm_silu(v->X.p, v->N.p, d, ch, 2 * ch, mod), dt, s));
+    return conv3d(dt, pad_t, v->conv_out, v->N.p, out, d, EPI_UNPATCH, nullptr, post, s);
 }
 
 int crop_cl(const void* src, void* dst, size_t esz, int B, int T, int H, int W, int C, int t0, int t1, int h0, int h1, int w0, int w1, hipStream_t s) {
     int64_t n = (int64_t)B * (t1 - t0) * (h1 - h0) * (w1 - w0) * C * (int64_t)esz;
-    int64_t blocks = cdiv64(n, 256); if (blocks > 16384) blocks = 16384; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(cl_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const unsigned char*)src, (unsigned char*)dst, (int)esz,
+    hipLaunchKernelGGL(cl_window_kernel, dim3(ltx_grid1d(n, 16384)), dim3(256), 0, s, (const unsigned char*)src, (unsigned char*)dst, (int)esz,
                        B, T, H, W, C, t0, t1, h0, h1, w0, w1);
     LTX_CHECK_LAUNCH();
     return LTX_OK;
@@ -782,7 +662,7 @@ extern "C" int ltx_vae_prepare_latents(ltx_vae* v, const float* tokens, const fl
 
 // =====================================================================================================================
 // encode side: LtxVideoEncoder3d (vae.rs:1316-1469) + posterior + tiled encodes.  Same layout as the decoder: activations
-// channels-last in the model dtype, every 3x3x3 conv through ltx_launch_gemm (the measured conv kernels, pad_t = 2).
+// channels-last in the model dtype, every 3x3x3 conv through conv3d.h's conv3d (the measured conv kernels, pad_t = 2).
 //   patchify            one gather kernel, coalesced on the read side: [B,3,F,H,W] -> [B,F,H/4,W/4,48]
 //   resnet              the decoder's, without modulation / noise / timestep (norm2 in conv1's epilogue where that form applies)
 //   downsampler         one conv whose epilogue (EPI_S2D, kernels.h: the mirror of EPI_D2S) scatters to the space-to-depth
@@ -885,34 +765,21 @@ __global__ void moments_tokens_kernel(const float* __restrict__ mom, const float
     }
 }
 
-inline dim3 enc_grid(int64_t n) { int64_t b = cdiv64(n, 256); if (b > 65536) b = 65536; if (b < 1) b = 1; return dim3((unsigned)b); }
+inline dim3 enc_grid(int64_t n) { return dim3(ltx_grid1d(n, 65536)); }
 
 void down_stride(int type, int* st, int* sh, int* sw) {      // DownsampleType::stride, vae.rs:487-496
     *st = type == LTX_DOWN_SPATIAL ? 1 : 2; *sh = type == LTX_DOWN_TEMPORAL ? 1 : 2; *sw = *sh;
 }
 
-int enc_load_resnet(ltx_vae_encoder* e, const WeightMap& wm, const std::string& prefix, int ch, ResnetW* r) {
-    LTX_TRY(load_conv(e->dtype, e->owned, wm, prefix + ".conv1", ch, ch, PERM_NONE, 0, &r->c1));
-    LTX_TRY(load_conv(e->dtype, e->owned, wm, prefix + ".conv2", ch, ch, PERM_NONE, 0, &r->c2));
-    return LTX_OK;
-}
-
 int enc_build(ltx_vae_encoder* e, const ltx_weight* weights, size_t n_weights) {
     const ltx_vae_encoder_config& c = e->cfg;
-    std::vector<ltx_weight> renamed; std::vector<std::string> names;
-    names.reserve(n_weights); renamed.reserve(n_weights);
-    for (size_t i = 0; i < n_weights; ++i) {
-        std::string nm = weights[i].name ? weights[i].name : "";
-        if (nm.rfind("encoder.", 0) == 0) nm = nm.substr(8);
-        names.push_back(nm);
-    }
-    for (size_t i = 0; i < n_weights; ++i) { ltx_weight w = weights[i]; w.name = names[i].c_str(); renamed.push_back(w); }
-    WeightMap wm(renamed.data(), renamed.size());
+    const BareNames bare(weights, n_weights, "encoder.");
+    WeightMap wm(bare.w.data(), bare.w.size());
     // vae.rs:1388-1394 loads norm_out.weight when the checkpoint has one (no released checkpoint does; else ones): refused, not ignored
     if (wm.find("norm_out.weight")) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder checkpoint carries 'norm_out.weight': a weighted norm_out is not implemented (the presets' RMS norm has no weight)");
     const int nb = c.n_blocks;
     e->cin_p = c.in_channels * c.patch_size * c.patch_size * c.patch_size_t;
-    LTX_TRY(load_conv(e->dtype, e->owned, wm, "conv_in", e->cin_p, c.block_out_channels[0], PERM_NONE, 0, &e->conv_in));
+    LTX_TRY(load_conv(e->dtype, e->owned, wm, "conv_in", e->cin_p, c.block_out_channels[0], LTX_PERM_NONE, 0, &e->conv_in));
     e->downs.resize(nb - 1);
     int cur = c.block_out_channels[0];
     for (int i = 0; i < nb - 1; ++i) {
@@ -920,7 +787,7 @@ int enc_build(ltx_vae_encoder* e, const ltx_weight* weights, size_t n_weights) {
         const std::string p = "down_blocks." + std::to_string(i);
         d.ch = cur; d.cout = c.block_out_channels[i + 1];
         d.res.resize(c.layers_per_block[i]);
-        for (int k = 0; k < c.layers_per_block[i]; ++k) LTX_TRY(enc_load_resnet(e, wm, p + ".resnets." + std::to_string(k), cur, &d.res[k]));
+        for (int k = 0; k < c.layers_per_block[i]; ++k) LTX_TRY(load_resnet_convs(e->dtype, e->owned, wm, p + ".resnets." + std::to_string(k), cur, &d.res[k]));
         d.has_down = c.spatiotemporal_scaling[i] != 0;
         if (d.has_down) {
             down_stride(c.downsample_types[i], &d.st, &d.sh, &d.sw);
@@ -928,7 +795,7 @@ int enc_build(ltx_vae_encoder* e, const ltx_weight* weights, size_t n_weights) {
             if (d.cout % nsub != 0 || (cur * nsub) % d.cout != 0 || (d.cout / nsub) % 4 != 0)
                 LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder downsampler: channels must divide by the stride volume (and the conv's by 4)");
             d.cc = d.cout / nsub; d.group = cur * nsub / d.cout;                       // vae.rs:516-517
-            LTX_TRY(load_conv(e->dtype, e->owned, wm, p + ".downsamplers.0.conv", cur, d.cc, PERM_NONE, 0, &d.down));
+            LTX_TRY(load_conv(e->dtype, e->owned, wm, p + ".downsamplers.0.conv", cur, d.cc, LTX_PERM_NONE, 0, &d.down));
             d.down.st = d.st; d.down.sh = d.sh; d.down.sw = d.sw; d.down.group = d.group;
         } else if (d.cout != cur) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder down block without a downsampler cannot change the channel count");
         cur = d.cout;
@@ -936,7 +803,7 @@ int enc_build(ltx_vae_encoder* e, const ltx_weight* weights, size_t n_weights) {
     e->mid_ch = cur;
     const int nmid = std::max(c.layers_per_block[nb - 1] - 1, 0);                      // vae.rs:1382-1386
     e->mid.resize(nmid);
-    for (int k = 0; k < nmid; ++k) LTX_TRY(enc_load_resnet(e, wm, "mid_block.resnets." + std::to_string(k), cur, &e->mid[k]));
+    for (int k = 0; k < nmid; ++k) LTX_TRY(load_resnet_convs(e->dtype, e->owned, wm, "mid_block.resnets." + std::to_string(k), cur, &e->mid[k]));
     // conv_out: latent_channels + 1 outputs (vae.rs:1396-1405), padded with zero weights to the GEMM's multiple of 4
     e->nmom = c.latent_channels + 1; e->nmom_pad = (e->nmom + 3) / 4 * 4;
     {
@@ -958,31 +825,14 @@ int enc_build(ltx_vae_encoder* e, const ltx_weight* weights, size_t n_weights) {
         }
         if (rc == LTX_OK) {
             ltx_weight pad[2] = {*w, *b};
-            pad[0].name = "conv_out.conv.weight"; pad[0].data = pw.p; pad[0].on_device = 1; pad[0].shape[0] = e->nmom_pad;
-            pad[1].name = "conv_out.conv.bias"; pad[1].data = pb.p; pad[1].on_device = 1; pad[1].shape[0] = e->nmom_pad;
-            WeightMap wp(pad, 2);
-            rc = load_conv(e->dtype, e->owned, wp, "conv_out", cur, e->nmom_pad, PERM_NONE, 0, &e->conv_out);
+            pad[0].data = pw.p; pad[0].on_device = 1; pad[0].shape[0] = e->nmom_pad;
+            pad[1].data = pb.p; pad[1].on_device = 1; pad[1].shape[0] = e->nmom_pad;
+            rc = conv_upload(e->dtype, e->owned, &pad[0], &pad[1], cur, e->nmom_pad, LTX_PERM_NONE, 0, &e->conv_out);
         }
         pw.release(); pb.release();
         if (rc != LTX_OK) return rc;
     }
     return LTX_OK;
-}
-
-int enc_resnet(ltx_vae_encoder* e, const ResnetW& r, int ch, const Dims& d, hipStream_t s) {
-    const int dt = e->dtype;
-    RowNormArgs rn; rn.x = e->X.p; rn.y = e->N.p; rn.rows = d.vox(); rn.D = ch; rn.ldx = ch; rn.ldy = ch;
-    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W; rn.mod_stride = 0;
-    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-    if (fuse_norm2(dt, 2, r.c1, d, ch)) {          // norm2 + SiLU in conv1's epilogue, no modulation tables (PostNorm scale / shift null)
-        PostNorm pn; pn.on = 1; pn.eps = rn.eps; pn.act = 1; pn.mod_stride = 0;
-        LTX_TRY(conv3d(dt, 2, r.c1, e->N.p, e->C.p, d, EPI_BIAS, nullptr, 0, s, &pn));
-        return conv3d(dt, 2, r.c2, e->C.p, e->X.p, d, EPI_RESID, e->X.p, 0, s);
-    }
-    LTX_TRY(conv3d(dt, 2, r.c1, e->N.p, e->C.p, d, EPI_BIAS, nullptr, 0, s));
-    rn.x = e->C.p;
-    LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-    return conv3d(dt, 2, r.c2, e->N.p, e->X.p, d, EPI_RESID, e->X.p, 0, s);
 }
 
 // latent dims of an encoder call on nt x nh x nw samples, or LTX_ERR_ARG where the reference's reshapes fail
@@ -1035,16 +885,14 @@ int encoder_forward(ltx_vae_encoder* e, const void* video, int vdt, int B, int F
     }
     LTX_TRY(conv3d(dt, 2, e->conv_in, e->Y.p, e->X.p, d, EPI_BIAS, nullptr, 0, s));
     for (const DownBlockW& b : e->downs) {
-        for (const ResnetW& r : b.res) LTX_TRY(enc_resnet(e, r, b.ch, d, s));
+        for (const ResnetW& r : b.res) LTX_TRY(resnet_plain(dt, 2, r, b.ch, d, nullptr, 0, e->X.p, e->N.p, e->C.p, s));
         if (!b.has_down) continue;
         LTX_TRY(conv3d(dt, 2, b.down, e->X.p, e->Y.p, d, EPI_S2D, e->X.p, 0, s));      // conv + scatter + grouped-mean residual in the epilogue
         std::swap(e->X, e->Y);
         d.T = (d.T + b.st - 1) / b.st; d.H /= b.sh; d.W /= b.sw;
     }
-    for (const ResnetW& r : e->mid) LTX_TRY(enc_resnet(e, r, e->mid_ch, d, s));
-    RowNormArgs rn; rn.x = e->X.p; rn.y = e->N.p; rn.rows = d.vox(); rn.D = e->mid_ch; rn.ldx = e->mid_ch; rn.ldy = e->mid_ch;
-    rn.kind = 0; rn.eps = 1e-8f; rn.act = 1; rn.rows_per_batch = (int64_t)d.T * d.H * d.W;
-    LTX_TRY(ltx_launch_rownorm(rn, dt, s));                                                               // norm_out + SiLU (vae.rs:1455-1459)
+    for (const ResnetW& r : e->mid) LTX_TRY(resnet_plain(dt, 2, r, e->mid_ch, d, nullptr, 0, e->X.p, e->N.p, e->C.p, s));
+    LTX_TRY(ltx_launch_rownorm(norm_silu(e->X.p, e->N.p, d, e->mid_ch, 0, nullptr), dt, s));      // norm_out + SiLU (vae.rs:1455-1459)
     LTX_TRY(conv3d(dt, 2, e->conv_out, e->N.p, e->C.p, d, EPI_BIAS, nullptr, 0, s));
     const int64_t S = (int64_t)d.T * d.H * d.W, n = (int64_t)B * e->nmom * S;
     if (mean_direct) {
@@ -1325,19 +1173,7 @@ extern "C" int ltx_op_downsample3d(const void* x, const void* w, const void* bia
     if (B < 1 || T < 1 || H < 1 || W < 1 || Cin < 8 || Cin % 8 != 0 || Cout < nsub || Cout % nsub != 0 || (Cout / nsub) % 4 != 0 || (Cin * nsub) % Cout != 0)
         LTX_FAIL(LTX_ERR_ARG, "ltx_op_downsample3d: bad shape");
     if ((T + st - 1) % st != 0 || H % sh != 0 || W % sw != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_downsample3d: frames + 1, height and width must divide by the stride");
-    const int dt = dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32; const size_t esz = ltx_dt_size(dt);
-    hipStream_t s = (hipStream_t)stream;
-    const int cc = Cout / nsub;
-    ConvW cw; cw.cin = Cin; cw.cout = cc; cw.st = st; cw.sh = sh; cw.sw = sw; cw.group = Cin * nsub / Cout;
-    DevBuf wb, bb;
-    int rc = wb.ensure((size_t)cc * Cin * 27 * esz); if (rc == LTX_OK) rc = bb.ensure((size_t)cc * esz + 16);
-    const int wdt = wdtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    if (rc == LTX_OK) rc = ltx_pack_conv(w, wdt, wb.p, dt, cc, Cin, 27, PERM_NONE, 0, s);
-    if (rc == LTX_OK) rc = ltx_pack_conv(bias, wdt, bb.p, dt, cc, 1, 1, PERM_NONE, 0, s);
-    cw.w = wb.p; cw.b = bb.p;
-    Dims d{B, T, H, W};
-    if (rc == LTX_OK) rc = conv3d(dt, 2, cw, x, y, d, EPI_S2D, x, 0, s);
-    if (hipStreamSynchronize(s) != hipSuccess && rc == LTX_OK) { ltx_set_error("ltx_op_downsample3d: stream failed"); rc = LTX_ERR_HIP; }
-    wb.release(); bb.release();
-    return rc;
+    ConvW cw; cw.cin = Cin; cw.cout = Cout / nsub; cw.st = st; cw.sh = sh; cw.sw = sw; cw.group = Cin * nsub / Cout;
+    return conv3d_unpacked(dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, 2, cw, w, bias, wdtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, LTX_PERM_NONE,
+                           x, y, Dims{B, T, H, W}, EPI_S2D, x, 0, (hipStream_t)stream);
 }

@@ -5,7 +5,7 @@
 #include <vector>
 
 #include "../../include/ltxhip_lora.h"
-#include "../../include/ltxhip_weights.h"
+#include "weight_list.h"
 #include "../csrc/errors.h"
 
 namespace {
@@ -47,27 +47,10 @@ extern "C" int ltx_lora_create_from_file(const ltx_dit* like, const char* path, 
     *out = nullptr;
     ltx_safetensors* st = nullptr;
     LTX_TRY(ltx_safetensors_open(path, &st));
-    const size_t count = ltx_safetensors_count(st);
-    std::vector<ltx_weight> ws;
-    ws.reserve(count);
-    int rc = LTX_OK;
-    for (size_t i = 0; i < count && rc == LTX_OK; ++i) {
-        const char *name = nullptr, *dtype = nullptr; int ndim = 0; const int64_t* shape = nullptr; const void* data = nullptr; size_t nbytes = 0;
-        rc = ltx_safetensors_tensor(st, i, &name, &dtype, &ndim, &shape, &data, &nbytes);
-        if (rc != LTX_OK) break;
+    std::vector<ltx_weight> ws;      // not an adapter tensor: ignored, as ltx_lora_create does
+    int rc = ltx_safetensors_weight_list(st, "ltx_lora_create_from_file", [](const char* name) {
         char mod[512]; int role = 0;
-        if (ltx_lora_parse_key(name, mod, sizeof(mod), &role) != LTX_OK) continue;      // not an adapter tensor: ignored, as ltx_lora_create does
-        ltx_weight w; memset(&w, 0, sizeof(w));
-        if (!strcmp(dtype, "F32")) w.dtype = LTX_F32;
-        else if (!strcmp(dtype, "BF16")) w.dtype = LTX_BF16;
-        else { ltx_set_error(std::string("ltx_lora_create_from_file: tensor '") + name + "' is " + dtype + " (F32 and BF16 are read)"); rc = LTX_ERR_UNSUPPORTED; break; }
-        if (ndim > 5) { ltx_set_error(std::string("ltx_lora_create_from_file: tensor '") + name + "' has more than 5 dimensions"); rc = LTX_ERR_ARG; break; }
-        int64_t numel = 1;
-        for (int d = 0; d < ndim; ++d) { w.shape[d] = shape[d]; numel *= shape[d]; }
-        if ((size_t)numel * (w.dtype == LTX_BF16 ? 2 : 4) != nbytes) { ltx_set_error(std::string("ltx_lora_create_from_file: tensor '") + name + "': byte count does not match its shape"); rc = LTX_ERR_ARG; break; }
-        w.name = name; w.data = data; w.ndim = ndim; w.on_device = 0;      // (name and data point into the mapping, alive until close)
-        ws.push_back(w);
-    }
+        return ltx_lora_parse_key(name, mod, sizeof(mod), &role) == LTX_OK; }, &ws);
     if (rc == LTX_OK) rc = ltx_lora_create(like, ws.data(), ws.size(), strict, out, n_unmatched);
     ltx_safetensors_close(st);
     return rc;

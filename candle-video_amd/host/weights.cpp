@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ltxhip_weights.h"
+#include "weight_list.h"
 #include "../csrc/errors.h"
 
 namespace {
@@ -280,6 +280,28 @@ extern "C" int ltx_safetensors_tensor(const ltx_safetensors* st, size_t i, const
     if (shape) *shape = e.shape.data();
     if (data) *data = e.data;
     if (nbytes) *nbytes = e.nbytes;
+    return LTX_OK;
+}
+
+int ltx_safetensors_weight_list(const ltx_safetensors* st, const char* who, const std::function<bool(const char*)>& keep, std::vector<ltx_weight>* out) {
+    const size_t count = ltx_safetensors_count(st);
+    out->reserve(out->size() + count);
+    for (size_t i = 0; i < count; ++i) {
+        const char *name = nullptr, *dtype = nullptr; int ndim = 0; const int64_t* shape = nullptr; const void* data = nullptr; size_t nbytes = 0;
+        LTX_TRY(ltx_safetensors_tensor(st, i, &name, &dtype, &ndim, &shape, &data, &nbytes));
+        if (!name || !keep(name)) continue;
+        const std::string tensor = std::string(who) + ": tensor '" + name + "'";
+        ltx_weight w; memset(&w, 0, sizeof(w));
+        if (!strcmp(dtype, "F32")) w.dtype = LTX_F32;
+        else if (!strcmp(dtype, "BF16")) w.dtype = LTX_BF16;
+        else LTX_FAIL(LTX_ERR_UNSUPPORTED, tensor + " is " + dtype + " (F32 and BF16 are read)");
+        if (ndim > 5) LTX_FAIL(LTX_ERR_ARG, tensor + " has more than 5 dimensions");
+        int64_t numel = 1;
+        for (int d = 0; d < ndim; ++d) { w.shape[d] = shape[d]; numel *= shape[d]; }
+        if ((size_t)numel * (w.dtype == LTX_BF16 ? 2 : 4) != nbytes) LTX_FAIL(LTX_ERR_ARG, tensor + ": byte count does not match its shape");
+        w.name = name; w.data = data; w.ndim = ndim; w.on_device = 0;
+        out->push_back(w);
+    }
     return LTX_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/ltxhip_weights.h"
 #include "../../include/ltxhip_presets.h"
 #include "../../include/ltxhip_frames.h"
+#include "../../candle-video_amd/host/weight_list.h"
 
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "CHECK failed: %s (line %d): %s\n", #c, __LINE__, ltx_last_error()); return 1; } } while (0)
 
@@ -91,6 +92,22 @@ int main(int argc, char** argv) {
         }
     }
     CHECK(ltx_safetensors_open((dir + "/does_not_exist").c_str(), &st) != 0);
+    // ---- the *_create_from_file functions' weight list: a kept tensor, a skipped one, and an F16 one that only fails when it is kept
+    {
+        const std::string hdr = "{\"w\":{\"dtype\":\"F32\",\"shape\":[2,3],\"data_offsets\":[0,24]},\"b\":{\"dtype\":\"BF16\",\"shape\":[4],\"data_offsets\":[24,32]},"
+                                "\"h\":{\"dtype\":\"F16\",\"shape\":[2],\"data_offsets\":[32,36]}}";
+        write_file(dir + "/list.safetensors", safetensors_blob(hdr, 36));
+        CHECK(ltx_safetensors_open((dir + "/list.safetensors").c_str(), &st) == 0 && ltx_safetensors_count(st) == 3);
+        std::vector<ltx_weight> ws;
+        CHECK(ltx_safetensors_weight_list(st, "caller", [](const char* n) { return !std::strcmp(n, "w"); }, &ws) == 0 && ws.size() == 1);
+        CHECK(!std::strcmp(ws[0].name, "w") && ws[0].dtype == LTX_F32 && ws[0].ndim == 2 && ws[0].shape[0] == 2 && ws[0].shape[1] == 3 && !ws[0].on_device);
+        unsigned acc = 0; for (size_t j = 0; j < 24; ++j) acc += ((const unsigned char*)ws[0].data)[j];
+        CHECK(acc == 24);
+        CHECK(ltx_safetensors_weight_list(st, "caller", [](const char* n) { return std::strcmp(n, "h") != 0; }, &ws) == 0 && ws.size() == 3);
+        const int rc = ltx_safetensors_weight_list(st, "caller", [](const char*) { return true; }, &ws);
+        CHECK(rc == 4 && std::strstr(ltx_last_error(), "caller: tensor 'h' is F16"));
+        ltx_safetensors_close(st);
+    }
     // ---- file resolution (loader.rs:341-397): index file with shards, plain directory, tiny output buffer
     mkdir((dir + "/ckpt").c_str(), 0755);
     write_file(dir + "/ckpt/a.safetensors", safetensors_blob(good_hdr, 32));
