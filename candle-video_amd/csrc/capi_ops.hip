@@ -1,6 +1,7 @@
 // Kernel-level C entry points (include/ltxhip_ops.h) — thin argument marshalling only.
 #include "conv3d.h"
 #include "../../include/ltxhip_ops.h"
+#include "../../include/ltxhip_upsampler_st.h"
 
 static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
 
@@ -300,6 +301,19 @@ extern "C" int ltx_op_upsample3d(const void* x, const void* w, const void* bias,
     if (Cout % 8 != 0 || Cin % 8 != 0) LTX_FAIL(LTX_ERR_ARG, "upsample3d: channels must be multiples of 8");
     return conv_common(x, w, bias, wdtype, y, residual ? x : nullptr, B, T, H, W, Cin, Cout, causal, dtype, EPI_D2S, LTX_PERM_D2S, 0, (hipStream_t)stream);
 }
+// the latent upsampler's shuffle stage (ltxhip_upsampler_st.h): guarded in, guarded out, the placement in the conv's epilogue
+extern "C" int ltx_op_conv3d_shuffle(const void* x, const void* w, const void* bias, int wdtype, void* y,
+                                     int B, int F, int H, int W, int Cin, int O, int st, int ss, int dtype, ltx_stream stream) {
+    if (!x || !w || !bias || !y) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_shuffle: null tensor");
+    if (!((st == 2 && ss == 1) || (st == 2 && ss == 2) || (st == 1 && ss == 2))) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_shuffle: the factors (st, ss) are (2,1), (2,2) or (1,2)");
+    if ((dtype != 0 && dtype != 1) || (wdtype != 0 && wdtype != 1)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_shuffle: bad dtype");
+    const int nsub = st * ss * ss;
+    if (B < 1 || F < 1 || H < 1 || W < 1 || F > (1 << 29) || H > (1 << 29) || W > (1 << 29)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_shuffle: bad shape");
+    if (Cin < 8 || Cin % 8 != 0 || O < 4 * nsub || O % (4 * nsub) != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_shuffle: Cin must be a multiple of 8 and O a multiple of 4 x the sub-pixel count");
+    if ((int64_t)B * (2 * F + 1) * (2 * H) * (2 * W) * std::max(Cin, O) > (1LL << 40)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_conv3d_shuffle: shape too large");
+    ConvW cw; cw.cin = Cin; cw.cout = O; cw.nsub = nsub;
+    return conv3d_unpacked(dtc(dtype), 1, cw, w, bias, dtc(wdtype), LTX_PERM_D2S, x, y, Dims{B, F + 2, H, W}, EPI_D2S_G, nullptr, 0, (hipStream_t)stream);
+}
 extern "C" int ltx_op_conv_out_unpatchify(const void* x, const void* w, const void* bias, int wdtype, float* y,
                                           int B, int T, int H, int W, int Cin, int Cout, int causal, int postprocess, int dtype, ltx_stream stream) {
     if (Cout % 16 != 0) LTX_FAIL(LTX_ERR_ARG, "conv_out: Cout must be a multiple of 16 (patch 4x4)");
@@ -328,7 +342,7 @@ extern "C" int ltx_op_gemm_plan(int M, int N, int K, int conv, int ntaps, int T,
 
 // Read-only probe of the GEMM dispatch: the described call with dense strides and aligned dummy pointers (never dereferenced)
 extern "C" int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B, int T, int H, int W, int epi, int dtype, int flags, char* name, int cap) {
-    if (!name || cap < 1 || M < 1 || N < 1 || K < 1 || epi < EPI_BIAS || epi > EPI_S2D) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_route: bad argument");
+    if (!name || cap < 1 || M < 1 || N < 1 || K < 1 || epi < EPI_BIAS || epi > EPI_D2S_G) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_route: bad argument");
     if (conv && (ntaps < 1 || B < 1 || T < 1 || H < 1 || W < 1 || (int64_t)B * T * H * W != M)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_route: conv calls need M = B T H W");
     void* const p = reinterpret_cast<void*>((uintptr_t)4096); float* const f = reinterpret_cast<float*>(p);
     const bool res = epi == EPI_GATE_RESID || epi == EPI_RESID;
@@ -344,6 +358,12 @@ extern "C" int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B
         g.conv = 1; g.B = B; g.T = T; g.H = H; g.Wd = W; g.Cin = K; g.ntaps = ntaps; g.kh = g.kw = ntaps == 27 ? 3 : 1; g.pad_t = 2;
         if (epi == EPI_D2S) { g.Cf = N / 8; g.Cr = K / 8; g.To = 2 * T - 1; g.Ho = 2 * H; g.Wo = 2 * W; }
         if (epi == EPI_S2D) { g.s2_st = g.s2_sh = g.s2_sw = 2; g.To = (T + 1) / 2; g.Ho = H / 2; g.Wo = W / 2; }
+        // (the guarded depth-to-space of the latent upsampler: T counts its two guard frames; the factors the channel count admits)
+        if (epi == EPI_D2S_G) {
+            if (T < 3 || N % 8 != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_route: the guarded depth-to-space call needs T >= 3 and N a multiple of 8");
+            const int fs = N % 32 == 0 ? 2 : 1;
+            g.pad_t = 1; g.s2_st = 2; g.s2_sh = g.s2_sw = fs; g.Cf = N / (2 * fs * fs); g.To = 2 * T - 3; g.Ho = fs * H; g.Wo = fs * W;
+        }
         if (flags & LTX_ROUTE_PN) { g.pn_on = 1; g.pn_eps = 1e-6f; g.pn_act = 1; }
     }
     GemmRoute r;

@@ -9,7 +9,7 @@ struct ConvW {
     void* b = nullptr;   // [N]
     int cin = 0, cout = 0;
     int st = 1, sh = 1, sw = 1, group = 1;   // EPI_S2D (encoder downsampler convs): strides and residual group size (vae.rs:516)
-    int nsub = 8;        // depth-to-space convs: output channels per final channel, 8 = (2, 2, 2), 4 = (1, 2, 2)
+    int nsub = 8;        // depth-to-space convs: output channels per final channel, 8 = (2, 2, 2), 4 = (1, 2, 2); EPI_D2S_G also 2 = (2, 1, 1)
 };
 struct Dims { int B, T, H, W; int64_t vox() const { return (int64_t)B * T * H * W; } };
 struct PostNorm { int on = 0; float eps = 0.f; int act = 0; int mod_stride = 0; const float* scale = nullptr; const float* shift = nullptr; };
@@ -25,7 +25,7 @@ int conv_upload(int dtype, std::vector<void*>& owned, const ltx_weight* w, const
                 ConvPackFn pack_w = nullptr);
 
 // The launch-side description of the conv over all of d (operand pointers A / C / resid left to the caller), with the EPI_D2S /
-// EPI_S2D geometry and, with pn, the fused output norm
+// EPI_S2D / EPI_D2S_G geometry (the last one: d.T counts the two guard frames) and, with pn, the fused output norm
 GemmArgs conv_args(const ConvW& cw, const Dims& d, int pad_t, int epi, const PostNorm* pn = nullptr);
 int conv_chunk(int dtype, const ConvW& cw, const Dims& d);      // samples per launch
 bool fuse_norm2(int dtype, int pad_t, const ConvW& cw, const Dims& d_all, int ch);

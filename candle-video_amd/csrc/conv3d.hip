@@ -58,6 +58,11 @@ GemmArgs conv_args(const ConvW& cw, const Dims& d, int pad_t, int epi, const Pos
     g.pad_t = pad_t;                                  // vae.rs:383-412
     if (epi == EPI_D2S) { g.Cf = cw.cout / cw.nsub; g.Cr = cw.cin / cw.nsub; g.To = cw.nsub == 4 ? d.T : 2 * d.T - 1; g.Ho = 2 * d.H; g.Wo = 2 * d.W; g.d2s_sp = cw.nsub == 4; }
     if (epi == EPI_S2D) { g.s2_st = cw.st; g.s2_sh = cw.sh; g.s2_sw = cw.sw; g.s2_group = cw.group; g.To = (d.T + cw.st - 1) / cw.st; g.Ho = d.H / cw.sh; g.Wo = d.W / cw.sw; }
+    if (epi == EPI_D2S_G) {                            // guarded in, guarded out (kernels.h): nsub 2 = (2,1,1), 8 = (2,2,2), 4 = (1,2,2)
+        const int ft = cw.nsub == 4 ? 1 : 2, fs = cw.nsub == 2 ? 1 : 2;
+        g.Cf = cw.cout / cw.nsub; g.s2_st = ft; g.s2_sh = g.s2_sw = fs;
+        g.To = ft == 2 ? 2 * d.T - 3 : d.T; g.Ho = fs * d.H; g.Wo = fs * d.W;
+    }
     if (pn && pn->on) { g.pn_on = 1; g.pn_eps = pn->eps; g.pn_act = pn->act; g.pn_mod_stride = pn->mod_stride; g.pn_scale = pn->scale; g.pn_shift = pn->shift; }
     return g;
 }
@@ -99,7 +104,7 @@ int conv3d(int dtype, int pad_t, const ConvW& cw, const void* x, void* y, const 
     const int nb = conv_chunk(dtype, cw, d);
     const GemmArgs all = conv_args(cw, d, pad_t, epi, pn);
     size_t out_b, res_b = (size_t)per * cw.cin * esz;     // bytes per sample of the output / residual tensor
-    if (epi == EPI_D2S) out_b = (size_t)all.To * all.Ho * all.Wo * all.Cf * esz;
+    if (epi == EPI_D2S || epi == EPI_D2S_G) out_b = (size_t)all.To * all.Ho * all.Wo * all.Cf * esz;
     else if (epi == EPI_S2D) out_b = (size_t)all.To * all.Ho * all.Wo * cw.cout * cw.st * cw.sh * cw.sw * esz;
     else if (epi == EPI_UNPATCH) out_b = (size_t)(cw.cout / 16) * d.T * (4 * d.H) * (4 * d.W) * sizeof(float);
     else res_b = out_b = (size_t)per * cw.cout * esz;

@@ -587,7 +587,7 @@ __global__ __launch_bounds__(WGM * WGN * 64) void conv_halo_kernel(const GemmArg
                 }
             }
         }
-    } else if constexpr (EPI == EPI_D2S || EPI == EPI_UNPATCH || EPI == EPI_BIAS) {
+    } else if constexpr (EPI == EPI_D2S || EPI == EPI_UNPATCH || EPI == EPI_BIAS || EPI == EPI_D2S_G) {
         float bias4[FN][4];
 #pragma unroll
         for (int fn = 0; fn < FN; ++fn) {
@@ -698,6 +698,7 @@ int launch_halo_epi(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_RESID: return launch_halo<BN, WGM, WGN, EPI_RESID, PIPE>(g, s);
         case EPI_D2S: return launch_halo<BN, WGM, WGN, EPI_D2S, PIPE>(g, s);
         case EPI_S2D: return launch_halo<BN, WGM, WGN, EPI_S2D, PIPE>(g, s);
+        case EPI_D2S_G: return launch_halo<BN, WGM, WGN, EPI_D2S_G, PIPE>(g, s);
     }
     LTX_FAIL(LTX_ERR_ARG, "conv_halo: unsupported epilogue");
 }
@@ -712,7 +713,7 @@ bool ltx_conv_halo_eligible(const GemmArgs& g, int epi, int bn) {
         if (epi != EPI_UNPATCH || g.N > 48 || g.N % 4 != 0) return false;
     } else {
         if (g.N % bn != 0) return false;
-        if (epi != EPI_BIAS && epi != EPI_RESID && epi != EPI_D2S && epi != EPI_S2D) return false;
+        if (epi != EPI_BIAS && epi != EPI_RESID && epi != EPI_D2S && epi != EPI_S2D && epi != EPI_D2S_G) return false;
     }
     if (g.c_seg_shift) return false;
     // a tile addresses the three frames around it: those (not the tensor) and the weights must stay below 2 GiB

@@ -171,6 +171,7 @@ int launch_t(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_D2S: hipLaunchKernelGGL((gemm_kernel<T, EPI_D2S, CONV>), grid, block, 0, s, g); break;
         case EPI_UNPATCH: hipLaunchKernelGGL((gemm_kernel<T, EPI_UNPATCH, CONV>), grid, block, 0, s, g); break;
         case EPI_S2D: hipLaunchKernelGGL((gemm_kernel<T, EPI_S2D, CONV>), grid, block, 0, s, g); break;
+        case EPI_D2S_G: hipLaunchKernelGGL((gemm_kernel<T, EPI_D2S_G, CONV>), grid, block, 0, s, g); break;
         default: LTX_FAIL(LTX_ERR_ARG, "gemm: bad epilogue");
     }
     LTX_CHECK_LAUNCH();
@@ -188,8 +189,14 @@ int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s) {
     if (g.K % ch != 0) LTX_FAIL(LTX_ERR_ARG, "gemm: K must be a multiple of the 16-byte chunk");
     if (g.N % 4 != 0) LTX_FAIL(LTX_ERR_ARG, "gemm: N must be a multiple of 4");
     if (!g.conv && g.lda % ch != 0) LTX_FAIL(LTX_ERR_ARG, "gemm: lda must be 16-byte aligned");
-    if ((epi == EPI_D2S || epi == EPI_UNPATCH || epi == EPI_S2D) && !g.conv) LTX_FAIL(LTX_ERR_ARG, "gemm: d2s/unpatch need conv mode");
+    if ((epi == EPI_D2S || epi == EPI_UNPATCH || epi == EPI_S2D || epi == EPI_D2S_G) && !g.conv) LTX_FAIL(LTX_ERR_ARG, "gemm: d2s/unpatch need conv mode");
     if (epi == EPI_S2D && (!g.resid || g.s2_st * g.s2_sh * g.s2_sw < 2 || g.s2_group < 1)) LTX_FAIL(LTX_ERR_ARG, "gemm: the space-to-depth epilogue needs the input tensor and its strides");
+    if (epi == EPI_D2S_G) {
+        const int ft = g.s2_st, fs = g.s2_sh;
+        if (g.resid || g.s2_sw != fs || (ft != 1 && ft != 2) || (fs != 1 && fs != 2) || ft * fs < 2 || g.Cf < 4 || g.Cf % 4 != 0 || g.N != g.Cf * ft * fs * fs ||
+            g.T < 3 || g.To != (ft == 2 ? 2 * g.T - 3 : g.T) || g.Ho != fs * g.H || g.Wo != fs * g.Wd)
+            LTX_FAIL(LTX_ERR_ARG, "gemm: the guarded depth-to-space epilogue needs factors (2,1), (2,2) or (1,2), N = factors x Cf, Cf a multiple of 4 and the guarded output geometry");
+    }
     if (g.rowsq && (g.conv || g.c_seg_shift || epi == EPI_D2S || epi == EPI_UNPATCH)) LTX_FAIL(LTX_ERR_ARG, "gemm: rowsq needs a dense linear output");
     // route (gemm_big.hip: which kernel, which plan), refuse (operands that kernel does not read), launch
     GemmRoute r;

@@ -540,6 +540,7 @@ int launch_epi(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_D2S: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_D2S, CONV>(g, s); break;
         case EPI_UNPATCH: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_UNPATCH, CONV>(g, s); break;
         case EPI_S2D: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_S2D, CONV>(g, s); break;
+        case EPI_D2S_G: if constexpr (CONV) return launch_one<BM, BN, WGM, WGN, EPI_D2S_G, CONV>(g, s); break;
     }
     LTX_FAIL(LTX_ERR_ARG, "gemm_big: bad epilogue");
 }
@@ -669,7 +670,7 @@ std::atomic<int> g_autotune{1};      // ltx_set_autotune(0): never measure insid
 
 PlanKey plan_key(const GemmArgs& g, int epi) {
     PlanKey key; memset(&key, 0, sizeof(key));
-    key.M = g.M; key.N = g.N; key.K = g.K; key.conv = g.conv ? (epi == EPI_D2S ? 2 : 1) : (g.defer_parts ? 3 : 0);
+    key.M = g.M; key.N = g.N; key.K = g.K; key.conv = g.conv ? ((epi == EPI_D2S || epi == EPI_D2S_G) ? 2 : 1) : (g.defer_parts ? 3 : 0);
     if (g.conv) { key.ntaps = g.ntaps; key.T = g.T; key.H = g.H; key.W = g.Wd; }
     return key;
 }
@@ -702,6 +703,8 @@ bool plan_valid(const GemmArgs& g, int epi, GemmPlan p) {
     if (!plan_shape_valid(plan_key(g, epi), p)) return false;
     // the encoder's space-to-depth epilogue lives in the gemm_big tiles and the halo-staged kernel
     if (epi == EPI_S2D && p.fam != kPlanBig && p.fam != kPlanHalo) return false;
+    // ... and so does the latent upsampler's guarded depth-to-space epilogue
+    if (epi == EPI_D2S_G && p.fam != kPlanBig && p.fam != kPlanHalo) return false;
     switch (p.fam) {
         case kPlanBig: return true;
         case kPlanP8: return ltx_gemm_p8_fits(g);
@@ -749,7 +752,8 @@ namespace {
 int tune_plan(const GemmArgs& g_in, int epi, hipStream_t s, GemmPlan* best_plan) {
     // plain bias epilogue into a scratch [M, N] output - except the upsamplers' depth-to-space convs, measured with their own epilogue
     // (its scattered 8-byte stores cost the kernels differently; the output, (2T - 1) x 2H x 2W x N / 8 rows, fits the same scratch)
-    const int tepi = (g_in.conv && epi == EPI_D2S) ? EPI_D2S : EPI_BIAS;
+    // (the guarded form of the latent upsampler likewise: at most (2T - 3) x 2H x 2W x N / 8, (2T - 3) x H x W x N / 2 or T x 2H x 2W x N / 4 rows)
+    const int tepi = (g_in.conv && (epi == EPI_D2S || epi == EPI_D2S_G)) ? epi : EPI_BIAS;
     GemmArgs g = g_in;
     void* scratch = nullptr;
     // (a call that leaves its K ranges to the consumer - GemmArgs::defer_parts - is measured in that form, on the ring tiles that serve it)

@@ -1,5 +1,5 @@
 // Shared pieces of the GEMM / implicit-GEMM kernels: MFMA wrappers, 4-wide loads/stores and the fused
-// epilogues (bias, GELU-tanh, gate*x+residual, residual, depth-to-space(+residual), unpatchify).
+// epilogues (bias, GELU-tanh, gate*x+residual, residual, depth-to-space(+residual), guarded depth-to-space, unpatchify).
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -148,6 +148,19 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, int m, int nb, float
             s2d_residual<T>(g, b, t, h, w, nb, pass, res);
             s2d_store<T>(g, b, t, h, w, nb, pass, v, res);
         }
+    } else if constexpr (EPI == EPI_D2S_G) {
+        // the latent upsampler's shuffle conv (kernels.h): placement between guarded tensors, zeros to the output's guard frames
+        int w = m % g.Wd; int t1 = m / g.Wd;
+        int h = t1 % g.H; int t2 = t1 / g.H;
+        int t = t2 % g.T; int b = t2 / g.T;
+        const int s = nb / g.Cf, co = nb - s * g.Cf;
+        const int fs = g.s2_sh;                        // 1 or 2 (s2_sw the same)
+        const int p3 = s & (fs - 1), p2 = (s >> (fs - 1)) & (fs - 1), p1 = s >> (2 * (fs - 1));
+        const int j = g.s2_st == 2 ? 2 * t + p1 - 2 : t;
+        if (j < 0 || j > g.To - 1) return;
+        if (j == 0 || j == g.To - 1) { v[0] = 0.f; v[1] = 0.f; v[2] = 0.f; v[3] = 0.f; }
+        const int64_t o = ((((int64_t)b * g.To + j) * g.Ho + (fs * h + p2)) * g.Wo + (fs * w + p3)) * g.Cf + co;
+        store4<T>(C + o, v);
     } else if constexpr (EPI == EPI_UNPATCH) {
         // conv_out + unpatchify (vae.rs:1626-1654); channels re-ordered at pack time to
         // n' = (c*4 + off_h)*4 + off_w.  Output is f32 NCTHW [B, N/16, T, 4H, 4W].

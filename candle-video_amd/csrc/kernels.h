@@ -27,7 +27,7 @@ bool ltx_prof_kernel_events(hipEvent_t* a, hipEvent_t* b);
     } while (0)
 
 // ---------------- GEMM / implicit-GEMM conv (gemm.hip) ----------------
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_GATE_RESID = 2, EPI_RESID = 3, EPI_D2S = 4, EPI_UNPATCH = 5, EPI_S2D = 6 };
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_GATE_RESID = 2, EPI_RESID = 3, EPI_D2S = 4, EPI_UNPATCH = 5, EPI_S2D = 6, EPI_D2S_G = 7 };
 
 struct GemmArgs {
     const void* A = nullptr;      // [M, lda] (linear) or channels-last activation [B,T,H,W,Cin] (conv)
@@ -53,6 +53,12 @@ struct GemmArgs {
     // consecutive packed channels of resid = x [B,T,H,W,Cin] re-arranged the same way (frame index clamped the same way).
     // C [B,To,Ho,Wo,N*st*sh*sw]; the conv value and the mean are each rounded to T before they are added.
     int s2_st = 1, s2_sh = 1, s2_sw = 1, s2_group = 1;
+    // EPI_D2S_G (the latent upsampler's shuffle conv, upsampler.hip): depth-to-space between GUARDED tensors.  A [B,T,H,W,Cin] and
+    // C [B,To,Ho,Wo,Cf] both carry one guard frame at each end of T (T = F + 2).  Factors (s2_st, s2_sh = s2_sw), each 1 or 2, one of
+    // (2,1) (2,2) (1,2); packed channel n' = s*Cf + c with s = (p1*s2_sh + p2)*s2_sw + p3 goes to channel c of guarded output voxel
+    // (j, s2_sh*h + p2, s2_sw*w + p3), j = 2t + p1 - 2 (s2_st == 2: output frame 0 of the shuffle is dropped, To = 2T - 3) or j = t
+    // (To = T).  j == 0 and j == To - 1 are the output's guard frames: zeros are stored there; j outside [0, To) stores nothing.
+    // Every voxel of C, guards included, then has exactly one writer.  No residual.
     // EPI_BIAS only: output split into column segments of width 1 << c_seg_shift, segment j a dense [M, ldc] matrix at
     // C + j * c_seg_stride elements (fused q|k|v projection -> three contiguous matrices); 0 = one [M, ldc] matrix
     int c_seg_shift = 0; int64_t c_seg_stride = 0;

@@ -13,6 +13,10 @@
 //   pixel shuffle  upsampler.0 (a per-frame Conv2d) runs as a 27-tap conv whose off-centre temporal taps are zero (3x the work on one
 //                  conv out of 4 n + 3), output channels permuted at load so that a sub-pixel's channels are contiguous; one kernel
 //                  moves 16-byte chunks to (2h + p1, 2w + p2) and zeroes the guards
+//   the temporal and spatiotemporal kinds (ltxhip_upsampler_st.h): upsampler.0 is a true Conv3d there, and its shuffle crosses T with a
+//                  dropped first frame.  The conv's epilogue (EPI_D2S_G, kernels.h) writes the guarded [B, Fo + 2, Ho, Wo, mid] tensor
+//                  directly - value, zero (the output's guard frames) or nothing per conv voxel and sub-pixel - so there is neither a
+//                  shuffle kernel nor a zeroing pass; the spatial kind keeps its kernels (and its bits)
 //   token side     unpack + de-normalise into the guarded layout, normalise + pack out of it, AdaIN (slab partials, merge, apply),
 //                  re-noise
 #include <algorithm>
@@ -20,7 +24,7 @@
 #include <set>
 #include "conv3d.h"
 #include "../host/weight_list.h"
-#include "../../include/ltxhip_upsampler.h"
+#include "../../include/ltxhip_upsampler_st.h"
 #include "../../include/ltxhip_weights.h"
 
 namespace {
@@ -410,7 +414,10 @@ int check_cfg(const ltx_upsampler_config* c, const char* who) {
 
 struct ltx_upsampler {
     ltx_upsampler_config cfg{};
+    int sp = 1, tm = 0;              // the kind: spatial / temporal factor 2 (ltxhip_upsampler_st.h); (1, 0) is the spatial kind of ltxhip_upsampler.h
     int dtype = LTX_DT_BF16, device = 0;
+    int Fo(int F) const { return tm ? 2 * F - 1 : F; }
+    int So(int X) const { return sp ? 2 * X : X; }
     ConvW initial_conv, up, final_conv;
     UpNorm initial_norm;
     std::vector<UpRes> res, post;
@@ -451,14 +458,16 @@ int pack_conv2d(const void* src, int sdt, void* dst, int ddt, int cout, int cin)
     return LTX_OK;
 }
 
-// conv2d != 0: upsampler.0, [cout, cin, 3, 3] -> the 27-tap form with the sub-pixel permutation (Cf = cout / 4)
+// conv2d = 1: the spatial kind's upsampler.0, [cout, cin, 3, 3] -> the 27-tap form with the sub-pixel permutation (Cf = cout / 4);
+// conv2d = 2: the other kinds' upsampler.0, a Conv3d whose output channels take the same permutation (Cf = cin, nsub = cout / cin)
 int load_conv(ltx_upsampler* u, const WeightMap& wm, const std::string& prefix, int cin, int cout, int conv2d, ConvW* c) {
     int rc = LTX_OK;
-    const ltx_weight* w = conv2d ? find_shaped(wm, prefix + ".weight", {cout, cin, 3, 3}, &rc) : find_shaped(wm, prefix + ".weight", {cout, cin, 3, 3, 3}, &rc);
+    const ltx_weight* w = conv2d == 1 ? find_shaped(wm, prefix + ".weight", {cout, cin, 3, 3}, &rc) : find_shaped(wm, prefix + ".weight", {cout, cin, 3, 3, 3}, &rc);
     if (!w) return rc;
     const ltx_weight* b = find_shaped(wm, prefix + ".bias", {cout}, &rc);
     if (!b) return rc;
-    if (conv2d) return conv_upload(u->dtype, u->owned, w, b, cin, cout, LTX_PERM_D2S, cout / 4, c, pack_conv2d);
+    if (conv2d == 1) return conv_upload(u->dtype, u->owned, w, b, cin, cout, LTX_PERM_D2S, cout / 4, c, pack_conv2d);
+    if (conv2d == 2) return conv_upload(u->dtype, u->owned, w, b, cin, cout, LTX_PERM_D2S, cin, c);
     return conv_upload(u->dtype, u->owned, w, b, cin, cout, LTX_PERM_NONE, 0, c);
 }
 int load_norm(ltx_upsampler* u, const WeightMap& wm, const std::string& prefix, int ch, UpNorm* n) {
@@ -481,7 +490,8 @@ int up_build(ltx_upsampler* u, const ltx_weight* weights, size_t n) {
     LTX_TRY(load_norm(u, wm, "initial_norm", c.mid_channels, &u->initial_norm));
     u->res.resize(c.num_blocks_per_stage); u->post.resize(c.num_blocks_per_stage);
     for (int i = 0; i < c.num_blocks_per_stage; ++i) LTX_TRY(load_res(u, wm, "res_blocks." + std::to_string(i), c.mid_channels, &u->res[i]));
-    LTX_TRY(load_conv(u, wm, "upsampler.0", c.mid_channels, 4 * c.mid_channels, 1, &u->up));
+    if (u->sp && !u->tm) LTX_TRY(load_conv(u, wm, "upsampler.0", c.mid_channels, 4 * c.mid_channels, 1, &u->up));
+    else LTX_TRY(load_conv(u, wm, "upsampler.0", c.mid_channels, (u->sp ? 8 : 2) * c.mid_channels, 2, &u->up));
     for (int i = 0; i < c.num_blocks_per_stage; ++i) LTX_TRY(load_res(u, wm, "post_upsample_res_blocks." + std::to_string(i), c.mid_channels, &u->post[i]));
     LTX_TRY(load_conv(u, wm, "final_conv", c.mid_channels, c.in_channels, 0, &u->final_conv));
     return LTX_OK;
@@ -504,18 +514,18 @@ int up_res(ltx_upsampler* u, const UpRes& r, const Dims& d, int ch, hipStream_t 
 int up_ensure(ltx_upsampler* u, int B, int F, int H, int W) {
     const ltx_upsampler_config& c = u->cfg;
     const size_t esz = ltx_dt_size(u->dtype);
-    const int64_t hi = (int64_t)B * (F + 2) * (2 * H) * (2 * W);
+    const int64_t hi = (int64_t)B * (u->Fo(F) + 2) * u->So(H) * u->So(W);
     const size_t act = (size_t)hi * std::max(c.mid_channels, c.in_channels) * esz;
     LTX_TRY(u->X.ensure(act)); LTX_TRY(u->Cb.ensure(act)); LTX_TRY(u->Nb.ensure(act));
     LTX_TRY(u->zin.ensure((size_t)B * (F + 2) * H * W * c.in_channels * esz));
     GnGeom q;
-    if (!gn_geom(B, F, 2 * H, 2 * W, c.mid_channels, kGroups, 1, &q)) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler: bad geometry");
+    if (!gn_geom(B, u->Fo(F), u->So(H), u->So(W), c.mid_channels, kGroups, 1, &q)) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler: bad geometry");
     size_t pb = gn_part_bytes(q);
     if (gn_geom(B, F, H, W, c.mid_channels, kGroups, 1, &q)) pb = std::max(pb, gn_part_bytes(q));
     return u->part.ensure(pb);
 }
 
-// zin [B, F + 2, H, W, in_channels] (guards zero) -> Cb [B, F + 2, 2H, 2W, in_channels] (guards: garbage, not read by the callers)
+// zin [B, F + 2, H, W, in_channels] (guards zero) -> Cb [B, Fo + 2, Ho, Wo, in_channels] (guards: garbage, not read by the callers)
 int up_forward_cl(ltx_upsampler* u, int B, int F, int H, int W, hipStream_t s) {
     const ltx_upsampler_config& c = u->cfg;
     const int mid = c.mid_channels;
@@ -523,6 +533,12 @@ int up_forward_cl(ltx_upsampler* u, int B, int F, int H, int W, hipStream_t s) {
     LTX_TRY(conv3d(u->dtype, 1, u->initial_conv, u->zin.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s));
     LTX_TRY(up_gn(u, u->initial_norm, u->Cb.p, u->X.p, nullptr, d, mid, s));
     for (auto& r : u->res) LTX_TRY(up_res(u, r, d, mid, s));
+    if (u->tm) {
+        // conv + shuffle + dropped frame + zero guards in one launch, into the buffer that becomes the activation
+        LTX_TRY(conv3d(u->dtype, 1, u->up, u->X.p, u->Nb.p, d, EPI_D2S_G, nullptr, 0, s));
+        std::swap(u->X, u->Nb);
+        d.T = u->Fo(F) + 2;
+    } else {
     LTX_TRY(conv3d(u->dtype, 1, u->up, u->X.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s));
     {
         const int64_t n = d.vox() * 4 * (mid / (u->dtype == LTX_DT_BF16 ? 8 : 4));
@@ -530,7 +546,8 @@ int up_forward_cl(ltx_upsampler* u, int B, int F, int H, int W, hipStream_t s) {
         else hipLaunchKernelGGL(pixel_shuffle_kernel<float>, up_grid(n), dim3(256), 0, s, (const float*)u->Cb.p, (float*)u->X.p, B, d.T, H, W, mid);
         LTX_CHECK_LAUNCH();
     }
-    d.H *= 2; d.W *= 2;
+    }
+    d.H = u->So(H); d.W = u->So(W);
     for (auto& r : u->post) LTX_TRY(up_res(u, r, d, mid, s));
     return conv3d(u->dtype, 1, u->final_conv, u->X.p, u->Cb.p, d, EPI_BIAS, nullptr, 0, s);
 }
@@ -538,7 +555,8 @@ int up_forward_cl(ltx_upsampler* u, int B, int F, int H, int W, hipStream_t s) {
 int check_shape(const char* who, const ltx_upsampler* u, int B, int F, int H, int W) {
     if (!u) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null handle");
     if (B < 1 || F < 1 || H < 1 || W < 1) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": bad shape");
-    if ((int64_t)B * (F + 2) * (2 * H) * (2 * W) * std::max(u->cfg.mid_channels, u->cfg.in_channels) > (1LL << 40)) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": shape too large");
+    if (F > (1 << 29) || H > (1 << 29) || W > (1 << 29)) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": shape too large");
+    if ((int64_t)B * (u->Fo(F) + 2) * u->So(H) * u->So(W) * std::max(u->cfg.mid_channels, u->cfg.in_channels) > (1LL << 40)) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": shape too large");
     return LTX_OK;
 }
 
@@ -551,35 +569,87 @@ extern "C" void ltx_upsampler_config_default(ltx_upsampler_config* cfg) {
     cfg->in_channels = 128; cfg->mid_channels = 512; cfg->num_blocks_per_stage = 4;
 }
 
-extern "C" int ltx_upsampler_create(const ltx_upsampler_config* cfg, const ltx_weight* weights, size_t n_weights,
-                                    ltx_dtype model_dtype, int device, ltx_upsampler** out) {
-    if (!out) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_create: null output");
+namespace {
+// the one constructor: (sp, tm) = (1, 0) the spatial kind
+int up_create(const char* who, const ltx_upsampler_config* cfg, int sp, int tm, const ltx_weight* weights, size_t n_weights,
+              ltx_dtype model_dtype, int device, ltx_upsampler** out) {
+    if (!out) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null output");
     *out = nullptr;
-    LTX_TRY(check_cfg(cfg, "ltx_upsampler_create"));
-    if (!weights && n_weights) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_create: null weights");
+    LTX_TRY(check_cfg(cfg, who));
+    if (!weights && n_weights) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null weights");
     HIP_TRY(hipSetDevice(device));
     ltx_upsampler* u = new ltx_upsampler();
-    u->cfg = *cfg; u->dtype = model_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32; u->device = device;
+    u->cfg = *cfg; u->sp = sp; u->tm = tm; u->dtype = model_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32; u->device = device;
     const int rc = up_build(u, weights, n_weights);
     if (rc != LTX_OK) { u->free_all(); delete u; return rc; }
     *out = u;
     return LTX_OK;
 }
-
-extern "C" int ltx_upsampler_create_from_file(const ltx_upsampler_config* cfg, const char* path, ltx_dtype model_dtype, int device, ltx_upsampler** out) {
-    if (!out) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_create_from_file: null output");
+int up_create_from_file(const char* who, const ltx_upsampler_config* cfg, int sp, int tm, const char* path, ltx_dtype model_dtype, int device, ltx_upsampler** out) {
+    if (!out) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null output");
     *out = nullptr;
-    if (!path) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_create_from_file: null path");
-    LTX_TRY(check_cfg(cfg, "ltx_upsampler_create_from_file"));
+    if (!path) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null path");
+    LTX_TRY(check_cfg(cfg, who));
     const std::vector<std::string> keys = up_keys(*cfg);
     const std::set<std::string> wanted(keys.begin(), keys.end());
     ltx_safetensors* st = nullptr;
     LTX_TRY(ltx_safetensors_open(path, &st));
     std::vector<ltx_weight> ws;      // not one of the model's tensors: ignored, as ltx_upsampler_create does
-    int rc = ltx_safetensors_weight_list(st, "ltx_upsampler_create_from_file", [&](const char* name) { return wanted.count(name) != 0; }, &ws);
-    if (rc == LTX_OK) rc = ltx_upsampler_create(cfg, ws.data(), ws.size(), model_dtype, device, out);
+    int rc = ltx_safetensors_weight_list(st, who, [&](const char* name) { return wanted.count(name) != 0; }, &ws);
+    if (rc == LTX_OK) rc = up_create(who, cfg, sp, tm, ws.data(), ws.size(), model_dtype, device, out);
     ltx_safetensors_close(st);
     return rc;
+}
+// -> the three-field config and the flags; both flags 0 (or a value other than 0 / 1) is refused
+int split_st_cfg(const char* who, const ltx_upsampler_st_config* c, ltx_upsampler_config* base) {
+    if (!c) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null config");
+    if ((c->spatial_upsample != 0 && c->spatial_upsample != 1) || (c->temporal_upsample != 0 && c->temporal_upsample != 1))
+        LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": spatial_upsample and temporal_upsample are 0 or 1");
+    if (!c->spatial_upsample && !c->temporal_upsample) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": spatial_upsample or temporal_upsample must be set");
+    base->in_channels = c->in_channels; base->mid_channels = c->mid_channels; base->num_blocks_per_stage = c->num_blocks_per_stage;
+    return LTX_OK;
+}
+}  // namespace
+
+extern "C" int ltx_upsampler_create(const ltx_upsampler_config* cfg, const ltx_weight* weights, size_t n_weights,
+                                    ltx_dtype model_dtype, int device, ltx_upsampler** out) {
+    return up_create("ltx_upsampler_create", cfg, 1, 0, weights, n_weights, model_dtype, device, out);
+}
+
+extern "C" void ltx_upsampler_st_config_default(ltx_upsampler_st_config* cfg) {
+    if (!cfg) return;
+    cfg->in_channels = 128; cfg->mid_channels = 512; cfg->num_blocks_per_stage = 4; cfg->spatial_upsample = 1; cfg->temporal_upsample = 0;
+}
+extern "C" int ltx_upsampler_create_st(const ltx_upsampler_st_config* cfg, const ltx_weight* weights, size_t n_weights,
+                                       ltx_dtype model_dtype, int device, ltx_upsampler** out) {
+    if (out) *out = nullptr;
+    ltx_upsampler_config base;
+    LTX_TRY(split_st_cfg("ltx_upsampler_create_st", cfg, &base));
+    if (!cfg->temporal_upsample) return ltx_upsampler_create(&base, weights, n_weights, model_dtype, device, out);
+    return up_create("ltx_upsampler_create_st", &base, cfg->spatial_upsample, 1, weights, n_weights, model_dtype, device, out);
+}
+extern "C" int ltx_upsampler_create_from_file_st(const ltx_upsampler_st_config* cfg, const char* path, ltx_dtype model_dtype, int device, ltx_upsampler** out) {
+    if (out) *out = nullptr;
+    ltx_upsampler_config base;
+    LTX_TRY(split_st_cfg("ltx_upsampler_create_from_file_st", cfg, &base));
+    if (!cfg->temporal_upsample) return ltx_upsampler_create_from_file(&base, path, model_dtype, device, out);
+    return up_create_from_file("ltx_upsampler_create_from_file_st", &base, cfg->spatial_upsample, 1, path, model_dtype, device, out);
+}
+extern "C" int ltx_upsampler_get_st_config(const ltx_upsampler* u, ltx_upsampler_st_config* out) {
+    if (!u || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_get_st_config: null argument");
+    out->in_channels = u->cfg.in_channels; out->mid_channels = u->cfg.mid_channels; out->num_blocks_per_stage = u->cfg.num_blocks_per_stage;
+    out->spatial_upsample = u->sp; out->temporal_upsample = u->tm;
+    return LTX_OK;
+}
+extern "C" int ltx_upsampler_out_shape(const ltx_upsampler* u, int F, int H, int W, int* Fo, int* Ho, int* Wo) {
+    if (!u || !Fo || !Ho || !Wo) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_out_shape: null argument");
+    if (F < 1 || H < 1 || W < 1 || F > (1 << 29) || H > (1 << 29) || W > (1 << 29)) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_out_shape: bad shape");
+    *Fo = u->Fo(F); *Ho = u->So(H); *Wo = u->So(W);
+    return LTX_OK;
+}
+
+extern "C" int ltx_upsampler_create_from_file(const ltx_upsampler_config* cfg, const char* path, ltx_dtype model_dtype, int device, ltx_upsampler** out) {
+    return up_create_from_file("ltx_upsampler_create_from_file", cfg, 1, 0, path, model_dtype, device, out);
 }
 
 extern "C" void ltx_upsampler_destroy(ltx_upsampler* u) {
@@ -603,7 +673,8 @@ extern "C" int ltx_upsampler_forward(ltx_upsampler* u, const void* latents, ltx_
     hipLaunchKernelGGL(ncthw_to_guarded_kernel, up_grid((int64_t)B * (F + 2) * HW * C), dim3(256), 0, s, latents, iodt, u->zin.p, u->dtype, B, F, HW, C);
     LTX_CHECK_LAUNCH();
     LTX_TRY(up_forward_cl(u, B, F, H, W, s));
-    hipLaunchKernelGGL(guarded_to_ncthw_kernel, up_grid((int64_t)B * F * 4 * HW * C), dim3(256), 0, s, (const void*)u->Cb.p, u->dtype, out, iodt, B, F, 4 * HW, C);
+    const int Fo = u->Fo(F); const int64_t HWo = (int64_t)u->So(H) * u->So(W);
+    hipLaunchKernelGGL(guarded_to_ncthw_kernel, up_grid((int64_t)B * Fo * HWo * C), dim3(256), 0, s, (const void*)u->Cb.p, u->dtype, out, iodt, B, Fo, HWo, C);
     LTX_CHECK_LAUNCH();
     return LTX_OK;
 }
@@ -624,8 +695,9 @@ extern "C" int ltx_latent_upsample_tokens(ltx_upsampler* u, const ltx_vae* vae, 
                        u->zin.p, u->dtype, B, F, HW, C);
     LTX_CHECK_LAUNCH();
     LTX_TRY(up_forward_cl(u, B, F, H, W, s));
-    hipLaunchKernelGGL(guarded_to_tokens_kernel, up_grid((int64_t)B * F * 4 * HW * C), dim3(256), 0, s, (const void*)u->Cb.p, u->dtype, mean, sd, vc.scaling_factor,
-                       tokens_hi, B, F, 4 * HW, C);
+    const int Fo = u->Fo(F); const int64_t HWo = (int64_t)u->So(H) * u->So(W);
+    hipLaunchKernelGGL(guarded_to_tokens_kernel, up_grid((int64_t)B * Fo * HWo * C), dim3(256), 0, s, (const void*)u->Cb.p, u->dtype, mean, sd, vc.scaling_factor,
+                       tokens_hi, B, Fo, HWo, C);
     LTX_CHECK_LAUNCH();
     return LTX_OK;
 }
@@ -692,9 +764,16 @@ extern "C" int ltx_pipeline_call_multiscale(ltx_dit* dit, ltx_vae* vae, ltx_upsa
                                             const float* decode_noise, int B, int K, float* latents_hi_out, float* out_video, ltx_stream stream) {
     if (!dit || !vae || !up || !p_first || !p_second || !latents_lo || !noise_hi || !latents_hi_out) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: null argument");
     if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: bad batch");
-    if (p_second->height != 2 * p_first->height || p_second->width != 2 * p_first->width)
-        LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: the second pass must run at exactly twice the first pass's height and width");
-    if (p_second->num_frames != p_first->num_frames) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: both passes must have the same num_frames");
+    // the geometry rule follows the handle's kind (ltxhip_upsampler_st.h)
+    if (up->sp) {
+        if (p_second->height != 2 * p_first->height || p_second->width != 2 * p_first->width)
+            LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: the second pass must run at exactly twice the first pass's height and width");
+    } else if (p_second->height != p_first->height || p_second->width != p_first->width)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: with a temporal upsampler both passes must have the same height and width");
+    if (up->tm) {
+        if (p_first->num_frames < 1 || p_first->num_frames > (1 << 29) || p_second->num_frames != 2 * p_first->num_frames - 1)
+            LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: with a temporal or spatiotemporal upsampler the second pass must have 2 * num_frames - 1 frames of the first");
+    } else if (p_second->num_frames != p_first->num_frames) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: both passes must have the same num_frames");
     if (p_first->height % 32 != 0 || p_first->width % 32 != 0) LTX_FAIL(LTX_ERR_ARG, "`height` and `width` must be divisible by 32");
     ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc));
     ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
@@ -705,9 +784,15 @@ extern "C" int ltx_pipeline_call_multiscale(ltx_dit* dit, ltx_vae* vae, ltx_upsa
     const int C = dc.in_channels;
     if (C != up->cfg.in_channels) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: upsampler and transformer disagree on the latent channels");
     const int64_t S = (int64_t)F * H * W;
-    if (4 * S > 2147483647LL) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: too many tokens");
+    const int Fo = up->Fo(F), Ho = up->So(H), Wo = up->So(W);
+    const int64_t S_hi = (int64_t)Fo * Ho * Wo;      // 4 S for the spatial kind
+    if (4 * S > 2147483647LL || S_hi > 2147483647LL) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: too many tokens");
+    // the second pass derives its own latent grid from p_second: it must be the one the upsampler writes
+    if (up->tm && ((p_second->num_frames - 1) / vc.temporal_compression_ratio + 1 != Fo ||p_second->height / vc.spatial_compression_ratio != Ho ||
+        p_second->width / vc.spatial_compression_ratio != Wo))
+        LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: the second pass's latent grid is not the upsampler's output (num_frames - 1 must be a multiple of the VAE's temporal compression)");
     float sigma0 = 0.f;
-    LTX_TRY(ltx_pipeline_first_sigma(p_second, (int)(4 * S), &sigma0));
+    LTX_TRY(ltx_pipeline_first_sigma(p_second, (int)S_hi, &sigma0));
 
     ltx_pipeline_params p1 = *p_first;
     p1.output_latent = 1;
@@ -719,8 +804,8 @@ extern "C" int ltx_pipeline_call_multiscale(ltx_dit* dit, ltx_vae* vae, ltx_upsa
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     HIP_TRY(hipEventRecord(e0, s));
     LTX_TRY(ltx_latent_upsample_tokens(up, vae, latents_lo, B, F, H, W, latents_hi_out, stream));
-    LTX_TRY(ltx_latent_adain(latents_hi_out, latents_lo, B, (int)(4 * S), (int)S, C, adain_factor, stream));
-    LTX_TRY(ltx_latent_renoise(latents_hi_out, noise_hi, sigma0, (size_t)B * 4 * S * C, stream));
+    LTX_TRY(ltx_latent_adain(latents_hi_out, latents_lo, B, (int)S_hi, (int)S, C, adain_factor, stream));
+    LTX_TRY(ltx_latent_renoise(latents_hi_out, noise_hi, sigma0, (size_t)B * S_hi * C, stream));
     HIP_TRY(hipEventRecord(e1, s));
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(&t_ms_timing[4], e0, e1));
@@ -744,5 +829,22 @@ extern "C" int ltx_op_groupnorm(const void* x, void* y, const void* resid, const
     LTX_TRY(part.ensure(gn_part_bytes(q)));
     LTX_TRY(gn_launch(dt, x, y, resid, weight, bias, q, eps, (flags & LTX_GN_SILU) != 0, part.as<float>(), s));
     HIP_TRY(hipStreamSynchronize(s));      // (the partials are freed here)
+    return LTX_OK;
+}
+
+// the spatial kind's stand-alone shuffle pass as an op (ltxhip_upsampler_st.h): what EPI_D2S_G folds into the conv, for measurements
+extern "C" int ltx_op_pixel_shuffle_guarded(const void* x, void* y, int B, int F, int H, int W, int C, int dtype, ltx_stream stream) {
+    if (!x || !y) LTX_FAIL(LTX_ERR_ARG, "ltx_op_pixel_shuffle_guarded: null tensor");
+    if (dtype != LTX_F32 && dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_op_pixel_shuffle_guarded: bad dtype");
+    const int ch = dtype == LTX_BF16 ? 8 : 4;
+    if (B < 1 || F < 1 || H < 1 || W < 1 || C < ch || C % ch != 0 || F > (1 << 29) || H > (1 << 29) || W > (1 << 29) ||
+        (int64_t)B * (F + 2) * (2 * H) * (2 * W) * C > (1LL << 40))
+        LTX_FAIL(LTX_ERR_ARG, "ltx_op_pixel_shuffle_guarded: bad shape (C a multiple of the 16-byte chunk)");
+    if ((((uintptr_t)x) | ((uintptr_t)y)) & 15) LTX_FAIL(LTX_ERR_ARG, "ltx_op_pixel_shuffle_guarded: tensors must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)B * (F + 2) * H * W * 4 * (C / ch);
+    if (dtype == LTX_BF16) hipLaunchKernelGGL(pixel_shuffle_kernel<bf16_t>, up_grid(n), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, B, F + 2, H, W, C);
+    else hipLaunchKernelGGL(pixel_shuffle_kernel<float>, up_grid(n), dim3(256), 0, s, (const float*)x, (float*)y, B, F + 2, H, W, C);
+    LTX_CHECK_LAUNCH();
     return LTX_OK;
 }

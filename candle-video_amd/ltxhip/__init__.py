@@ -275,6 +275,26 @@ for _name, _sig in _UP_SIGS.items():
     _fn.argtypes = _sig
     _fn.restype = None if _name in ("ltx_upsampler_config_default", "ltx_upsampler_destroy") else C.c_int
 LTX_GN_SILU, LTX_GN_GUARDS = 1, 2
+
+
+class UpsamplerStConfigC(C.Structure):           # ltx_upsampler_st_config (include/ltxhip_upsampler_st.h)
+    _fields_ = [("in_channels", C.c_int), ("mid_channels", C.c_int), ("num_blocks_per_stage", C.c_int),
+                ("spatial_upsample", C.c_int), ("temporal_upsample", C.c_int)]
+
+
+# include/ltxhip_upsampler_st.h (kept apart like the four above)
+_UP_ST_SIGS = {
+    "ltx_upsampler_st_config_default": [_vp], "ltx_upsampler_create_st": [_vp, _vp, _sz, _i, _i, _vp],
+    "ltx_upsampler_create_from_file_st": [_vp, C.c_char_p, _i, _i, _vp], "ltx_upsampler_get_st_config": [_vp, _vp],
+    "ltx_upsampler_out_shape": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "ltx_op_conv3d_shuffle": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ltx_op_pixel_shuffle_guarded": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+}
+UPSAMPLER_ST_SYMBOLS = sorted(_UP_ST_SIGS)
+for _name, _sig in _UP_ST_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = None if _name == "ltx_upsampler_st_config_default" else C.c_int
 # the ten LoRA targets of a block, in the order of ltx_dit_read_linear's `which`
 LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0",
                 "ff.net.0.proj", "ff.net.2")
@@ -1253,20 +1273,34 @@ class LatentUpsamplerConfig:
     in_channels: int = 128
     mid_channels: int = 512
     num_blocks_per_stage: int = 4
+    spatial_upsample: bool = True         # (True, False): the spatial kind of ltxhip_upsampler.h; the others: ltxhip_upsampler_st.h
+    temporal_upsample: bool = False
 
     def to_c(self) -> "UpsamplerConfigC":
         return UpsamplerConfigC(self.in_channels, self.mid_channels, self.num_blocks_per_stage)
 
+    def to_st_c(self) -> "UpsamplerStConfigC":
+        return UpsamplerStConfigC(self.in_channels, self.mid_channels, self.num_blocks_per_stage, int(self.spatial_upsample), int(self.temporal_upsample))
+
+    @property
+    def is_spatial_kind(self) -> bool:
+        return bool(self.spatial_upsample) and not self.temporal_upsample
+
 
 class LatentUpsampler:
-    """The latent upsampler (spatial x2 in latent space) over ltx_upsampler_*; weight names as in the header."""
+    """The latent upsampler over ltx_upsampler_*: spatial (H, W x2), temporal (F -> 2F - 1) or both, by the config's two flags; weight
+    names as in the headers.  The spatial kind goes through the constructors of ltxhip_upsampler.h, the others through the _st ones."""
 
     def __init__(self, config: LatentUpsamplerConfig, weights: Dict[str, torch.Tensor], dtype: torch.dtype = torch.bfloat16, device: int = 0):
         self.config, self.dtype = config, dtype
         c = config.to_c()
         arr, keep = _make_weights(weights)
         self._h = C.c_void_p()
-        _check(lib.ltx_upsampler_create(C.byref(c), arr, C.c_size_t(len(weights)), _dt(dtype), device, C.byref(self._h)))
+        if config.is_spatial_kind:
+            _check(lib.ltx_upsampler_create(C.byref(c), arr, C.c_size_t(len(weights)), _dt(dtype), device, C.byref(self._h)))
+        else:
+            cs = config.to_st_c()
+            _check(lib.ltx_upsampler_create_st(C.byref(cs), arr, C.c_size_t(len(weights)), _dt(dtype), device, C.byref(self._h)))
         del keep
 
     @classmethod
@@ -1275,7 +1309,11 @@ class LatentUpsampler:
         self.config, self.dtype = config, dtype
         c = config.to_c()
         self._h = C.c_void_p()
-        _check(lib.ltx_upsampler_create_from_file(C.byref(c), path.encode(), _dt(dtype), device, C.byref(self._h)))
+        if config.is_spatial_kind:
+            _check(lib.ltx_upsampler_create_from_file(C.byref(c), path.encode(), _dt(dtype), device, C.byref(self._h)))
+        else:
+            cs = config.to_st_c()
+            _check(lib.ltx_upsampler_create_from_file_st(C.byref(cs), path.encode(), _dt(dtype), device, C.byref(self._h)))
         return self
 
     def __del__(self):
@@ -1289,23 +1327,35 @@ class LatentUpsampler:
         _check(lib.ltx_upsampler_get_config(self._h, C.byref(c)))
         return c
 
+    def get_st_config(self) -> "UpsamplerStConfigC":
+        c = UpsamplerStConfigC()
+        _check(lib.ltx_upsampler_get_st_config(self._h, C.byref(c)))
+        return c
+
+    def out_shape(self, F: int, H: int, W: int) -> Tuple[int, int, int]:
+        """the latent grid (Fo, Ho, Wo) this handle maps (F, H, W) to (ltx_upsampler_out_shape; host only)"""
+        fo, ho, wo = C.c_int(), C.c_int(), C.c_int()
+        _check(lib.ltx_upsampler_out_shape(self._h, int(F), int(H), int(W), C.byref(fo), C.byref(ho), C.byref(wo)))
+        return fo.value, ho.value, wo.value
+
     def forward(self, latents: torch.Tensor) -> torch.Tensor:
-        """[B, in_channels, F, H, W] (f32 or bf16, un-normalised) -> [B, in_channels, F, 2H, 2W] of the same dtype"""
+        """[B, in_channels, F, H, W] (f32 or bf16, un-normalised) -> [B, in_channels, *out_shape(F, H, W)] of the same dtype"""
         io = latents.dtype if latents.dtype in (torch.float32, torch.bfloat16) else torch.float32
         z = _dev(latents, io)
         if z.dim() != 5 or z.shape[1] != self.config.in_channels:
             raise LtxError("latents must be [B, in_channels, F, H, W]")
         B, Cn, F, H, W = z.shape
-        out = torch.empty(B, Cn, F, 2 * H, 2 * W, dtype=io, device=z.device)
+        out = torch.empty(B, Cn, *self.out_shape(F, H, W), dtype=io, device=z.device)
         _check(lib.ltx_upsampler_forward(self._h, _ptr(z), _dt(io), B, F, H, W, _ptr(out), _stream()))
         return out
 
     def upsample_tokens(self, vae: "AutoencoderKLLtxVideo", tokens: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
-        """packed normalised tokens [B, F*H*W, C] f32 -> [B, F*2H*2W, C] f32 (un-normalise, forward, normalise)"""
+        """packed normalised tokens [B, F*H*W, C] f32 -> [B, Fo*Ho*Wo, C] f32 (un-normalise, forward, normalise)"""
         t = _dev(tokens, torch.float32)
         B = t.shape[0]
         _expect("tokens", t, (B, F * H * W, self.config.in_channels))
-        out = torch.empty(B, F * 4 * H * W, self.config.in_channels, dtype=torch.float32, device=t.device)
+        fo, ho, wo = self.out_shape(F, H, W)
+        out = torch.empty(B, fo * ho * wo, self.config.in_channels, dtype=torch.float32, device=t.device)
         _check(lib.ltx_latent_upsample_tokens(self._h, vae._h, _ptr(t), B, F, H, W, _ptr(out), _stream()))
         return out
 
@@ -1379,7 +1429,7 @@ class LtxMultiScalePipeline:
              prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
              negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
              decode_noise: Optional[torch.Tensor] = None, adain_factor: float = 1.0, interrupt=None, on_step=None):
-        """Returns (first-pass latents [B,S,C], second-pass latents [B,4S,C], video or None).  interrupt / on_step as LtxPipeline.call;
+        """Returns (first-pass latents [B,S,C], second-pass latents [B,Fo*Ho*Wo,C] (4S for the spatial kind), video or None).  interrupt / on_step as LtxPipeline.call;
         both passes see them."""
         lo = _dev(latents_lo, torch.float32).clone()
         nh = _dev(noise_hi, torch.float32)
@@ -1395,14 +1445,16 @@ class LtxMultiScalePipeline:
         F, H, W = (first.num_frames - 1) // tr + 1, first.height // sr, first.width // sr
         Cin = self.transformer.config.in_channels
         S = F * H * W
+        Fo, Ho, Wo = self.upsampler.out_shape(F, H, W)
+        S_hi = Fo * Ho * Wo
         # the C entry takes raw pointers: every tensor is checked against the geometry first
         _expect("latents_lo", lo, (B, S, Cin))
-        _expect("noise_hi", nh, (B, 4 * S, Cin))
+        _expect("noise_hi", nh, (B, S_hi, Cin))
         _expect("prompt_embeds", pe, (B, K, self.transformer.config.caption_channels))
         _expect("prompt_attention_mask", pm, (B, K))
         if ne is not None: _expect("negative_prompt_embeds", ne, (B, K, self.transformer.config.caption_channels))
         if nm is not None: _expect("negative_prompt_attention_mask", nm, (B, K))
-        if dn is not None: _expect("decode_noise", dn, (B, Cin, F, 2 * H, 2 * W))
+        if dn is not None: _expect("decode_noise", dn, (B, Cin, Fo, Ho, Wo))
         keep = []
         p1, p2 = _params_c(first, self.vae, keep), _params_c(second, self.vae, keep)
         hook_exc = []
@@ -1419,13 +1471,13 @@ class LtxMultiScalePipeline:
             cb = StepFn(_hook); keep.append(cb)
             p1.on_step = C.cast(cb, C.c_void_p)
             p2.on_step = C.cast(cb, C.c_void_p)
-        hi = torch.empty(B, 4 * S, Cin, dtype=torch.float32, device=lo.device)
+        hi = torch.empty(B, S_hi, Cin, dtype=torch.float32, device=lo.device)
         video = None
         if not second.output_latent:
             if second.output_rgb8:
-                video = torch.empty(B, (F - 1) * tr + 1, 2 * H * sr, 2 * W * sr, 3, dtype=torch.uint8, device=lo.device)
+                video = torch.empty(B, (Fo - 1) * tr + 1, Ho * sr, Wo * sr, 3, dtype=torch.uint8, device=lo.device)
             else:
-                video = torch.empty(B, 3, (F - 1) * tr + 1, 2 * H * sr, 2 * W * sr, dtype=torch.float32, device=lo.device)
+                video = torch.empty(B, 3, (Fo - 1) * tr + 1, Ho * sr, Wo * sr, dtype=torch.float32, device=lo.device)
         _check(lib.ltx_pipeline_call_multiscale(self.transformer._h, self.vae._h, self.upsampler._h, C.byref(p1), C.byref(p2), float(adain_factor),
                                                 _ptr(lo), _ptr(nh), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
                                                 _ptr(hi), _ptr(video), _stream()))
@@ -1931,6 +1983,36 @@ class ops:
         _check(lib.ltx_op_upsample3d(_ptr(x_cl.contiguous()), _ptr(w.contiguous()), _ptr(bias.to(w.dtype).contiguous()), _dt(w.dtype), _ptr(y),
                                      B, T, H, W, Cin, Cout, int(causal), int(residual), _dt(x_cl.dtype), _stream()))
         return y
+
+    @staticmethod
+    def conv3d_shuffle(x_cl, w, bias, st, ss, out=None):
+        """The latent upsampler's shuffle stage (ltx_op_conv3d_shuffle): x_cl [B, F + 2, H, W, Cin] channels-last with zero guard
+        frames, w [O, Cin, 3, 3, 3], factors (st, ss) one of (2,1), (2,2), (1,2) -> the guarded [B, Fo + 2, Ho, Wo, O / (st*ss*ss)].
+        out: a pre-allocated (pre-filled) output of that shape, for tests that watch what the kernel leaves alone."""
+        x = x_cl.contiguous()
+        B, Ft, H, W, Cin = x.shape
+        F = Ft - 2
+        O = w.shape[0]
+        nsub = st * ss * ss
+        shape = (B, (2 * F - 1 if st == 2 else F) + 2, ss * H, ss * W, O // max(nsub, 1))
+        if out is None:
+            out = torch.empty(shape, dtype=x.dtype, device=x.device)
+        elif tuple(out.shape) != shape or out.dtype != x.dtype or not out.is_contiguous():
+            raise LtxError(f"conv3d_shuffle: out must be a contiguous {shape} tensor of the input's dtype")
+        _check(lib.ltx_op_conv3d_shuffle(_ptr(x), _ptr(w.contiguous()), _ptr(bias.to(w.dtype).contiguous()), _dt(w.dtype), _ptr(out),
+                                         B, F, H, W, Cin, O, int(st), int(ss), _dt(x.dtype), _stream()))
+        return out
+
+    @staticmethod
+    def pixel_shuffle_guarded(x_cl, out=None):
+        """the spatial kind's stand-alone shuffle pass (ltx_op_pixel_shuffle_guarded): x_cl [B, F + 2, H, W, 4C], channel s*C + c ->
+        [B, F + 2, 2H, 2W, C] with zero guard frames; asynchronous"""
+        x = x_cl.contiguous()
+        B, Ft, H, W, C4 = x.shape
+        if out is None:
+            out = torch.empty(B, Ft, 2 * H, 2 * W, C4 // 4, dtype=x.dtype, device=x.device)
+        _check(lib.ltx_op_pixel_shuffle_guarded(_ptr(x), _ptr(out), B, Ft - 2, H, W, C4 // 4, _dt(x.dtype), _stream()))
+        return out
 
     @staticmethod
     def downsample3d(x_cl, w, bias, down_type):

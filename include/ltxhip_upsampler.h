@@ -42,7 +42,9 @@ int ltx_upsampler_create_from_file(const ltx_upsampler_config* cfg, const char* 
 void ltx_upsampler_destroy(ltx_upsampler* up);
 int ltx_upsampler_get_config(const ltx_upsampler* up, ltx_upsampler_config* out);
 
-/* latents [B,in_channels,F,H,W] io_dtype -> out [B,in_channels,F,2H,2W] io_dtype (un-normalised latents, as the VAE decodes them) */
+/* latents [B,in_channels,F,H,W] io_dtype -> out [B,in_channels,F,2H,2W] io_dtype (un-normalised latents, as the VAE decodes them).
+ * A handle of another kind (ltxhip_upsampler_st.h) writes [B,in_channels,Fo,Ho,Wo], the grid of ltx_upsampler_out_shape; the same holds
+ * for ltx_latent_upsample_tokens ([B, Fo*Ho*Wo, C]) and ltx_upsampler_warmup below. */
 int ltx_upsampler_forward(ltx_upsampler* up, const void* latents, ltx_dtype io_dtype, int B, int F, int H, int W, void* out, ltx_stream stream);
 
 /* The round trip on the packed tokens the denoise loop carries:
@@ -76,7 +78,10 @@ int ltx_upsampler_warmup(ltx_upsampler* up, int B, int F, int H, int W, ltx_stre
  *   ltx_latent_adain(latents_hi_out, latents_lo, B, 4 S, S, C, adain_factor)
  *   ltx_latent_renoise(latents_hi_out, noise_hi, ltx_pipeline_first_sigma(p_second, 4 S), B * 4 S * C)
  *   ltx_pipeline_call(dit, vae, p_second, latents_hi_out, ..., decode_noise, out_video)
- * p_second->height / width must be exactly twice p_first's and num_frames equal, else LTX_ERR_ARG.
+ * p_second->height / width must be exactly twice p_first's and num_frames equal, else LTX_ERR_ARG.  (The rule follows the handle's
+ * kind, ltxhip_upsampler_st.h: a temporal or spatiotemporal handle needs p_second->num_frames == 2 * p_first->num_frames - 1, a temporal
+ * one equal height and width; noise_hi and latents_hi_out are then [B, Fo*Ho*Wo, C], decode_noise [B, C, Fo, Ho, Wo], and the caller
+ * owns p_second->frame_rate.)
  *   latents_lo     [B, S, C] f32, the first pass's start noise; holds the first pass's result afterwards
  *   noise_hi       [B, 4 S, C] f32, the noise of the re-noise step
  *   latents_hi_out [B, 4 S, C] f32, the second pass's latents (its result afterwards)

@@ -702,7 +702,9 @@ impl HipVae {
 // Latent upsampler (include/ltxhip_upsampler.h): the step between the two passes of the multi-scale recipe
 // ------------------------------------------------------------------------------------------------------------------
 
-/// The latent upsampler (Conv3d + GroupNorm network, spatial x2 in latent space); no counterpart in the reference.
+/// The latent upsampler (Conv3d + GroupNorm network); no counterpart in the reference.  `from_file` loads the spatial kind (H, W x2),
+/// `from_file_st` any kind of include/ltxhip_upsampler_st.h: temporal (F -> 2F - 1 latent frames) or spatiotemporal.  Both give the same
+/// handle; `out_shape` tells the grid a handle writes, and `upsample_tokens` sizes its result by it.
 pub struct HipLatentUpsampler {
     h: *mut sys::ltx_upsampler,
     ccfg: sys::ltx_upsampler_config,
@@ -717,7 +719,22 @@ impl HipLatentUpsampler {
         Ok(Self { h, ccfg: *cfg, device: device as c_int })
     }
 
-    /// packed normalised tokens [B, F*H*W, C] f32 -> [B, F*2H*2W, C] f32 with `vae`'s latent statistics (ltx_latent_upsample_tokens)
+    pub fn from_file_st(cfg: &sys::ltx_upsampler_st_config, path: &Path, dtype: DType, device: usize) -> Result<Self> {
+        let cpath = CString::new(path.to_string_lossy().as_bytes()).map_err(candle_core::Error::wrap)?;
+        let mut h: *mut sys::ltx_upsampler = ptr::null_mut();
+        check(unsafe { sys::ltx_upsampler_create_from_file_st(cfg, cpath.as_ptr(), model_dtype(dtype)?, device as c_int, &mut h) })?;
+        let ccfg = sys::ltx_upsampler_config { in_channels: cfg.in_channels, mid_channels: cfg.mid_channels, num_blocks_per_stage: cfg.num_blocks_per_stage };
+        Ok(Self { h, ccfg, device: device as c_int })
+    }
+
+    /// the latent grid (Fo, Ho, Wo) this handle maps (F, H, W) to (ltx_upsampler_out_shape; host only)
+    pub fn out_shape(&self, f: usize, h: usize, w: usize) -> Result<(usize, usize, usize)> {
+        let (mut fo, mut ho, mut wo) = (0 as c_int, 0 as c_int, 0 as c_int);
+        check(unsafe { sys::ltx_upsampler_out_shape(self.h as *const sys::ltx_upsampler, f as c_int, h as c_int, w as c_int, &mut fo, &mut ho, &mut wo) })?;
+        Ok((fo as usize, ho as usize, wo as usize))
+    }
+
+    /// packed normalised tokens [B, F*H*W, C] f32 -> [B, Fo*Ho*Wo, C] f32 (F*2H*2W for the spatial kind) with `vae`'s latent statistics (ltx_latent_upsample_tokens)
     pub fn upsample_tokens(&self, vae: &HipVae, tokens: &Tensor, f: usize, h: usize, w: usize) -> Result<Tensor> {
         let (b, s, c) = tokens.dims3()?;
         if s != f * h * w || c != self.ccfg.in_channels as usize {
@@ -727,7 +744,9 @@ impl HipLatentUpsampler {
         let mut xin = DeviceBuf::new(self.device);
         let mut out_d = DeviceBuf::new(self.device);
         let x_d = xin.upload(&x)?;
-        let n = b * 4 * s * c;
+        let (fo, ho, wo) = self.out_shape(f, h, w)?;
+        let s_hi = fo * ho * wo;
+        let n = b * s_hi * c;
         let o_d = out_d.ensure(n * 4)?;
         check(unsafe {
             sys::ltx_latent_upsample_tokens(self.h, vae.h as *const sys::ltx_vae, x_d as *const f32, b as c_int, f as c_int, h as c_int, w as c_int,
@@ -736,7 +755,7 @@ impl HipLatentUpsampler {
         let mut out = vec![0f32; n];
         check(unsafe { sys::ltx_memcpy_d2h(out.as_mut_ptr() as *mut c_void, o_d as *const c_void, n * 4, ptr::null_mut()) })?;
         check(unsafe { sys::ltx_stream_synchronize(ptr::null_mut()) })?;
-        Tensor::from_vec(out, (b, 4 * s, c), &Device::Cpu)
+        Tensor::from_vec(out, (b, s_hi, c), &Device::Cpu)
     }
 
     pub fn raw(&self) -> *mut sys::ltx_upsampler {

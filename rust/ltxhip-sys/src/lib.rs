@@ -355,3 +355,32 @@ extern "C" {
     pub fn ltx_op_groupnorm(x: *const c_void, y: *mut c_void, resid: *const c_void, weight: *const c_void, bias: *const c_void, b: c_int, f: c_int, h: c_int,
                             w: c_int, c: c_int, groups: c_int, eps: c_float, flags: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_upsampler_st.h: the temporal and spatiotemporal kinds of the latent upsampler (the same handle type) ----
+
+/// `ltx_upsampler_st_config`: the upsampler network and its kind (both flags 0 is refused; (1, 0) is the spatial kind).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_upsampler_st_config {
+    pub in_channels: c_int,
+    pub mid_channels: c_int,
+    pub num_blocks_per_stage: c_int,
+    pub spatial_upsample: c_int,
+    pub temporal_upsample: c_int,
+}
+
+pub const UPSAMPLER_ST_LAYOUT_LTX_UPSAMPLER_ST_CONFIG: (usize, usize) = (20, 4);
+const _: () = assert!(size_of::<ltx_upsampler_st_config>() == UPSAMPLER_ST_LAYOUT_LTX_UPSAMPLER_ST_CONFIG.0 && align_of::<ltx_upsampler_st_config>() == UPSAMPLER_ST_LAYOUT_LTX_UPSAMPLER_ST_CONFIG.1);
+
+extern "C" {
+    pub fn ltx_upsampler_st_config_default(cfg: *mut ltx_upsampler_st_config);
+    pub fn ltx_upsampler_create_st(cfg: *const ltx_upsampler_st_config, weights: *const ltx_weight, n_weights: usize, model_dtype: c_int, device: c_int,
+                                   out: *mut *mut ltx_upsampler) -> c_int;
+    pub fn ltx_upsampler_create_from_file_st(cfg: *const ltx_upsampler_st_config, path: *const c_char, model_dtype: c_int, device: c_int,
+                                             out: *mut *mut ltx_upsampler) -> c_int;
+    pub fn ltx_upsampler_get_st_config(up: *const ltx_upsampler, out: *mut ltx_upsampler_st_config) -> c_int;
+    pub fn ltx_upsampler_out_shape(up: *const ltx_upsampler, f: c_int, h: c_int, w: c_int, fo: *mut c_int, ho: *mut c_int, wo: *mut c_int) -> c_int;
+    pub fn ltx_op_conv3d_shuffle(x: *const c_void, w: *const c_void, bias: *const c_void, wdtype: c_int, y: *mut c_void, b: c_int, f: c_int, h: c_int,
+                                 wd: c_int, cin: c_int, o: c_int, st: c_int, ss: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_pixel_shuffle_guarded(x: *const c_void, y: *mut c_void, b: c_int, f: c_int, h: c_int, w: c_int, c: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
+}
