@@ -13,10 +13,14 @@
 //     accumulator values a lane owns are contiguous in the destination).
 // The packed token layout the denoise loop carries ([B, F*H*W, 128]) IS channels-last, so
 // unpack_latents is free on this path.
+//
+// Tiling: the geometry of both sides' tiled paths is a VaeTilePlan (host/tile_plan.h), built once per call; this file only
+// walks it - assemble_spatial (tiles of a plane), place_temporal (windows of frames), batched_leaf_decode (the plan's leaves).
 #include <cstring>
 #include <deque>
 #include "conv3d.h"
 #include "options.h"
+#include "../host/tile_plan.h"
 #include "../../include/ltxhip_frames.h"
 #include "../../include/ltxhip_encoder.h"
 #include "../../include/ltxhip_ops.h"
@@ -318,68 +322,50 @@ int crop_cl(const void* src, void* dst, size_t esz, int B, int T, int H, int W, 
     return LTX_OK;
 }
 
-struct Tile { float* p; int t, h, w; };   // decoded f32 NCTHW tile [B*3, t, h, w]
+struct Tile { float* p; int t, h, w; };   // f32 NCTHW tile [BC, t, h, w]: decoded samples, or encoded moments
 
-// tiled_decode (vae.rs:2225-2290) of a channels-last latent window; result into `out` (dims oT,oH,oW given)
-// `pre` (optional): the leaf tiles already decoded, in this loop's order (batched_leaf_decode) - then nothing is decoded here.
-int tiled_decode(ltx_vae* v, const void* z, int B, int F, int H, int W, const TimeVec* tv, const ltx_tiling& tl,
-                 float* out, std::deque<DevBuf>& pool, size_t& pool_used, hipStream_t s, const std::vector<float*>* pre = nullptr) {
-    const ltx_vae_config& c = v->cfg;
-    const int r = c.spatial_compression_ratio, tr = c.temporal_compression_ratio;
-    const size_t esz = ltx_dt_size(v->dtype);
-    const int tmin_h = tl.tile_sample_min_height / r, tmin_w = tl.tile_sample_min_width / r;
-    const int ts_h = tl.tile_sample_stride_height / r, ts_w = tl.tile_sample_stride_width / r;
-    if (ts_h < 1 || ts_w < 1) LTX_FAIL(LTX_ERR_ARG, "tiling: stride must be >= one latent");
-    const int blend_h = std::max(tl.tile_sample_min_height - tl.tile_sample_stride_height, 0);
-    const int blend_w = std::max(tl.tile_sample_min_width - tl.tile_sample_stride_width, 0);
-    const int oT = (F - 1) * tr + 1, oH = H * r, oW = W * r, BC = B * c.out_channels;
-    auto take = [&](size_t bytes, DevBuf** b) -> int {
+// The spatial walk of tiled_decode and tiled_encode (vae.rs:2259-2290 / :2190-2223): per tile of the plan, row-major,
+// produce(row span, col span, take, &tile) fills the tile (take(bytes, &p): the next buffer of `pool`); then blend_v with the
+// (already blended) tile above, blend_h with the one to the left, and the tile's kept corner goes into `out` [BC, tile.t, oH, oW].
+template <typename Produce>
+int assemble_spatial(const VaeTilePlan& plan, Produce produce, int BC, float* out, std::deque<DevBuf>& pool, hipStream_t s) {
+    size_t pool_used = 0;
+    auto take = [&](size_t bytes, float** p) -> int {
         if (pool_used >= pool.size()) pool.emplace_back();
-        *b = &pool[pool_used++];
-        return (*b)->ensure(bytes);
+        DevBuf& b = pool[pool_used++];
+        LTX_TRY(b.ensure(bytes));
+        *p = b.as<float>();
+        return LTX_OK;
     };
     std::vector<Tile> prev, cur;
-    int oy = 0; size_t leaf = 0;
-    for (int i = 0; i < H; i += ts_h) {
+    int oy = 0;
+    for (size_t ri = 0; ri < plan.rows.size(); ++ri) {
         cur.clear();
-        int ox = 0; int row_h = 0;
-        for (int j = 0; j < W; j += ts_w) {
-            const int h1 = std::min(i + tmin_h, H), w1 = std::min(j + tmin_w, W);
-            const int th = h1 - i, tw = w1 - j;
-            Tile t; t.t = oT; t.h = th * r; t.w = tw * r;
-            if (pre) {
-                if (leaf >= pre->size()) LTX_FAIL(LTX_ERR_ARG, "tiled decode: fewer pre-decoded leaves than tiles");
-                t.p = (*pre)[leaf++];
-            } else {
-                LTX_TRY(v->tile_lat.ensure((size_t)B * F * th * tw * c.latent_channels * esz));
-                LTX_TRY(crop_cl(z, v->tile_lat.p, esz, B, F, H, W, c.latent_channels, 0, F, i, h1, j, w1, s));
-                DevBuf* tb = nullptr;
-                LTX_TRY(take((size_t)BC * t.t * t.h * t.w * sizeof(float), &tb));
-                t.p = tb->as<float>();
-                LTX_TRY(decoder_forward(v, v->tile_lat.p, B, F, th, tw, tv, 0, t.p, s));
-            }
-            const size_t ci = cur.size();
-            if (!prev.empty()) {        // blend_v with the (already blended) tile above
+        int ox = 0, row_h = 0;
+        for (size_t ci = 0; ci < plan.cols.size(); ++ci) {
+            Tile t{};
+            LTX_TRY(produce(plan.rows[ri], plan.cols[ci], take, &t));
+            if (ri > 0) {               // blend_v
                 BlendArgs ba; ba.a = prev[ci].p; ba.b = t.p; ba.dst = t.p; ba.BC = BC;
                 ba.at = prev[ci].t; ba.ah = prev[ci].h; ba.aw = prev[ci].w; ba.a_len = prev[ci].h;
                 ba.bt = ba.dt = t.t; ba.bh = ba.dh = t.h; ba.bw = ba.dw = t.w;
-                ba.dim = 3; ba.blend = std::min(blend_h, std::min(prev[ci].h, t.h));
+                ba.dim = 3; ba.blend = std::min(plan.blend_h, std::min(prev[ci].h, t.h));
                 ba.et = t.t; ba.eh = ba.blend; ba.ew = std::min(t.w, prev[ci].w);
                 LTX_TRY(ltx_launch_blend(ba, s));
             }
-            if (ci > 0) {               // blend_h with the (already blended) tile to the left
+            if (ci > 0) {               // blend_h
                 BlendArgs ba; ba.a = cur[ci - 1].p; ba.b = t.p; ba.dst = t.p; ba.BC = BC;
                 ba.at = cur[ci - 1].t; ba.ah = cur[ci - 1].h; ba.aw = cur[ci - 1].w; ba.a_len = cur[ci - 1].w;
                 ba.bt = ba.dt = t.t; ba.bh = ba.dh = t.h; ba.bw = ba.dw = t.w;
-                ba.dim = 4; ba.blend = std::min(blend_w, std::min(cur[ci - 1].w, t.w));
+                ba.dim = 4; ba.blend = std::min(plan.blend_w, std::min(cur[ci - 1].w, t.w));
                 ba.et = t.t; ba.eh = std::min(t.h, cur[ci - 1].h); ba.ew = ba.blend;
                 LTX_TRY(ltx_launch_blend(ba, s));
             }
             cur.push_back(t);
-            const int hs = std::min(tl.tile_sample_stride_height, t.h), ws = std::min(tl.tile_sample_stride_width, t.w);
-            const int ch = std::min(hs, oH - oy), cw_ = std::min(ws, oW - ox);
+            const int hs = std::min(plan.keep_h, t.h), ws = std::min(plan.keep_w, t.w);
+            const int ch = std::min(hs, plan.oH - oy), cw_ = std::min(ws, plan.oW - ox);
             if (ch > 0 && cw_ > 0)
-                LTX_TRY(ltx_launch_copy_window(t.p, t.t, t.h, t.w, out, oT, oH, oW, BC, oT, ch, cw_, 0, oy, ox, s));
+                LTX_TRY(ltx_launch_copy_window(t.p, t.t, t.h, t.w, out, t.t, plan.oH, plan.oW, BC, t.t, ch, cw_, 0, oy, ox, s));
             ox += ws; row_h = hs;
         }
         oy += row_h;
@@ -388,33 +374,74 @@ int tiled_decode(ltx_vae* v, const void* z, int B, int F, int H, int W, const Ti
     return LTX_OK;
 }
 
+// One step of the temporal walks (vae.rs:2400-2434 / :2322-2347): window li arrives as `buf` [BC, phys, oH, oW]; the plan says
+// which frame it loses and how many it gives.  Those go into `out` at frame `ot`, blended against the RAW previous window
+// (row[idx - 1], not its blended form), which *prev carries from step to step.
+struct TWin { const float* p = nullptr; int len = 0, phys = 0; };   // logical start, logical length, physical frame count
+int place_temporal(const VaeTilePlan& plan, int li, const float* buf, int phys, TWin* prev, int BC, float* out, int ot, int* keep, hipStream_t s) {
+    const VaeTilePlan::Frames f = plan.frames(li, phys);
+    const TWin cur{buf + (size_t)f.skip * plan.oH * plan.oW, f.len, phys};
+    const int n = std::min(f.keep, plan.oT - ot);
+    if (n > 0) {
+        LTX_TRY(ltx_launch_copy_window(cur.p, phys, plan.oH, plan.oW, out, plan.oT, plan.oH, plan.oW, BC, n, plan.oH, plan.oW, ot, 0, 0, s));
+        if (li > 0) {
+            BlendArgs ba; ba.a = prev->p; ba.b = cur.p; ba.dst = out; ba.BC = BC;
+            ba.at = prev->phys; ba.ah = plan.oH; ba.aw = plan.oW; ba.a_len = prev->len;
+            ba.bt = phys; ba.bh = plan.oH; ba.bw = plan.oW; ba.dt = plan.oT; ba.dh = plan.oH; ba.dw = plan.oW; ba.ot = ot;
+            ba.dim = 2; ba.blend = std::min(plan.blend_t, std::min(prev->len, cur.len));
+            ba.et = std::min(ba.blend, n); ba.eh = plan.oH; ba.ew = plan.oW;
+            LTX_TRY(ltx_launch_blend(ba, s));
+        }
+    }
+    *prev = cur; *keep = f.keep;
+    return LTX_OK;
+}
+
+// tiled_decode (vae.rs:2225-2290) of a channels-last latent window of F frames; result into `out` [BC, (F-1)*tr+1, oH, oW]
+// `pre` (optional): the window's leaf tiles already decoded, in plan order (batched_leaf_decode) - then nothing is decoded here.
+int tiled_decode(ltx_vae* v, const void* z, int B, int F, int H, int W, const TimeVec* tv, const VaeTilePlan& plan,
+                 float* out, hipStream_t s, const std::vector<float*>* pre = nullptr) {
+    const ltx_vae_config& c = v->cfg;
+    const int r = c.spatial_compression_ratio, BC = B * c.out_channels;
+    const size_t esz = ltx_dt_size(v->dtype);
+    auto dims = [&](TileSpan row, TileSpan col, Tile* t) { t->t = (F - 1) * c.temporal_compression_ratio + 1; t->h = (row.i1 - row.i0) * r; t->w = (col.i1 - col.i0) * r; };
+    size_t leaf = 0;
+    auto next_leaf = [&](TileSpan row, TileSpan col, auto&, Tile* t) -> int {
+        if (leaf >= pre->size()) LTX_FAIL(LTX_ERR_ARG, "tiled decode: fewer pre-decoded leaves than tiles");
+        dims(row, col, t); t->p = (*pre)[leaf++];
+        return LTX_OK;
+    };
+    auto decode_tile = [&](TileSpan row, TileSpan col, auto& take, Tile* t) -> int {
+        const int th = row.i1 - row.i0, tw = col.i1 - col.i0;
+        dims(row, col, t);
+        LTX_TRY(v->tile_lat.ensure((size_t)B * F * th * tw * c.latent_channels * esz));
+        LTX_TRY(crop_cl(z, v->tile_lat.p, esz, B, F, H, W, c.latent_channels, 0, F, row.i0, row.i1, col.i0, col.i1, s));
+        LTX_TRY(take((size_t)BC * t->t * t->h * t->w * sizeof(float), &t->p));
+        return decoder_forward(v, v->tile_lat.p, B, F, th, tw, tv, 0, t->p, s);
+    };
+    return pre ? assemble_spatial(plan, next_leaf, BC, out, v->tilebufs, s) : assemble_spatial(plan, decode_tile, BC, out, v->tilebufs, s);
+}
+
 // Leaf tiles of the framewise + spatially tiled decode, decoded up front in batches.  The reference's tiled decode is a serial
 // loop of independent `decoder.forward` calls on small latents (vae.rs:2382-2408 around :2246-2257; C2: 52 calls of at most
 // 3 x 16 x 16 latents), whose first stages cannot fill the chip one tile at a time (the mid block of one tile is 768
 // voxels).  Leaves that share a latent shape - the same spatial tile of different temporal windows - are stacked along the
 // batch axis (up to 16 samples per decoder call), and the blends then run over the decoded tiles in exactly the reference's
 // order (tiled_decode with `pre`).  A decoder call on a batch gives each sample the bits it gets alone: no op crosses samples.
-// per_window[li] = the window's leaves in tiled_decode's loop order.  LTX_VAE_TILE_BATCH=0: one call per leaf (A/B aid).
-int batched_leaf_decode(ltx_vae* v, const void* z, int B, int F, int H, int W, const TimeVec* tv, const ltx_tiling& tl,
+// per_window[li] = the window's leaves in plan order, rows x cols.  LTX_VAE_TILE_BATCH=0: one call per leaf (A/B aid).
+int batched_leaf_decode(ltx_vae* v, const void* z, int B, int F, int H, int W, const TimeVec* tv, const VaeTilePlan& plan,
                         std::vector<std::vector<float*>>& per_window, hipStream_t s) {
     const ltx_vae_config& c = v->cfg;
     const int r = c.spatial_compression_ratio, tr = c.temporal_compression_ratio;
     const size_t esz = ltx_dt_size(v->dtype);
-    const int tmin_t = tl.tile_sample_min_num_frames / tr, tstride_t = tl.tile_sample_stride_num_frames / tr;
-    const int tmin_h = tl.tile_sample_min_height / r, tmin_w = tl.tile_sample_min_width / r;
-    const int ts_h = tl.tile_sample_stride_height / r, ts_w = tl.tile_sample_stride_width / r;
-    if (tstride_t < 1 || ts_h < 1 || ts_w < 1) LTX_FAIL(LTX_ERR_ARG, "tiling: stride must be >= one latent");
     struct Leaf { int li, slot, t0, t1, h0, h1, w0, w1; };
     std::vector<Leaf> leaves;
-    int nwin = 0;
-    for (int i = 0; i < F; i += tstride_t, ++nwin) {
-        const int t1 = std::min(i + tmin_t + 1, F);
+    for (size_t li = 0; li < plan.windows.size(); ++li) {
         int slot = 0;
-        for (int y = 0; y < H; y += ts_h)
-            for (int x = 0; x < W; x += ts_w) leaves.push_back({nwin, slot++, i, t1, y, std::min(y + tmin_h, H), x, std::min(x + tmin_w, W)});
+        for (const TileSpan& row : plan.rows)
+            for (const TileSpan& col : plan.cols) leaves.push_back({(int)li, slot++, plan.windows[li].i0, plan.windows[li].i1, row.i0, row.i1, col.i0, col.i1});
     }
-    per_window.assign(nwin, {});
-    for (const Leaf& l : leaves) if ((int)per_window[l.li].size() <= l.slot) per_window[l.li].resize(l.slot + 1, nullptr);
+    per_window.assign(plan.windows.size(), std::vector<float*>(plan.rows.size() * plan.cols.size(), nullptr));
     auto elems = [&](const Leaf& l) { return (size_t)B * c.out_channels * ((size_t)(l.t1 - l.t0 - 1) * tr + 1) * ((size_t)(l.h1 - l.h0) * r) * ((size_t)(l.w1 - l.w0) * r); };
     size_t total = 0;
     for (const Leaf& l : leaves) total += elems(l);
@@ -474,73 +501,44 @@ int batched_leaf_decode(ltx_vae* v, const void* z, int B, int F, int H, int W, c
     return LTX_OK;
 }
 
+struct ScopedBuf : DevBuf { ~ScopedBuf() { release(); } };   // a buffer that lives for one call
+
 int decode_cl(ltx_vae* v, const void* z, int B, int F, int H, int W, const TimeVec* tv, const ltx_tiling* tl, int post, float* out, hipStream_t s) {
     const ltx_vae_config& c = v->cfg;
-    const int r = c.spatial_compression_ratio, tr = c.temporal_compression_ratio;
+    const int tr = c.temporal_compression_ratio, BC = B * c.out_channels;
     const size_t esz = ltx_dt_size(v->dtype);
-    const int BC = B * c.out_channels;
-    const int oT = (F - 1) * tr + 1, oH = H * r, oW = W * r;
-    const bool framewise = tl && tl->use_framewise_decoding && F > tl->tile_sample_min_num_frames / tr;
-    const bool spatial = tl && tl->use_tiling && (W > tl->tile_sample_min_width / r || H > tl->tile_sample_min_height / r);
-    if (!framewise && !spatial) return decoder_forward(v, z, B, F, H, W, tv, post, out, s);     // vae.rs:2065 (post == 2: RGB8 from conv_out's epilogue)
+    VaeTilePlan plan;
+    LTX_TRY(vae_decode_tile_plan(c.spatial_compression_ratio, tr, tl, F, H, W, &plan));
+    const int oT = plan.oT, oH = plan.oH, oW = plan.oW;
+    if (plan.mode == VaeTilePlan::kDirect) return decoder_forward(v, z, B, F, H, W, tv, post, out, s);     // vae.rs:2065 (post == 2: RGB8 from conv_out's epilogue)
     // RGB8 output of a TILED decode: the blends run on f32 tiles - decode into a scratch video, convert with the frame kernel (same bits)
     if (post == 2) {
         LTX_TRY(v->rgbtmp.ensure((size_t)BC * oT * oH * oW * sizeof(float)));
         LTX_TRY(decode_cl(v, z, B, F, H, W, tv, tl, 1, v->rgbtmp.as<float>(), s));
         return ltx_video_to_rgb8(v->rgbtmp.as<float>(), B, oT, oH, oW, reinterpret_cast<uint8_t*>(out), (ltx_stream)s);
     }
-    size_t pool_used = 0;
-    if (!framewise) {
-        LTX_TRY(tiled_decode(v, z, B, F, H, W, tv, *tl, out, v->tilebufs, pool_used, s));
+    if (plan.mode == VaeTilePlan::kSpatial) {
+        LTX_TRY(tiled_decode(v, z, B, F, H, W, tv, plan, out, s));
     } else {
         // temporal_tiled_decode (vae.rs:2358-2434)
-        const int tmin_t = tl->tile_sample_min_num_frames / tr, tstride_t = tl->tile_sample_stride_num_frames / tr;
-        if (tstride_t < 1) LTX_FAIL(LTX_ERR_ARG, "tiling: temporal stride must be >= one latent frame");
-        const int blend_t = std::max(tl->tile_sample_min_num_frames - tl->tile_sample_stride_num_frames, 0);
-        const int tmin_h = tl->tile_sample_min_height / r, tmin_w = tl->tile_sample_min_width / r;
-        DevBuf zt;                       // temporal latent window
+        ScopedBuf zt;                    // temporal latent window
         std::vector<std::vector<float*>> pre;                 // spatially tiled windows: every leaf decoded up front, in batches
-        if (tl->use_tiling && (H > tmin_h || W > tmin_w)) LTX_TRY(batched_leaf_decode(v, z, B, F, H, W, tv, *tl, pre, s));
-        int prev_t = 0, prev_stride = 0; int ot = 0; int li = 0;
-        for (int i = 0; i < F; i += tstride_t, ++li) {
-            const int t1 = std::min(i + tmin_t + 1, F), nf = t1 - i;
-            int rc = zt.ensure((size_t)B * nf * H * W * c.latent_channels * esz);
-            if (rc != LTX_OK) { zt.release(); return rc; }
-            rc = crop_cl(z, zt.p, esz, B, F, H, W, c.latent_channels, i, t1, 0, H, 0, W, s);
-            if (rc != LTX_OK) { zt.release(); return rc; }
+        if (plan.window_tiled) LTX_TRY(batched_leaf_decode(v, z, B, F, H, W, tv, plan, pre, s));
+        TWin prev; int ot = 0;
+        for (size_t li = 0; li < plan.windows.size(); ++li) {
+            const TileSpan win = plan.windows[li]; const int nf = win.i1 - win.i0;
+            LTX_TRY(zt.ensure((size_t)B * nf * H * W * c.latent_channels * esz));
+            LTX_TRY(crop_cl(z, zt.p, esz, B, F, H, W, c.latent_channels, win.i0, win.i1, 0, H, 0, W, s));
             const int dT = (nf - 1) * tr + 1;
             DevBuf& cur = v->tiles[li & 1];
-            rc = cur.ensure((size_t)BC * dT * oH * oW * sizeof(float));
-            if (rc != LTX_OK) { zt.release(); return rc; }
-            const bool sp = tl->use_tiling && (H > tmin_h || W > tmin_w);
-            size_t pu = 0;
-            rc = sp ? tiled_decode(v, zt.p, B, nf, H, W, tv, *tl, cur.as<float>(), v->tilebufs, pu, s, pre.empty() ? nullptr : &pre[li])
-                    : decoder_forward(v, zt.p, B, nf, H, W, tv, 0, cur.as<float>(), s);
-            if (rc != LTX_OK) { zt.release(); return rc; }
-            // "if i > 0: decoded = decoded[:, :, :-1]" — keep the buffer, shrink the logical length
-            int curT = dT; const int stride_full = dT;      // physical T stride of the buffer
-            if (li > 0 && curT > 1) curT -= 1;
-            // result_row: first tile keeps stride+1 frames, later tiles blend_t(row[idx-1], tile) then keep `stride`
-            const int keep = li > 0 ? std::min(tl->tile_sample_stride_num_frames, curT) : std::min(tl->tile_sample_stride_num_frames + 1, curT);
-            const int n = std::min(keep, oT - ot);
-            if (n > 0) {
-                rc = ltx_launch_copy_window(cur.as<float>(), stride_full, oH, oW, out, oT, oH, oW, BC, n, oH, oW, ot, 0, 0, s);
-                if (rc != LTX_OK) { zt.release(); return rc; }
-                if (li > 0) {       // blend against the RAW previous tile (row[idx-1]), written straight into `out`
-                    BlendArgs ba; ba.a = v->tiles[(li - 1) & 1].as<float>(); ba.b = cur.as<float>(); ba.dst = out; ba.BC = BC;
-                    ba.at = prev_stride; ba.ah = oH; ba.aw = oW; ba.a_len = prev_t;
-                    ba.bt = stride_full; ba.bh = oH; ba.bw = oW; ba.dt = oT; ba.dh = oH; ba.dw = oW; ba.ot = ot;
-                    ba.dim = 2; ba.blend = std::min(blend_t, std::min(prev_t, curT));
-                    ba.et = std::min(ba.blend, n); ba.eh = oH; ba.ew = oW;
-                    rc = ltx_launch_blend(ba, s);
-                    if (rc != LTX_OK) { zt.release(); return rc; }
-                }
-            }
+            LTX_TRY(cur.ensure((size_t)BC * dT * oH * oW * sizeof(float)));
+            LTX_TRY(plan.window_tiled ? tiled_decode(v, zt.p, B, nf, H, W, tv, plan, cur.as<float>(), s, &pre[li])
+                                      : decoder_forward(v, zt.p, B, nf, H, W, tv, 0, cur.as<float>(), s));
+            int keep = 0;
+            LTX_TRY(place_temporal(plan, (int)li, cur.as<float>(), dT, &prev, BC, out, ot, &keep, s));
             ot += keep;
-            prev_t = curT; prev_stride = stride_full;
         }
-        HIP_TRY(hipStreamSynchronize(s));
-        zt.release();
+        HIP_TRY(hipStreamSynchronize(s));    // zt is freed on the way out: not before the stream is done with it
     }
     if (post) LTX_TRY(ltx_launch_postprocess(out, (int64_t)BC * oT * oH * oW, s));
     return LTX_OK;
@@ -908,72 +906,29 @@ int encoder_forward(ltx_vae_encoder* e, const void* video, int vdt, int B, int F
     return LTX_OK;
 }
 
-// tiled_encode (vae.rs:2158-2223) of the frames [t0, t0+nt) of `video`: tiles in sample space, blends on the f32 moments
+// tiled_encode (vae.rs:2158-2223) of the frames [t0, t0+nt) of `video`: tiles in sample space, blends on the f32 moments;
+// result into `out` [BC, oT, oH, oW]
 int tiled_encode(ltx_vae_encoder* e, const void* video, int vdt, int B, int F, int H, int W, int t0, int nt,
-                 const ltx_tiling& tl, float* out, int oT, int oH, int oW, size_t& pool_used, hipStream_t s) {
-    const int r = e->cfg.spatial_compression_ratio;
+                 const VaeTilePlan& plan, float* out, int oT, hipStream_t s) {
     const int BC = B * e->nmom;
-    if (tl.tile_sample_stride_height < r || tl.tile_sample_stride_width < r) LTX_FAIL(LTX_ERR_ARG, "tiling: stride must be >= one latent");
-    const int ls_h = tl.tile_sample_stride_height / r, ls_w = tl.tile_sample_stride_width / r;
-    const int blend_h = std::max(tl.tile_sample_min_height / r - ls_h, 0), blend_w = std::max(tl.tile_sample_min_width / r - ls_w, 0);
-    auto take = [&](size_t bytes, DevBuf** b) -> int {
-        if (pool_used >= e->tilebufs.size()) e->tilebufs.emplace_back();
-        *b = &e->tilebufs[pool_used++];
-        return (*b)->ensure(bytes);
+    auto encode_tile = [&](TileSpan row, TileSpan col, auto& take, Tile* t) -> int {
+        const int nh = row.i1 - row.i0, nw = col.i1 - col.i0;
+        LTX_TRY(enc_out_dims(e, nt, nh, nw, &t->t, &t->h, &t->w));
+        if (t->t != oT) LTX_FAIL(LTX_ERR_ARG, "tiled encode: tile frame count mismatch");
+        LTX_TRY(take((size_t)BC * t->t * t->h * t->w * sizeof(float), &t->p));
+        return encoder_forward(e, video, vdt, B, F, H, W, t0, nt, row.i0, nh, col.i0, nw, t->p, s);
     };
-    std::vector<Tile> prev, cur;
-    int oy = 0;
-    for (int i = 0; i < H; i += tl.tile_sample_stride_height) {
-        cur.clear();
-        int ox = 0, row_h = 0;
-        for (int j = 0; j < W; j += tl.tile_sample_stride_width) {
-            const int h1 = std::min(i + tl.tile_sample_min_height, H), w1 = std::min(j + tl.tile_sample_min_width, W);
-            Tile t;
-            LTX_TRY(enc_out_dims(e, nt, h1 - i, w1 - j, &t.t, &t.h, &t.w));
-            DevBuf* tb = nullptr;
-            LTX_TRY(take((size_t)BC * t.t * t.h * t.w * sizeof(float), &tb));
-            t.p = tb->as<float>();
-            LTX_TRY(encoder_forward(e, video, vdt, B, F, H, W, t0, nt, i, h1 - i, j, w1 - j, t.p, s));
-            const size_t ci = cur.size();
-            if (!prev.empty()) {        // blend_v with the (already blended) tile above
-                BlendArgs ba; ba.a = prev[ci].p; ba.b = t.p; ba.dst = t.p; ba.BC = BC;
-                ba.at = prev[ci].t; ba.ah = prev[ci].h; ba.aw = prev[ci].w; ba.a_len = prev[ci].h;
-                ba.bt = ba.dt = t.t; ba.bh = ba.dh = t.h; ba.bw = ba.dw = t.w;
-                ba.dim = 3; ba.blend = std::min(blend_h, std::min(prev[ci].h, t.h));
-                ba.et = t.t; ba.eh = ba.blend; ba.ew = std::min(t.w, prev[ci].w);
-                LTX_TRY(ltx_launch_blend(ba, s));
-            }
-            if (ci > 0) {               // blend_h with the (already blended) tile to the left
-                BlendArgs ba; ba.a = cur[ci - 1].p; ba.b = t.p; ba.dst = t.p; ba.BC = BC;
-                ba.at = cur[ci - 1].t; ba.ah = cur[ci - 1].h; ba.aw = cur[ci - 1].w; ba.a_len = cur[ci - 1].w;
-                ba.bt = ba.dt = t.t; ba.bh = ba.dh = t.h; ba.bw = ba.dw = t.w;
-                ba.dim = 4; ba.blend = std::min(blend_w, std::min(cur[ci - 1].w, t.w));
-                ba.et = t.t; ba.eh = std::min(t.h, cur[ci - 1].h); ba.ew = ba.blend;
-                LTX_TRY(ltx_launch_blend(ba, s));
-            }
-            cur.push_back(t);
-            const int hs = std::min(ls_h, t.h), ws = std::min(ls_w, t.w);
-            const int ch = std::min(hs, oH - oy), cw_ = std::min(ws, oW - ox);
-            if (t.t != oT) LTX_FAIL(LTX_ERR_ARG, "tiled encode: tile frame count mismatch");
-            if (ch > 0 && cw_ > 0)
-                LTX_TRY(ltx_launch_copy_window(t.p, t.t, t.h, t.w, out, oT, oH, oW, BC, oT, ch, cw_, 0, oy, ox, s));
-            ox += ws; row_h = hs;
-        }
-        oy += row_h;
-        prev = cur;
-    }
-    return LTX_OK;
+    return assemble_spatial(plan, encode_tile, BC, out, e->tilebufs, s);
 }
 
 // encode_z (vae.rs:2017-2035) -> e->mom [B,L+1,F',H/r,W/r]; *oT/oH/oW = latent dims
 int encode_moments(ltx_vae_encoder* e, const void* video, int vdt, int B, int F, int H, int W, const ltx_tiling* tl,
                    const ltx_encode_tiling* et, int* oT, int* oH, int* oW, hipStream_t s,
                    float* mean_direct = nullptr, float* logvar_direct = nullptr, bool* direct_done = nullptr) {
-    const int r = e->cfg.spatial_compression_ratio, tr = e->cfg.temporal_compression_ratio;
     const int BC = B * e->nmom;
-    const bool framewise = tl && et && et->use_framewise_encoding && F > tl->tile_sample_min_num_frames;
-    const bool spatial = tl && tl->use_tiling && (H > tl->tile_sample_min_height || W > tl->tile_sample_min_width);
-    if (!framewise && !spatial) {
+    VaeTilePlan plan;
+    LTX_TRY(vae_encode_tile_plan(e->cfg.spatial_compression_ratio, e->cfg.temporal_compression_ratio, tl, et, F, H, W, &plan));
+    if (plan.mode == VaeTilePlan::kDirect) {
         LTX_TRY(enc_out_dims(e, F, H, W, oT, oH, oW));
         if (mean_direct) {       // one encoder call: conv_out's rows go straight to the caller's mean / logvar
             if (direct_done) *direct_done = true;
@@ -982,53 +937,31 @@ int encode_moments(ltx_vae_encoder* e, const void* video, int vdt, int B, int F,
         LTX_TRY(e->mom.ensure((size_t)BC * *oT * *oH * *oW * sizeof(float)));
         return encoder_forward(e, video, vdt, B, F, H, W, 0, F, 0, H, 0, W, e->mom.as<float>(), s);
     }
-    if (r < 1 || tr < 1 || H % r != 0 || W % r != 0) LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes (tiled encode: height and width must be multiples of the compression ratio)");
-    *oH = H / r; *oW = W / r; *oT = (F - 1) / tr + 1;                                             // vae.rs:2162-2163, 2298
-    LTX_TRY(e->mom.ensure((size_t)BC * *oT * *oH * *oW * sizeof(float)));
-    size_t pool_used = 0;
-    if (!framewise) {
-        int t, h, w; LTX_TRY(enc_out_dims(e, F, std::min(H, tl->tile_sample_min_height), std::min(W, tl->tile_sample_min_width), &t, &h, &w));
-        if (t != *oT) LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes (frame count)");
-        return tiled_encode(e, video, vdt, B, F, H, W, 0, F, *tl, e->mom.as<float>(), *oT, *oH, *oW, pool_used, s);
+    *oT = plan.oT; *oH = plan.oH; *oW = plan.oW;
+    LTX_TRY(e->mom.ensure((size_t)BC * plan.oT * plan.oH * plan.oW * sizeof(float)));
+    float* out = e->mom.as<float>();
+    const int tile_h = plan.rows[0].i1 - plan.rows[0].i0, tile_w = plan.cols[0].i1 - plan.cols[0].i0;      // the whole plane where the windows are not tiled
+    if (plan.mode == VaeTilePlan::kSpatial) {
+        int t, h, w; LTX_TRY(enc_out_dims(e, F, tile_h, tile_w, &t, &h, &w));
+        if (t != plan.oT) LTX_FAIL(LTX_ERR_ARG, "input not divisible by patch sizes (frame count)");
+        return tiled_encode(e, video, vdt, B, F, H, W, 0, F, plan, out, plan.oT, s);
     }
     // temporal_tiled_encode (vae.rs:2294-2357)
-    if (tl->tile_sample_stride_num_frames < tr) LTX_FAIL(LTX_ERR_ARG, "tiling: temporal stride must be >= one latent frame");
-    const int ls_t = tl->tile_sample_stride_num_frames / tr;
-    const int blend_t = std::max(tl->tile_sample_min_num_frames / tr - ls_t, 0);
-    float* out = e->mom.as<float>();
-    const float* prev_p = nullptr; int prev_len = 0, prev_phys = 0;
-    int ot = 0, li = 0;
-    for (int i = 0; i < F; i += tl->tile_sample_stride_num_frames, ++li) {
-        const int t1 = std::min(i + tl->tile_sample_min_num_frames + 1, F), nf = t1 - i;
-        const bool sp = tl->use_tiling && (H > tl->tile_sample_min_height || W > tl->tile_sample_min_width);
+    TWin prev; int ot = 0;
+    for (size_t li = 0; li < plan.windows.size(); ++li) {
+        const TileSpan win = plan.windows[li]; const int nf = win.i1 - win.i0;
         int tt, th, tw;
-        LTX_TRY(enc_out_dims(e, nf, sp ? std::min(H, tl->tile_sample_min_height) : H, sp ? std::min(W, tl->tile_sample_min_width) : W, &tt, &th, &tw));
-        if (!sp && (th != *oH || tw != *oW)) LTX_FAIL(LTX_ERR_ARG, "temporal tiled encode: tile plane mismatch");
+        LTX_TRY(enc_out_dims(e, nf, tile_h, tile_w, &tt, &th, &tw));
+        if (!plan.window_tiled && (th != plan.oH || tw != plan.oW)) LTX_FAIL(LTX_ERR_ARG, "temporal tiled encode: tile plane mismatch");
         DevBuf& cur = e->ttiles[li & 1];
-        LTX_TRY(cur.ensure((size_t)BC * tt * *oH * *oW * sizeof(float)));
-        size_t pu = 0;
-        if (sp) LTX_TRY(tiled_encode(e, video, vdt, B, F, H, W, i, nf, *tl, cur.as<float>(), tt, *oH, *oW, pu, s));
-        else LTX_TRY(encoder_forward(e, video, vdt, B, F, H, W, i, nf, 0, H, 0, W, cur.as<float>(), s));
-        // "if i == 0: tile = tile[:, :, 1:]" (vae.rs:2322-2327): the logical tile starts one frame into the buffer
-        const float* cp = cur.as<float>(); int len = tt;
-        if (li == 0) { cp += (size_t)*oH * *oW; len -= 1; }
-        const int keep = li > 0 ? std::min(ls_t, len) : std::min(ls_t + 1, len);
-        const int n = std::min(keep, *oT - ot);
-        if (n > 0) {
-            LTX_TRY(ltx_launch_copy_window(cp, tt, *oH, *oW, out, *oT, *oH, *oW, BC, n, *oH, *oW, ot, 0, 0, s));
-            if (li > 0) {           // blend_t against the RAW previous tile (row[idx - 1], vae.rs:2338-2342), straight into `out`
-                BlendArgs ba; ba.a = prev_p; ba.b = cp; ba.dst = out; ba.BC = BC;
-                ba.at = prev_phys; ba.ah = *oH; ba.aw = *oW; ba.a_len = prev_len;
-                ba.bt = tt; ba.bh = *oH; ba.bw = *oW; ba.dt = *oT; ba.dh = *oH; ba.dw = *oW; ba.ot = ot;
-                ba.dim = 2; ba.blend = std::min(blend_t, std::min(prev_len, len));
-                ba.et = std::min(ba.blend, n); ba.eh = *oH; ba.ew = *oW;
-                if (ba.blend > 0) LTX_TRY(ltx_launch_blend(ba, s));
-            }
-        }
+        LTX_TRY(cur.ensure((size_t)BC * tt * plan.oH * plan.oW * sizeof(float)));
+        if (plan.window_tiled) LTX_TRY(tiled_encode(e, video, vdt, B, F, H, W, win.i0, nf, plan, cur.as<float>(), tt, s));
+        else LTX_TRY(encoder_forward(e, video, vdt, B, F, H, W, win.i0, nf, 0, H, 0, W, cur.as<float>(), s));
+        int keep = 0;
+        LTX_TRY(place_temporal(plan, (int)li, cur.as<float>(), tt, &prev, BC, out, ot, &keep, s));
         ot += std::max(keep, 0);
-        prev_p = cp; prev_len = len; prev_phys = tt;
     }
-    if (ot < *oT) LTX_FAIL(LTX_ERR_ARG, "temporal tiled encode: the tiles do not cover the latent frames (frame count / tile parameters)");
+    if (ot < plan.oT) LTX_FAIL(LTX_ERR_ARG, "temporal tiled encode: the tiles do not cover the latent frames (frame count / tile parameters)");
     return LTX_OK;
 }
 

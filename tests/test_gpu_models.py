@@ -681,6 +681,22 @@ def test_vae_spatial_only_tiled_decode(hip):
     assert out.shape == ref.shape and rel_max(out, ref) <= 1e-3, rel_max(out, ref)
 
 
+def test_vae_framewise_decode_without_spatial_tiling(hip):
+    """use_framewise_decoding alone (vae.rs:2358-2434 with use_tiling off): every temporal window is one decoder call on the whole
+    plane, blended along time only.  f32 mode against the oracle's framewise decode, which is not the untiled one."""
+    cfg, w, model = _variant(hip, torch.float32, decoder_spatiotemporal_scaling=(True, False), temporal_compression_ratio=2)
+    for o in (cfg, model):
+        o.tile_sample_min_num_frames = 4; o.tile_sample_stride_num_frames = 2
+    model.use_framewise_decoding = True; model.use_tiling = False
+    z = torch.randn(1, 16, 5, 3, 4, generator=torch.Generator().manual_seed(6)); ts = torch.tensor([0.05])
+    ref = O.vae_decode(w, cfg, z, ts, use_framewise_decoding=True)
+    plain = O.vae_decode(w, cfg, z, ts)
+    assert rel_max(ref, plain) > 1e-2                                            # the oracle's two paths differ on this input
+    out = model.decode(z.to(DEV), ts).cpu()
+    assert out.shape == ref.shape == (1, 3, 9, 48, 64) and rel_max(out, ref) <= 1e-3, rel_max(out, ref)
+    assert rel_max(out, plain) > 1e-2                                            # and the framewise path ran
+
+
 def test_vae_noise_injection(hip):
     """decoder_inject_noise (vae.rs:676-689, 741-753, 784, 809): resnets of a flagged block add plane[h, w] * per_channel_scaleN[c] after
     conv1 and conv2.  Plane k of a handle = Pcg32(seed, k).randn(H * W) on both sides: f32 mode vs the oracle (untiled, batch 2: one
