@@ -180,6 +180,30 @@ extern "C" int ltx_op_qknorm_rope(void* x, int64_t rows, int D, int ld, const vo
     return ltx_launch_qknorm_rope(a, dtc(dtype), (hipStream_t)stream);
 }
 
+extern "C" int ltx_op_qknorm_rope_segs(void* x, int64_t rows, int D, int ld, int nseg, int64_t seg_stride, const void* w0, const void* w1, const void* w0b,
+                                       float eps, const float* cos, const float* sin, float out_scale0, int dtype, ltx_stream stream) {
+    if (!x || !w0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_qknorm_rope_segs: null tensor");
+    if ((cos == nullptr) != (sin == nullptr) || seg_stride < 0) LTX_FAIL(LTX_ERR_ARG, "ltx_op_qknorm_rope_segs: cos and sin go together; seg_stride >= 0");
+    QkNormRopeArgs a; a.x = x; a.rows = rows; a.D = D; a.ld = ld; a.nseg = nseg; a.seg_stride = seg_stride; a.w0 = w0; a.w1 = w1; a.w0b = w0b;
+    a.eps = eps; a.cos = cos; a.sin = sin; a.out_scale0 = out_scale0;
+    return ltx_launch_qknorm_rope(a, dtc(dtype), (hipStream_t)stream);
+}
+
+extern "C" int ltx_op_norm_route(int64_t rows, int D, int dtype, int kind, int flags, int act, int64_t rows_per_batch, int presum_n, int nparts, char* name, int cap) {
+    if (!name || cap < 1 || rows < 1 || D < 1 || presum_n < 0 || nparts < 0 || (flags & ~7)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_norm_route: bad argument");
+    NormRouteArgs r;
+    r.dtype = dtc(dtype); r.rows = rows; r.D = D; r.kind = kind; r.act = act; r.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
+    r.scale = (flags & LTX_NORM_SCALE) != 0; r.shift = (flags & LTX_NORM_SHIFT) != 0; r.weight = (flags & LTX_NORM_WEIGHT) != 0;
+    r.presum = presum_n != 0; r.presum_n = presum_n; r.parts = nparts != 0; r.nparts = nparts;
+    snprintf(name, (size_t)cap, "%s", ltx_rownorm_route_name(ltx_rownorm_route(r).route));
+    return LTX_OK;
+}
+extern "C" int ltx_op_qknorm_route(int64_t rows, int D, int dtype, char* name, int cap) {
+    if (!name || cap < 1 || rows < 1 || D < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_qknorm_route: bad argument");
+    snprintf(name, (size_t)cap, "%s", ltx_qknorm_route_name(ltx_qknorm_route(dtc(dtype), rows, D, nullptr)));
+    return LTX_OK;
+}
+
 extern "C" int ltx_op_rope_table(float* cos, float* sin, const float* coords, int B, int F, int H, int W, int D,
                                  const float* rope_scale_host, ltx_stream stream) {
     if (!cos || !sin) LTX_FAIL(LTX_ERR_ARG, "ltx_op_rope_table: null tensor");

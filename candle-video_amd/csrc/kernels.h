@@ -175,6 +175,26 @@ struct RowNormArgs {
 };
 int ltx_launch_rownorm(const RowNormArgs& a, int dtype, hipStream_t s);
 
+// Which kernel of rownorm.hip serves a call: ONE decision (ltx_rownorm_route), read by the launcher - which only switches on it -
+// and by the read-only probe ltx_op_norm_route.  It reads the shape, the dtype and which operands are present under the current
+// options; no pointer, no device.  NORM_REFUSED: the launcher fails the call with LTX_ERR_ARG and `why`.
+enum NormRoute { NORM_REFUSED = 0, NORM_NARROW, NORM_BLOCK, NORM_WIDE, NORM_REREAD, NORM_PRESUM, NORM_PRESUM_LEAN,
+                 NORM_WIDE_DEFER, NORM_WIDE_DEFER4, NORM_BLOCK_DEFER, NORM_BLOCK_DEFER4,
+                 NORM_WIDE_ROWS };     // (experiment builds under x_rownorm_rows=1 only)
+struct NormRouteArgs {
+    int dtype = LTX_DT_BF16; int64_t rows = 0; int D = 0; int kind = 0;
+    bool scale = false, shift = false, weight = false; int act = 0; int64_t rows_per_batch = 1;
+    bool presum = false; int presum_n = 0;      // RowNormArgs::presum given, and its partials per row
+    bool parts = false; int nparts = 0;         // RowNormArgs::parts given, and the number of K ranges
+};
+struct NormDecision {
+    NormRoute route = NORM_REFUSED; const char* why = nullptr;
+    int presum_r = 4; bool presum_wide = false, presum_nt = false;      // NORM_PRESUM: rows per thread, a wave inside one row group, streaming hints
+};
+NormRouteArgs ltx_rownorm_route_args(const RowNormArgs& a, int dtype);
+NormDecision ltx_rownorm_route(const NormRouteArgs& r);
+const char* ltx_rownorm_route_name(NormRoute r);      // "narrow", "block", "wide", "reread", "presum", "presum_lean", "wide_defer", ... ; "refused"
+
 struct QkNormRopeArgs {
     void* x = nullptr;            // in place, nseg segments of width D at x + j*D in each row
     int64_t rows = 0; int D = 0; int ld = 0; int nseg = 1;
@@ -186,6 +206,10 @@ struct QkNormRopeArgs {
     float out_scale0 = 1.f;       // extra factor on segment 0's output (q): lets attention fold scale*log2(e) into Q
 };
 int ltx_launch_qknorm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t s);
+// The same for the q/k pass (probe: ltx_op_qknorm_route): the decision reads dtype, rows and D alone
+enum QkNormRoute { QKNORM_REFUSED = 0, QKNORM_BLOCK, QKNORM_FUSED4, QKNORM_FUSED8, QKNORM_CACHED, QKNORM_REREAD };
+QkNormRoute ltx_qknorm_route(int dtype, int64_t rows, int D, const char** why);
+const char* ltx_qknorm_route_name(QkNormRoute r);     // "block", "fused4", "fused8", "cached", "reread"; "refused"
 
 struct RopeTableArgs {
     float* cos = nullptr; float* sin = nullptr;   // [B*S, D/2]

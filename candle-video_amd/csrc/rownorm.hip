@@ -835,33 +835,36 @@ int pick_lpr(int nch) {
     return lpr;
 }
 
+// The launches of ltx_rownorm_route's answers: nothing is decided here.
 template <typename T>
-void launch_rownorm_t(const RowNormArgs& a, int lpr, int nch, hipStream_t s) {
+void launch_rownorm_t(const RowNormArgs& a, const NormDecision& d, int lpr, int nch, hipStream_t s) {
     const int rpw = 64 / lpr;
-    if (nch <= lpr && a.rows >= (int64_t)rpw * NSLOT * 4 * 64) {       // narrow rows, enough of them: NSLOT rows per lane group
+    const dim3 block_grid((unsigned)a.rows);                                     // one row per block
+    const dim3 wave_grid((unsigned)cdiv64(a.rows, (int64_t)4 * rpw));            // rpw rows per wave
+    switch (d.route) {
+    case NORM_NARROW: {                                                          // NSLOT rows per lane group
         const int64_t rows_per_block = (int64_t)4 * rpw * NSLOT;
         LTX_LAUNCH_TIMED((rownorm_kernel<T, 1>), dim3((unsigned)cdiv64(a.rows, rows_per_block)), dim3(256), 0, s, a, lpr);
-    } else if (a.rows <= 512 && nch > 64 && nch <= 512) {                  // few wide rows: one row per block
-        const dim3 grid((unsigned)a.rows);
-        if (a.parts && a.nparts == 4) LTX_LAUNCH_TIMED((rownorm_block_kernel<T, 4>), grid, dim3(256), 0, s, a);
-        else if (a.parts) LTX_LAUNCH_TIMED((rownorm_block_kernel<T, 1>), grid, dim3(256), 0, s, a);
-        else LTX_LAUNCH_TIMED((rownorm_block_kernel<T, 0>), grid, dim3(256), 0, s, a);
-    } else {
-        // (measured and left out, round 3: four rows per wave with the scale / shift operands cached in registers - 312 blocks
-        // instead of 1248 - ran the DiT's 4992 x 2048 rows in 15.9 us against 12.8 us: the pass is bound by how many row loads are
-        // in flight across the chip, not by the operand traffic through the vector-memory path)
-        const int64_t rows_per_block = 4 * rpw;
-        dim3 grid((unsigned)cdiv64(a.rows, rows_per_block));
-        // wide rows (one wave per row, <= 4 chunks per lane), enough of them: four rows per wave, two in flight (LTX_ROWNORM_ROWS=0: one row per wave)
-#ifdef LTX_EXPERIMENTS     // x_rownorm_rows=1: measured 17.3 us against 12.7 us (lab notes R4.4)
-        if (lpr == 64 && nch <= 4 * 64 && a.rows >= 2048 && ltx_exp("rownorm_rows", 0) == 1) {
-            constexpr int R = 4;
-            const int waves = (int)cdiv64(a.rows, R);
-            const int blocks = (waves + 3) / 4;
-            LTX_LAUNCH_TIMED((rownorm_rows_kernel<T, 4, R, 2>), dim3((unsigned)blocks), dim3(256), 0, s, a, blocks * 4);
-            return;
-        }
+        break;
+    }
+    case NORM_BLOCK: LTX_LAUNCH_TIMED((rownorm_block_kernel<T, 0>), block_grid, dim3(256), 0, s, a); break;
+    case NORM_BLOCK_DEFER: LTX_LAUNCH_TIMED((rownorm_block_kernel<T, 1>), block_grid, dim3(256), 0, s, a); break;
+    case NORM_BLOCK_DEFER4: LTX_LAUNCH_TIMED((rownorm_block_kernel<T, 4>), block_grid, dim3(256), 0, s, a); break;
+    // (measured and left out, round 3: four rows per wave with the scale / shift operands cached in registers - 312 blocks
+    // instead of 1248 - ran the DiT's 4992 x 2048 rows in 15.9 us against 12.8 us: the pass is bound by how many row loads are
+    // in flight across the chip, not by the operand traffic through the vector-memory path)
+#ifdef LTX_EXPERIMENTS     // x_rownorm_rows=1: four rows per wave, two in flight; measured 17.3 us against 12.7 us (lab notes R4.4)
+    case NORM_WIDE_ROWS: {
+        constexpr int R = 4;
+        const int waves = (int)cdiv64(a.rows, R);
+        const int blocks = (waves + 3) / 4;
+        LTX_LAUNCH_TIMED((rownorm_rows_kernel<T, 4, R, 2>), dim3((unsigned)blocks), dim3(256), 0, s, a, blocks * 4);
+        break;
+    }
 #endif
+    case NORM_WIDE_DEFER4: LTX_LAUNCH_TIMED((rownorm_kernel<T, 0, 4>), wave_grid, dim3(256), 0, s, a, lpr); break;
+    case NORM_WIDE_DEFER: LTX_LAUNCH_TIMED((rownorm_kernel<T, 0, 1>), wave_grid, dim3(256), 0, s, a, lpr); break;
+    case NORM_WIDE: {
         // LTX_ROWNORM_OCC=n (experiment): at most n blocks per CU, by asking for 160 KiB / n of LDS the kernel never touches -
         // several generations of blocks instead of one, so that the stores of one overlap the loads of the next
         int shm = 0;
@@ -870,54 +873,106 @@ void launch_rownorm_t(const RowNormArgs& a, int lpr, int nch, hipStream_t s) {
             static std::atomic<unsigned long long> occ_devs{0};
             (void)ltx_set_max_dyn_smem(occ_devs, reinterpret_cast<const void*>(&rownorm_kernel<T, 0>), 163840);
         }
-        if (a.parts && a.nparts == 4) LTX_LAUNCH_TIMED((rownorm_kernel<T, 0, 4>), grid, dim3(256), 0, s, a, lpr);       // (launcher-checked: WIDE rows)
-        else if (a.parts) LTX_LAUNCH_TIMED((rownorm_kernel<T, 0, 1>), grid, dim3(256), 0, s, a, lpr);
-        else if (nch <= NSLOT * lpr) LTX_LAUNCH_TIMED((rownorm_kernel<T, 0>), grid, dim3(256), shm, s, a, lpr);
-        else LTX_LAUNCH_TIMED((rownorm_kernel<T, 2>), grid, dim3(256), 0, s, a, lpr);
+        LTX_LAUNCH_TIMED((rownorm_kernel<T, 0>), wave_grid, dim3(256), shm, s, a, lpr);
+        break;
+    }
+    case NORM_REREAD: LTX_LAUNCH_TIMED((rownorm_kernel<T, 2>), wave_grid, dim3(256), 0, s, a, lpr); break;
+    default: break;                                                              // (the presum routes: launch_presum)
     }
 }
 
+template <typename T, int R>
+void launch_presum_r(const RowNormArgs& a, const NormDecision& d, int nch, int rpb, hipStream_t s) {
+    const dim3 grid((unsigned)cdiv64(a.rows, (int64_t)rpb * R));
+    if (d.presum_wide) LTX_LAUNCH_TIMED((rownorm_presum_kernel<T, R, true>), grid, dim3(256), 0, s, a, nch, rpb);
+    else LTX_LAUNCH_TIMED((rownorm_presum_kernel<T, R, false>), grid, dim3(256), 0, s, a, nch, rpb);
+}
+
+void launch_presum(const RowNormArgs& a, const NormDecision& d, int dtype, int nch, hipStream_t s) {
+    const int rpb = 256 / nch;
+    const dim3 grid4((unsigned)cdiv64(a.rows, (int64_t)rpb * 4));
+    if (d.route == NORM_PRESUM_LEAN) LTX_LAUNCH_TIMED((rownorm_presum_lean_kernel<4>), grid4, dim3(256), 0, s, a, nch, rpb);
+    else if (dtype != LTX_DT_BF16) launch_presum_r<float, 4>(a, d, nch, rpb, s);
+    else if (d.presum_nt) LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 4, true, true>), grid4, dim3(256), 0, s, a, nch, rpb);
+    else if (d.presum_r == 2) launch_presum_r<bf16_t, 2>(a, d, nch, rpb, s);
+    else if (d.presum_r == 8) launch_presum_r<bf16_t, 8>(a, d, nch, rpb, s);
+    else launch_presum_r<bf16_t, 4>(a, d, nch, rpb, s);
+}
+
+NormDecision refuse_norm(const char* why) { NormDecision d; d.route = NORM_REFUSED; d.why = why; return d; }
+
 }  // namespace
+
+NormRouteArgs ltx_rownorm_route_args(const RowNormArgs& a, int dtype) {
+    NormRouteArgs r;
+    r.dtype = dtype; r.rows = a.rows; r.D = a.D; r.kind = a.kind;
+    r.scale = a.scale != nullptr; r.shift = a.shift != nullptr; r.weight = a.weight != nullptr; r.act = a.act; r.rows_per_batch = a.rows_per_batch;
+    r.presum = a.presum != nullptr; r.presum_n = a.presum_n; r.parts = a.parts != nullptr; r.nparts = a.nparts;
+    return r;
+}
+
+// The one place where a row-norm call's kernel is chosen (kernels.h).  Shape thresholds, in this order:
+//   narrow : the row fits one chunk per lane of its lane group (nch <= lpr) and there are >= 2048 * (64 / lpr) rows
+//   block  : at most 512 rows of 65 .. 512 chunks
+//   wide   : the row fits NSLOT chunks per lane;  reread: it does not
+NormDecision ltx_rownorm_route(const NormRouteArgs& r) {
+    NormDecision d;
+    const int ch = r.dtype == LTX_DT_BF16 ? 8 : 4;
+    if (r.D < ch || r.D % ch != 0) return refuse_norm("rownorm: D/ld must be multiples of the 16-byte chunk");
+    if (r.scale != r.shift) return refuse_norm("rownorm: scale and shift go together");
+    const int nch = r.D / ch, lpr = pick_lpr(nch), rpw = 64 / lpr;
+    const bool narrow = nch <= lpr && r.rows >= (int64_t)rpw * NSLOT * 4 * 64;           // narrow rows, enough of them
+    const bool block_rows = r.rows <= 512 && nch > 64 && nch <= 512;                      // few wide rows: one row per block
+    const bool cached = nch <= NSLOT * lpr;
+    if (r.parts && (r.presum || narrow || (!cached && !block_rows) || r.nparts < 1 || r.nparts > 16 || r.D % 8))
+        return refuse_norm("rownorm: deferred rows need whole-row lanes (D of at most 64 x 8 chunks), 1..16 parts of [rows, D] f32 and an output for the finished rows");
+    if (r.presum && (r.kind != 0 || r.presum_n < 4 || r.presum_n % 4 != 0 || nch > 256 || (nch & (nch - 1)) || r.rows >= 2147483647LL || r.rows_per_batch >= 2147483647LL))
+        return refuse_norm("rownorm: presum serves RMS rows of a power-of-two number (<= 256) of 16-byte chunks with a multiple of 4 partials");
+    if (r.presum) {
+        const int rpb = 256 / nch;
+        int R = 4;                                           // rows per thread (LTX_NORM_PRESUM_R = 2 / 4 / 8: tuning aid; bf16)
+        if (r.dtype == LTX_DT_BF16) { const int v = ltx_exp("norm_presum_r", 4); if (v == 2 || v == 4 || v == 8) R = v; }
+        const bool wide = nch >= 64;
+        // the DiT's case on the kernel that has nothing to decide (LTX_NORM_LEAN=0: the general one; same bits)
+        const bool lean_on = ltx_opt().norm_lean != 0, nt = ltx_exp("norm_nt", 0) != 0;
+        const bool lean = lean_on && r.dtype == LTX_DT_BF16 && wide && R == 4 && r.scale && !r.weight && r.act == 0 && r.presum_n <= 16 &&
+                          r.rows % ((int64_t)rpb * 4) == 0 && r.rows_per_batch % 4 == 0 && !nt;
+        d.route = lean ? NORM_PRESUM_LEAN : NORM_PRESUM;
+        d.presum_r = R; d.presum_wide = wide; d.presum_nt = r.dtype == LTX_DT_BF16 && R == 4 && wide && nt;
+        return d;
+    }
+    if (narrow) d.route = NORM_NARROW;
+    else if (block_rows) d.route = !r.parts ? NORM_BLOCK : (r.nparts == 4 ? NORM_BLOCK_DEFER4 : NORM_BLOCK_DEFER);
+#ifdef LTX_EXPERIMENTS
+    // wide rows (one wave per row, <= 4 chunks per lane), enough of them: four rows per wave, two in flight
+    else if (lpr == 64 && nch <= 4 * 64 && r.rows >= 2048 && ltx_exp("rownorm_rows", 0) == 1) d.route = NORM_WIDE_ROWS;
+#endif
+    else if (r.parts) d.route = r.nparts == 4 ? NORM_WIDE_DEFER4 : NORM_WIDE_DEFER;      // (checked above: the row fits the lanes)
+    else d.route = cached ? NORM_WIDE : NORM_REREAD;
+    return d;
+}
+
+const char* ltx_rownorm_route_name(NormRoute r) {
+    static const char* const names[] = {"refused", "narrow", "block", "wide", "reread", "presum", "presum_lean",
+                                        "wide_defer", "wide_defer4", "block_defer", "block_defer4", "wide_rows"};
+    return names[r];
+}
 
 int ltx_launch_rownorm(const RowNormArgs& a, int dtype, hipStream_t s) {
     const int ch = dtype == LTX_DT_BF16 ? 8 : 4;
     if (a.rows <= 0) return LTX_OK;
     if (a.D % ch != 0 || a.ldx % ch != 0 || a.ldy % ch != 0) LTX_FAIL(LTX_ERR_ARG, "rownorm: D/ld must be multiples of the 16-byte chunk");
-    if ((a.scale == nullptr) != (a.shift == nullptr)) LTX_FAIL(LTX_ERR_ARG, "rownorm: scale and shift go together");
-    const int nch = a.D / ch, lpr = pick_lpr(nch);
-    if (a.parts) {
-        const int rpw = 64 / lpr;
-        const bool narrow = nch <= lpr && a.rows >= (int64_t)rpw * NSLOT * 4 * 64;
-        const bool block_rows = a.rows <= 512 && nch > 64 && nch <= 512;          // one row per block (rownorm_block_kernel)
-        if (a.presum || narrow || (nch > NSLOT * lpr && !block_rows) || a.nparts < 1 || a.nparts > 16 || !a.x_out || a.part_stride < a.rows * a.D || a.D % 8 ||
-            ((uintptr_t)a.parts & 15) || (a.d_gate && (((uintptr_t)a.d_gate & 15) || a.d_gate_stride % 4)))
-            LTX_FAIL(LTX_ERR_ARG, "rownorm: deferred rows need whole-row lanes (D of at most 64 x 8 chunks), 1..16 parts of [rows, D] f32 and an output for the finished rows");
-    }
     // (every argument check sits in front of ltx_prof_begin: a failure after it would leave the timing record open)
-    if (a.presum && (a.kind != 0 || a.presum_n < 4 || a.presum_n % 4 != 0 || nch > 256 || (nch & (nch - 1)) || a.rows >= 2147483647LL || a.rows_per_batch >= 2147483647LL))
-        LTX_FAIL(LTX_ERR_ARG, "rownorm: presum serves RMS rows of a power-of-two number (<= 256) of 16-byte chunks with a multiple of 4 partials");
+    const NormDecision d = ltx_rownorm_route(ltx_rownorm_route_args(a, dtype));
+    if (d.route == NORM_REFUSED) LTX_FAIL(LTX_ERR_ARG, d.why);
+    if (a.parts && (!a.x_out || a.part_stride < a.rows * a.D || ((uintptr_t)a.parts & 15) || (a.d_gate && (((uintptr_t)a.d_gate & 15) || a.d_gate_stride % 4))))
+        LTX_FAIL(LTX_ERR_ARG, "rownorm: deferred rows need whole-row lanes (D of at most 64 x 8 chunks), 1..16 parts of [rows, D] f32 and an output for the finished rows");
+    const int nch = a.D / ch, lpr = pick_lpr(nch);
     void* tok = nullptr;
     ltx_prof_begin(LTX_PROF_ROWNORM, 2.0 * (double)a.rows * a.D * (dtype == LTX_DT_BF16 ? 2 : 4), s, &tok);
-    if (a.presum) {
-        const int rpb = 256 / nch;
-        int R = 4;                                           // rows per thread (LTX_NORM_PRESUM_R = 2 / 4 / 8: tuning aid)
-        { const int v = ltx_exp("norm_presum_r", 4); if (v == 2 || v == 4 || v == 8) R = v; }
-        const dim3 grid((unsigned)cdiv64(a.rows, (int64_t)rpb * R));
-        const bool wide = nch >= 64;
-        // the DiT's case on the kernel that has nothing to decide (LTX_NORM_LEAN=0: the general one; same bits)
-        const bool lean_on = ltx_opt().norm_lean != 0, nt = ltx_exp("norm_nt", 0) != 0;
-        const bool lean = lean_on && dtype == LTX_DT_BF16 && wide && R == 4 && a.scale && !a.weight && a.act == 0 && a.presum_n <= 16 &&
-                          a.rows % ((int64_t)rpb * 4) == 0 && a.rows_per_batch % 4 == 0 && !nt;
-        if (lean) LTX_LAUNCH_TIMED((rownorm_presum_lean_kernel<4>), grid, dim3(256), 0, s, a, nch, rpb);
-        else if (dtype == LTX_DT_BF16) {
-            if (R == 2) { if (wide) LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 2, true>), grid, dim3(256), 0, s, a, nch, rpb); else LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 2, false>), grid, dim3(256), 0, s, a, nch, rpb); }
-            else if (R == 4 && wide && nt) LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 4, true, true>), grid, dim3(256), 0, s, a, nch, rpb);
-            else if (R == 4) { if (wide) LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 4, true>), grid, dim3(256), 0, s, a, nch, rpb); else LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 4, false>), grid, dim3(256), 0, s, a, nch, rpb); }
-            else { if (wide) LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 8, true>), grid, dim3(256), 0, s, a, nch, rpb); else LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 8, false>), grid, dim3(256), 0, s, a, nch, rpb); }
-        } else if (wide) LTX_LAUNCH_TIMED((rownorm_presum_kernel<float, 4, true>), dim3((unsigned)cdiv64(a.rows, (int64_t)rpb * 4)), dim3(256), 0, s, a, nch, rpb);
-        else LTX_LAUNCH_TIMED((rownorm_presum_kernel<float, 4, false>), dim3((unsigned)cdiv64(a.rows, (int64_t)rpb * 4)), dim3(256), 0, s, a, nch, rpb);
-    } else if (dtype == LTX_DT_BF16) launch_rownorm_t<bf16_t>(a, lpr, nch, s);
-    else launch_rownorm_t<float>(a, lpr, nch, s);
+    if (d.route == NORM_PRESUM || d.route == NORM_PRESUM_LEAN) launch_presum(a, d, dtype, nch, s);
+    else if (dtype == LTX_DT_BF16) launch_rownorm_t<bf16_t>(a, d, lpr, nch, s);
+    else launch_rownorm_t<float>(a, d, lpr, nch, s);
     ltx_prof_end(tok, s);
     LTX_CHECK_LAUNCH();
     return LTX_OK;
@@ -1002,25 +1057,50 @@ __global__ __launch_bounds__(256) void qknorm_rope_block_kernel(const QkNormRope
 }
 }  // namespace
 
+// The one place where the q/k pass's kernel is chosen (kernels.h).
+QkNormRoute ltx_qknorm_route(int dtype, int64_t rows, int D, const char** why) {
+    const int ch = dtype == LTX_DT_BF16 ? 8 : 4;
+    if (D < ch || D % ch != 0) { if (why) *why = "qknorm: D/ld must be multiples of the 16-byte chunk"; return QKNORM_REFUSED; }
+    const int nch = D / ch, lpr = pick_lpr(nch);
+    const bool cached = nch <= NSLOT * lpr;
+    if (dtype == LTX_DT_BF16) {
+        if (rows <= 512 && nch > 64 && nch <= 512) return QKNORM_BLOCK;              // few wide rows: one row per block
+        if (nch <= 4 * lpr) return QKNORM_FUSED4;
+        // the 13B model's 4096-wide rows: eight chunks per lane, the table still read once for q and k (LTX_QKNORM_FUSED8=0: the two-pass kernel)
+        if (nch <= 8 * lpr && ltx_exp("qknorm_fused8", 1)) return QKNORM_FUSED8;
+    }
+    return cached ? QKNORM_CACHED : QKNORM_REREAD;
+}
+
+const char* ltx_qknorm_route_name(QkNormRoute r) {
+    static const char* const names[] = {"refused", "block", "fused4", "fused8", "cached", "reread"};
+    return names[r];
+}
+
 int ltx_launch_qknorm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t s) {
     const int ch = dtype == LTX_DT_BF16 ? 8 : 4;
     if (a.rows <= 0) return LTX_OK;
     if (a.D % ch != 0 || a.ld % ch != 0) LTX_FAIL(LTX_ERR_ARG, "qknorm: D/ld must be multiples of the 16-byte chunk");
     if (a.nseg < 1 || a.nseg > 2 || !a.w0 || (a.nseg == 2 && !a.w1)) LTX_FAIL(LTX_ERR_ARG, "qknorm: bad segments/weights");
+    const char* why = nullptr;
+    const QkNormRoute route = ltx_qknorm_route(dtype, a.rows, a.D, &why);
+    if (route == QKNORM_REFUSED) LTX_FAIL(LTX_ERR_ARG, why);
     const int nch = a.D / ch, lpr = pick_lpr(nch);
     const int64_t rows_per_block = 4 * (64 / lpr);
     dim3 grid((unsigned)cdiv64(a.rows, rows_per_block)), block(256);
-    const bool cached = nch <= NSLOT * lpr;
-    if (dtype == LTX_DT_BF16) {
-        if (a.rows <= 512 && nch > 64 && nch <= 512) hipLaunchKernelGGL((qknorm_rope_block_kernel<bf16_t>), dim3((unsigned)a.rows), block, 0, s, a);      // few wide rows: one row per block
-        else if (nch <= 4 * lpr) hipLaunchKernelGGL((qknorm_rope_fused_kernel<bf16_t, 4>), grid, block, 0, s, a, lpr);
-        // the 13B model's 4096-wide rows: eight chunks per lane, the table still read once for q and k (LTX_QKNORM_FUSED8=0: the two-pass kernel)
-        else if (nch <= 8 * lpr && ltx_exp("qknorm_fused8", 1)) hipLaunchKernelGGL((qknorm_rope_fused_kernel<bf16_t, 8, 2>), grid, block, 0, s, a, lpr);
-        else if (cached) hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t, true>), grid, block, 0, s, a, lpr);
-        else hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t, false>), grid, block, 0, s, a, lpr);
-    } else {
-        if (cached) hipLaunchKernelGGL((qknorm_rope_kernel<float, true>), grid, block, 0, s, a, lpr);
+    const bool bf16 = dtype == LTX_DT_BF16;
+    switch (route) {
+    case QKNORM_BLOCK: hipLaunchKernelGGL((qknorm_rope_block_kernel<bf16_t>), dim3((unsigned)a.rows), block, 0, s, a); break;
+    case QKNORM_FUSED4: hipLaunchKernelGGL((qknorm_rope_fused_kernel<bf16_t, 4>), grid, block, 0, s, a, lpr); break;
+    case QKNORM_FUSED8: hipLaunchKernelGGL((qknorm_rope_fused_kernel<bf16_t, 8, 2>), grid, block, 0, s, a, lpr); break;
+    case QKNORM_CACHED:
+        if (bf16) hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t, true>), grid, block, 0, s, a, lpr);
+        else hipLaunchKernelGGL((qknorm_rope_kernel<float, true>), grid, block, 0, s, a, lpr);
+        break;
+    default:
+        if (bf16) hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t, false>), grid, block, 0, s, a, lpr);
         else hipLaunchKernelGGL((qknorm_rope_kernel<float, false>), grid, block, 0, s, a, lpr);
+        break;
     }
     LTX_CHECK_LAUNCH();
     return LTX_OK;

@@ -134,6 +134,8 @@ _SIGS = {
     "ltx_op_attention_rowsq": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _i, _f, _vp],
     "ltx_op_rownorm": [_vp, _vp, _i64, _i, _i, _f, _vp, _vp, _vp, _i64, _i, _i, _i, _vp],
     "ltx_op_qknorm_rope": [_vp, _i64, _i, _i, _vp, _f, _vp, _vp, _i, _vp],
+    "ltx_op_qknorm_rope_segs": [_vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _f, _vp, _vp, _f, _i, _vp],
+    "ltx_op_norm_route": [_i64, _i, _i, _i, _i, _i, _i64, _i, _i, C.c_char_p, _i], "ltx_op_qknorm_route": [_i64, _i, _i, C.c_char_p, _i],
     "ltx_op_rope_table": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "ltx_op_timestep_embedding": [_vp, _i, _i, _f, _i, _vp, _vp],
     "ltx_op_attention": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp],
@@ -1905,6 +1907,34 @@ class ops:
         _check(lib.ltx_op_qknorm_rope(_ptr(x), C.c_int64(rows), D, D, _ptr(weight), C.c_float(eps), _ptr(cos), _ptr(sin),
                                       _dt(x.dtype), _stream()))
         return x
+
+    @staticmethod
+    def qknorm_rope_segs(x, rows, D, ld, nseg, seg_stride, w0, w1=None, w0b=None, eps=1e-5, cos=None, sin=None, out_scale0=1.0):
+        """q/k RMS norm + RoPE the way the DiT calls it, IN PLACE on the caller's buffer x (any shape; never copied): nseg segments
+        of D columns of row m at element m * ld + j * (seg_stride or D).  Segment 0: w0 [* w0b], out_scale0; segment 1: w1."""
+        if not x.is_contiguous():
+            raise LtxError("qknorm_rope_segs: the buffer is used as it lies in memory; pass a contiguous tensor")
+        _check(lib.ltx_op_qknorm_rope_segs(_ptr(x), C.c_int64(rows), D, ld, nseg, C.c_int64(seg_stride), _ptr(w0), _ptr(w1), _ptr(w0b),
+                                           C.c_float(eps), _ptr(cos), _ptr(sin), C.c_float(out_scale0), _dt(x.dtype), _stream()))
+        return x
+
+    @staticmethod
+    def norm_route(rows, D, dtype=torch.bfloat16, kind=0, scale=False, shift=None, weight=False, act=0, rows_per_batch=1, presum_n=0, nparts=0) -> str:
+        """which kernel of csrc/rownorm.hip serves the described ops.rownorm / rownorm_presum (presum_n partials per row) /
+        rownorm_deferred (nparts K ranges) call under the current options: "narrow", "block", "wide", "reread", "presum",
+        "presum_lean", "wide_defer", "wide_defer4", "block_defer", "block_defer4" - or "refused" where the op raises LtxError.
+        scale / shift / weight: whether the operand is passed (shift defaults to scale).  Nothing is launched; no device is needed."""
+        buf = C.create_string_buffer(32)
+        flags = (1 if scale else 0) | (2 if (scale if shift is None else shift) else 0) | (4 if weight else 0)
+        _check(lib.ltx_op_norm_route(C.c_int64(rows), D, _dt(dtype), kind, flags, act, C.c_int64(rows_per_batch), presum_n, nparts, buf, 32))
+        return buf.value.decode()
+
+    @staticmethod
+    def qknorm_route(rows, D, dtype=torch.bfloat16) -> str:
+        """the same for ops.qknorm_rope / qknorm_rope_segs: "block", "fused4", "fused8", "cached", "reread" or "refused"."""
+        buf = C.create_string_buffer(32)
+        _check(lib.ltx_op_qknorm_route(C.c_int64(rows), D, _dt(dtype), buf, 32))
+        return buf.value.decode()
 
     @staticmethod
     def timestep_embedding(timesteps, vae_flavour=False, multiplier=1.0, dtype=torch.float32, device="cuda"):

@@ -88,6 +88,26 @@ int ltx_op_rownorm(const void* x, void* y, int64_t rows, int D, int kind, float 
 int ltx_op_qknorm_rope(void* x, int64_t rows, int D, int ld, const void* weight, float eps,
                        const float* cos, const float* sin, int dtype, ltx_stream stream);
 
+/* The same pass the way the DiT calls it (LtxAttention::forward: norm_q / norm_k + RoPE on q and k of one fused projection), in
+ * place on a caller-owned buffer: nseg = 1 or 2 segments of D columns per row, segment j of row m at
+ * x + m * ld + j * (seg_stride ? seg_stride : D) elements - adjacent column blocks of a [rows, ld] row (seg_stride 0) or dense
+ * planes seg_stride elements apart.  Segment 0: x * r * w0 [* w0b], rotated, times out_scale0 (r = 1 / sqrt(mean(x^2) + eps));
+ * segment 1: x * r * w1, rotated with the same table row.  w1 NULL needs nseg = 1; w0b may be NULL; cos / sin both or neither.
+ * Nothing outside the nseg segments of the first `rows` rows is written. */
+int ltx_op_qknorm_rope_segs(void* x, int64_t rows, int D, int ld, int nseg, int64_t seg_stride, const void* w0, const void* w1, const void* w0b,
+                            float eps, const float* cos, const float* sin, float out_scale0, int dtype, ltx_stream stream);
+
+/* Diagnostic, read-only: which kernel of csrc/rownorm.hip serves a described call under the current options.  The launchers
+ * switch on the same decision.  Nothing is launched, no device and no pointer are needed; dense rows (ld = D) are assumed.
+ *   ltx_op_norm_route: ltx_op_rownorm (presum_n = nparts = 0), ltx_op_rownorm_presum (presum_n partials per row) or
+ *     ltx_op_rownorm_deferred (nparts K ranges); flags say which operands are passed.  Names: "narrow", "block", "wide", "reread",
+ *     "presum", "presum_lean", "wide_defer", "wide_defer4", "block_defer", "block_defer4" ("wide_rows": experiment builds).
+ *   ltx_op_qknorm_route: ltx_op_qknorm_rope / ltx_op_qknorm_rope_segs.  Names: "block", "fused4", "fused8", "cached", "reread".
+ * Both write "refused" where the launch would fail the described arguments with LTX_ERR_ARG. */
+enum { LTX_NORM_SCALE = 1, LTX_NORM_SHIFT = 2, LTX_NORM_WEIGHT = 4 };
+int ltx_op_norm_route(int64_t rows, int D, int dtype, int kind, int flags, int act, int64_t rows_per_batch, int presum_n, int nparts, char* name, int cap);
+int ltx_op_qknorm_route(int64_t rows, int D, int dtype, char* name, int cap);
+
 /* get_timestep_embedding, dim 256, order [cos | sin]: flavour 0 = the DiT's (ltx_transformer.rs:271-309, frequencies
  * 1/10000^(i/128)), 1 = the VAE's (vae.rs:172-198, exp(-ln(1e4) i / 128), timestep first multiplied by `multiplier` =
  * timestep_scale_multiplier, :1668-1676).  In bf16 the timestep is rounded to bf16 first (:1051).  timesteps: HOST [n], n <= 8;
