@@ -2,6 +2,7 @@
 #include "conv3d.h"
 #include "../../include/ltxhip_ops.h"
 #include "../../include/ltxhip_upsampler_st.h"
+#include "../../include/ltxhip_stg.h"
 
 static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
 
@@ -94,6 +95,11 @@ extern "C" int ltx_op_shift_gemv(const void* w, const void* bias, const float* s
 extern "C" int ltx_op_mod_scale(const void* h, const float* scale, int scale_stride, void* y, int B, int64_t rows_per_batch, int D, int dtype, ltx_stream stream) {
     if (!h || !scale || !y || B < 1 || rows_per_batch < 1 || D < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_mod_scale: bad argument");
     return ltx_launch_mod_scale(h, scale, scale_stride, y, B, rows_per_batch, D, dtc(dtype), (hipStream_t)stream);
+}
+// the copy of the STG attention modes (ltxhip_stg.h): whole batch rows of src into dst, one launch
+extern "C" int ltx_op_stg_fill(void* dst, int ldd, const void* src, int lds, const unsigned char* rows, int B, int S, int D, ltx_dtype dtype, ltx_stream stream) {
+    if (!dst || !src || !rows || B < 1 || S < 1 || D < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_stg_fill: bad argument");
+    return ltx_launch_stg_fill(dst, ldd, src, lds, rows, B, S, D, dtc(dtype), (hipStream_t)stream);
 }
 extern "C" int ltx_op_scale_cols(const void* w, const float* scale, void* out, int64_t N, int K, int dtype, ltx_stream stream) {
     if (!w || !scale || !out || N < 1 || K < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_scale_cols: bad argument");

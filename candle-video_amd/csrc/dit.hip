@@ -9,6 +9,7 @@
 #include "model_util.h"
 #include "options.h"
 #include "../../include/ltxhip_cond.h"
+#include "../../include/ltxhip_stg.h"
 #include "lora.h"
 
 struct DitBlock {
@@ -68,6 +69,7 @@ struct ltx_dit {
     float* rope_freqs = nullptr;     // [D/6]
     float* inv_freq = nullptr;       // [128]
     std::vector<int> skip_blocks;
+    int stg_mode = LTX_STG_TRANSFORMER_BLOCK;      // what a skip_layer_mask perturbs (include/ltxhip_stg.h): handle state, like the skip list
     // The five caches of the forward: text_context, time_tables, scaled_weights, group_tables, rope_tables (the last one is rope_key
     // over cosb / sinb: a function of the geometry, not of the weights, and owns no memory).
     std::deque<DitCtx> ctxs;         // deque: entries must not move while `ctx` points at one
@@ -243,6 +245,21 @@ extern "C" void ltx_dit_destroy(ltx_dit* m) {
 extern "C" int ltx_dit_set_skip_blocks(ltx_dit* m, const int* blocks, int n) {
     if (!m || n < 0 || (n > 0 && !blocks)) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_skip_blocks: bad argument");
     m->skip_blocks.assign(blocks, blocks + n);
+    return LTX_OK;
+}
+
+// ---- STG modes (include/ltxhip_stg.h) ----
+extern "C" int ltx_dit_set_stg_mode(ltx_dit* m, ltx_stg_mode mode) {
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_stg_mode: null handle");
+    const int v = (int)mode;
+    if (v != LTX_STG_TRANSFORMER_BLOCK && v != LTX_STG_ATTENTION_SKIP && v != LTX_STG_ATTENTION_VALUES)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_stg_mode: unknown mode " + std::to_string(v) + " (0 transformer_block, 1 attention_skip, 2 attention_values)");
+    m->stg_mode = v;
+    return LTX_OK;
+}
+extern "C" int ltx_dit_get_stg_mode(const ltx_dit* m, ltx_stg_mode* out) {
+    if (!m || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_stg_mode: null argument");
+    *out = (ltx_stg_mode)m->stg_mode;
     return LTX_OK;
 }
 
@@ -593,9 +610,11 @@ struct DitCarry {             // what a block leaves for the next one (and the l
     }
 };
 struct DitLayerIn { DitTables tab; const DitWfold* we = nullptr; const DitCtx* ctx = nullptr; const float* skip_layer_mask = nullptr; };      // what the forward hands every block
-// does block l run: not in the skip list (:1094-1096), not skipped by every row of the mask (all-ones rows make the block an exact identity, :1098-1123)
+// does block l run: not in the skip list (:1094-1096), not skipped by every row of the mask (all-ones rows make the block an exact identity, :1098-1123).
+// In an attention mode (ltxhip_stg.h) the mask perturbs the self-attention and the block runs for every row: only the skip list removes it.
 bool block_runs(const ltx_dit* m, const float* skip_layer_mask, int B, int l) {
     for (int sb : m->skip_blocks) if (sb == l) return false;
+    if (m->stg_mode != LTX_STG_TRANSFORMER_BLOCK) return true;
     bool all = skip_layer_mask != nullptr;
     for (int b = 0; all && b < B; ++b) all = skip_layer_mask[(size_t)l * B + b] == 1.f;
     return !all;
@@ -614,6 +633,11 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     TimeVec mv; mv.n = B; bool any = false;
     for (int i = 0; i < 8; ++i) mv.t[i] = 0.f;
     if (in.skip_layer_mask) for (int bb = 0; bb < B; ++bb) { mv.t[bb] = in.skip_layer_mask[(size_t)l * B + bb]; any |= mv.t[bb] != 0.f; }
+    // An attention mode (ltxhip_stg.h; mask values 0 / 1, checked by the forward): the perturbed rows hand to_out their n or v in place
+    // of the attention output and the block is otherwise an unmasked one - no copy of the input, no blend, an unmasked block's carry.
+    const bool stg_attn = any && m->stg_mode != LTX_STG_TRANSFORMER_BLOCK;
+    unsigned char pert[8] = {0};
+    if (stg_attn) { for (int bb = 0; bb < B; ++bb) pert[bb] = mv.t[bb] != 0.f; any = false; }
     if (any) {
         HIP_TRY(hipMemcpyAsync(m->orig.p, m->h.p, M * D * esz, hipMemcpyDeviceToDevice, s));
         // the row partials of the kept rows travel with them (restored after the blend): a batch whose rows skip different
@@ -645,7 +669,37 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     AttnArgs at; at.q = m->qkv.p; at.k = (char*)m->qkv.p + (size_t)p.seg * esz; at.v = (char*)m->qkv.p + (size_t)2 * p.seg * esz; at.o = m->attn.p;
     at.ldq = at.ldk = at.ldv = p.ldqkv; at.ldo = D; at.B = B; at.Sq = S; at.Sk = S; at.heads = H; at.hd = hd; at.scale = attn_scale;
     at.q_prescaled = p.fold_q ? 1 : 0;
-    LTX_TRY(ltx_launch_attention(at, dt, s));
+    if (!stg_attn) LTX_TRY(ltx_launch_attention(at, dt, s));
+    else {
+        auto for_runs = [&](bool perturbed, auto&& fn) -> int {      // fn(b0, b1) for every maximal run [b0, b1) of batch rows that are / are not perturbed
+            for (int b0 = 0; b0 < B; ++b0) {
+                int b1 = b0;
+                while (b1 < B && (pert[b1] != 0) == perturbed) ++b1;
+                if (b1 > b0) { LTX_TRY(fn(b0, b1)); b0 = b1; }
+            }
+            return LTX_OK;
+        };
+        // attention for the runs of unperturbed batch rows only (one launch per run, none if every row is perturbed): batch rows never
+        // interact, so those rows get the bits of the whole-batch launch
+        LTX_TRY(for_runs(false, [&](int b0, int b1) {
+            AttnArgs ar = at; ar.B = b1 - b0;
+            const size_t in_off = (size_t)b0 * S * p.ldqkv * esz;
+            ar.q = (const char*)at.q + in_off; ar.k = (const char*)at.k + in_off; ar.v = (const char*)at.v + in_off; ar.o = (char*)at.o + (size_t)b0 * S * D * esz;
+            return ltx_launch_attention(ar, dt, s);
+        }));
+        if (m->stg_mode == LTX_STG_ATTENTION_VALUES) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, at.v, p.ldqkv, pert, B, S, D, dt, s));      // to_out(v): v with its bias, before the head split
+        else if (!fold1) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, m->n.p, D, pert, B, S, D, dt, s));      // to_out(n): the norm pass above left n whole in m->n
+        else
+            // norm fold: n is never materialised (m->n holds h (.) (1 + scale_msa), or the factor rides on the weights), but h is still
+            // the block's input here: the row norm over the perturbed batch rows alone, straight into their rows of m->attn
+            LTX_TRY(for_runs(true, [&](int b0, int b1) {
+                RowNormArgs rp = rn; rp.presum = nullptr; rp.presum_n = 0;
+                const size_t row_off = (size_t)b0 * S * D * esz, tab_off = (size_t)b0 * (NB / B) * 6 * D;      // whole batch rows, and their table rows (G per batch row)
+                rp.x = (const char*)m->h.p + row_off; rp.y = (char*)m->attn.p + row_off; rp.rows = (int64_t)(b1 - b0) * S;
+                rp.shift = ada + tab_off; rp.scale = ada + D + tab_off;
+                return ltx_launch_rownorm(rp, dt, s);
+            }));
+    }
     // h = h + gate_msa * to_out(attn)     (gate_msa = row 2)
     LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, p.Sg));
     st.hsq_valid = false;
@@ -769,6 +823,11 @@ int dit_forward_chunks(ltx_dit* m, const void* hidden, const void* enc, const fl
                        ltx_dtype io_dtype, void* out, ltx_stream stream) {
     const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
     const int L = m->cfg.num_layers;
+    if (skip_layer_mask && m->stg_mode != LTX_STG_TRANSFORMER_BLOCK)      // the attention modes replace an operand of to_out: there is nothing to blend
+        for (size_t i = 0; i < (size_t)L * B; ++i)
+            if (skip_layer_mask[i] != 0.f && skip_layer_mask[i] != 1.f)
+                LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: skip_layer_mask[" + std::to_string(i / B) + ", " + std::to_string(i % B) + "] = " + std::to_string(skip_layer_mask[i]) +
+                                      ": the attention STG modes take 0 and 1 only (fractional masks: LTX_STG_TRANSFORMER_BLOCK)");
     std::vector<float> mask_chunk;
     float t_row[8];
     for (int b0 = 0; b0 < B; b0 += 8) {

@@ -100,6 +100,17 @@ __global__ void mod_scale_kernel(const void* h, const float* scale, int scale_st
     }
 }
 
+// STG attention modes (include/ltxhip_stg.h): whole batch rows of src into dst - row (sel[j] * S + s) of both, row_vecs 16-byte
+// chunks each, leading dimensions in chunks.  One launch for every selected batch row; a pure HBM copy, 16 bytes per lane.
+__global__ __launch_bounds__(256) void stg_fill_kernel(uint4* __restrict__ dst, int64_t ldd_v, const uint4* __restrict__ src, int64_t lds_v, StgRows sel, int64_t S, int row_vecs) {
+    const int64_t n = (int64_t)sel.n * S * row_vecs;
+    GRID_STRIDE(i, n) {
+        const int c = (int)(i % row_vecs); const int64_t t = i / row_vecs;
+        const int64_t row = (int64_t)sel.b[(int)(t / S)] * S + t % S;
+        dst[row * ldd_v + c] = src[row * lds_v + c];
+    }
+}
+
 // W'[n][k] = W[n][k] * (1 + scale[k]) in the model dtype (norm fold through the consumer's weights: dit.hip, DitTimeEntry::wfold)
 __global__ void scale_cols_kernel(const void* W, const float* scale, void* out, int64_t N, int K, int dt) {
     const int64_t n = N * K;
@@ -366,6 +377,25 @@ int ltx_launch_skip_blend(void* h, const void* orig, const TimeVec& m, int64_t r
 int ltx_launch_mod_scale(const void* h, const float* scale, int scale_stride, void* y, int B, int64_t rows_per_batch, int D, int dtype, hipStream_t s) {
     hipLaunchKernelGGL(mod_scale_kernel, grid_for((int64_t)B * rows_per_batch * D), dim3(256), 0, s, h, scale, scale_stride, y, B, rows_per_batch, D, dtype);
     LTX_CHECK_LAUNCH(); return LTX_OK;
+}
+int ltx_launch_stg_fill(void* dst, int ldd, const void* src, int lds, const unsigned char* rows_host, int B, int64_t S, int D, int dtype, hipStream_t s) {
+    const int ch = dtype == LTX_DT_BF16 ? 8 : 4;           // elements of a 16-byte chunk
+    if (!dst || !src || !rows_host || B < 1 || S < 1 || D < 1 || ldd < D || lds < D) LTX_FAIL(LTX_ERR_ARG, "stg_fill: bad argument");
+    if (D % ch != 0 || ldd % ch != 0 || lds % ch != 0 || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15))
+        LTX_FAIL(LTX_ERR_ARG, "stg_fill: the row length and both leading dimensions must be multiples of 16 bytes and both pointers 16-byte aligned");
+    StgRows sel; sel.n = 0;
+    auto flush = [&]() -> int {
+        if (sel.n == 0) return LTX_OK;
+        hipLaunchKernelGGL(stg_fill_kernel, grid_for((int64_t)sel.n * S * (D / ch)), dim3(256), 0, s, reinterpret_cast<uint4*>(dst), (int64_t)(ldd / ch),
+                           reinterpret_cast<const uint4*>(src), (int64_t)(lds / ch), sel, S, D / ch);
+        LTX_CHECK_LAUNCH(); sel.n = 0; return LTX_OK;
+    };
+    for (int b = 0; b < B; ++b) {                           // (a forward has at most 8 batch rows: one launch)
+        if (!rows_host[b]) continue;
+        sel.b[sel.n++] = b;
+        if (sel.n == LTX_MAX_BATCH) LTX_TRY(flush());
+    }
+    return flush();
 }
 int ltx_launch_scale_cols(const void* W, const float* scale, void* out, int64_t N, int K, int dtype, hipStream_t s) {
     hipLaunchKernelGGL(scale_cols_kernel, grid_for(N * K), dim3(256), 0, s, W, scale, out, N, K, dtype);

@@ -281,6 +281,11 @@ int ltx_launch_key_compact(const float* bias, int B, int K, int* idx, int* count
 int ltx_launch_gather_rows(const void* src, void* dst, const int* idx, const int* count, int nl, int B, int K, int row_bytes, hipStream_t s);
 // h = h*(1-m_b) + orig*m_b
 int ltx_launch_skip_blend(void* h, const void* orig, const TimeVec& m, int64_t rows_per_batch, int D, int dtype, hipStream_t s);
+// STG attention modes (include/ltxhip_stg.h): dst[b*S + s, 0:D] = src[b*S + s, 0:D] for the batch rows with rows_host[b] != 0 (HOST
+// u8 [B], read before the call returns; the selected rows travel in the kernel arguments, LTX_MAX_BATCH a launch).  16-byte
+// accesses: D, ldd, lds multiples of the chunk and aligned pointers, else LTX_ERR_ARG.  No row selected: no launch.
+struct StgRows { int n; int b[LTX_MAX_BATCH]; };
+int ltx_launch_stg_fill(void* dst, int ldd, const void* src, int lds, const unsigned char* rows_host, int B, int64_t S, int D, int dtype, hipStream_t s);
 int ltx_launch_scale_cols(const void* W, const float* scale, void* out, int64_t N, int K, int dtype, hipStream_t s);      // out[n][k] = W[n][k] * (1 + scale[k])
 int ltx_launch_mod_scale(const void* h, const float* scale, int scale_stride, void* y, int B, int64_t rows_per_batch, int D, int dtype, hipStream_t s);   // y = h (.) (1 + scale[b])
 

@@ -2,7 +2,10 @@
 // Reference: LtxVideoTransformer3DModelConfig defaults (ltx_transformer.rs:30-58), AutoencoderKLLtxVideoConfig defaults
 // (vae.rs:68-103), tiling parameters (vae.rs:1860-1880), the 0.9.8 distilled call (configs.rs:223-240, main.rs:627).
 #include <cstring>
+#include <string>
 #include "../../include/ltxhip.h"
+#include "../../include/ltxhip_stg.h"
+#include "../csrc/errors.h"
 
 extern "C" void ltx_dit_config_default(ltx_dit_config* c) {
     c->in_channels = 128; c->out_channels = 128; c->patch_size = 1; c->patch_size_t = 1;
@@ -37,3 +40,13 @@ extern "C" void ltx_pipeline_params_default(ltx_pipeline_params* p) {
     p->postprocess = 1;
 }
 
+// The STG mode names of the published inference configs (include/ltxhip_stg.h); host only
+extern "C" int ltx_stg_mode_from_name(const char* name, ltx_stg_mode* out) {
+    if (!name || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_stg_mode_from_name: null argument");
+    static const struct { const char* name; ltx_stg_mode mode; } kNames[] = {
+        {"transformer_block", LTX_STG_TRANSFORMER_BLOCK}, {"attention_skip", LTX_STG_ATTENTION_SKIP}, {"attention_values", LTX_STG_ATTENTION_VALUES}};
+    for (const auto& e : kNames) if (std::strcmp(name, e.name) == 0) { *out = e.mode; return LTX_OK; }
+    if (std::strcmp(name, "residual") == 0)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_stg_mode_from_name: 'residual' acts inside an attention module that owns a residual connection; this model's blocks have none, so the mode is not offered");
+    LTX_FAIL(LTX_ERR_ARG, std::string("ltx_stg_mode_from_name: unknown STG mode '") + name + "' (transformer_block, attention_skip, attention_values)");
+}

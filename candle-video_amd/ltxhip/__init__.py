@@ -297,6 +297,30 @@ for _name, _sig in _UP_ST_SIGS.items():
     _fn = getattr(lib, _name)
     _fn.argtypes = _sig
     _fn.restype = None if _name == "ltx_upsampler_st_config_default" else C.c_int
+
+
+# include/ltxhip_stg.h (kept apart like the five above)
+_STG_SIGS = {
+    "ltx_dit_set_stg_mode": [_vp, _i], "ltx_dit_get_stg_mode": [_vp, C.POINTER(C.c_int)],
+    "ltx_stg_mode_from_name": [C.c_char_p, C.POINTER(C.c_int)],
+    "ltx_op_stg_fill": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp],
+}
+STG_SYMBOLS = sorted(_STG_SIGS)
+for _name, _sig in _STG_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
+LTX_STG_TRANSFORMER_BLOCK, LTX_STG_ATTENTION_SKIP, LTX_STG_ATTENTION_VALUES = 0, 1, 2
+STG_MODES = ("transformer_block", "attention_skip", "attention_values")      # ltx_stg_mode, by value
+
+
+def stg_mode_from_name(name: str) -> int:
+    """ltx_stg_mode of a published config's `stg_mode` string (host only; 'residual' and unknown names raise)"""
+    out = C.c_int(0)
+    _check(lib.ltx_stg_mode_from_name(name.encode() if name is not None else None, C.byref(out)))
+    return out.value
+
+
 # the ten LoRA targets of a block, in the order of ltx_dit_read_linear's `which`
 LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0",
                 "ff.net.0.proj", "ff.net.2")
@@ -491,6 +515,17 @@ class LtxVideoTransformer3DModel:
         _check(lib.ltx_dit_forward_frames(self._h, _ptr(h), _ptr(e), _floats(t), _ptr(m), B, S, K, num_frames, height, width,
                                           rs, _ptr(vc), slm, _dt(io), _ptr(out), _stream()))
         return out
+
+    # ---- STG modes (include/ltxhip_stg.h): handle state, so every forward with a skip_layer_mask and LtxPipeline.call obey it
+    def set_stg_mode(self, mode):
+        """what a skip_layer_mask perturbs: 'transformer_block' (default), 'attention_skip', 'attention_values' - or the ltx_stg_mode value"""
+        _check(lib.ltx_dit_set_stg_mode(self._h, stg_mode_from_name(mode) if isinstance(mode, str) else int(mode)))
+
+    @property
+    def stg_mode(self) -> str:
+        out = C.c_int(0)
+        _check(lib.ltx_dit_get_stg_mode(self._h, C.byref(out)))
+        return STG_MODES[out.value]
 
     # ---- LoRA adapters (include/ltxhip_lora.h): handle state, so LtxPipeline.call runs on whatever is set
     def set_adapters(self, loras: Sequence["LtxLora"] = (), scales: Optional[Sequence[float]] = None):
@@ -1807,6 +1842,21 @@ class ops:
         y = torch.empty_like(h)
         _check(lib.ltx_op_mod_scale(_ptr(h.contiguous()), _ptr(scale), scale.shape[-1], _ptr(y), rows // rows_per_batch, C.c_int64(rows_per_batch), D, _dt(h.dtype), _stream()))
         return y
+
+    @staticmethod
+    def stg_fill(dst, src, rows, S, D=None):
+        """in place on dst: dst[b*S + s, :D] = src[b*S + s, :D] for the batch rows with rows[b] truthy (ltx_op_stg_fill).  dst, src:
+        2-D views [B*S, >= D] of one dtype with unit column stride - their row strides are the leading dimensions, so a column slice
+        of a wider matrix (the v segment of q|k|v) is passed as it is"""
+        if not dst.is_cuda or not src.is_cuda or dst.dim() != 2 or src.dim() != 2 or dst.dtype != src.dtype or dst.stride(1) != 1 or src.stride(1) != 1:
+            raise LtxError("stg_fill: dst and src must be 2-D GPU tensors of one dtype with contiguous rows")
+        B = len(rows)
+        D = min(dst.shape[1], src.shape[1]) if D is None else D
+        if dst.shape[0] != B * S or src.shape[0] != B * S or D > dst.shape[1] or D > src.shape[1]:
+            raise LtxError(f"stg_fill: dst / src must have {B} x {S} rows of at least {D} columns")
+        r = (C.c_ubyte * max(B, 1))(*[1 if v else 0 for v in rows])
+        _check(lib.ltx_op_stg_fill(_ptr(dst), dst.stride(0), _ptr(src), src.stride(0), r, B, S, D, _dt(dst.dtype), _stream()))
+        return dst
 
     @staticmethod
     def scale_cols(w, scale):

@@ -207,6 +207,23 @@ impl HipDit {
     pub(crate) fn handle(&self) -> *mut sys::ltx_dit {
         self.h
     }
+
+    /// What a `skip_layer_mask` perturbs (include/ltxhip_stg.h): `"transformer_block"` (the trait's own form and the default),
+    /// `"attention_skip"` or `"attention_values"` - the `stg_mode` strings of the published inference configs.  Handle state, like
+    /// the skip list: every later forward with a mask, and the pipeline calls on this handle, obey it.
+    pub fn set_stg_mode(&mut self, name: &str) -> Result<()> {
+        let cname = CString::new(name).map_err(candle_core::Error::wrap)?;
+        let mut mode: c_int = sys::LTX_STG_TRANSFORMER_BLOCK;
+        check(unsafe { sys::ltx_stg_mode_from_name(cname.as_ptr(), &mut mode) })?;
+        check(unsafe { sys::ltx_dit_set_stg_mode(self.h, mode) })
+    }
+
+    /// The mode in force, as the `ltx_stg_mode` value (`sys::LTX_STG_*`).
+    pub fn stg_mode(&self) -> Result<c_int> {
+        let mut mode: c_int = sys::LTX_STG_TRANSFORMER_BLOCK;
+        check(unsafe { sys::ltx_dit_get_stg_mode(self.h, &mut mode) })?;
+        Ok(mode)
+    }
 }
 
 impl Drop for HipDit {

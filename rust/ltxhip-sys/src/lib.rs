@@ -384,3 +384,18 @@ extern "C" {
                                  wd: c_int, cin: c_int, o: c_int, st: c_int, ss: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
     pub fn ltx_op_pixel_shuffle_guarded(x: *const c_void, y: *mut c_void, b: c_int, f: c_int, h: c_int, w: c_int, c: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_stg.h: what a skip_layer_mask perturbs (the whole block, or the self-attention inside it) ----
+
+/// `ltx_stg_mode` (a C enum: passed as `c_int`).
+pub const LTX_STG_TRANSFORMER_BLOCK: c_int = 0;
+pub const LTX_STG_ATTENTION_SKIP: c_int = 1;
+pub const LTX_STG_ATTENTION_VALUES: c_int = 2;
+
+extern "C" {
+    pub fn ltx_dit_set_stg_mode(m: *mut ltx_dit, mode: c_int) -> c_int;
+    pub fn ltx_dit_get_stg_mode(m: *const ltx_dit, out: *mut c_int) -> c_int;
+    pub fn ltx_stg_mode_from_name(name: *const c_char, out: *mut c_int) -> c_int;
+    pub fn ltx_op_stg_fill(dst: *mut c_void, ldd: c_int, src: *const c_void, lds: c_int, rows: *const u8, b: c_int, s: c_int, d: c_int, dtype: c_int,
+                           stream: ltx_stream) -> c_int;
+}
