@@ -232,6 +232,172 @@ __global__ __launch_bounds__(256) void guidance_held_vec_kernel(GuidanceArgs a) 
         *reinterpret_cast<f32x4*>(a.latents + i) = y;
     }
 }
+// ---- the scheduled mix (include/ltxhip_guidance.h): CFG-star, two rescale forms ----
+// A batch row of n elements starts at element b * n of every tensor, so with all bases 16-byte aligned (8 for bf16 predictions) the
+// row splits the same way in each: `head` elements up to the next 16-byte boundary, nch chunks of four, the rest.  The elements
+// outside the chunks (at most 6 of an aligned row; all of them when a base is not aligned: vec == 0) go one by one.
+struct RowSplit {
+    int64_t head, nch, nsc;
+    __device__ __forceinline__ int64_t scalar_elem(int64_t k) const { return k < head ? k : k + 4 * nch; }
+};
+__device__ __forceinline__ RowSplit row_split(int64_t n, int b, int vec) {
+    RowSplit r;
+    if (!vec) { r.head = 0; r.nch = 0; r.nsc = n; return r; }
+    const int64_t mis = (4 - (((int64_t)b * n) & 3)) & 3;
+    r.head = mis < n ? mis : n; r.nch = (n - r.head) >> 2; r.nsc = n - 4 * r.nch;
+    return r;
+}
+enum { MOM_T = 0, MOM_U, MOM_P, MOM_TT, MOM_UU, MOM_PP, MOM_TU, MOM_TP, MOM_UP, MOM_N };
+// Sum t, u, p, t^2, u^2, p^2, tu, tp, up of one batch row in f64: everything the mean and variance of any c = at t + au u + ap p
+// and CFG-star's alpha need.  HU / HP: the branch exists (an absent one is not read; a template parameter, so no load sits behind a
+// runtime select).  Per block: lanes -> wave (shuffles) -> the four waves through LDS in wave order -> ONE partial in part[b][block][9].
+template <typename P, bool HU, bool HP>
+__global__ __launch_bounds__(256) void guidance_moments_kernel(const P* __restrict__ tp, const P* __restrict__ up, const P* __restrict__ pp,
+                                                               int64_t n, int vec, double* __restrict__ part) {
+    const int b = blockIdx.y;
+    const RowSplit rs = row_split(n, b, vec);
+    const int64_t base = (int64_t)b * n;
+    double acc[MOM_N];
+#pragma unroll
+    for (int q = 0; q < MOM_N; ++q) acc[q] = 0.0;
+    auto add = [&](float tf, float uf, float pf) {
+        const double t = tf; acc[MOM_T] += t; acc[MOM_TT] += t * t;
+        if (HU) { const double u = uf; acc[MOM_U] += u; acc[MOM_UU] += u * u; acc[MOM_TU] += t * u; }
+        if (HP) { const double p = pf; acc[MOM_P] += p; acc[MOM_PP] += p * p; acc[MOM_TP] += t * p; }
+        if (HU && HP) acc[MOM_UP] += (double)uf * (double)pf;
+    };
+    const int64_t stride = (int64_t)gridDim.x * 256, first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t ch = first; ch < rs.nch; ch += stride) {
+        const int64_t i = base + rs.head + 4 * ch;
+        float t[4], u[4] = {0.f, 0.f, 0.f, 0.f}, p[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4<P>(tp + i, t);
+        if (HU) ld4<P>(up + i, u);
+        if (HP) ld4<P>(pp + i, p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) add(t[k], u[k], p[k]);
+    }
+    for (int64_t k = first; k < rs.nsc; k += stride) {
+        const int64_t i = base + rs.scalar_elem(k);
+        add(to_f32(tp[i]), HU ? to_f32(up[i]) : 0.f, HP ? to_f32(pp[i]) : 0.f);
+    }
+#pragma unroll
+    for (int q = 0; q < MOM_N; ++q)
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);
+    __shared__ double sh[4][MOM_N];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < MOM_N; ++q) sh[wave][q] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < MOM_N) part[((int64_t)b * gridDim.x + blockIdx.x) * MOM_N + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+// One block per batch row: the row's partials are summed in one fixed tree, thread 0 turns the nine sums into
+// alpha = <t,u> / (<u,u> + 1e-8) and factor = r * (std t / std c) + (1 - r), each computed in f64 and rounded to f32 once.
+// use_alpha / resc: the step has them (otherwise 1).  at, au (times alpha), ap: c = at t + au alpha u + ap p in front of the rescale.
+__global__ __launch_bounds__(256) void guidance_finish_kernel(const double* __restrict__ part, int nblk, int64_t n, int use_alpha, int resc,
+                                                              float at_f, float au_f, float ap_f, float r_f, float* __restrict__ scal, float* __restrict__ scal_out) {
+    const int b = blockIdx.x;
+    // thread k holds partial k (nblk <= 256: every load is in flight at once, not one round trip per partial); then the moments
+    // kernel's own fixed tree - lanes by shuffles, the four waves through LDS in wave order
+    double acc[MOM_N];
+#pragma unroll
+    for (int q = 0; q < MOM_N; ++q) acc[q] = (int)threadIdx.x < nblk ? part[((int64_t)b * nblk + threadIdx.x) * MOM_N + q] : 0.0;
+#pragma unroll
+    for (int q = 0; q < MOM_N; ++q)
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);
+    __shared__ double sh[4][MOM_N];
+    __shared__ double S[MOM_N];
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < MOM_N; ++q) sh[threadIdx.x >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < MOM_N) S[threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float alpha = 1.0f, factor = 1.0f;
+    if (use_alpha) alpha = (float)(S[MOM_TU] / (S[MOM_UU] + 1e-8));
+    if (resc) {
+        const double N = (double)n, at = at_f, au = (double)au_f * (double)alpha, ap = ap_f, r = r_f;
+        const double sc = at * S[MOM_T] + au * S[MOM_U] + ap * S[MOM_P];
+        const double scc = at * at * S[MOM_TT] + au * au * S[MOM_UU] + ap * ap * S[MOM_PP] + 2.0 * (at * au * S[MOM_TU] + at * ap * S[MOM_TP] + au * ap * S[MOM_UP]);
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);         // one element: the unbiased variance is 0 / 0
+        const double vt = n > 1 ? (S[MOM_TT] - S[MOM_T] * S[MOM_T] / N) / (N - 1.0) : nan;
+        const double vc = n > 1 ? (scc - sc * sc / N) / (N - 1.0) : nan;
+        factor = (float)(r * (sqrt(vt) / sqrt(vc)) + (1.0 - r));
+    }
+    scal[2 * b] = alpha; scal[2 * b + 1] = factor;
+    if (scal_out) { scal_out[2 * b] = alpha; scal_out[2 * b + 1] = factor; }
+}
+// the combined prediction of one element: roundings spelled out as in step_pred (one fused multiply-add per guidance term)
+__device__ __forceinline__ float mix_ex(const GuidanceArgs& a, int form, bool resc, float alpha, float factor, float t, float u, float p) {
+#pragma clang fp contract(off)
+    float c = t;
+    if (a.uncond) { const float us = alpha * u; c = __builtin_fmaf(a.guidance_scale, t - us, us); }
+    if (form == 0) {
+        if (resc) c = factor * c;
+        if (a.pert) c = __builtin_fmaf(a.stg_scale, t - p, c);
+    } else {
+        if (a.pert) c = __builtin_fmaf(a.stg_scale, t - p, c);
+        if (resc) c = c * factor;
+    }
+    return c;
+}
+// 16-byte accesses on the chunks of a row (row_split); every load of an iteration is issued in front of its stores.  A chunk whose
+// four elements are all held reads the predictions only if noise_out wants them and leaves the latents alone; a chunk that a frame
+// boundary cuts writes a held element's own bits back.  scal: (alpha, factor) per batch row, or null (both 1).
+template <typename P>
+__global__ __launch_bounds__(256) void guidance_apply_ex_kernel(GuidanceArgs a, int form, int resc_i, int vec, const float* __restrict__ scal) {
+    const int b = blockIdx.y;
+    const int64_t n = a.n_per_batch, base = (int64_t)b * n;
+    const RowSplit rs = row_split(n, b, vec);
+    const bool resc = resc_i != 0;
+    const float alpha = scal ? scal[2 * b] : 1.0f, factor = scal ? scal[2 * b + 1] : 1.0f;
+    const P* tp = reinterpret_cast<const P*>(a.text); const P* up = reinterpret_cast<const P*>(a.uncond); const P* pp = reinterpret_cast<const P*>(a.pert);
+    const unsigned char* hold = a.hold ? a.hold + (int64_t)b * a.num_frames : nullptr;
+    const bool one_frame = hold && (a.frame_elems & 3) == 0 && rs.head == 0;     // a chunk never crosses a frame boundary
+    const int64_t stride = (int64_t)gridDim.x * 256, first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t ch = first; ch < rs.nch; ch += stride) {
+        const int64_t j0 = rs.head + 4 * ch, i = base + j0;
+        bool h[4] = {false, false, false, false};
+        if (one_frame) h[0] = h[1] = h[2] = h[3] = hold[j0 / a.frame_elems] != 0;
+        else if (hold) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) h[k] = hold[(j0 + k) / a.frame_elems] != 0;
+        }
+        const bool skip_x = !a.latents || (h[0] && h[1] && h[2] && h[3]);
+        if (skip_x && !a.noise_out) continue;
+        float t[4], u[4] = {0.f, 0.f, 0.f, 0.f}, p[4] = {0.f, 0.f, 0.f, 0.f}, c[4];
+        ld4<P>(tp + i, t);
+        if (up) ld4<P>(up + i, u);
+        if (pp) ld4<P>(pp + i, p);
+        f32x4 x = {0.f, 0.f, 0.f, 0.f}, nz = {0.f, 0.f, 0.f, 0.f};
+        if (!skip_x) {
+            x = *reinterpret_cast<const f32x4*>(a.latents + i);
+            if (a.step_noise) nz = *reinterpret_cast<const f32x4*>(a.step_noise + i);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = mix_ex(a, form, resc, alpha, factor, t[k], u[k], p[k]);
+        if (a.noise_out) *reinterpret_cast<f32x4*>(a.noise_out + i) = (f32x4){c[0], c[1], c[2], c[3]};
+        if (skip_x) continue;
+        f32x4 y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = h[k] ? x[k] : step_update(a, x[k], c[k], nz[k]);
+        *reinterpret_cast<f32x4*>(a.latents + i) = y;
+    }
+    for (int64_t k = first; k < rs.nsc; k += stride) {
+        const int64_t j = rs.scalar_elem(k), i = base + j;
+        const bool held = hold && hold[j / a.frame_elems] != 0;
+        const bool skip_x = !a.latents || held;
+        if (skip_x && !a.noise_out) continue;
+        const float t = to_f32(tp[i]), u = up ? to_f32(up[i]) : 0.f, p = pp ? to_f32(pp[i]) : 0.f;
+        const float x = skip_x ? 0.f : a.latents[i], nz = (!skip_x && a.step_noise) ? a.step_noise[i] : 0.f;
+        const float c = mix_ex(a, form, resc, alpha, factor, t, u, p);
+        if (a.noise_out) a.noise_out[i] = c;
+        if (!skip_x) a.latents[i] = step_update(a, x, c, nz);
+    }
+}
 // one block row per (batch row, frame): a held frame is copied in 16-byte chunks (or element-wise when the frame is not a multiple of 4)
 __global__ __launch_bounds__(256) void cond_apply_kernel(float* latents, const float* cond, int Fc, const unsigned char* hold, int F, int64_t frame_elems, int vec) {
     const int bf = blockIdx.y, b = bf / F, f = bf - b * F;
@@ -428,6 +594,67 @@ int ltx_launch_guidance_step(const GuidanceArgs& a, hipStream_t s) {
 int ltx_launch_guidance_step_held(const GuidanceArgs& a, hipStream_t s) {
     if (!a.hold) LTX_FAIL(LTX_ERR_ARG, "guidance (held): hold is required");
     return ltx_launch_guidance_step(a, s);
+}
+// ---- the scheduled mix (include/ltxhip_guidance.h) ----
+namespace {
+// blocks of the moments pass per batch row: 2048 elements each, 256 at most - a function of n alone, so the partials' order is too
+inline int moments_blocks(int64_t n) { const int64_t b = cdiv64(n, 2048); return (int)(b > 256 ? 256 : (b < 1 ? 1 : b)); }
+template <typename P>
+void launch_moments(const GuidanceArgs& g, bool with_pert, int vec, int nblk, double* part, hipStream_t s) {
+    const dim3 grid((unsigned)nblk, (unsigned)g.B);
+    // the perturbed prediction is read only where it is part of the rescaled c (LTX_RESCALE_MIX)
+    const P* t = reinterpret_cast<const P*>(g.text); const P* u = reinterpret_cast<const P*>(g.uncond); const P* p = with_pert ? reinterpret_cast<const P*>(g.pert) : nullptr;
+    if (u && p) hipLaunchKernelGGL((guidance_moments_kernel<P, true, true>), grid, dim3(256), 0, s, t, u, p, g.n_per_batch, vec, part);
+    else if (u) hipLaunchKernelGGL((guidance_moments_kernel<P, true, false>), grid, dim3(256), 0, s, t, u, p, g.n_per_batch, vec, part);
+    else if (p) hipLaunchKernelGGL((guidance_moments_kernel<P, false, true>), grid, dim3(256), 0, s, t, u, p, g.n_per_batch, vec, part);
+    else hipLaunchKernelGGL((guidance_moments_kernel<P, false, false>), grid, dim3(256), 0, s, t, u, p, g.n_per_batch, vec, part);
+}
+}  // namespace
+size_t ltx_guidance_ex_ws_bytes(int B, int64_t n_per_batch) {
+    if (B < 1 || n_per_batch < 1) return 0;
+    const size_t bytes = (size_t)B * moments_blocks(n_per_batch) * MOM_N * sizeof(double) + (size_t)B * 2 * sizeof(float);
+    return (bytes + 15) & ~(size_t)15;
+}
+int ltx_launch_guidance_step_ex(const GuidanceExArgs& a, hipStream_t s) {
+    const GuidanceArgs& g = a.g;
+    if (!g.text || g.B < 1 || g.B > 65535 || g.n_per_batch < 1 || g.n_per_batch > (1LL << 40)) LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex: text prediction, 1 <= B <= 65535 and 1 <= n <= 2^40 required");
+    if (!g.latents && !g.noise_out && !a.scalars_out) LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex: nothing to write (latents, noise_pred_out and scalars_out are all null)");
+    if (a.rescale_form != 0 && a.rescale_form != 1) LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex: unknown rescale_form " + std::to_string(a.rescale_form) + " (0 = LTX_RESCALE_CFG, 1 = LTX_RESCALE_MIX)");
+    if (a.cfg_star != 0 && a.cfg_star != 1) LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex: cfg_star must be 0 or 1");
+    if (g.step_noise && !g.latents) LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex: the stochastic update needs latents");
+    if (g.hold && (g.num_frames < 1 || g.frame_elems < 1 || (int64_t)g.num_frames * g.frame_elems != g.n_per_batch))
+        LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex (held): n must equal num_frames * frame_elems");
+    if (!a.ws || ((uintptr_t)a.ws & 15)) LTX_FAIL(LTX_ERR_ARG, "guidance_step_ex: a 16-byte aligned workspace of ltx_guidance_ws_bytes(B, n) is required");
+    const bool bf = g.pred_dtype == LTX_DT_BF16;
+    const uintptr_t pa = bf ? 7 : 15;
+    const int vec = !((uintptr_t)g.text & pa) && !((uintptr_t)g.uncond & pa) && !((uintptr_t)g.pert & pa) &&
+                    !((uintptr_t)g.latents & 15) && !((uintptr_t)g.noise_out & 15) && !((uintptr_t)g.step_noise & 15);
+    const bool use_alpha = a.cfg_star && g.uncond;
+    const bool resc = a.rescale_form == 0 ? (g.uncond && g.guidance_rescale > 0.0f) : (g.pert && g.guidance_rescale != 1.0f);
+    const bool need = use_alpha || resc;
+    const int nblk = moments_blocks(g.n_per_batch);
+    double* part = reinterpret_cast<double*>(a.ws);
+    float* scal = reinterpret_cast<float*>(part + (size_t)g.B * nblk * MOM_N);
+    if (need) {
+        const bool with_pert = a.rescale_form == 1 && g.pert;
+        if (bf) launch_moments<bf16_t>(g, with_pert, vec, nblk, part, s); else launch_moments<float>(g, with_pert, vec, nblk, part, s);
+        LTX_CHECK_LAUNCH();
+    }
+    if (need || a.scalars_out) {
+        // c in front of the rescale = at t + au alpha u + ap p
+        float at = g.uncond ? g.guidance_scale : 1.0f, au = g.uncond ? 1.0f - g.guidance_scale : 0.0f, ap = 0.0f;
+        if (a.rescale_form == 1 && g.pert) { at += g.stg_scale; ap = -g.stg_scale; }
+        hipLaunchKernelGGL(guidance_finish_kernel, dim3((unsigned)g.B), dim3(256), 0, s, part, need ? nblk : 0, g.n_per_batch, use_alpha ? 1 : 0, resc ? 1 : 0,
+                           at, au, ap, g.guidance_rescale, scal, a.scalars_out);
+        LTX_CHECK_LAUNCH();
+    }
+    if (!g.latents && !g.noise_out) return LTX_OK;
+    int64_t units = vec ? (g.n_per_batch >> 2) : g.n_per_batch; if (units < 8) units = 8;      // (the scalar rest of an aligned row is at most 6 elements)
+    int64_t bx = cdiv64(units, 256); if (bx > (1 << 20)) bx = 1 << 20;
+    const dim3 grid((unsigned)bx, (unsigned)g.B);
+    if (bf) hipLaunchKernelGGL(guidance_apply_ex_kernel<bf16_t>, grid, dim3(256), 0, s, g, a.rescale_form, resc ? 1 : 0, vec, need ? scal : nullptr);
+    else hipLaunchKernelGGL(guidance_apply_ex_kernel<float>, grid, dim3(256), 0, s, g, a.rescale_form, resc ? 1 : 0, vec, need ? scal : nullptr);
+    LTX_CHECK_LAUNCH(); return LTX_OK;
 }
 int ltx_launch_cond_apply(float* latents, const float* cond, int Fc, const unsigned char* hold_dev, int B, int F, int64_t frame_elems, hipStream_t s) {
     if (!latents || !cond || !hold_dev || B < 1 || F < 1 || Fc < 1 || frame_elems < 1) LTX_FAIL(LTX_ERR_ARG, "cond_apply: bad argument");

@@ -314,6 +314,17 @@ struct GuidanceArgs {
 };
 int ltx_launch_guidance_step(const GuidanceArgs& a, hipStream_t s);
 int ltx_launch_guidance_step_held(const GuidanceArgs& a, hipStream_t s);
+// The mix of include/ltxhip_guidance.h (CFG-star, the two rescale forms) and the same scheduler update: a moments pass (nine sums per
+// batch row, one partial per block in `ws`, no atomics), a fixed-order finish (alpha, factor per row) and a 16-byte apply pass.
+// g.stats is not used; g.uncond / g.pert null = the branch is absent and is not read.
+struct GuidanceExArgs {
+    GuidanceArgs g;
+    int cfg_star = 0, rescale_form = 0;     // ltx_rescale_form
+    void* ws = nullptr;                     // device, ltx_guidance_ex_ws_bytes(B, n_per_batch), 16-byte aligned
+    float* scalars_out = nullptr;           // optional device f32 [B][2]: alpha, factor
+};
+size_t ltx_guidance_ex_ws_bytes(int B, int64_t n_per_batch);
+int ltx_launch_guidance_step_ex(const GuidanceExArgs& a, hipStream_t s);
 // latents[b][f] = cond[b][f] for the frames with hold_dev[b * F + f] != 0 (f < Fc); latents f32 [B, F, frame_elems], cond f32 [B, Fc, frame_elems]
 int ltx_launch_cond_apply(float* latents, const float* cond, int Fc, const unsigned char* hold_dev, int B, int F, int64_t frame_elems, hipStream_t s);
 

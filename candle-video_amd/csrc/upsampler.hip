@@ -26,6 +26,7 @@
 #include "../host/weight_list.h"
 #include "../../include/ltxhip_upsampler_st.h"
 #include "../../include/ltxhip_weights.h"
+#include "../../include/ltxhip_guidance.h"
 
 namespace {
 
@@ -757,11 +758,29 @@ extern "C" int ltx_pipeline_multiscale_last_timing(float ms[9]) {
     return LTX_OK;
 }
 
+// one pass of the two: under its guidance schedule (include/ltxhip_guidance.h) or, without one, on its params' scalars
+static int multiscale_pass(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched, float* latents,
+                           const float* prompt_embeds, const float* prompt_mask, const float* neg_embeds, const float* neg_mask,
+                           const float* decode_noise, int B, int K, float* out_video, ltx_stream stream) {
+    if (sched) return ltx_pipeline_call_sched(dit, vae, p, sched, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return ltx_pipeline_call(dit, vae, p, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+}
+
 extern "C" int ltx_pipeline_call_multiscale(ltx_dit* dit, ltx_vae* vae, ltx_upsampler* up,
                                             const ltx_pipeline_params* p_first, const ltx_pipeline_params* p_second, float adain_factor,
                                             float* latents_lo, const float* noise_hi,
                                             const float* prompt_embeds, const float* prompt_mask, const float* neg_embeds, const float* neg_mask,
                                             const float* decode_noise, int B, int K, float* latents_hi_out, float* out_video, ltx_stream stream) {
+    return ltx_pipeline_call_multiscale_sched(dit, vae, up, p_first, p_second, nullptr, nullptr, adain_factor, latents_lo, noise_hi, prompt_embeds, prompt_mask,
+                                              neg_embeds, neg_mask, decode_noise, B, K, latents_hi_out, out_video, stream);
+}
+
+extern "C" int ltx_pipeline_call_multiscale_sched(ltx_dit* dit, ltx_vae* vae, ltx_upsampler* up,
+                                                  const ltx_pipeline_params* p_first, const ltx_pipeline_params* p_second,
+                                                  const ltx_guidance_schedule* sched_first, const ltx_guidance_schedule* sched_second, float adain_factor,
+                                                  float* latents_lo, const float* noise_hi,
+                                                  const float* prompt_embeds, const float* prompt_mask, const float* neg_embeds, const float* neg_mask,
+                                                  const float* decode_noise, int B, int K, float* latents_hi_out, float* out_video, ltx_stream stream) {
     if (!dit || !vae || !up || !p_first || !p_second || !latents_lo || !noise_hi || !latents_hi_out) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: null argument");
     if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_multiscale: bad batch");
     // the geometry rule follows the handle's kind (ltxhip_upsampler_st.h)
@@ -796,7 +815,7 @@ extern "C" int ltx_pipeline_call_multiscale(ltx_dit* dit, ltx_vae* vae, ltx_upsa
 
     ltx_pipeline_params p1 = *p_first;
     p1.output_latent = 1;
-    LTX_TRY(ltx_pipeline_call(dit, vae, &p1, latents_lo, prompt_embeds, prompt_mask, neg_embeds, neg_mask, nullptr, B, K, nullptr, stream));
+    LTX_TRY(multiscale_pass(dit, vae, &p1, sched_first, latents_lo, prompt_embeds, prompt_mask, neg_embeds, neg_mask, nullptr, B, K, nullptr, stream));
     LTX_TRY(ltx_pipeline_last_timing(t_ms_timing));
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -809,7 +828,7 @@ extern "C" int ltx_pipeline_call_multiscale(ltx_dit* dit, ltx_vae* vae, ltx_upsa
     HIP_TRY(hipEventRecord(e1, s));
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(&t_ms_timing[4], e0, e1));
-    LTX_TRY(ltx_pipeline_call(dit, vae, p_second, latents_hi_out, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream));
+    LTX_TRY(multiscale_pass(dit, vae, p_second, sched_second, latents_hi_out, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream));
     return ltx_pipeline_last_timing(t_ms_timing + 5);
 }
 

@@ -4,10 +4,12 @@
 // 646-668), src/utils/deterministic_rng.rs (:11-81), examples/ltx-video/main.rs (:567-646).
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "../csrc/model_util.h"
 #include "../csrc/options.h"
 #include "../../include/ltxhip_cond.h"
+#include "../../include/ltxhip_guidance.h"
 
 // calculate_shift (t2v_pipeline.rs:159-169), f32 arithmetic
 extern "C" float ltx_calculate_shift(int seq_len, int base_seq_len, int max_seq_len, float base_shift, float max_shift) {
@@ -262,6 +264,71 @@ extern "C" int ltx_guidance_step_stochastic_held(const void* text, const void* u
     return ltx_launch_guidance_step_held(a, (hipStream_t)stream);
 }
 
+// ---- per-step guidance schedules, CFG-star, the two rescale forms (include/ltxhip_guidance.h) ----
+// the argument checks every entry point of a schedule shares; num_layers < 0: the model is not known (the host-only resolve)
+static int guidance_schedule_check(const ltx_guidance_schedule* sc, int num_layers) {
+    if (!sc) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: null schedule");
+    if (sc->n < 1 || sc->n > 64) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: n must be 1..64, got " + std::to_string(sc->n));
+    if (!sc->guidance_scale || !sc->stg_scale || !sc->rescale || !sc->skip_offsets) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: guidance_scale, stg_scale, rescale and skip_offsets are required");
+    if (sc->rescale_form != LTX_RESCALE_CFG && sc->rescale_form != LTX_RESCALE_MIX)
+        LTX_FAIL(LTX_ERR_ARG, "guidance schedule: unknown rescale_form " + std::to_string(sc->rescale_form) + " (0 = LTX_RESCALE_CFG, 1 = LTX_RESCALE_MIX)");
+    if (sc->cfg_star != 0 && sc->cfg_star != 1) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: cfg_star must be 0 or 1");
+    if (sc->skip_offsets[0] != 0) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: skip_offsets must start at 0");
+    for (int j = 0; j < sc->n; ++j) {
+        const std::string at = " in entry " + std::to_string(j);
+        if (!std::isfinite(sc->guidance_scale[j]) || !std::isfinite(sc->stg_scale[j]) || !std::isfinite(sc->rescale[j])) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: non-finite scale" + at);
+        if (sc->guidance_timesteps && !std::isfinite(sc->guidance_timesteps[j])) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: non-finite guidance_timesteps value" + at);
+        if (sc->stg_scale[j] < 0.0f) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: negative stg_scale" + at);
+        if (sc->skip_offsets[j + 1] < sc->skip_offsets[j]) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: skip_offsets decrease" + at);
+        if (sc->skip_offsets[j + 1] > sc->skip_offsets[j] && !sc->skip_blocks) LTX_FAIL(LTX_ERR_ARG, "guidance schedule: skip_blocks is null but a block list is not empty" + at);
+        for (int k = sc->skip_offsets[j]; k < sc->skip_offsets[j + 1]; ++k)
+            if (sc->skip_blocks[k] < 0 || (num_layers >= 0 && sc->skip_blocks[k] >= num_layers))
+                LTX_FAIL(LTX_ERR_ARG, "guidance schedule: block index " + std::to_string(sc->skip_blocks[k]) + " outside the model" + at);
+    }
+    return LTX_OK;
+}
+
+extern "C" int ltx_guidance_schedule_resolve(const ltx_guidance_schedule* sched, const float* sigmas, int N, int* entry_of_step) {
+    LTX_TRY(guidance_schedule_check(sched, -1));
+    if (!sigmas || !entry_of_step || N < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_schedule_resolve: sigmas, entry_of_step and N >= 1 are required");
+    if (!sched->guidance_timesteps) {
+        if (sched->n != 1 && sched->n != N)
+            LTX_FAIL(LTX_ERR_ARG, "guidance schedule: without guidance_timesteps n must be 1 or the number of steps (" + std::to_string(N) + "), got " + std::to_string(sched->n));
+        for (int i = 0; i < N; ++i) entry_of_step[i] = sched->n == 1 ? 0 : i;
+        return LTX_OK;
+    }
+    for (int i = 0; i < N; ++i) {
+        int best = 0; double dbest = std::fabs((double)sched->guidance_timesteps[0] - (double)sigmas[i]);
+        for (int j = 1; j < sched->n; ++j) {
+            const double d = std::fabs((double)sched->guidance_timesteps[j] - (double)sigmas[i]);
+            if (d < dbest) { dbest = d; best = j; }      // (strictly: the first minimum wins a tie)
+        }
+        entry_of_step[i] = best;
+    }
+    return LTX_OK;
+}
+
+extern "C" size_t ltx_guidance_ws_bytes(int B, int64_t n) { return ltx_guidance_ex_ws_bytes(B, n); }
+
+extern "C" int ltx_guidance_step_ex(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype,
+                                    float* latents, float* noise_pred_out, int B, int64_t n,
+                                    float guidance_scale, float guidance_rescale, float stg_scale, int cfg_star, int rescale_form,
+                                    float dt, float sigma, float sigma_next, const float* step_noise,
+                                    const unsigned char* hold, int num_frames, int64_t frame_elems,
+                                    void* ws, float* scalars_out, ltx_stream stream) {
+    if (!std::isfinite(guidance_scale) || !std::isfinite(guidance_rescale) || !std::isfinite(stg_scale)) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_ex: non-finite scale");
+    if (stg_scale < 0.0f) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_ex: negative stg_scale");
+    if (pred_dtype != LTX_F32 && pred_dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_ex: bad dtype");
+    GuidanceExArgs a;
+    a.g.text = text; a.g.uncond = uncond; a.g.pert = perturbed; a.g.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
+    a.g.latents = latents; a.g.noise_out = noise_pred_out; a.g.B = B; a.g.n_per_batch = n;
+    a.g.guidance_scale = guidance_scale; a.g.guidance_rescale = guidance_rescale; a.g.stg_scale = stg_scale;
+    if (step_noise) { a.g.sigma = sigma; a.g.sigma_next = sigma_next; a.g.step_noise = step_noise; } else a.g.dt = dt;
+    if (hold) { a.g.hold = hold; a.g.num_frames = num_frames; a.g.frame_elems = frame_elems; }
+    a.cfg_star = cfg_star; a.rescale_form = rescale_form; a.ws = ws; a.scalars_out = scalars_out;
+    return ltx_launch_guidance_step_ex(a, (hipStream_t)stream);
+}
+
 extern "C" int ltx_cond_apply(float* latents, const float* cond_tokens, int cond_frames, const unsigned char* hold,
                               int B, int num_frames, int tokens_per_frame, int channels, ltx_stream stream) {
     if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_apply: hold is required");
@@ -305,7 +372,7 @@ namespace {
 // Device scratch of the denoise loop, kept per (thread, device) across calls: per-call hipMalloc/hipFree (an implicit
 // device sync each) and the coords rebuild + blocking upload cost ~1 ms per video for nothing.
 struct PipeCache {
-    DevBuf p_text, p_uncond, p_pert, stats, coords, hold;
+    DevBuf p_text, p_uncond, p_pert, stats, coords, hold, gws;
     DevBuf g_lat, g_emb, g_mask, g_pred, g_coords;      // the guidance branches of a step as one forward: inputs / predictions of all branches
     int coords_key[6] = {-1, -1, -1, -1, -1, -1};      // B, F, H, W, frame_rate, ratios packed
 };
@@ -345,8 +412,20 @@ int ltx_pipeline_schedule(const ltx_pipeline_params* p, int S, std::vector<float
     return ltx_sched_set_timesteps(sig_in.data(), N, mu, 1, 1.0f, p->shift_terminal, p->use_shift_terminal, sig->data(), ts->data());
 }
 
+// A schedule resolved against the call's sigmas (include/ltxhip_guidance.h): what each step's guidance is.
+struct StepGuidance {
+    const ltx_guidance_schedule* sc = nullptr;
+    std::vector<int> entry;                                 // entry_of_step [N]
+    float g(int i) const { return sc->guidance_scale[entry[i]]; }
+    float s(int i) const { return sc->stg_scale[entry[i]]; }
+    float r(int i) const { return sc->rescale[entry[i]]; }
+    const int* skip(int i) const { return sc->skip_blocks + sc->skip_offsets[entry[i]]; }      // (never read when n_skip is 0)
+    int n_skip(int i) const { return sc->skip_offsets[entry[i] + 1] - sc->skip_offsets[entry[i]]; }
+};
+
 // hold: HOST u8 [B, F'] or null - the held latent frames of ltx_pipeline_call_cond (include/ltxhip_cond.h); null: ltx_pipeline_call
-static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const unsigned char* hold,
+// plan: null - the scalars of `p` on every step; else the branches, scales and perturbed blocks are the step's own (ltx_pipeline_call_sched)
+static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const unsigned char* hold, const StepGuidance* plan,
                         float* latents, const float* prompt_embeds, const float* prompt_mask,
                         const float* neg_embeds, const float* neg_mask, const float* decode_noise,
                         int B, int K, float* out_video, ltx_stream stream) {
@@ -355,7 +434,12 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     // check_inputs (:313-365)
     if (p->height % 32 != 0 || p->width % 32 != 0) LTX_FAIL(LTX_ERR_ARG, "`height` and `width` must be divisible by 32");
     if (p->num_inference_steps < 1) LTX_FAIL(LTX_ERR_ARG, "num_inference_steps must be >= 1");
-    const bool do_cfg = p->guidance_scale > 1.0f, do_stg = p->stg_scale > 0.0f;      // :304-310
+    // :304-310; under a schedule: whether ANY step has the branch (the steps decide for themselves below)
+    bool do_cfg = p->guidance_scale > 1.0f, do_stg = p->stg_scale > 0.0f;
+    if (plan) {
+        do_cfg = do_stg = false;
+        for (int i = 0; i < p->num_inference_steps; ++i) { do_cfg = do_cfg || plan->g(i) > 1.0f; do_stg = do_stg || plan->s(i) > 0.0f; }
+    }
     if (do_cfg && (!neg_embeds || !neg_mask)) LTX_FAIL(LTX_ERR_ARG, "classifier-free guidance needs negative embeddings and mask");
     if (p->stochastic_sampling && !p->step_noise) LTX_FAIL(LTX_ERR_ARG, "stochastic_sampling needs step_noise [steps,B,S*C]");
     hipStream_t s = (hipStream_t)stream;
@@ -367,7 +451,8 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     const int64_t n = (int64_t)S * C;
 
     // skip blocks: permanent iff STG is off (:691-697)
-    if (p->skip_block_list) {
+    if (plan) LTX_TRY(ltx_dit_set_skip_blocks(dit, nullptr, 0));      // a schedule never skips a block for good
+    else if (p->skip_block_list) {
         if (!do_stg) LTX_TRY(ltx_dit_set_skip_blocks(dit, p->skip_block_list, p->n_skip_blocks));
         else LTX_TRY(ltx_dit_set_skip_blocks(dit, nullptr, 0));
     }
@@ -384,6 +469,7 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     if (do_cfg) { LTX_TRY(pc.p_uncond.ensure(pred_bytes)); sc.p_uncond = pc.p_uncond.p; }
     if (do_stg) { LTX_TRY(pc.p_pert.ensure(pred_bytes)); sc.p_pert = pc.p_pert.p; }
     LTX_TRY(pc.stats.ensure(64 * B)); sc.stats = pc.stats.p;
+    if (plan) LTX_TRY(pc.gws.ensure(ltx_guidance_ex_ws_bytes(B, n)));
     if (hold) {                                      // device copy for the update kernels (the model's per-frame timesteps are built on the host)
         LTX_TRY(pc.hold.ensure((size_t)B * F));
         HIP_TRY(hipMemcpyAsync(pc.hold.p, hold, (size_t)B * F, hipMemcpyHostToDevice, s));
@@ -412,7 +498,7 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     // rounds of the chip per attention launch and fewer one-round grids (one C3 step 61.8 -> 58.1 ms).  guidance_batch=0: the
     // reference's three calls.
     const int nbr = 1 + (do_cfg ? 1 : 0) + (do_stg ? 1 : 0);
-    const bool gbatch = nbr > 1 && nbr * B <= 8 && ltx_opt().guidance_batch;
+    const bool gbatch = !plan && nbr > 1 && nbr * B <= 8 && ltx_opt().guidance_batch;      // (a schedule: per step, below)
     const int Dt = dc.caption_channels;
     std::vector<float> g_slm;
     if (gbatch) {
@@ -436,10 +522,33 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             LTX_TRY(put(prompt_embeds, prompt_mask));
         }
     }
+    // Under a schedule the branches differ from step to step.  The inputs of all three lie in the order above, B rows each - slot 0
+    // negative prompt, slot 1 prompt, slot 2 prompt again - so every composition is a contiguous run of slots: uncond + text slots
+    // 0-1, text + perturbed slots 1-2, all three 0-2 (text alone is no batch: the caller's own tensors).  The DiT's text context is
+    // keyed by (embeddings, mask, rows): these four are exactly the four entries it keeps (text_context, dit.hip), each computed once
+    // per call.  Whether a step's branches fit the 8-row pass is judged per step.
+    bool sched_gb = false;
+    if (plan && ltx_opt().guidance_batch)
+        for (int i = 0; i < N; ++i) { const int nb = 1 + (plan->g(i) > 1.0f ? 1 : 0) + (plan->s(i) > 0.0f ? 1 : 0); sched_gb = sched_gb || (nb > 1 && nb * B <= 8); }
+    if (sched_gb) {
+        const int GB = 3 * B;
+        LTX_TRY(pc.g_lat.ensure((size_t)GB * n * sizeof(float))); LTX_TRY(pc.g_pred.ensure((size_t)GB * n * sizeof(float)));
+        LTX_TRY(pc.g_emb.ensure((size_t)GB * K * Dt * sizeof(float))); LTX_TRY(pc.g_mask.ensure((size_t)GB * K * sizeof(float)));
+        LTX_TRY(pc.g_coords.ensure((size_t)GB * S * 3 * sizeof(float)));
+        auto put = [&](int slot, const float* e, const float* mk) -> int {
+            HIP_TRY(hipMemcpyAsync(pc.g_emb.as<float>() + (size_t)slot * B * K * Dt, e, (size_t)B * K * Dt * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(pc.g_mask.as<float>() + (size_t)slot * B * K, mk, (size_t)B * K * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(pc.g_coords.as<float>() + (size_t)slot * B * S * 3, sc.coords, (size_t)B * S * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return LTX_OK;
+        };
+        if (do_cfg) LTX_TRY(put(0, neg_embeds, neg_mask));
+        LTX_TRY(put(1, prompt_embeds, prompt_mask));
+        if (do_stg) LTX_TRY(put(2, prompt_embeds, prompt_mask));
+    }
     for (auto& e : sc.ev) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(sc.ev[0], s));
     std::vector<float> stg_mask;
-    if (do_stg) {                                    // :911-923
+    if (do_stg && !plan) {                           // :911-923
         stg_mask.assign((size_t)L * B, 0.0f);
         for (int i = 0; i < p->n_skip_blocks; ++i) { int li = p->skip_block_list[i]; if (li >= 0 && li < L) for (int b = 0; b < B; ++b) stg_mask[(size_t)li * B + b] = 1.0f; }
     }
@@ -465,8 +574,14 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
         LTX_TRY(sc.new_event(&e0)); LTX_TRY(sc.new_event(&e1)); LTX_TRY(sc.new_event(&e2));
         HIP_TRY(hipEventRecord(e0, s));
         // held frames: the model sees timestep 0 for their tokens and t_i for the rest, in every guidance branch
+        // the branches of THIS step (a schedule: uncond iff g > 1, perturbed iff s > 0)
+        bool cfg_i = do_cfg, stg_i = do_stg, gb_i = gbatch; int nbr_i = nbr;
+        if (plan) {
+            cfg_i = plan->g(i) > 1.0f; stg_i = plan->s(i) > 0.0f; nbr_i = 1 + (cfg_i ? 1 : 0) + (stg_i ? 1 : 0);
+            gb_i = sched_gb && nbr_i > 1 && nbr_i * B <= 8;
+        }
         if (hold) {
-            tframes.resize((size_t)(gbatch ? nbr : 1) * B * F);
+            tframes.resize((size_t)(gb_i ? nbr_i : 1) * B * F);
             for (size_t r = 0; r < tframes.size() / ((size_t)B * F); ++r)
                 for (size_t j = 0; j < (size_t)B * F; ++j) tframes[r * B * F + j] = hold[j] ? 0.0f : (float)ts[i];
         }
@@ -474,7 +589,23 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             if (hold) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
             return ltx_dit_forward(dit, x, emb, tvals, mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
         };
-        if (gbatch) {
+        void *pt = sc.p_text, *pu = sc.p_uncond, *pp = sc.p_pert;
+        auto skip_rows = [&](std::vector<float>& m, int rows, int row0) {      // ones on the step's block list for rows [row0, row0 + B) of [L, rows]
+            m.assign((size_t)L * rows, 0.0f);
+            for (int k = 0; k < plan->n_skip(i); ++k) for (int b = 0; b < B; ++b) m[(size_t)plan->skip(i)[k] * rows + row0 + b] = 1.0f;
+        };
+        if (plan && gb_i) {
+            const int r0 = cfg_i ? 0 : 1, rows = nbr_i * B;                      // the step's slots: [r0, r0 + nbr_i)
+            for (int r = 0; r < nbr_i; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if (stg_i) skip_rows(g_slm, rows, (nbr_i - 1) * B);
+            LTX_TRY(forward(pc.g_lat.p, pc.g_emb.as<float>() + (size_t)r0 * B * K * Dt, pc.g_mask.as<float>() + (size_t)r0 * B * K, rows,
+                            pc.g_coords.as<float>() + (size_t)r0 * B * S * 3, stg_i ? g_slm.data() : nullptr, pc.g_pred.as<float>() + (size_t)r0 * B * n));
+            pu = pc.g_pred.as<float>(); pt = pc.g_pred.as<float>() + (size_t)B * n; pp = pc.g_pred.as<float>() + (size_t)2 * B * n;
+        } else if (plan) {
+            if (cfg_i) LTX_TRY(forward(latents, neg_embeds, neg_mask, B, coords, nullptr, pu));
+            LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, nullptr, pt));
+            if (stg_i) { skip_rows(stg_mask, B, 0); LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, stg_mask.data(), pp)); }
+        } else if (gbatch) {
             for (int r = 0; r < nbr; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
             LTX_TRY(forward(pc.g_lat.p, pc.g_emb.p, pc.g_mask.as<float>(), nbr * B, pc.g_coords.as<float>(), do_stg ? g_slm.data() : nullptr, pc.g_pred.p));
         } else {
@@ -485,7 +616,18 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
         HIP_TRY(hipEventRecord(e1, s));
         // guidance mix (:941-962) + scheduler.step (:987; scheduler.rs:544-581): dt = sigma_next - sigma
         const float dts = sig[i + 1] - sig[i];
-        {
+        if (plan) {                                  // the mix of include/ltxhip_guidance.h on the branches that ran
+            GuidanceExArgs ge;
+            GuidanceArgs& ga = ge.g;
+            ga.text = pt; ga.uncond = cfg_i ? pu : nullptr; ga.pert = stg_i ? pp : nullptr; ga.pred_dtype = LTX_DT_F32;
+            ga.latents = latents; ga.B = B; ga.n_per_batch = n;
+            ga.guidance_scale = plan->g(i); ga.guidance_rescale = plan->r(i); ga.stg_scale = plan->s(i);
+            if (p->stochastic_sampling) { ga.sigma = sig[i]; ga.sigma_next = sig[i + 1]; ga.step_noise = p->step_noise + (size_t)i * B * n; }
+            else ga.dt = dts;
+            if (hold) { ga.hold = pc.hold.as<unsigned char>(); ga.num_frames = F; ga.frame_elems = (int64_t)H * W * C; }
+            ge.cfg_star = plan->sc->cfg_star; ge.rescale_form = plan->sc->rescale_form; ge.ws = pc.gws.p;
+            LTX_TRY(ltx_launch_guidance_step_ex(ge, s));
+        } else {
             GuidanceArgs ga;
             ga.text = sc.p_text; ga.uncond = do_cfg ? sc.p_uncond : nullptr; ga.pert = do_stg ? sc.p_pert : nullptr; ga.pred_dtype = LTX_DT_F32;
             ga.latents = latents; ga.B = B; ga.n_per_batch = n; ga.stats = reinterpret_cast<double*>(sc.stats);
@@ -525,7 +667,7 @@ extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_
                                  float* latents, const float* prompt_embeds, const float* prompt_mask,
                                  const float* neg_embeds, const float* neg_mask, const float* decode_noise,
                                  int B, int K, float* out_video, ltx_stream stream) {
-    return pipeline_run(dit, vae, p, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return pipeline_run(dit, vae, p, nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
 }
 
 extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_conditioning* cond,
@@ -540,7 +682,47 @@ extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipe
     bool any = false;
     for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) any = any || cond->hold[j] != 0;
     // nothing held: ltx_pipeline_call itself
-    return pipeline_run(dit, vae, p, any ? cond->hold : nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return pipeline_run(dit, vae, p, any ? cond->hold : nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+}
+
+// ---- the pipeline calls under a guidance schedule (include/ltxhip_guidance.h) ----
+extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched,
+                                       const ltx_conditioning* cond, float* latents, const float* prompt_embeds, const float* prompt_mask,
+                                       const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                                       int B, int K, float* out_video, ltx_stream stream) {
+    if (!dit || !p || !sched || B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_sched: null argument");
+    if (cond && !cond->hold) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_sched: conditioning without a hold mask");
+    ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
+    LTX_TRY(guidance_schedule_check(sched, dc.num_layers));
+    // the sigmas the denoise loop will run (the same geometry rule and the same builder)
+    int ts_ratio = 8, sp_ratio = 32;
+    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; sp_ratio = vc.spatial_compression_ratio; }
+    if (ts_ratio < 1 || sp_ratio < 1 || p->num_frames < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_sched: bad geometry");
+    const int F = (p->num_frames - 1) / ts_ratio + 1, S = F * (p->height / sp_ratio) * (p->width / sp_ratio);
+    std::vector<float> sig; std::vector<int64_t> ts;
+    LTX_TRY(ltx_pipeline_schedule(p, S, &sig, &ts));
+    const int N = p->num_inference_steps;
+    StepGuidance plan; plan.sc = sched; plan.entry.assign(N, 0);
+    LTX_TRY(ltx_guidance_schedule_resolve(sched, sig.data(), N, plan.entry.data()));
+    const unsigned char* hold = nullptr;
+    if (cond) for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) if (cond->hold[j]) { hold = cond->hold; break; }
+    // The same values on every step, no CFG-star, the reference's rescale: the unscheduled call on those values, its kernels and bits.
+    // (An entry with s == 0 perturbs nothing and skips nothing: its list is not handed on, and the handle's own list is cleared.)
+    bool constant = !sched->cfg_star && sched->rescale_form == LTX_RESCALE_CFG;
+    for (int i = 1; i < N && constant; ++i) {
+        constant = plan.g(i) == plan.g(0) && plan.s(i) == plan.s(0) && plan.r(i) == plan.r(0);
+        if (constant && plan.s(0) > 0.0f && plan.entry[i] != plan.entry[0])
+            constant = plan.n_skip(i) == plan.n_skip(0) && (plan.n_skip(0) == 0 || !std::memcmp(plan.skip(i), plan.skip(0), sizeof(int) * plan.n_skip(0)));
+    }
+    if (constant) {
+        static const int none = 0;
+        ltx_pipeline_params q = *p;
+        q.guidance_scale = plan.g(0); q.stg_scale = plan.s(0); q.guidance_rescale = plan.r(0);
+        const bool stg = plan.s(0) > 0.0f && plan.n_skip(0) > 0;
+        q.skip_block_list = stg ? plan.skip(0) : &none; q.n_skip_blocks = stg ? plan.n_skip(0) : 0;
+        return pipeline_run(dit, vae, &q, hold, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    }
+    return pipeline_run(dit, vae, p, hold, &plan, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
 }
 
 // ---- warm-up: everything a first call would otherwise do inside the caller's forward --------------------------------

@@ -321,6 +321,75 @@ def stg_mode_from_name(name: str) -> int:
     return out.value
 
 
+class GuidanceScheduleC(C.Structure):            # ltx_guidance_schedule (include/ltxhip_guidance.h)
+    _fields_ = [("n", C.c_int), ("guidance_scale", C.POINTER(C.c_float)), ("stg_scale", C.POINTER(C.c_float)), ("rescale", C.POINTER(C.c_float)),
+                ("skip_blocks", C.POINTER(C.c_int)), ("skip_offsets", C.POINTER(C.c_int)), ("guidance_timesteps", C.POINTER(C.c_float)),
+                ("cfg_star", C.c_int), ("rescale_form", C.c_int)]
+
+
+# include/ltxhip_guidance.h (kept apart like the six above)
+_GUIDANCE_SIGS = {
+    "ltx_guidance_schedule_resolve": [_vp, _vp, _i, _vp],
+    "ltx_guidance_ws_bytes": [_i, _i64],
+    "ltx_guidance_step_ex": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _f, _f, _f, _i, _i, _f, _f, _f, _vp, _vp, _i, _i64, _vp, _vp, _vp],
+    "ltx_pipeline_call_sched": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "ltx_pipeline_call_multiscale_sched": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+}
+GUIDANCE_SYMBOLS = sorted(_GUIDANCE_SIGS)
+for _name, _sig in _GUIDANCE_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_size_t if _name == "ltx_guidance_ws_bytes" else C.c_int
+LTX_RESCALE_CFG, LTX_RESCALE_MIX = 0, 1
+RESCALE_FORMS = ("cfg", "mix")                   # ltx_rescale_form, by value
+
+
+@dataclass
+class GuidanceSchedule:
+    """ltx_guidance_schedule: one (guidance_scale, stg_scale, rescale, perturbed block list) per entry; a step takes the entry whose
+    guidance_timesteps value is nearest its sigma (without guidance_timesteps: one entry for every step, or one per step).
+    rescale_form: 'cfg' (the reference: rescale the CFG mix, then add the STG term) or 'mix' (the published recipes: rescale the whole
+    mix on perturbed steps, 1 = off).  The rule is spelled out in include/ltxhip_guidance.h."""
+    guidance_scale: Sequence[float]
+    stg_scale: Sequence[float]
+    rescale: Sequence[float]
+    skip_block_list: Optional[Sequence[Sequence[int]]] = None
+    guidance_timesteps: Optional[Sequence[float]] = None
+    cfg_star: bool = False
+    rescale_form: object = "cfg"
+
+    def to_c(self, keep: list) -> GuidanceScheduleC:
+        n = len(self.guidance_scale)
+        skip = [list(b) for b in self.skip_block_list] if self.skip_block_list is not None else [[] for _ in range(n)]
+        if not (len(self.stg_scale) == len(self.rescale) == len(skip) == n) or (self.guidance_timesteps is not None and len(self.guidance_timesteps) != n):
+            raise LtxError("GuidanceSchedule: every list must have one value per entry")
+        form = RESCALE_FORMS.index(self.rescale_form) if isinstance(self.rescale_form, str) and self.rescale_form in RESCALE_FORMS else self.rescale_form
+        if isinstance(form, str):
+            raise LtxError(f"GuidanceSchedule: unknown rescale_form {form!r} (one of {RESCALE_FORMS})")
+        g, s, r = _floats(self.guidance_scale), _floats(self.stg_scale), _floats(self.rescale)
+        flat = [int(b) for blocks in skip for b in blocks]
+        offs = [0]
+        for blocks in skip:
+            offs.append(offs[-1] + len(blocks))
+        sb, so = (C.c_int * max(len(flat), 1))(*flat), (C.c_int * (n + 1))(*offs)
+        keep += [g, s, r, sb, so]
+        c = GuidanceScheduleC(n, C.cast(g, _fp), C.cast(s, _fp), C.cast(r, _fp), C.cast(sb, C.POINTER(C.c_int)), C.cast(so, C.POINTER(C.c_int)), None,
+                              int(self.cfg_star), int(form))
+        if self.guidance_timesteps is not None:
+            gt = _floats(self.guidance_timesteps); keep.append(gt)
+            c.guidance_timesteps = C.cast(gt, _fp)
+        return c
+
+    def resolve(self, sigmas: Sequence[float]) -> List[int]:
+        """entry of every step that starts at sigmas[i] (ltx_guidance_schedule_resolve; host only)"""
+        keep = []
+        c = self.to_c(keep)
+        sg = _floats(sigmas)
+        out = (C.c_int * max(len(sigmas), 1))()
+        _check(lib.ltx_guidance_schedule_resolve(C.byref(c), sg, len(sigmas), out))
+        return list(out)[:len(sigmas)]
+
+
 # the ten LoRA targets of a block, in the order of ltx_dit_read_linear's `which`
 LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0",
                 "ff.net.0.proj", "ff.net.2")
@@ -1127,6 +1196,60 @@ def guidance_combine(text, uncond=None, perturbed=None, guidance_scale=1.0, guid
     return out
 
 
+def _rescale_form(form) -> int:
+    if isinstance(form, str):
+        if form not in RESCALE_FORMS:
+            raise LtxError(f"unknown rescale_form {form!r} (one of {RESCALE_FORMS})")
+        return RESCALE_FORMS.index(form)
+    return int(form)
+
+
+def guidance_step_ex(text, latents=None, uncond=None, perturbed=None, guidance_scale=1.0, guidance_rescale=0.0, stg_scale=0.0,
+                     cfg_star=False, rescale_form="cfg", dt=0.0, sigma=0.0, sigma_next=0.0, step_noise=None, hold=None, num_frames=None,
+                     want_noise_pred=False, want_scalars=False):
+    """The mix of include/ltxhip_guidance.h (CFG-star, rescale_form 'cfg' / 'mix') and the scheduler update on a copy of `latents`
+    (ltx_guidance_step_ex).  uncond / perturbed None = the branch is absent.  hold [B, num_frames] (device u8 tensor or host values):
+    those latent frames keep their bits.  Returns a dict: 'latents' (None without latents), 'noise_pred' f32 (want_noise_pred),
+    'scalars' f32 [B, 2] = (alpha, factor) per batch row (want_scalars)."""
+    t = _dev(text)
+    u = _dev(uncond, t.dtype) if uncond is not None else None
+    p = _dev(perturbed, t.dtype) if perturbed is not None else None
+    B, n = t.shape[0], t[0].numel()
+    x = _dev(latents, torch.float32).clone() if latents is not None else None
+    if x is not None and (x.shape[0] != B or x[0].numel() != n):
+        raise LtxError("guidance_step_ex: predictions and latents must agree in shape")
+    for name, v in (("uncond", u), ("perturbed", p)):
+        if v is not None and v.shape != t.shape:
+            raise LtxError(f"guidance_step_ex: {name} must have the shape of text")
+    nz = _dev(step_noise, torch.float32) if step_noise is not None else None
+    if nz is not None and (x is None or nz.numel() != B * n):
+        raise LtxError("guidance_step_ex: the stochastic update needs latents and step_noise of their shape")
+    hd, nf = None, 1
+    if hold is not None:
+        if num_frames is None or num_frames < 1 or n % num_frames != 0:
+            raise LtxError("guidance_step_ex: hold needs num_frames dividing the per-row element count")
+        nf = int(num_frames)
+        hd = hold.to(torch.uint8).contiguous() if torch.is_tensor(hold) and hold.is_cuda else torch.tensor(list(_hold_host(hold, B, nf)), dtype=torch.uint8).to(t.device)
+        if hd.numel() != B * nf:
+            raise LtxError(f"hold must have {B} x {nf} entries")
+    out = torch.empty(t.shape, dtype=torch.float32, device=t.device) if want_noise_pred else None
+    sc = torch.empty(B, 2, dtype=torch.float32, device=t.device) if want_scalars else None
+    ws = torch.empty(max(int(lib.ltx_guidance_ws_bytes(B, C.c_int64(n))), 16) // 8 + 2, dtype=torch.float64, device=t.device)
+    _check(lib.ltx_guidance_step_ex(_ptr(t), _ptr(u), _ptr(p), _dt(t.dtype), _ptr(x), _ptr(out), B, C.c_int64(n),
+                                    C.c_float(guidance_scale), C.c_float(guidance_rescale), C.c_float(stg_scale), int(bool(cfg_star)), _rescale_form(rescale_form),
+                                    C.c_float(dt), C.c_float(sigma), C.c_float(sigma_next), _ptr(nz), _ptr(hd), nf, C.c_int64(n // nf),
+                                    _ptr(ws), _ptr(sc), _stream()))
+    return {"latents": x, "noise_pred": out, "scalars": sc}
+
+
+def guidance_combine_ex(text, uncond=None, perturbed=None, guidance_scale=1.0, guidance_rescale=0.0, stg_scale=0.0, cfg_star=False,
+                        rescale_form="cfg", want_scalars=False):
+    """guidance_combine under include/ltxhip_guidance.h: the f32 combined prediction, or (prediction, scalars [B, 2]) with want_scalars"""
+    r = guidance_step_ex(text, None, uncond, perturbed, guidance_scale, guidance_rescale, stg_scale, cfg_star, rescale_form,
+                         want_noise_pred=True, want_scalars=want_scalars)
+    return (r["noise_pred"], r["scalars"]) if want_scalars else r["noise_pred"]
+
+
 def pcg32_randn(seed: int, shape: Sequence[int], inc: int = 1442695040888963407) -> torch.Tensor:
     """Pcg32::new(seed, inc).randn(shape) (deterministic_rng.rs; main.rs:568) -> CPU f32 tensor."""
     n = 1
@@ -1206,8 +1329,10 @@ class LtxPipeline:
     def call(self, args: PipelineCall, latents: torch.Tensor, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
              negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
              decode_noise: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
-             interrupt=None, on_step=None, hold=None):
+             interrupt=None, on_step=None, hold=None, schedule: Optional["GuidanceSchedule"] = None):
         """Returns (final_latents [B,S,C] f32, video [B,3,frames,H,W] f32 or None).
+        schedule: a GuidanceSchedule (ltx_pipeline_call_sched, with `hold` or without) - the guidance of every step comes from it and
+        the scalar guidance fields and skip_block_list of `args` are ignored.
         hold [B, F'] (truthy = held): image-to-video / clip continuation (ltx_pipeline_call_cond) - `latents` carries the held
         latent frames already (cond_apply); they see timestep 0 and leave the call unchanged.
         step_noise [steps,B,S,C] f32: the per-step draws of the stochastic-sampling scheduler (required iff enabled).
@@ -1283,7 +1408,16 @@ class LtxPipeline:
                 video = torch.empty(B, (F - 1) * tr + 1, H * sr, W * sr, 3, dtype=torch.uint8, device=lat.device)
             else:
                 video = torch.empty(B, 3, (F - 1) * tr + 1, H * sr, W * sr, dtype=torch.float32, device=lat.device)
-        if hold is not None:
+        if schedule is not None:
+            sched = schedule.to_c(keep)
+            cond = None
+            if hold is not None:
+                hh = _hold_host(hold, B, F); keep.append(hh)
+                cond = ConditioningC(C.cast(hh, C.POINTER(C.c_ubyte)))
+            _check(lib.ltx_pipeline_call_sched(self.transformer._h, self.vae._h if self.vae is not None else None, C.byref(p), C.byref(sched),
+                                               C.byref(cond) if cond is not None else None, _ptr(lat), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                               _ptr(video), _stream()))
+        elif hold is not None:
             hh = _hold_host(hold, B, F); keep.append(hh)
             cond = ConditioningC(C.cast(hh, C.POINTER(C.c_ubyte)))
             _check(lib.ltx_pipeline_call_cond(self.transformer._h, self.vae._h if self.vae is not None else None, C.byref(p), C.byref(cond),
@@ -1465,8 +1599,11 @@ class LtxMultiScalePipeline:
     def call(self, first: PipelineCall, second: PipelineCall, latents_lo: torch.Tensor, noise_hi: torch.Tensor,
              prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
              negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
-             decode_noise: Optional[torch.Tensor] = None, adain_factor: float = 1.0, interrupt=None, on_step=None):
-        """Returns (first-pass latents [B,S,C], second-pass latents [B,Fo*Ho*Wo,C] (4S for the spatial kind), video or None).  interrupt / on_step as LtxPipeline.call;
+             decode_noise: Optional[torch.Tensor] = None, adain_factor: float = 1.0, interrupt=None, on_step=None,
+             schedule: Optional["GuidanceSchedule"] = None, schedule_second: Optional["GuidanceSchedule"] = None):
+        """schedule / schedule_second: a GuidanceSchedule for the first / second pass (ltx_pipeline_call_multiscale_sched); a pass
+        without one runs on its PipelineCall's scalars.
+        Returns (first-pass latents [B,S,C], second-pass latents [B,Fo*Ho*Wo,C] (4S for the spatial kind), video or None).  interrupt / on_step as LtxPipeline.call;
         both passes see them."""
         lo = _dev(latents_lo, torch.float32).clone()
         nh = _dev(noise_hi, torch.float32)
@@ -1515,9 +1652,17 @@ class LtxMultiScalePipeline:
                 video = torch.empty(B, (Fo - 1) * tr + 1, Ho * sr, Wo * sr, 3, dtype=torch.uint8, device=lo.device)
             else:
                 video = torch.empty(B, 3, (Fo - 1) * tr + 1, Ho * sr, Wo * sr, dtype=torch.float32, device=lo.device)
-        _check(lib.ltx_pipeline_call_multiscale(self.transformer._h, self.vae._h, self.upsampler._h, C.byref(p1), C.byref(p2), float(adain_factor),
-                                                _ptr(lo), _ptr(nh), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
-                                                _ptr(hi), _ptr(video), _stream()))
+        if schedule is not None or schedule_second is not None:
+            s1 = schedule.to_c(keep) if schedule is not None else None
+            s2 = schedule_second.to_c(keep) if schedule_second is not None else None
+            _check(lib.ltx_pipeline_call_multiscale_sched(self.transformer._h, self.vae._h, self.upsampler._h, C.byref(p1), C.byref(p2),
+                                                          C.byref(s1) if s1 is not None else None, C.byref(s2) if s2 is not None else None, float(adain_factor),
+                                                          _ptr(lo), _ptr(nh), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                                          _ptr(hi), _ptr(video), _stream()))
+        else:
+            _check(lib.ltx_pipeline_call_multiscale(self.transformer._h, self.vae._h, self.upsampler._h, C.byref(p1), C.byref(p2), float(adain_factor),
+                                                    _ptr(lo), _ptr(nh), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                                    _ptr(hi), _ptr(video), _stream()))
         ms = (C.c_float * 9)()
         _check(lib.ltx_pipeline_multiscale_last_timing(ms))
         self.last_timing_ms = tuple(ms)

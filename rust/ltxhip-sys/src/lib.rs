@@ -399,3 +399,46 @@ extern "C" {
     pub fn ltx_op_stg_fill(dst: *mut c_void, ldd: c_int, src: *const c_void, lds: c_int, rows: *const u8, b: c_int, s: c_int, d: c_int, dtype: c_int,
                            stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_guidance.h: per-step guidance schedules, CFG-star and the two rescale forms ----
+
+/// `ltx_rescale_form` (a C enum: passed as `c_int`).
+pub const LTX_RESCALE_CFG: c_int = 0;
+pub const LTX_RESCALE_MIX: c_int = 1;
+
+/// `ltx_guidance_schedule`: HOST arrays, one value per entry; entry j perturbs `skip_blocks[skip_offsets[j] .. skip_offsets[j + 1])`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_guidance_schedule {
+    pub n: c_int,
+    pub guidance_scale: *const c_float,
+    pub stg_scale: *const c_float,
+    pub rescale: *const c_float,
+    pub skip_blocks: *const c_int,
+    pub skip_offsets: *const c_int,
+    pub guidance_timesteps: *const c_float,
+    pub cfg_star: c_int,
+    pub rescale_form: c_int,
+}
+
+pub const GUIDANCE_LAYOUT_LTX_GUIDANCE_SCHEDULE: (usize, usize) = (64, 8);
+const _: () = assert!(size_of::<ltx_guidance_schedule>() == GUIDANCE_LAYOUT_LTX_GUIDANCE_SCHEDULE.0 && align_of::<ltx_guidance_schedule>() == GUIDANCE_LAYOUT_LTX_GUIDANCE_SCHEDULE.1);
+
+extern "C" {
+    pub fn ltx_guidance_schedule_resolve(sched: *const ltx_guidance_schedule, sigmas: *const c_float, n_steps: c_int, entry_of_step: *mut c_int) -> c_int;
+    pub fn ltx_guidance_ws_bytes(b: c_int, n: i64) -> usize;
+    pub fn ltx_guidance_step_ex(text: *const c_void, uncond: *const c_void, perturbed: *const c_void, pred_dtype: c_int, latents: *mut c_float,
+                                noise_pred_out: *mut c_float, b: c_int, n: i64, guidance_scale: c_float, guidance_rescale: c_float, stg_scale: c_float,
+                                cfg_star: c_int, rescale_form: c_int, dt: c_float, sigma: c_float, sigma_next: c_float, step_noise: *const c_float,
+                                hold: *const u8, num_frames: c_int, frame_elems: i64, ws: *mut c_void, scalars_out: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_call_sched(dit: *mut ltx_dit, vae: *mut ltx_vae, p: *const ltx_pipeline_params, sched: *const ltx_guidance_schedule,
+                                   cond: *const ltx_conditioning, latents: *mut c_float, prompt_embeds: *const c_float, prompt_mask: *const c_float,
+                                   neg_embeds: *const c_float, neg_mask: *const c_float, decode_noise: *const c_float, b: c_int, k: c_int,
+                                   out_video: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_call_multiscale_sched(dit: *mut ltx_dit, vae: *mut ltx_vae, up: *mut ltx_upsampler, p_first: *const ltx_pipeline_params,
+                                              p_second: *const ltx_pipeline_params, sched_first: *const ltx_guidance_schedule,
+                                              sched_second: *const ltx_guidance_schedule, adain_factor: c_float, latents_lo: *mut c_float,
+                                              noise_hi: *const c_float, prompt_embeds: *const c_float, prompt_mask: *const c_float, neg_embeds: *const c_float,
+                                              neg_mask: *const c_float, decode_noise: *const c_float, b: c_int, k: c_int, latents_hi_out: *mut c_float,
+                                              out_video: *mut c_float, stream: ltx_stream) -> c_int;
+}
