@@ -707,7 +707,8 @@ extern "C" int ltx_dbg_xtrace(unsigned* out, int n) { return hipMemcpyFromSymbol
 // The units of one block (after K/V and the key bias sit in LDS), for a key set of NKB blocks of 32 keys: everything that scales
 // with the number of keys (S MFMAs, exps, P V MFMAs, bias registers) is sized by NKB, chosen per BLOCK from the number of keys
 // its batch row really has (AttnArgs::k_count, or Sk): BASELINE's prompts keep 32 of 128 text tokens.
-template <bool B2D, int NKB>
+// PONLY (AttnArgs::p_out): the unit ends at the softmax - the row-normalised probabilities go out as bf16, no P V product.
+template <bool B2D, int NKB, bool PONLY = false>
 __device__ __forceinline__ void cross64_units(const AttnArgs& a, int groups, const unsigned char* smem, const float* sbias, int b, int head, int grp) {
     constexpr int HD = 64, KROW = 128, VROW = 128, KCPR = 8, VCPR = 8, NKS = 4, NDB = 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -830,11 +831,43 @@ __device__ __forceinline__ void cross64_units(const AttnArgs& a, int groups, con
             for (int i = 0; i < 16; i += 2) {
                 f32x2 p = {__builtin_amdgcn_exp2f(sacc[kb][i] - mt), __builtin_amdgcn_exp2f(sacc[kb][i + 1] - mt)};
                 ls2 += p;
+                if constexpr (PONLY) { sacc[kb][i] = p[0]; sacc[kb][i + 1] = p[1]; }
+                else {
                 pf[kb][i >> 3][i & 7] = (bf16_t)p[0];
                 pf[kb][i >> 3][(i & 7) + 1] = (bf16_t)p[1];
+                }
             }
         float l = ls2[0] + ls2[1];
         l += __shfl_xor(l, 32);
+        if constexpr (PONLY) {
+            // P[row][head * KP + key]: a lane holds the weights of keys 32 kb + 16s + 8(j >> 2) + 4h + (j & 3) of its query in sacc[kb][8s + j]; the two
+            // halves of the wave trade their middle groups of four (one permlane32 swap per dword), after which a lane owns the
+            // eight consecutive keys from 16s + 8h: one 16-byte store.  Key blocks from NKB up to KP / 32 (a batch row with fewer
+            // keys than the widest one) are zeros; so is every key from the row's count on (bias -inf: exp2 gives +0.0f).
+            const float inv = 1.0f / l;
+            const int kp = a.ldp / a.heads, qr = uj * 32 + r;
+            bf16_t* P = reinterpret_cast<bf16_t*>(a.p_out) + ((int64_t)b * a.Sq + (qr < a.Sq ? qr : 0)) * a.ldp + head * kp + 8 * h;
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+                    uint32_t u[4];
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const bf16x2 t = {(bf16_t)(sacc[kb][8 * s2 + 2 * jj] * inv), (bf16_t)(sacc[kb][8 * s2 + 2 * jj + 1] * inv)};
+                        u[jj] = __builtin_bit_cast(uint32_t, t);
+                    }
+                    const auto sa = __builtin_amdgcn_permlane32_swap(u[0], u[2], false, false);
+                    const auto sb = __builtin_amdgcn_permlane32_swap(u[1], u[3], false, false);
+                    const u32x4 o4 = {sa[0], sb[0], sa[1], sb[1]};
+                    if (qr < a.Sq) *reinterpret_cast<u32x4*>(P + kb * 32 + s2 * 16) = o4;
+                    __builtin_amdgcn_sched_barrier(0);      // one group of eight at a time: hoisting every product first costs 64 registers and spills
+                }
+            const u32x4 z4 = {0u, 0u, 0u, 0u};
+            for (int kb = NKB; kb * 32 < kp; ++kb)
+                if (qr < a.Sq) { *reinterpret_cast<u32x4*>(P + kb * 32) = z4; *reinterpret_cast<u32x4*>(P + kb * 32 + 16) = z4; }
+        } else {
         // O^T = V^T . P^T
         f32x16 acc_o[NDB];
         constexpr int NSTEP = NDB * NKB * 2;                 // step n = d*(2*NKB) + kb*2 + s
@@ -873,6 +906,7 @@ __device__ __forceinline__ void cross64_units(const AttnArgs& a, int groups, con
                 }
         }
         }
+        }
 #pragma unroll
         for (int j = 0; j < UB; ++j) {
 #pragma unroll
@@ -887,7 +921,7 @@ __device__ __forceinline__ void cross64_units(const AttnArgs& a, int groups, con
 #endif
 }
 
-template <bool B2D>          // B2D: a [heads, Sq, Sk] bias on top of the key bias (T5 self-attention over <= 128 tokens)
+template <bool B2D, bool PONLY = false>          // B2D: a [heads, Sq, Sk] bias on top of the key bias (T5 self-attention over <= 128 tokens); PONLY: AttnArgs::p_out
 __global__ __launch_bounds__(256, B2D ? 2 : XATTN_WPS) void attn_cross64_kernel(const AttnArgs a, int groups) {
     constexpr int HD = 64, KROW = 128, VROW = 128, KCPR = 8, VCPR = 8;
     __shared__ __attribute__((aligned(16))) unsigned char smem[XKV * (KROW + VROW)];
@@ -902,6 +936,7 @@ __global__ __launch_bounds__(256, B2D ? 2 : XATTN_WPS) void attn_cross64_kernel(
     // keys this batch row really has: the first k_count[b] rows of its K / V / bias (AttnArgs::k_count), or all Sk
     int nkeys = a.Sk;
     if (a.k_count) { nkeys = __builtin_amdgcn_readfirstlane(a.k_count[b]); if (nkeys > a.Sk) nkeys = a.Sk; if (nkeys < 1) nkeys = 1; }
+    if constexpr (PONLY) { const int kp = a.ldp / a.heads; if (nkeys > kp) nkeys = kp; }      // a head's KP columns bound what is stored (the launcher checks KP against Sk; the counts are device data)
     const int nkb = (nkeys + 31) >> 5;
 
     // K/V -> LDS by buffer LDS-DMA: 16 pieces of 8 rows per matrix, 4 + 4 per wave; only the key blocks that are multiplied
@@ -918,7 +953,7 @@ __global__ __launch_bounds__(256, B2D ? 2 : XATTN_WPS) void attn_cross64_kernel(
             const uint32_t ko = (uint32_t)row * (uint32_t)a.ldk * 2u + (uint32_t)kswz<KCPR>(row, pc) * 16u;
             const uint32_t vo = (uint32_t)row * (uint32_t)a.ldv * 2u + (uint32_t)vswz<VCPR>(row, pc) * 16u;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(smem + piece * 1024), 16, (int)ko, 0, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(smem + XKV * KROW + piece * 1024), 16, (int)vo, 0, 0, 0);
+            if constexpr (!PONLY) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(smem + XKV * KROW + piece * 1024), 16, (int)vo, 0, 0, 0);
         }
         if (tid < XKV) {
             float bv = tid < nkeys ? 0.f : -INFINITY;
@@ -929,10 +964,10 @@ __global__ __launch_bounds__(256, B2D ? 2 : XATTN_WPS) void attn_cross64_kernel(
         __syncthreads();
     }
     switch (nkb) {                                          // block-uniform
-        case 1: cross64_units<B2D, 1>(a, groups, smem, sbias, b, head, grp); break;
-        case 2: cross64_units<B2D, 2>(a, groups, smem, sbias, b, head, grp); break;
-        case 3: cross64_units<B2D, 3>(a, groups, smem, sbias, b, head, grp); break;
-        default: cross64_units<B2D, 4>(a, groups, smem, sbias, b, head, grp); break;
+        case 1: cross64_units<B2D, 1, PONLY>(a, groups, smem, sbias, b, head, grp); break;
+        case 2: cross64_units<B2D, 2, PONLY>(a, groups, smem, sbias, b, head, grp); break;
+        case 3: cross64_units<B2D, 3, PONLY>(a, groups, smem, sbias, b, head, grp); break;
+        default: cross64_units<B2D, 4, PONLY>(a, groups, smem, sbias, b, head, grp); break;
     }
 }
 
@@ -1026,7 +1061,12 @@ bool ltx_attention_prescale_ok(int hd) {
 int ltx_launch_attention(const AttnArgs& a, int dtype, hipStream_t s) {
     if (a.Sq <= 0 || a.Sk <= 0 || a.heads <= 0) LTX_FAIL(LTX_ERR_ARG, "attention: empty problem");
     void* tok = nullptr;
-    ltx_prof_begin(a.bias || a.Sq != a.Sk ? LTX_PROF_ATTN_CROSS : LTX_PROF_ATTN_SELF, 4.0 * a.B * a.heads * (double)a.Sq * a.Sk * a.hd, s, &tok);
+    if (a.p_out) {      // (argument checks in front of ltx_prof_begin: a failure after it would leave the timing record open)
+        const int kp = a.heads > 0 && a.ldp % a.heads == 0 ? a.ldp / a.heads : 0;
+        if (dtype != LTX_DT_BF16 || !ltx_attention_cross64_ok(a.hd, a.Sk) || a.bias2d || kp < 32 || kp % 32 != 0 || kp > XKV || (!a.k_count && kp < a.Sk) || ((uintptr_t)a.p_out & 15))
+            LTX_FAIL(LTX_ERR_ARG, "attention: p_out is served by the short-key-set head_dim-64 kernel only (bf16, no bias2d, ldp = heads x KP with KP a multiple of 32 that holds every key, 16-byte aligned)");
+    }
+    ltx_prof_begin(a.bias || a.Sq != a.Sk ? LTX_PROF_ATTN_CROSS : LTX_PROF_ATTN_SELF, (a.p_out ? 2.0 : 4.0) * a.B * a.heads * (double)a.Sq * a.Sk * a.hd, s, &tok);
     struct End { void* t; hipStream_t s; ~End() { ltx_prof_end(t, s); } } end_{tok, s};
     if (dtype == LTX_DT_BF16) {
         if (a.ldq % 8 || a.ldk % 8 || a.ldv % 8 || a.ldo % 4) LTX_FAIL(LTX_ERR_ARG, "attention: strides must be 16-byte aligned");
@@ -1063,7 +1103,9 @@ int ltx_launch_attention(const AttnArgs& a, int dtype, hipStream_t s) {
             if (a.bias2d) {
                 if (a.Sk % 4 || ((uintptr_t)a.bias2d & 15)) LTX_FAIL(LTX_ERR_ARG, "attention: bias2d needs Sk % 4 == 0 and a 16-byte aligned table");
                 LTX_LAUNCH_TIMED(attn_cross64_kernel<true>, dim3((unsigned)(a.B * a.heads * groups)), block, 0, s, ax, groups);
-            } else
+            } else if (a.p_out)
+            LTX_LAUNCH_TIMED((attn_cross64_kernel<false, true>), dim3((unsigned)(a.B * a.heads * groups)), block, 0, s, ax, groups);
+            else
             LTX_LAUNCH_TIMED(attn_cross64_kernel<false>, dim3((unsigned)(a.B * a.heads * groups)), block, 0, s, ax, groups);
             LTX_CHECK_LAUNCH();
             return LTX_OK;

@@ -283,6 +283,69 @@ extern "C" int ltx_op_attention_compact(const void* q, const void* k, const void
     return LTX_OK;
 }
 
+// ---- attn2.to_out folded into the text context (xattn_fold.hip): the decision, KP, and the two kernels on their own ----
+extern "C" int ltx_op_xattn_fold_route(int dtype, int head_dim, int heads, int D, int KP, int B, int compact, int* fold) {
+    if (!fold) LTX_FAIL(LTX_ERR_ARG, "ltx_op_xattn_fold_route: null result");
+    *fold = ltx_xattn_fold_route(dtc(dtype), head_dim, heads, D, KP, B, compact != 0) ? 1 : 0;
+    return LTX_OK;
+}
+extern "C" int ltx_op_xattn_fold_kp(const int* counts_host, int B, int* KP) {
+    if (!counts_host || !KP || B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_xattn_fold_kp: bad argument");
+    *KP = ltx_xattn_fold_kp(counts_host, B);
+    return LTX_OK;
+}
+extern "C" int ltx_op_xattn_fold_build(const void* v, const float* key_bias, const void* wo, int B, int K, int heads, int KP, void* vo, int* counts_out, ltx_stream stream) {
+    if (!v || !key_bias || !wo || !vo || B < 1 || K < 1 || heads < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_xattn_fold_build: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int D = heads * 64;
+    void *vc = nullptr, *bc = nullptr, *idx = nullptr, *cnt = nullptr, *tab = nullptr;
+    auto free_all = [&]() { for (void* p : {vc, bc, idx, cnt, tab}) if (p) (void)hipFree(p); };
+    const size_t rows = (size_t)B * K;
+    if (hipMalloc(&vc, rows * D * 2) != hipSuccess || hipMalloc(&bc, rows * 4) != hipSuccess || hipMalloc(&idx, rows * 4) != hipSuccess ||
+        hipMalloc(&cnt, (size_t)B * 4) != hipSuccess || hipMalloc(&tab, sizeof(XFoldPtrs)) != hipSuccess) { free_all(); LTX_FAIL(LTX_ERR_HIP, "hipMalloc"); }
+    const XFoldPtrs host{wo, vc};
+    int rc = ltx_launch_key_compact(key_bias, B, K, (int*)idx, (int*)cnt, (float*)bc, s);
+    if (rc == LTX_OK) rc = ltx_launch_gather_rows(v, vc, (const int*)idx, (const int*)cnt, 1, B, K, D * 2, s);
+    if (rc == LTX_OK && hipMemcpyAsync(tab, &host, sizeof(host), hipMemcpyHostToDevice, s) != hipSuccess) rc = LTX_ERR_HIP;
+    if (rc == LTX_OK) {
+        XFoldArgs a; a.tab = (const XFoldPtrs*)tab; a.vo = vo; a.L = 1; a.B = B; a.K = K; a.ldv = D; a.D = D; a.H = heads; a.KP = KP;
+        rc = ltx_launch_xattn_fold(a, s);
+    }
+    if (rc == LTX_OK && counts_out && hipMemcpyAsync(counts_out, cnt, (size_t)B * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = LTX_ERR_HIP;
+    const hipError_t e = hipStreamSynchronize(s);
+    free_all();
+    if (rc != LTX_OK) return rc;
+    if (e != hipSuccess) { ltx_set_error(hipGetErrorString(e)); return LTX_ERR_HIP; }
+    return LTX_OK;
+}
+extern "C" int ltx_op_attention_probs(const void* q, const void* k, void* p_out, int B, int Sq, int Sk, int heads, int KP, float scale, const float* key_bias,
+                                      const float* q_rowsq, int q_rowsq_n, float q_rowsq_eps, int* counts_out, ltx_stream stream) {
+    if (!q || !k || !p_out || !key_bias || B < 1 || heads < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_op_attention_probs: bad argument");
+    if (!ltx_attention_cross64_ok(64, Sk)) LTX_FAIL(LTX_ERR_ARG, "ltx_op_attention_probs: at most 128 keys, the short-key-set kernel enabled");
+    hipStream_t s = (hipStream_t)stream;
+    const int D = heads * 64;
+    void *kc = nullptr, *bc = nullptr, *idx = nullptr, *cnt = nullptr;
+    auto free_all = [&]() { for (void* p : {kc, bc, idx, cnt}) if (p) (void)hipFree(p); };
+    const size_t rows = (size_t)B * Sk;
+    if (hipMalloc(&kc, rows * D * 2) != hipSuccess || hipMalloc(&bc, rows * 4) != hipSuccess || hipMalloc(&idx, rows * 4) != hipSuccess ||
+        hipMalloc(&cnt, (size_t)B * 4) != hipSuccess) { free_all(); LTX_FAIL(LTX_ERR_HIP, "hipMalloc"); }
+    int rc = ltx_launch_key_compact(key_bias, B, Sk, (int*)idx, (int*)cnt, (float*)bc, s);
+    if (rc == LTX_OK) rc = ltx_launch_gather_rows(k, kc, (const int*)idx, (const int*)cnt, 1, B, Sk, D * 2, s);
+    if (rc == LTX_OK) {
+        AttnArgs a; a.q = q; a.k = kc; a.v = kc; a.ldq = D; a.ldk = D; a.ldv = D; a.ldo = D;
+        a.B = B; a.Sq = Sq; a.Sk = Sk; a.heads = heads; a.hd = 64; a.scale = scale; a.bias = (const float*)bc; a.k_count = (const int*)cnt;
+        a.p_out = p_out; a.ldp = heads * KP;
+        if (q_rowsq) { a.q_rowsq = q_rowsq; a.q_rowsq_n = q_rowsq_n; a.q_rowsq_D = D; a.q_rowsq_eps = q_rowsq_eps; }
+        rc = ltx_launch_attention(a, LTX_DT_BF16, s);
+    }
+    if (rc == LTX_OK && counts_out && hipMemcpyAsync(counts_out, cnt, (size_t)B * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = LTX_ERR_HIP;
+    const hipError_t e = hipStreamSynchronize(s);
+    free_all();
+    if (rc != LTX_OK) return rc;
+    if (e != hipSuccess) { ltx_set_error(hipGetErrorString(e)); return LTX_ERR_HIP; }
+    return LTX_OK;
+}
+
 extern "C" int ltx_op_attention_prescaled(const void* q, const void* k, const void* v, void* o, int B, int Sq, int Sk, int heads, int hd,
                                           int ldq, int ldk, int ldv, int ldo, ltx_stream stream) {
     if (!q || !k || !v || !o) LTX_FAIL(LTX_ERR_ARG, "ltx_op_attention_prescaled: null tensor");

@@ -26,7 +26,12 @@ struct DitCtx {                      // cached text context (text_context below)
     // multiplies ceil(count / 32) key blocks instead of ceil(K / 32) - BASELINE's prompts keep 32 of 128 text tokens
     bool compact = false;
     DevBuf kvc, biasc, kidx, kcount; // [L][B*K][2D], [B*K] f32, [B*K] int, [B] int
-    void release() { kv.release(); bias.release(); kvc.release(); biasc.release(); kidx.release(); kcount.release(); valid = false; }
+    // attn2.to_out folded into the context (xattn_fold.hip; compact contexts that ltx_xattn_fold_route accepts): vo = V Wo2^T per
+    // layer and batch row, [L][B][D][H * KP] - a function of the prompt AND the weights.  KP: the widest row's kept keys, rounded up
+    // to the cross kernel's 32-key block, read back from kcount once per context build.
+    bool fold_vo = false, vo_oom = false; int KP = 0, fold_opt = 0;      // fold_opt: option xattn_fold_vo when the entry was built (part of its key); vo_oom: no memory for vo
+    DevBuf vo, votab; std::vector<XFoldPtrs> votab_host; int counts_host[8] = {0};
+    void release() { kv.release(); bias.release(); kvc.release(); biasc.release(); kidx.release(); kcount.release(); vo.release(); votab.release(); valid = false; }
 };
 
 // AdaLayerNormSingle's output for one set of timesteps (ltx_transformer.rs:262-309): a function of the timestep values and the
@@ -80,7 +85,8 @@ struct ltx_dit {
     bool wfold_off = false;          // norm_fold=2 gave up on this handle: more distinct timesteps in flight than scaled-weight copies (a schedule that would re-scale every step), or no memory for a copy
     // RoPE tables of the caching scope (ltx_dit_context_cache: the caller keeps coords / geometry constant inside it): what cosb / sinb hold
     struct { bool valid = false; const float* coords = nullptr; float rs[3] = {0, 0, 0}; bool has_rs = false; int B = 0, S = 0, F = 0, H = 0, W = 0; hipStream_t stream = nullptr; } rope_key;
-    // every cache that is a function of the weights (wcache keeps its allocations; wfold_off and the GEMM plans are not touched).
+    // every cache that is a function of the weights (wcache keeps its allocations; wfold_off and the GEMM plans are not touched):
+    // the scaled-weight copies, the text contexts (k / v projections and vo = V Wo2^T, DitCtx), the norm fold's per-timestep vectors.
     // A cache added to the forward is added HERE and to release_caches.
     void invalidate_weight_derived() {
         for (auto& e : wcache) e.valid = false;
@@ -305,10 +311,22 @@ GemmArgs gemm_q2(const DitPlan& p, const DitBlock& b, const DitOperands& x) {   
     if (p.fold_q2) g.rowsq = x.rsq;
     return g;
 }
-GemmArgs gemm_o2(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x) {      // h += to_out(attn); fold 1: + h (.) (1 + scale_mlp) into n for ff1
+// to_out folded into the text context (DitCtx::vo): batch row `row` alone - its weights are its own - reads the probabilities
+// (x.attn as [M, HK]) against vo [D, HK] of the layer and row; HK = heads * KP
+struct DitVo { const void* w = nullptr; int HK = 0, row = 0; };
+GemmArgs gemm_o2(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x, const DitVo* vo = nullptr) {      // h += to_out(attn); fold 1: + h (.) (1 + scale_mlp) into n for ff1
     GemmArgs g = gemm_base(p, b.o2, x.attn, p.D, x.h, p.D);
     g.resid = x.h; g.ldr = p.D; g.rowsq = p.presum ? x.hsq : nullptr;
     if (f == kFold1) { g.rows_per_batch = p.Sg; g.C2 = x.n; g.scale2 = x.ada + 4 * p.D; g.scale2_stride = 6 * p.D; }
+    if (vo) {
+        const size_t esz = ltx_dt_size(p.dt), r0 = (size_t)vo->row * p.S;      // whole batch rows, and their table rows (NB / B per batch row)
+        g.M = p.S; g.K = vo->HK; g.lda = vo->HK;
+        g.W = (const char*)vo->w + (size_t)vo->row * p.D * vo->HK * esz;
+        g.A = (const char*)x.attn + r0 * vo->HK * esz;
+        g.C = (char*)x.h + r0 * p.D * esz; g.resid = g.C;
+        if (g.rowsq) { g.rowsq += r0 * (p.D / 128); g.rowsq_in_epilogue = 1; }      // (vo_fits: the call reaches gemm_asm16 wherever the plan has presum)
+        if (f == kFold1) { g.C2 = (char*)x.n + r0 * p.D * esz; g.scale2 += (size_t)vo->row * (p.NB / p.B) * 6 * p.D; }
+    }
     return g;
 }
 GemmArgs gemm_ff1(const DitPlan& p, DitForm f, const DitBlock& b, const DitOperands& x) {
@@ -527,6 +545,25 @@ int scaled_weights(ltx_dit* m, const DitPlan& p, const float* timestep, const fl
     *out = we;
     return LTX_OK;
 }
+// Does the plan's to_out call fit in its folded form (A = P, W = vo, K = H * KP, one batch row)?  The plan was made for K = D: where
+// it counts on gemm_asm16's epilogue (row partials, the norm fold's second output) the folded call must reach that epilogue too,
+// else the context carries no vo for this plan and the forward runs the unfolded path.  The builder with stand-in operands, like the plan's own questions.
+bool vo_fits(const ltx_dit* m, const DitPlan& p, const DitCtx* ctx) {
+    void* const a = reinterpret_cast<void*>((uintptr_t)4096); float* const f = reinterpret_cast<float*>(a);
+    const DitOperands x{a, a, a, a, a, f, f, f, f, f, f, (const char*)a, m->cfg.norm_eps};
+    const DitVo vo{a, m->cfg.num_attention_heads * ctx->KP, 0};
+    const DitBlock& b = m->blocks[0];
+    if (vo.HK % 8 != 0 || vo.HK > p.D) return false;
+    if (p.nfold && !ltx_gemm_fold_ok(gemm_o2(p, kFold1, b, x, &vo), EPI_RESID)) return false;
+    if (p.presum && !ltx_gemm_asm16_fits(gemm_o2(p, kPass, b, x, &vo), EPI_RESID)) return false;
+    return true;
+}
+// Should this entry carry vo under plan p: the decision step on its KP, and the plan's to_out call in the folded form.  Part of an
+// entry's key, so that what a forward computes never depends on which plan built the entry it finds.
+bool vo_wanted(const ltx_dit* m, const DitPlan& p, const DitCtx* e) {
+    const ltx_dit_config& c = m->cfg;
+    return e->KP > 0 && !e->vo_oom && ltx_xattn_fold_route(p.dt, c.attention_head_dim, c.num_attention_heads, p.D, e->KP, e->B, e->compact) && vo_fits(m, p, e);
+}
 // Text context: caption projection (:186-190), mask bias (:1059-1070) and, for every layer, the cross-attention
 // K/V projections + k-RMSNorm (:667-672).  None of it depends on the timestep or the latents, so inside a
 // caching scope (ltx_dit_context_cache) it is computed once per (enc, mask) pair instead of once per forward.
@@ -535,18 +572,47 @@ int text_context(ltx_dit* m, const DitPlan& p, const void* enc, const float* enc
     const int D = p.D, L = c.num_layers, dt = p.dt, B = p.B, K = p.K;
     const int64_t MK = p.MK; const size_t esz = ltx_dt_size(dt);
     DitCtx* ctx = nullptr;
-    for (auto& e : m->ctxs) if (e.valid && e.enc == enc && e.mask == enc_mask && e.B == B && e.K == K && e.iodt == p.iodt && e.fold_q2 == p.fold_q2) ctx = &e;
+    for (auto& e : m->ctxs) if (e.valid && e.enc == enc && e.mask == enc_mask && e.B == B && e.K == K && e.iodt == p.iodt && e.fold_q2 == p.fold_q2 && e.fold_opt == ltx_opt().xattn_fold_vo && e.fold_vo == vo_wanted(m, p, &e)) ctx = &e;
     *out = ctx;
     if (ctx) return LTX_OK;
     if (m->ctxs.size() >= 4 || !m->ctx_mode) { for (auto& e : m->ctxs) e.valid = false; }
     for (auto& e : m->ctxs) if (!e.valid) { ctx = &e; break; }
     if (!ctx) { m->ctxs.emplace_back(); ctx = &m->ctxs.back(); }
     ctx->enc = enc; ctx->mask = enc_mask; ctx->B = B; ctx->K = K; ctx->iodt = p.iodt; ctx->fold_q2 = p.fold_q2;
+    ctx->fold_opt = ltx_opt().xattn_fold_vo; ctx->fold_vo = false; ctx->KP = 0; ctx->vo_oom = false;
     LTX_TRY(ctx->kv.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->bias.ensure(MK * sizeof(float)));
+    // Masked text tokens (bias -10000, :1059-1070) get softmax weight exp(s - 10000 - max) = +0.0f: exactly nothing.  Where the
+    // short-key-set kernel serves the layer, the keys that are left are moved to the front of their batch row once per context and
+    // the kernel sizes its work by their number (device-side count: no host synchronisation in any per-step kernel).
+    ctx->compact = enc_mask && dt == LTX_DT_BF16 && ltx_attention_cross64_ok(c.attention_head_dim, K) && ltx_opt().xattn_compact;     // xattn_compact=0: every layer multiplies all K keys (A/B aid)
+    if (ctx->compact) {
+        LTX_TRY(ctx->kvc.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->biasc.ensure(MK * sizeof(float)));
+        LTX_TRY(ctx->kidx.ensure(MK * sizeof(int))); LTX_TRY(ctx->kcount.ensure((size_t)B * sizeof(int)));
+    }
+    if (enc_mask) LTX_TRY(ltx_launch_mask_bias(ctx->bias.as<float>(), enc_mask, MK, s));
+    if (ctx->compact) LTX_TRY(ltx_launch_key_compact(ctx->bias.as<float>(), B, K, ctx->kidx.as<int>(), ctx->kcount.as<int>(), ctx->biasc.as<float>(), s));
+    // attn2.to_out folded into the context (xattn_fold.hip) where the decision step can say yes at all (its smallest KP): the counts
+    // come back to the host - the one synchronisation of a context build, once per prompt, behind two small kernels and in front of
+    // everything else - because KP sizes vo, which is allocated here, before the projections are launched.
+    const int H = c.num_attention_heads, hd = c.attention_head_dim;
+    if (ctx->compact && B <= 8 && ltx_xattn_fold_route(dt, hd, H, D, 32, B, true)) {
+        HIP_TRY(hipMemcpyAsync(ctx->counts_host, ctx->kcount.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ctx->KP = ltx_xattn_fold_kp(ctx->counts_host, B);
+        ctx->fold_vo = vo_wanted(m, p, ctx);      // ... and only where this plan's to_out call runs in the folded form
+        if (ctx->fold_vo) {
+            (void)ltx_take_oom();
+            int rc = ctx->vo.ensure((size_t)L * B * D * H * ctx->KP * esz);
+            if (rc == LTX_OK) rc = ctx->votab.ensure((size_t)L * sizeof(XFoldPtrs));
+            if (rc != LTX_OK) {      // no memory for vo: this entry runs the unfolded path (and is not rebuilt for it at every forward)
+                if (!ltx_take_oom()) return rc;
+                ctx->fold_vo = false; ctx->vo_oom = true;
+            }
+        }
+    }
     LTX_TRY(ltx_launch_cast(enc, p.iodt, m->encin.p, dt, MK * c.caption_channels, s));
     LTX_TRY(ltx_linear(m->cap1, m->encin.p, c.caption_channels, m->c1.p, D, (int)MK, dt, EPI_GELU, s));
     LTX_TRY(ltx_linear(m->cap2, m->c1.p, D, m->encp.p, D, (int)MK, dt, EPI_BIAS, s));
-    if (enc_mask) LTX_TRY(ltx_launch_mask_bias(ctx->bias.as<float>(), enc_mask, MK, s));
     for (int l = 0; l < L; ++l) {
         void* kvl = (char*)ctx->kv.p + (size_t)l * MK * 2 * D * esz;
         LTX_TRY(ltx_linear(m->blocks[l].kv2, m->encp.p, D, kvl, 2 * D, (int)MK, dt, EPI_BIAS, s));
@@ -554,15 +620,13 @@ int text_context(ltx_dit* m, const DitPlan& p, const void* enc, const float* enc
         if (p.fold_q2) k2.w0b = m->blocks[l].nq2;
         LTX_TRY(ltx_launch_qknorm_rope(k2, dt, s));
     }
-    // Masked text tokens (bias -10000, :1059-1070) get softmax weight exp(s - 10000 - max) = +0.0f: exactly nothing.  Where the
-    // short-key-set kernel serves the layer, the keys that are left are moved to the front of their batch row once per context and
-    // the kernel sizes its work by their number (device-side count: no host synchronisation).
-    ctx->compact = enc_mask && dt == LTX_DT_BF16 && ltx_attention_cross64_ok(c.attention_head_dim, K) && ltx_opt().xattn_compact;     // xattn_compact=0: every layer multiplies all K keys (A/B aid)
-    if (ctx->compact) {
-        LTX_TRY(ctx->kvc.ensure((size_t)L * MK * 2 * D * esz)); LTX_TRY(ctx->biasc.ensure(MK * sizeof(float)));
-        LTX_TRY(ctx->kidx.ensure(MK * sizeof(int))); LTX_TRY(ctx->kcount.ensure((size_t)B * sizeof(int)));
-        LTX_TRY(ltx_launch_key_compact(ctx->bias.as<float>(), B, K, ctx->kidx.as<int>(), ctx->kcount.as<int>(), ctx->biasc.as<float>(), s));
-        LTX_TRY(ltx_launch_gather_rows(ctx->kv.p, ctx->kvc.p, ctx->kidx.as<int>(), ctx->kcount.as<int>(), L, B, K, (int)(2 * D * esz), s));
+    if (ctx->compact) LTX_TRY(ltx_launch_gather_rows(ctx->kv.p, ctx->kvc.p, ctx->kidx.as<int>(), ctx->kcount.as<int>(), L, B, K, (int)(2 * D * esz), s));
+    if (ctx->fold_vo) {      // one launch for all layers; the table holds the weights as they are NOW (a LoRA switch invalidates the entry)
+        ctx->votab_host.resize(L);
+        for (int l = 0; l < L; ++l) ctx->votab_host[l] = XFoldPtrs{m->blocks[l].o2.w, (const char*)ctx->kvc.p + ((size_t)l * MK * 2 * D + D) * esz};
+        HIP_TRY(hipMemcpyAsync(ctx->votab.p, ctx->votab_host.data(), (size_t)L * sizeof(XFoldPtrs), hipMemcpyHostToDevice, s));
+        XFoldArgs fa; fa.tab = ctx->votab.as<XFoldPtrs>(); fa.vo = ctx->vo.p; fa.L = L; fa.B = B; fa.K = K; fa.ldv = 2 * D; fa.D = D; fa.H = H; fa.KP = ctx->KP;
+        LTX_TRY(ltx_launch_xattn_fold(fa, s));
     }
     ctx->valid = true;     // outside a caching scope the entry is invalidated again at the end of this forward
     *out = ctx;
@@ -609,7 +673,10 @@ struct DitCarry {             // what a block leaves for the next one (and the l
         rn.x_out = m->h.p; pending = false;
     }
 };
-struct DitLayerIn { DitTables tab; const DitWfold* we = nullptr; const DitCtx* ctx = nullptr; const float* skip_layer_mask = nullptr; };      // what the forward hands every block
+struct DitLayerIn {           // what the forward hands every block
+    DitTables tab; const DitWfold* we = nullptr; const DitCtx* ctx = nullptr; const float* skip_layer_mask = nullptr;
+    bool fold_vo = false;     // to_out runs on the context's vo (ctx->fold_vo: built only where this plan's to_out call fits in that form)
+};
 // does block l run: not in the skip list (:1094-1096), not skipped by every row of the mask (all-ones rows make the block an exact identity, :1098-1123).
 // In an attention mode (ltxhip_stg.h) the mask perturbs the self-attention and the block runs for every row: only the skip list removes it.
 bool block_runs(const ltx_dit* m, const float* skip_layer_mask, int B, int l) {
@@ -710,6 +777,8 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     ax.ldq = D; ax.ldk = ax.ldv = 2 * D; ax.ldo = D; ax.B = B; ax.Sq = S; ax.Sk = p.K; ax.heads = H; ax.hd = hd; ax.scale = attn_scale;
     ax.bias = ctx->mask ? ctx->bias.as<float>() : nullptr;
     if (ctx->compact) { ax.bias = ctx->biasc.as<float>(); ax.k_count = ctx->kcount.as<int>(); }
+    const int HK = H * ctx->KP;
+    if (in.fold_vo) { ax.p_out = m->attn.p; ax.ldp = HK; ax.o = nullptr; }      // the kernel stops at the softmax: P [M, H * KP] in m->attn (H * KP <= D)
     if (p.fold_q2) {
         LTX_TRY(ltx_launch_gemm(gemm_q2(p, b, x), dt, EPI_BIAS, s));
         ax.q_rowsq = m->rsq.as<float>(); ax.q_rowsq_n = D / 128; ax.q_rowsq_D = D; ax.q_rowsq_eps = 1e-5f;
@@ -719,7 +788,13 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         LTX_TRY(ltx_launch_qknorm_rope(q2, dt, s));
     }
     LTX_TRY(ltx_launch_attention(ax, dt, s));
-    if (fold_out) { LTX_TRY(ltx_launch_gemm(gemm_o2(p, kFold1, b, x), dt, EPI_RESID, s)); st.hs_valid = true; }
+    if (in.fold_vo) {      // h += P vo^T + b, one launch per batch row (its vo is its own)
+        for (int bb = 0; bb < B; ++bb) {
+            const DitVo vo{(const char*)ctx->vo.p + (size_t)l * B * D * HK * esz, HK, bb};
+            LTX_TRY(ltx_launch_gemm(gemm_o2(p, fold_out ? kFold1 : kPass, b, x, &vo), dt, EPI_RESID, s));
+        }
+        st.hs_valid = fold_out;
+    } else if (fold_out) { LTX_TRY(ltx_launch_gemm(gemm_o2(p, kFold1, b, x), dt, EPI_RESID, s)); st.hs_valid = true; }
     else LTX_TRY(linear_of(b.o2, gemm_o2(p, kPass, b, x), dt, EPI_RESID, s));
     st.hsq_valid = p.presum;
     // MLP (shift_mlp = row 3, scale_mlp = row 4, gate_mlp = row 5)
@@ -793,6 +868,7 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
     LTX_TRY(scaled_weights(m, p, timestep, in.tab.ada, s, &in.we));
     DitCtx* ctx = nullptr;
     LTX_TRY(text_context(m, p, enc, enc_mask, s, &ctx)); in.ctx = ctx;
+    in.fold_vo = ctx->fold_vo;
     LTX_TRY(rope_tables(m, p, num_frames, height, width, rope_scale, video_coords, s));
 
     DitCarry st;

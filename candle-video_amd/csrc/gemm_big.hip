@@ -847,6 +847,8 @@ int choose_plan(const GemmArgs& g, int epi, hipStream_t s, bool measure, GemmPla
     } else if (g.C2 || g.rs_sq) { // norm fold (kernels.h): only gemm_asm16's wide epilogue carries the second output / the row scale (ltx_gemm_fold_ok)
         if (!ltx_gemm_fold_ok(g, epi)) return LTX_OK;
         only = kPlanAsm16; model = base = asm16_pick(g);
+    } else if (g.rowsq && g.rowsq_in_epilogue && !g.conv && !(o.gemm_off & LTX_FAM_ASM16) && ltx_gemm_asm16_fits(g, epi)) {
+        only = kPlanAsm16; model = base = asm16_pick(g);      // GemmArgs::rowsq_in_epilogue: the family's own tile choice, or the measured plan where it is one of its tiles
     } else {
         model = base;
         // convs over planes of at most 512 voxels (C1's mid block, an edge tile of the tiled decode), all of them split shapes, on the

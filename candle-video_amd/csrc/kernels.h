@@ -68,6 +68,10 @@ struct GemmArgs {
     // ltx_rowsq_leaf / ltx_launch_rowsq - so the value does not depend on which kernel the plan picked: gemm_asm16's
     // epilogue produces it in place, every other kernel is followed by the stand-alone pass (ltx_launch_gemm).
     float* rowsq = nullptr;
+    // The caller counts on that by-product coming out of gemm_asm16's epilogue (a plan made for another K, dit.hip's folded to_out):
+    // where that family serves the call it is held to it - a measured plan of another family would be followed by the stand-alone
+    // pass, which costs more than the families differ by.  Speed only: every plan sums K in the same order.
+    int rowsq_in_epilogue = 0;
     // Norm fold (round 6; bf16, gemm_asm16's wide epilogue only - dit.hip asks ltx_gemm_fold_ok).  RMS norm + modulation
     //   y = h * r_m * (1 + sc) + sh,  r_m = 1 / sqrt(mean(h_m^2) + eps)     (LtxVideoTransformerBlock::forward, ltx_transformer.rs:847-851, 905-909)
     // followed by a linear layer equals  r_m * ((h (.) (1 + sc)) W^T) + (sh W^T + b): the layer that WRITES h also stores
@@ -244,6 +248,10 @@ struct AttnArgs {
     // bias is <= -5000 contributes exp(s - 5000 - max) = +0.0f exactly in f32 as long as scores stay within +-4000 of each other,
     // so dropping it changes nothing (ltx_transformer.rs:1059-1070 builds -10000 for masked text tokens).
     const int* k_count = nullptr;
+    // P-only mode (attn_cross64_kernel only; xattn_fold.hip): the kernel stops at the softmax and stores the row-normalised
+    // probabilities, bf16(p / l), to p_out[row][head * KP + k] for k < KP = ldp / heads (a multiple of 32, 16-byte stores): no P V
+    // product, v and o are not read or written.  A column at or behind the batch row's key count holds an exact zero.
+    void* p_out = nullptr; int ldp = 0;
     const int* gate_flag = nullptr; int gate_ticket = 0;   // attn_bf16_kernel<128>: run only if *gate_flag == gate_ticket (exact pass after attn_q128's overflow flag)
 };
 bool ltx_attention_q128_fits(const AttnArgs& a);           // attn_q128.hip: head_dim 128 one-wave-per-SIMD kernel
@@ -256,6 +264,16 @@ int ltx_launch_attention_q64(const AttnArgs& a, hipStream_t s);   // attn_q64.hi
 bool ltx_attention_q64_fits(const AttnArgs& a);   // attn_q64.hip: every row offset below 2^31 (its 32-bit buffer arithmetic)
 bool ltx_attention_prescale_ok(int hd);
 bool ltx_attention_cross64_ok(int hd, int Sk);   // shape-only: the short-key-set kernel serves the launch (k_count / bias2d / q_rowsq)
+// attn2.to_out folded into the cached text context (xattn_fold.hip).  ONE decision, read by dit.hip's text_context and by the
+// read-only probe ltx_op_xattn_fold_route: does a context of KP kept-key columns per head (ltx_xattn_fold_kp of the per-row
+// counts) carry vo = V Wo2^T, so that to_out runs on the probabilities with K = heads * KP?  Pure host code under the current options.
+bool ltx_xattn_fold_route(int dtype, int head_dim, int heads, int D, int KP, int B, bool compact);
+int ltx_xattn_fold_kp(const int* counts_host, int B);      // the largest count, rounded up to the cross kernel's 32-key block
+// vo[l][b][n][h * KP + k] = sum_{d < 64} Wo2_l[n][64 h + d] * V_l[b * K + k][64 h + d]: one launch for all layers (f32 accumulation,
+// one bf16 rounding; keys from K up are zeros).  tab: DEVICE table of L entries; v rows ldv elements apart; vo 16-byte aligned.
+struct XFoldPtrs { const void* w; const void* v; };      // a layer's Wo2 [D][D] and the first row of its V (bf16)
+struct XFoldArgs { const XFoldPtrs* tab = nullptr; void* vo = nullptr; int L = 0, B = 0, K = 0, ldv = 0, D = 0, H = 0, KP = 0; };
+int ltx_launch_xattn_fold(const XFoldArgs& a, hipStream_t s);
 bool ltx_attention_rowsq_ok(int hd, int Sk, int D);   // shape-only: cross attention can fold the q RMS-norm (AttnArgs::q_rowsq)           // whether the bf16 kernel has a q-prescaled instantiation for this head dim
 
 // ---------------- small elementwise kernels (elementwise.hip) ----------------

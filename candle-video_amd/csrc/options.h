@@ -29,6 +29,7 @@ struct LtxOptions {
     int norm_presum = 1;          // 0: row-reducing RMS norms; 2: the map whatever the shape
     int norm_lean = 1;            // 0: the general presum kernel (same bits as the lean one)
     int xattn_compact = 1;        // 0: cross attention multiplies every text key
+    int xattn_fold_vo = 1;        // 0: cross attention multiplies P V and attn2.to_out runs over D; 1: to_out folded into the text context where ltx_xattn_fold_route says so (xattn_fold.hip); 2: up to heads * KP = D instead of D / 2 (measurement arm)
     int attn_q64_stream = 0;      // 1: head_dim-64 self-attention as persistent workgroups streaming host-built item lists (attn_q64.hip; round 6: built, tested, 4 - 6 % behind the block grid)
     int norm_fold = 2;            // 0: the DiT's RMS norms between GEMMs as their own (presum) pass; 1: folded into the producer's / consumer's epilogues (dit.hip); 2: the (1 + scale) factor in per-timestep copies of the consumer's weights
     int norm_fold_copies = 10;    // norm_fold=2: scaled-weight copies kept per DiT handle (one per distinct timestep; 1.6 GB each at 2B: a distilled schedule's 7 + the warm-up's)

@@ -135,6 +135,9 @@ _SIGS = {
     "ltx_op_rownorm": [_vp, _vp, _i64, _i, _i, _f, _vp, _vp, _vp, _i64, _i, _i, _i, _vp],
     "ltx_op_qknorm_rope": [_vp, _i64, _i, _i, _vp, _f, _vp, _vp, _i, _vp],
     "ltx_op_qknorm_rope_segs": [_vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _f, _vp, _vp, _f, _i, _vp],
+    "ltx_op_xattn_fold_route": [_i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int)], "ltx_op_xattn_fold_kp": [C.POINTER(C.c_int), _i, C.POINTER(C.c_int)],
+    "ltx_op_xattn_fold_build": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "ltx_op_attention_probs": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _f, _vp, _vp],
     "ltx_op_norm_route": [_i64, _i, _i, _i, _i, _i, _i64, _i, _i, C.c_char_p, _i], "ltx_op_qknorm_route": [_i64, _i, _i, C.c_char_p, _i],
     "ltx_op_rope_table": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "ltx_op_timestep_embedding": [_vp, _i, _i, _f, _i, _vp, _vp],
@@ -2045,6 +2048,41 @@ class ops:
                                             D, D, D, D, C.c_float(scale), _ptr(key_bias.contiguous()), _ptr(q_rowsq) if q_rowsq is not None else None,
                                             q_rowsq.shape[-1] if q_rowsq is not None else 0, D, C.c_float(eps), _ptr(cnt), _stream()))
         return o, cnt
+
+    @staticmethod
+    def xattn_fold_route(dtype, head_dim, heads, KP, B=1, compact=True, D=None) -> bool:
+        """does a text context of KP kept-key columns per head carry vo = V Wo^T (attn2.to_out folded into the context, option
+        xattn_fold_vo)?  The decision the DiT's context build asks; nothing is launched, no device is needed."""
+        out = C.c_int(0)
+        _check(lib.ltx_op_xattn_fold_route(_dt(dtype), head_dim, heads, heads * head_dim if D is None else D, KP, B, int(bool(compact)), C.byref(out)))
+        return bool(out.value)
+
+    @staticmethod
+    def xattn_fold_kp(counts) -> int:
+        """KP of the kept-key counts of the batch rows: the largest, rounded up to the cross kernel's 32-key block"""
+        n = len(counts); out = C.c_int(0)
+        _check(lib.ltx_op_xattn_fold_kp((C.c_int * n)(*[int(c) for c in counts]), n, C.byref(out)))
+        return out.value
+
+    @staticmethod
+    def xattn_fold_build(v, key_bias, wo, heads, KP):
+        """vo [B, D, heads*KP] = V_kept Wo^T per head (bf16, head_dim 64): (vo, keys kept per batch row)"""
+        B, K, D = v.shape
+        vo = torch.empty(B, D, heads * KP, dtype=torch.bfloat16, device=v.device)
+        cnt = torch.zeros(B, dtype=torch.int32, device=v.device)
+        _check(lib.ltx_op_xattn_fold_build(_ptr(v.contiguous()), _ptr(key_bias.contiguous()), _ptr(wo.contiguous()), B, K, heads, KP, _ptr(vo), _ptr(cnt), _stream()))
+        return vo, cnt
+
+    @staticmethod
+    def attention_probs(q, k, heads, scale, key_bias, KP, q_rowsq=None, eps=1e-5):
+        """the cross kernel's P-only mode: p [B, Sq, heads*KP] bf16, the softmax weights of the kept keys (compacted to the front,
+        as ops.attention_compact does), zeros behind a row's count: (p, keys kept per batch row)"""
+        B, Sq, D = q.shape
+        p = torch.empty(B, Sq, heads * KP, dtype=torch.bfloat16, device=q.device)
+        cnt = torch.zeros(B, dtype=torch.int32, device=q.device)
+        _check(lib.ltx_op_attention_probs(_ptr(q.contiguous()), _ptr(k.contiguous()), _ptr(p), B, Sq, k.shape[1], heads, KP, C.c_float(scale), _ptr(key_bias.contiguous()),
+                                          _ptr(q_rowsq) if q_rowsq is not None else None, q_rowsq.shape[-1] if q_rowsq is not None else 0, C.c_float(eps), _ptr(cnt), _stream()))
+        return p, cnt
 
     @staticmethod
     def linear_segmented(x, w, bias, seg_width):

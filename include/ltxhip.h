@@ -304,6 +304,12 @@ int ltx_plan_load(const char* path);
  *                          timesteps, or a schedule with more distinct timesteps than norm_fold_copies (10), use form 1; a handle that
  *                          met such a schedule, or could not allocate a copy, frees its copies and stays on form 1)
  *   xattn_compact=0        cross attention multiplies every text key (differs from the default only for non-prefix masks)
+ *   xattn_fold_vo=0 | 2    cross attention multiplies P V and attn2.to_out runs over D, everywhere | (2) the fold up to heads * KP = D (measurement arm).  Default 1: where the text mask
+ *                          keeps few keys (heads * KP <= D / 2 with KP the kept keys rounded up to 32; bf16, head_dim 64) the text context
+ *                          also caches V Wo^T per layer and batch row, the cross kernel stops at the softmax and to_out multiplies
+ *                          the probabilities with K = heads * KP, one launch per batch row (another rounding: the probabilities, not
+ *                          the attention output, are rounded to bf16; 4 MB per layer and row at 2B with 32 keys kept; one host
+ *                          synchronisation per context build)
  *   dense_qkv=0            q | k | v as column slices of one [M, 3D] matrix (same bits; another memory layout)
  *   vae_fuse_norm=0        the resnet's second norm as its own pass (1, default: fused where the conv's grid is about one round of
  *                          the chip or more; 2: fused on smaller grids too)

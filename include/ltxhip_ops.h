@@ -140,6 +140,24 @@ int ltx_op_attention_rowsq(const void* q, const void* k, const void* v, void* o,
 int ltx_op_attention_compact(const void* q, const void* k, const void* v, void* o, int B, int Sq, int Sk, int heads, int hd,
                              int ldq, int ldk, int ldv, int ldo, float scale, const float* key_bias,
                              const float* q_rowsq, int q_rowsq_n, int q_rowsq_D, float q_rowsq_eps, int* counts_out, ltx_stream stream);
+/* attn2.to_out folded into the cached text context (csrc/xattn_fold.hip, option xattn_fold_vo): with P_h the row-normalised
+ * softmax of head h, h + (sum_h P_h V_h) Wo^T + b = h + sum_h P_h (V_h Wo_h^T) + b, and V_h Wo_h^T depends on the prompt and the
+ * weights alone.  KP = the largest kept-key count of the batch rows, rounded up to 32.
+ *   ltx_op_xattn_fold_route: read-only, the decision the DiT's context build asks - *fold = 1 where a compact bf16 head_dim-64
+ *     context of KP columns per head carries vo (heads * KP <= T * D, T = 1/2 measured: profiles/xattn_fold_vo_bench.md), else 0.
+ *     No device.
+ *   ltx_op_xattn_fold_kp: KP of HOST counts [B].
+ *   ltx_op_xattn_fold_build: the build kernel on one layer - v [B,K,heads*64] bf16 and key_bias [B,K] as ltx_op_attention_compact
+ *     takes them, wo [D,D] bf16; vo [B][D][heads*KP] bf16 with vo[b][n][h*KP + k] = sum_d wo[n][64h + d] * v_kept[b][k][64h + d]
+ *     (f32 accumulation, one bf16 rounding), exact zeros from a row's count on.  Blocks until done.
+ *   ltx_op_attention_probs: the cross kernel's P-only mode after the same compaction - p [B*Sq][heads*KP] bf16,
+ *     p[row][h*KP + k] = bf16(softmax weight of kept key k), exact zeros from the row's count on.  q_rowsq as in
+ *     ltx_op_attention_rowsq, may be NULL.  Blocks until done. */
+int ltx_op_xattn_fold_route(int dtype, int head_dim, int heads, int D, int KP, int B, int compact, int* fold);
+int ltx_op_xattn_fold_kp(const int* counts_host, int B, int* KP);
+int ltx_op_xattn_fold_build(const void* v, const float* key_bias, const void* wo, int B, int K, int heads, int KP, void* vo, int* counts_out, ltx_stream stream);
+int ltx_op_attention_probs(const void* q, const void* k, void* p_out, int B, int Sq, int Sk, int heads, int KP, float scale, const float* key_bias,
+                           const float* q_rowsq, int q_rowsq_n, float q_rowsq_eps, int* counts_out, ltx_stream stream);
 /* Same core for bf16, head_dim 64 or 128, no key bias, with q ALREADY multiplied by scale*log2(e) (the DiT self-attention
  * path folds that factor into the q RMSNorm+RoPE kernel): o = softmax_base2(q' k^T) v. */
 int ltx_op_attention_prescaled(const void* q, const void* k, const void* v, void* o, int B, int Sq, int Sk, int heads, int hd,
