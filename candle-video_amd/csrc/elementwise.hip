@@ -412,6 +412,45 @@ __global__ __launch_bounds__(256) void cond_apply_kernel(float* latents, const f
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < frame_elems; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
     }
 }
+// Keyframe conditioning (include/ltxhip_keyframes.h).  Both kernels: one block row per (table entry, batch row), one 16-byte chunk
+// (vec) or one element per thread and no loop - the grid covers the group, so no load follows a store in a thread.
+// cond_place: group tab.group[e] of the latents becomes a + s * (b - a), a its own value (the caller's noise) and b the item's frame;
+// s == 1 copies the item's bits (cond_apply_kernel's copy), s == 0 entries never reach the table.
+__global__ __launch_bounds__(256) void cond_place_kernel(float* latents, CondPlaceTab tab, int G, int64_t group_elems, int vec) {
+    const int e = blockIdx.y, b = blockIdx.z;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (vec ? group_elems >> 2 : group_elems)) return;
+    float* dst = latents + ((int64_t)b * G + tab.group[e]) * group_elems;
+    const float* src = tab.src[e] + (int64_t)b * tab.src_batch_stride[e];
+    const float s = tab.strength[e];
+    if (vec) {
+        const f32x4 y = reinterpret_cast<const f32x4*>(src)[i];
+        if (s == 1.0f) { reinterpret_cast<f32x4*>(dst)[i] = y; return; }
+        const f32x4 a = reinterpret_cast<const f32x4*>(dst)[i];
+        f32x4 r;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = __builtin_fmaf(s, y[k] - a[k], a[k]);
+        reinterpret_cast<f32x4*>(dst)[i] = r;
+    } else {
+        const float y = src[i];
+        dst[i] = s == 1.0f ? y : __builtin_fmaf(s, y - dst[i], dst[i]);
+    }
+}
+// cond_noise: latents = clean + k * noise on the hard-held groups tab.group[0 .. tab.n); all three tensors are [B, G, group_elems]
+__global__ __launch_bounds__(256) void cond_noise_kernel(float* latents, const float* clean, const float* noise, CondGroupTab tab, int G, int64_t group_elems, float k, int vec) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (vec ? group_elems >> 2 : group_elems)) return;
+    const int64_t base = ((int64_t)blockIdx.z * G + tab.group[blockIdx.y]) * group_elems;
+    if (vec) {
+        const f32x4 c = reinterpret_cast<const f32x4*>(clean + base)[i], z = reinterpret_cast<const f32x4*>(noise + base)[i];
+        f32x4 r;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = __builtin_fmaf(k, z[j], c[j]);
+        reinterpret_cast<f32x4*>(latents + base)[i] = r;
+    } else {
+        latents[base + i] = __builtin_fmaf(k, noise[base + i], clean[base + i]);
+    }
+}
 // the per-group modulation tables (kernels.h: ltx_launch_group_gather); one thread per 16-byte chunk of a destination row.  The value
 // indices of the launch's <= 128 groups travel by value (a kernel argument is copied when the launch is enqueued: no upload to wait for).
 __global__ __launch_bounds__(256) void group_gather_kernel(float* dst, int64_t dst_stride, const float* src, int64_t src_stride, GroupIdx idx, int g0, int ng, int c0, int nc, int nl, int width4) {
@@ -663,6 +702,50 @@ int ltx_launch_cond_apply(float* latents, const float* cond, int Fc, const unsig
     int64_t bx = cdiv64(vec ? frame_elems >> 2 : frame_elems, 256); if (bx > 256) bx = 256;
     hipLaunchKernelGGL(cond_apply_kernel, dim3((unsigned)bx, (unsigned)(B * F)), dim3(256), 0, s, latents, cond, Fc, hold_dev, F, frame_elems, vec);
     LTX_CHECK_LAUNCH(); return LTX_OK;
+}
+namespace {
+// the x extent of the two keyframe kernels: one thread per unit of a group, refused where a grid cannot hold it
+int cond_grid_x(int64_t group_elems, int vec, unsigned* bx) {
+    const int64_t n = cdiv64(vec ? group_elems >> 2 : group_elems, 256);
+    if (n > 0x7fffffffLL) LTX_FAIL(LTX_ERR_ARG, "keyframe conditioning: group too large");
+    *bx = (unsigned)n; return LTX_OK;
+}
+}  // namespace
+int ltx_launch_cond_place(float* latents, const CondPlaceEntry* entries, int n, int B, int G, int64_t group_elems, hipStream_t s) {
+    if (!latents || (n > 0 && !entries) || n < 0 || B < 1 || B > 65535 || G < 1 || group_elems < 1) LTX_FAIL(LTX_ERR_ARG, "cond_place: bad argument");
+    int vec = group_elems % 4 == 0 && !((uintptr_t)latents & 15);
+    for (int e = 0; e < n; ++e) {
+        if (!entries[e].src || entries[e].group < 0 || entries[e].group >= G || !(entries[e].strength >= 0.0f && entries[e].strength <= 1.0f))
+            LTX_FAIL(LTX_ERR_ARG, "cond_place: bad table entry " + std::to_string(e));
+        vec = vec && !((uintptr_t)entries[e].src & 15) && entries[e].src_batch_stride % 4 == 0;
+    }
+    unsigned bx = 0; LTX_TRY(cond_grid_x(group_elems, vec, &bx));
+    CondPlaceTab tab;
+    for (int e0 = 0; e0 < n; ) {
+        int m = 0;
+        for (; e0 < n && m < LTX_COND_TAB; ++e0) {
+            if (entries[e0].strength == 0.0f) continue;             // the noise's bits stay
+            tab.group[m] = entries[e0].group; tab.strength[m] = entries[e0].strength; tab.src[m] = entries[e0].src; tab.src_batch_stride[m] = entries[e0].src_batch_stride; ++m;
+        }
+        if (!m) continue;
+        hipLaunchKernelGGL(cond_place_kernel, dim3(bx, (unsigned)m, (unsigned)B), dim3(256), 0, s, latents, tab, G, group_elems, vec);
+        LTX_CHECK_LAUNCH();
+    }
+    return LTX_OK;
+}
+int ltx_launch_cond_noise(float* latents, const float* clean, const float* noise, const int* groups, int n, int B, int G, int64_t group_elems, float k, hipStream_t s) {
+    if (!latents || !clean || !noise || (n > 0 && !groups) || n < 0 || B < 1 || B > 65535 || G < 1 || group_elems < 1) LTX_FAIL(LTX_ERR_ARG, "cond_noise: bad argument");
+    for (int e = 0; e < n; ++e) if (groups[e] < 0 || groups[e] >= G) LTX_FAIL(LTX_ERR_ARG, "cond_noise: group " + std::to_string(groups[e]) + " outside the sequence");
+    const int vec = group_elems % 4 == 0 && !((uintptr_t)latents & 15) && !((uintptr_t)clean & 15) && !((uintptr_t)noise & 15);
+    unsigned bx = 0; LTX_TRY(cond_grid_x(group_elems, vec, &bx));
+    CondGroupTab tab;
+    for (int e0 = 0; e0 < n; e0 += LTX_COND_TAB) {
+        const int m = n - e0 < LTX_COND_TAB ? n - e0 : LTX_COND_TAB;
+        for (int e = 0; e < m; ++e) tab.group[e] = groups[e0 + e];
+        hipLaunchKernelGGL(cond_noise_kernel, dim3(bx, (unsigned)m, (unsigned)B), dim3(256), 0, s, latents, clean, noise, tab, G, group_elems, k, vec);
+        LTX_CHECK_LAUNCH();
+    }
+    return LTX_OK;
 }
 int ltx_launch_group_gather(float* dst, int64_t dst_stride, const float* src, int64_t src_stride, const int* idx_host, int c0, int nc, int nl, int ngroups, int width, hipStream_t s) {
     if (!dst || !src || !idx_host || nc < 1 || nl < 1 || ngroups < 1 || width < 4 || width % 4 || dst_stride % 4 || src_stride % 4 || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15))

@@ -345,6 +345,17 @@ size_t ltx_guidance_ex_ws_bytes(int B, int64_t n_per_batch);
 int ltx_launch_guidance_step_ex(const GuidanceExArgs& a, hipStream_t s);
 // latents[b][f] = cond[b][f] for the frames with hold_dev[b * F + f] != 0 (f < Fc); latents f32 [B, F, frame_elems], cond f32 [B, Fc, frame_elems]
 int ltx_launch_cond_apply(float* latents, const float* cond, int Fc, const unsigned char* hold_dev, int B, int F, int64_t frame_elems, hipStream_t s);
+// Keyframe conditioning (include/ltxhip_keyframes.h); latents f32 [B, G, group_elems].  The tables are HOST memory, read before the
+// call returns: they travel in the kernel arguments, LTX_COND_TAB entries a launch (one launch for every layout of a real video).
+// cond_place: group `group` of every batch row b becomes a + strength * (src[b * src_batch_stride ..] - a), a its value on entry;
+// strength 1 writes the source's bits, strength 0 entries are left out.  Entries apply independently: a group appears once.
+constexpr int LTX_COND_TAB = 64;
+struct CondPlaceEntry { int group = 0; float strength = 0.f; const float* src = nullptr; int64_t src_batch_stride = 0; };
+struct CondPlaceTab { const float* src[LTX_COND_TAB] = {}; int64_t src_batch_stride[LTX_COND_TAB] = {}; int group[LTX_COND_TAB] = {}; float strength[LTX_COND_TAB] = {}; };
+struct CondGroupTab { int group[LTX_COND_TAB] = {}; };
+int ltx_launch_cond_place(float* latents, const CondPlaceEntry* entries, int n, int B, int G, int64_t group_elems, hipStream_t s);
+// latents = clean + k * noise on the n listed groups of every batch row (clean and noise laid out like latents); others untouched
+int ltx_launch_cond_noise(float* latents, const float* clean, const float* noise, const int* groups, int n, int B, int G, int64_t group_elems, float k, hipStream_t s);
 
 // tokens [B,S,C] f32 -> channels-last T:  y = (x*std/sf + mean)*(1-ns) + noise*ns ; noise is NCTHW f32 [B,C,S] or null
 int ltx_launch_denorm_mix(const float* lat, const float* mean, const float* std_, float inv_sf, const float* noise,

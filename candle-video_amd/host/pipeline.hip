@@ -10,6 +10,8 @@
 #include "../csrc/options.h"
 #include "../../include/ltxhip_cond.h"
 #include "../../include/ltxhip_guidance.h"
+#include "../../include/ltxhip_keyframes.h"
+#include "cond_plan.h"
 
 // calculate_shift (t2v_pipeline.rs:159-169), f32 arithmetic
 extern "C" float ltx_calculate_shift(int seq_len, int base_seq_len, int max_seq_len, float base_shift, float max_shift) {
@@ -373,6 +375,7 @@ namespace {
 // device sync each) and the coords rebuild + blocking upload cost ~1 ms per video for nothing.
 struct PipeCache {
     DevBuf p_text, p_uncond, p_pert, stats, coords, hold, gws;
+    DevBuf kf_coords, kf_clean, kf_grid;                // a keyframe call: its own coordinates (never the geometry-keyed ones), the placed latents, the stripped grid
     DevBuf g_lat, g_emb, g_mask, g_pred, g_coords;      // the guidance branches of a step as one forward: inputs / predictions of all branches
     int coords_key[6] = {-1, -1, -1, -1, -1, -1};      // B, F, H, W, frame_rate, ratios packed
 };
@@ -423,9 +426,22 @@ struct StepGuidance {
     int n_skip(int i) const { return sc->skip_offsets[entry[i] + 1] - sc->skip_offsets[entry[i]]; }
 };
 
-// hold: HOST u8 [B, F'] or null - the held latent frames of ltx_pipeline_call_cond (include/ltxhip_cond.h); null: ltx_pipeline_call
+// A conditioned run (include/ltxhip_cond.h, ltxhip_keyframes.h): the sequence is G groups of h * w tokens per batch row, E extra ones
+// in front of the F' grid frames.  ltx_pipeline_call_cond fills it with the grid alone and one hold row; a keyframe call with its layout.
+struct CondRun {
+    int G = 0, E = 0;
+    std::vector<float> tcap;                 // [B, G]: the model sees min(t_i, tcap) for the group's tokens
+    std::vector<unsigned char> hold;         // [hold_rows, B, G], 1 = the group keeps its bits on the step; one row: the same on every step
+    int hold_rows = 1;
+    const float* coords = nullptr;           // HOST [G * h * w, 3] of one batch row; null: the grid's (E == 0), cached by geometry
+    std::vector<CondPlaceEntry> place;       // placement in front of the loop (empty: the latents arrive placed)
+    float noise_scale = 0.0f; const float* cond_noise = nullptr;      // noised holds: c and DEVICE [steps, B, G * h * w * C]
+    std::vector<int> hard;                   // ... and the groups they cover
+};
+
+// cr: null - ltx_pipeline_call
 // plan: null - the scalars of `p` on every step; else the branches, scales and perturbed blocks are the step's own (ltx_pipeline_call_sched)
-static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const unsigned char* hold, const StepGuidance* plan,
+static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const StepGuidance* plan,
                         float* latents, const float* prompt_embeds, const float* prompt_mask,
                         const float* neg_embeds, const float* neg_mask, const float* decode_noise,
                         int B, int K, float* out_video, ltx_stream stream) {
@@ -447,8 +463,12 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     int ts_ratio = 8, sp_ratio = 32;
     if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; sp_ratio = vc.spatial_compression_ratio; }
     const int F = (p->num_frames - 1) / ts_ratio + 1, H = p->height / sp_ratio, W = p->width / sp_ratio;   // :743-745
-    const int S = F * H * W, C = dc.in_channels, L = dc.num_layers;
+    const int G = cr ? cr->G : F, E = cr ? cr->E : 0;                      // groups of the sequence the model sees; the grid is its last F
+    const int S = G * H * W, C = dc.in_channels, L = dc.num_layers;
     const int64_t n = (int64_t)S * C;
+    if (cr && (G != E + F || cr->tcap.size() != (size_t)B * G || cr->hold.size() != (size_t)cr->hold_rows * B * G ||
+               (cr->hold_rows != 1 && cr->hold_rows != p->num_inference_steps) || (E > 0 && !cr->coords)))
+        LTX_FAIL(LTX_ERR_ARG, "pipeline: inconsistent conditioning description");
 
     // skip blocks: permanent iff STG is off (:691-697)
     if (plan) LTX_TRY(ltx_dit_set_skip_blocks(dit, nullptr, 0));      // a schedule never skips a block for good
@@ -459,7 +479,7 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     // sigmas / mu / timesteps (:750-791)
     const int N = p->num_inference_steps;
     std::vector<float> sig; std::vector<int64_t> ts;
-    LTX_TRY(ltx_pipeline_schedule(p, S, &sig, &ts));
+    LTX_TRY(ltx_pipeline_schedule(p, F * H * W, &sig, &ts));      // (the grid's tokens, with or without extra groups)
 
     PipeScratch sc;
     int cur_dev = 0; HIP_TRY(hipGetDevice(&cur_dev));
@@ -470,13 +490,22 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     if (do_stg) { LTX_TRY(pc.p_pert.ensure(pred_bytes)); sc.p_pert = pc.p_pert.p; }
     LTX_TRY(pc.stats.ensure(64 * B)); sc.stats = pc.stats.p;
     if (plan) LTX_TRY(pc.gws.ensure(ltx_guidance_ex_ws_bytes(B, n)));
-    if (hold) {                                      // device copy for the update kernels (the model's per-frame timesteps are built on the host)
-        LTX_TRY(pc.hold.ensure((size_t)B * F));
-        HIP_TRY(hipMemcpyAsync(pc.hold.p, hold, (size_t)B * F, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));            // (once per call, in front of the loop: `hold` is the caller's host memory)
+    if (cr) {                                        // device copy for the update kernels (the model's per-group timesteps are built on the host)
+        LTX_TRY(pc.hold.ensure(cr->hold.size()));
+        HIP_TRY(hipMemcpyAsync(pc.hold.p, cr->hold.data(), cr->hold.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));            // (once per call, in front of the loop)
     }
-    // video_coords [B,S,3] (:798-847): rebuilt only when the geometry changes
-    {
+    if (cr && cr->coords) {
+        // a layout's own coordinates: a buffer of their own, written on every call - the geometry-keyed one below is neither read nor
+        // re-keyed, and the pointer is stable for the whole call (the DiT's rope_key compares it inside the caching scope)
+        std::vector<float> all((size_t)B * S * 3);
+        for (int b = 0; b < B; ++b) std::memcpy(all.data() + (size_t)b * S * 3, cr->coords, sizeof(float) * S * 3);
+        LTX_TRY(pc.kf_coords.ensure(all.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(pc.kf_coords.p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        sc.coords = pc.kf_coords.p;
+    } else {
+        // video_coords [B,S,3] (:798-847): rebuilt only when the geometry changes
         const int key[6] = {B, F, H, W, p->frame_rate, ts_ratio * 1000 + sp_ratio};
         LTX_TRY(pc.coords.ensure((size_t)B * S * 3 * sizeof(float)));
         if (std::memcmp(key, pc.coords_key, sizeof(key)) != 0) {
@@ -547,6 +576,13 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     }
     for (auto& e : sc.ev) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(sc.ev[0], s));
+    const int64_t group_elems = (int64_t)H * W * C;
+    const bool noised = cr && cr->noise_scale > 0.0f && !cr->hard.empty();
+    if (cr && !cr->place.empty()) LTX_TRY(ltx_launch_cond_place(latents, cr->place.data(), (int)cr->place.size(), B, G, group_elems, s));
+    if (noised) {                                    // what placement wrote, for the noised holds of every step
+        LTX_TRY(pc.kf_clean.ensure((size_t)B * n * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(pc.kf_clean.p, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
     std::vector<float> stg_mask;
     if (do_stg && !plan) {                           // :911-923
         stg_mask.assign((size_t)L * B, 0.0f);
@@ -580,13 +616,18 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             cfg_i = plan->g(i) > 1.0f; stg_i = plan->s(i) > 0.0f; nbr_i = 1 + (cfg_i ? 1 : 0) + (stg_i ? 1 : 0);
             gb_i = sched_gb && nbr_i > 1 && nbr_i * B <= 8;
         }
-        if (hold) {
-            tframes.resize((size_t)(gb_i ? nbr_i : 1) * B * F);
-            for (size_t r = 0; r < tframes.size() / ((size_t)B * F); ++r)
-                for (size_t j = 0; j < (size_t)B * F; ++j) tframes[r * B * F + j] = hold[j] ? 0.0f : (float)ts[i];
+        if (cr) {
+            tframes.resize((size_t)(gb_i ? nbr_i : 1) * B * G);
+            for (size_t r = 0; r < tframes.size() / ((size_t)B * G); ++r)
+                for (size_t j = 0; j < (size_t)B * G; ++j) tframes[r * B * G + j] = std::fmin((float)ts[i], cr->tcap[j]);
         }
+        if (noised) {
+            const float kn = (float)((double)cr->noise_scale * (double)sig[i] * (double)sig[i]);
+            LTX_TRY(ltx_launch_cond_noise(latents, pc.kf_clean.as<float>(), cr->cond_noise + (size_t)i * B * n, cr->hard.data(), (int)cr->hard.size(), B, G, group_elems, kn, s));
+        }
+        const unsigned char* hold_i = cr ? pc.hold.as<unsigned char>() + (cr->hold_rows > 1 ? (size_t)i * B * G : 0) : nullptr;
         auto forward = [&](const void* x, const void* emb, const float* mk, int rows, const float* vc, const float* slm, void* pred) -> int {
-            if (hold) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
+            if (cr) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, G, H, W, nullptr, vc, slm, LTX_F32, pred, s);
             return ltx_dit_forward(dit, x, emb, tvals, mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
         };
         void *pt = sc.p_text, *pu = sc.p_uncond, *pp = sc.p_pert;
@@ -624,7 +665,7 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             ga.guidance_scale = plan->g(i); ga.guidance_rescale = plan->r(i); ga.stg_scale = plan->s(i);
             if (p->stochastic_sampling) { ga.sigma = sig[i]; ga.sigma_next = sig[i + 1]; ga.step_noise = p->step_noise + (size_t)i * B * n; }
             else ga.dt = dts;
-            if (hold) { ga.hold = pc.hold.as<unsigned char>(); ga.num_frames = F; ga.frame_elems = (int64_t)H * W * C; }
+            if (cr) { ga.hold = hold_i; ga.num_frames = G; ga.frame_elems = group_elems; }
             ge.cfg_star = plan->sc->cfg_star; ge.rescale_form = plan->sc->rescale_form; ge.ws = pc.gws.p;
             LTX_TRY(ltx_launch_guidance_step_ex(ge, s));
         } else {
@@ -634,7 +675,7 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             ga.guidance_scale = p->guidance_scale; ga.guidance_rescale = p->guidance_rescale; ga.stg_scale = p->stg_scale;
             if (p->stochastic_sampling) { ga.sigma = sig[i]; ga.sigma_next = sig[i + 1]; ga.step_noise = p->step_noise + (size_t)i * B * n; }
             else ga.dt = dts;
-            if (hold) { ga.hold = pc.hold.as<unsigned char>(); ga.num_frames = F; ga.frame_elems = (int64_t)H * W * C; }      // held frames keep their bits
+            if (cr) { ga.hold = hold_i; ga.num_frames = G; ga.frame_elems = group_elems; }      // held groups keep their bits
             LTX_TRY(ltx_launch_guidance_step(ga, s));
         }
         HIP_TRY(hipEventRecord(e2, s));
@@ -648,7 +689,15 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
         for (int b = 0; b < 8; ++b) { tdec[b] = p->decode_timestep; nsc[b] = p->decode_noise_scale; }
         ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc));
         const bool tc = vc.timestep_conditioning != 0;
-        LTX_TRY(ltx_vae_decode_tokens(vae, latents, tc ? decode_noise : nullptr, nsc, tc ? tdec : nullptr, B, F, H, W, p->tiling, p->postprocess, out_video, s));
+        // the extra groups are dropped: an offset for one batch row, one strided copy of the grid tokens for more
+        const float* grid = latents + (size_t)E * group_elems;
+        if (E > 0 && B > 1) {
+            const size_t row = (size_t)F * group_elems * sizeof(float);
+            LTX_TRY(pc.kf_grid.ensure((size_t)B * row));
+            HIP_TRY(hipMemcpy2DAsync(pc.kf_grid.p, row, grid, (size_t)n * sizeof(float), row, (size_t)B, hipMemcpyDeviceToDevice, s));
+            grid = pc.kf_grid.as<float>();
+        }
+        LTX_TRY(ltx_vae_decode_tokens(vae, grid, tc ? decode_noise : nullptr, nsc, tc ? tdec : nullptr, B, F, H, W, p->tiling, p->postprocess, out_video, s));
     }
     HIP_TRY(hipEventRecord(sc.ev[2], s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -670,6 +719,14 @@ extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_
     return pipeline_run(dit, vae, p, nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
 }
 
+// the held frames of include/ltxhip_cond.h as a conditioned run: the grid alone, one hold row, timestep 0 on a held frame
+static void cond_run_from_hold(const unsigned char* hold, int B, int F, CondRun* cr) {
+    cr->G = F; cr->E = 0; cr->hold_rows = 1;
+    cr->hold.assign(hold, hold + (size_t)B * F);
+    cr->tcap.resize((size_t)B * F);
+    for (size_t j = 0; j < cr->tcap.size(); ++j) cr->tcap[j] = hold[j] ? 0.0f : INFINITY;
+}
+
 extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_conditioning* cond,
                                       float* latents, const float* prompt_embeds, const float* prompt_mask,
                                       const float* neg_embeds, const float* neg_mask, const float* decode_noise,
@@ -681,11 +738,40 @@ extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipe
     const int F = (p->num_frames - 1) / ts_ratio + 1;
     bool any = false;
     for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) any = any || cond->hold[j] != 0;
+    CondRun cr;
+    if (any) cond_run_from_hold(cond->hold, B, F, &cr);
     // nothing held: ltx_pipeline_call itself
-    return pipeline_run(dit, vae, p, any ? cond->hold : nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return pipeline_run(dit, vae, p, any ? &cr : nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
 }
 
 // ---- the pipeline calls under a guidance schedule (include/ltxhip_guidance.h) ----
+// cr: the conditioned run or null; sig: the call's sigmas (ltx_pipeline_schedule at the grid's tokens)
+static int pipeline_run_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched, const CondRun* cr,
+                              const std::vector<float>& sig, float* latents, const float* prompt_embeds, const float* prompt_mask,
+                              const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                              int B, int K, float* out_video, ltx_stream stream) {
+    const int N = p->num_inference_steps;
+    StepGuidance plan; plan.sc = sched; plan.entry.assign(N, 0);
+    LTX_TRY(ltx_guidance_schedule_resolve(sched, sig.data(), N, plan.entry.data()));
+    // The same values on every step, no CFG-star, the reference's rescale: the unscheduled call on those values, its kernels and bits.
+    // (An entry with s == 0 perturbs nothing and skips nothing: its list is not handed on, and the handle's own list is cleared.)
+    bool constant = !sched->cfg_star && sched->rescale_form == LTX_RESCALE_CFG;
+    for (int i = 1; i < N && constant; ++i) {
+        constant = plan.g(i) == plan.g(0) && plan.s(i) == plan.s(0) && plan.r(i) == plan.r(0);
+        if (constant && plan.s(0) > 0.0f && plan.entry[i] != plan.entry[0])
+            constant = plan.n_skip(i) == plan.n_skip(0) && (plan.n_skip(0) == 0 || !std::memcmp(plan.skip(i), plan.skip(0), sizeof(int) * plan.n_skip(0)));
+    }
+    if (constant) {
+        static const int none = 0;
+        ltx_pipeline_params q = *p;
+        q.guidance_scale = plan.g(0); q.stg_scale = plan.s(0); q.guidance_rescale = plan.r(0);
+        const bool stg = plan.s(0) > 0.0f && plan.n_skip(0) > 0;
+        q.skip_block_list = stg ? plan.skip(0) : &none; q.n_skip_blocks = stg ? plan.n_skip(0) : 0;
+        return pipeline_run(dit, vae, &q, cr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    }
+    return pipeline_run(dit, vae, p, cr, &plan, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+}
+
 extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched,
                                        const ltx_conditioning* cond, float* latents, const float* prompt_embeds, const float* prompt_mask,
                                        const float* neg_embeds, const float* neg_mask, const float* decode_noise,
@@ -701,28 +787,123 @@ extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pip
     const int F = (p->num_frames - 1) / ts_ratio + 1, S = F * (p->height / sp_ratio) * (p->width / sp_ratio);
     std::vector<float> sig; std::vector<int64_t> ts;
     LTX_TRY(ltx_pipeline_schedule(p, S, &sig, &ts));
-    const int N = p->num_inference_steps;
-    StepGuidance plan; plan.sc = sched; plan.entry.assign(N, 0);
-    LTX_TRY(ltx_guidance_schedule_resolve(sched, sig.data(), N, plan.entry.data()));
-    const unsigned char* hold = nullptr;
-    if (cond) for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) if (cond->hold[j]) { hold = cond->hold; break; }
-    // The same values on every step, no CFG-star, the reference's rescale: the unscheduled call on those values, its kernels and bits.
-    // (An entry with s == 0 perturbs nothing and skips nothing: its list is not handed on, and the handle's own list is cleared.)
-    bool constant = !sched->cfg_star && sched->rescale_form == LTX_RESCALE_CFG;
-    for (int i = 1; i < N && constant; ++i) {
-        constant = plan.g(i) == plan.g(0) && plan.s(i) == plan.s(0) && plan.r(i) == plan.r(0);
-        if (constant && plan.s(0) > 0.0f && plan.entry[i] != plan.entry[0])
-            constant = plan.n_skip(i) == plan.n_skip(0) && (plan.n_skip(0) == 0 || !std::memcmp(plan.skip(i), plan.skip(0), sizeof(int) * plan.n_skip(0)));
+    CondRun cr; bool any = false;
+    if (cond) for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0) && !any; ++j) any = cond->hold[j] != 0;
+    if (any) cond_run_from_hold(cond->hold, B, F, &cr);
+    return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+}
+
+// ---- keyframe conditioning (include/ltxhip_keyframes.h): the layout is host/cond_plan.h's, these entries hand it on ----
+static int cond_plan_from_items(const ltx_cond_item* items, int n_items, int height, int width, int num_frames, int frame_rate, int ts_ratio, int sp_ratio, CondPlan* plan) {
+    if (n_items > 0 && !items) LTX_FAIL(LTX_ERR_ARG, "conditioning layout: items is null with n_items " + std::to_string(n_items));
+    if (sp_ratio < 1 || height < sp_ratio || width < sp_ratio) LTX_FAIL(LTX_ERR_ARG, "conditioning layout: height and width must hold one latent at least");
+    std::vector<CondItemGeom> geo((size_t)(n_items > 0 ? n_items : 0));
+    for (int i = 0; i < n_items; ++i) geo[(size_t)i] = {items[i].cond_frames, items[i].frame_index, items[i].strength};
+    std::string err;
+    if (!cond_plan_build(geo.data(), n_items, num_frames, height / sp_ratio, width / sp_ratio, ts_ratio, sp_ratio, frame_rate, plan, &err)) LTX_FAIL(LTX_ERR_ARG, err);
+    return LTX_OK;
+}
+
+extern "C" int ltx_cond_layout(const ltx_cond_item* items, int n_items, int height, int width, int num_frames, int frame_rate,
+                               int ts_ratio, int sp_ratio, int* E, int* G, ltx_cond_group* groups, int max_groups, float* coords) {
+    CondPlan plan;
+    LTX_TRY(cond_plan_from_items(items, n_items, height, width, num_frames, frame_rate, ts_ratio, sp_ratio, &plan));
+    if ((groups || coords) && plan.G > max_groups)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_cond_layout: the layout has " + std::to_string(plan.G) + " groups, the output holds " + std::to_string(max_groups));
+    if (E) *E = plan.E;
+    if (G) *G = plan.G;
+    if (groups) for (int g = 0; g < plan.G; ++g) groups[g] = {plan.groups[(size_t)g].item, plan.groups[(size_t)g].frame, plan.groups[(size_t)g].strength};
+    if (coords) std::memcpy(coords, plan.coords.data(), plan.coords.size() * sizeof(float));
+    return LTX_OK;
+}
+
+// the place table of a groups table: one entry per group an item owns (the launch leaves out strength 0)
+static int cond_place_entries(const ltx_cond_item* items, int n_items, const ltx_cond_group* groups, int G, int64_t group_elems, std::vector<CondPlaceEntry>* out) {
+    out->clear();
+    for (int g = 0; g < G; ++g) {
+        const ltx_cond_group& e = groups[g];
+        if (e.item < 0) continue;
+        if (e.item >= n_items || !items[e.item].tokens || e.item_frame < 0 || e.item_frame >= items[e.item].cond_frames || !(e.strength >= 0.0f && e.strength <= 1.0f))
+            LTX_FAIL(LTX_ERR_ARG, "conditioning: group " + std::to_string(g) + " names item " + std::to_string(e.item) + ", frame " + std::to_string(e.item_frame) +
+                                  ", strength " + std::to_string(e.strength) + ": no such frame of the items given, tokens missing, or strength outside [0, 1]");
+        CondPlaceEntry pe; pe.group = g; pe.strength = e.strength;
+        pe.src = items[e.item].tokens + (int64_t)e.item_frame * group_elems; pe.src_batch_stride = (int64_t)items[e.item].cond_frames * group_elems;
+        out->push_back(pe);
     }
-    if (constant) {
-        static const int none = 0;
-        ltx_pipeline_params q = *p;
-        q.guidance_scale = plan.g(0); q.stg_scale = plan.s(0); q.guidance_rescale = plan.r(0);
-        const bool stg = plan.s(0) > 0.0f && plan.n_skip(0) > 0;
-        q.skip_block_list = stg ? plan.skip(0) : &none; q.n_skip_blocks = stg ? plan.n_skip(0) : 0;
-        return pipeline_run(dit, vae, &q, hold, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return LTX_OK;
+}
+
+extern "C" int ltx_cond_place(float* latents, const ltx_cond_item* items, int n_items, const ltx_cond_group* groups, int G,
+                              int B, int tokens_per_group, int channels, ltx_stream stream) {
+    if (!latents || !groups || G < 1 || B < 1 || tokens_per_group < 1 || channels < 1 || n_items < 0 || (n_items > 0 && !items)) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_place: bad argument");
+    std::vector<CondPlaceEntry> place;
+    LTX_TRY(cond_place_entries(items, n_items, groups, G, (int64_t)tokens_per_group * channels, &place));
+    return ltx_launch_cond_place(latents, place.data(), (int)place.size(), B, G, (int64_t)tokens_per_group * channels, (hipStream_t)stream);
+}
+
+extern "C" int ltx_cond_noise(float* latents, const float* clean, const float* noise, const ltx_cond_group* groups, int G,
+                              int B, int tokens_per_group, int channels, float scale, float sigma, ltx_stream stream) {
+    if (!latents || !clean || !noise || !groups || G < 1 || B < 1 || tokens_per_group < 1 || channels < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_noise: bad argument");
+    if (!(scale > 0.0f) || !std::isfinite(scale) || !std::isfinite(sigma)) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_noise: scale must be > 0 and sigma finite, got " + std::to_string(scale) + ", " + std::to_string(sigma));
+    std::vector<int> hard;
+    for (int g = 0; g < G; ++g) if (groups[g].item >= 0 && cond_group_is_hard(groups[g].strength)) hard.push_back(g);
+    if (hard.empty()) return LTX_OK;
+    const float k = (float)((double)scale * (double)sigma * (double)sigma);
+    return ltx_launch_cond_noise(latents, clean, noise, hard.data(), (int)hard.size(), B, G, (int64_t)tokens_per_group * channels, k, (hipStream_t)stream);
+}
+
+extern "C" int ltx_cond_step_hold(const ltx_cond_group* groups, int G, float sigma, float timestep, unsigned char* hold_out, float* timesteps_out) {
+    if (!groups || G < 1 || !hold_out) LTX_FAIL(LTX_ERR_ARG, "ltx_cond_step_hold: groups, G >= 1 and hold_out are required");
+    for (int g = 0; g < G; ++g) {
+        hold_out[g] = cond_group_updates(sigma, groups[g].strength) ? 0 : 1;
+        if (timesteps_out) timesteps_out[g] = cond_group_timestep(timestep, groups[g].strength);
     }
-    return pipeline_run(dit, vae, p, hold, &plan, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return LTX_OK;
+}
+
+extern "C" int ltx_pipeline_call_keyframes(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched,
+                                           const ltx_cond_item* items, int n_items, float image_cond_noise_scale, const float* cond_noise,
+                                           float* latents, const float* prompt_embeds, const float* prompt_mask,
+                                           const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                                           int B, int K, float* out_video, ltx_stream stream) {
+    if (!dit || !p || B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_keyframes: null argument");
+    if (n_items < 0 || (n_items > 0 && !items)) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_keyframes: items is null with n_items " + std::to_string(n_items));
+    if (!(image_cond_noise_scale >= 0.0f) || !std::isfinite(image_cond_noise_scale)) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_keyframes: image_cond_noise_scale must be >= 0, got " + std::to_string(image_cond_noise_scale));
+    if (image_cond_noise_scale > 0.0f && !cond_noise) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_keyframes: image_cond_noise_scale " + std::to_string(image_cond_noise_scale) + " needs cond_noise [steps, B, S_ext*C]");
+    ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
+    if (sched) LTX_TRY(guidance_schedule_check(sched, dc.num_layers));
+    int ts_ratio = 8, sp_ratio = 32;
+    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; sp_ratio = vc.spatial_compression_ratio; }
+    CondPlan plan;
+    LTX_TRY(cond_plan_from_items(items, n_items, p->height, p->width, p->num_frames, p->frame_rate, ts_ratio, sp_ratio, &plan));
+    std::vector<float> sig; std::vector<int64_t> ts;
+    LTX_TRY(ltx_pipeline_schedule(p, plan.Fl * plan.hw, &sig, &ts));
+    const int N = p->num_inference_steps, G = plan.G;
+    bool any = false;
+    for (const CondGroup& g : plan.groups) any = any || g.item >= 0;
+    CondRun cr;
+    if (any) {
+        for (int i = 0; i < n_items; ++i) if (!items[i].tokens) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_keyframes: conditioning item " + std::to_string(i) + " has no tokens");
+        std::vector<ltx_cond_group> groups((size_t)G);
+        for (int g = 0; g < G; ++g) groups[(size_t)g] = {plan.groups[(size_t)g].item, plan.groups[(size_t)g].frame, plan.groups[(size_t)g].strength};
+        LTX_TRY(cond_place_entries(items, n_items, groups.data(), G, (int64_t)plan.hw * dc.in_channels, &cr.place));
+        cr.G = G; cr.E = plan.E; cr.hold_rows = N;
+        cr.tcap.resize((size_t)B * G); cr.hold.resize((size_t)N * B * G);
+        for (int b = 0; b < B; ++b)
+            for (int g = 0; g < G; ++g) {
+                const float sg = plan.groups[(size_t)g].strength;
+                cr.tcap[(size_t)b * G + g] = 1000.0f * (1.0f - sg);
+                for (int i = 0; i < N; ++i) cr.hold[((size_t)i * B + b) * G + g] = cond_group_updates(sig[i], sg) ? 0 : 1;
+            }
+        if (plan.E > 0) cr.coords = plan.coords.data();          // (E == 0: the grid's own, as ltx_pipeline_call_cond uses them)
+        if (image_cond_noise_scale > 0.0f) {
+            cr.noise_scale = image_cond_noise_scale; cr.cond_noise = cond_noise;
+            for (int g = 0; g < G; ++g) if (plan.groups[(size_t)g].item >= 0 && cond_group_is_hard(plan.groups[(size_t)g].strength)) cr.hard.push_back(g);
+        }
+    }
+    // no item owns a group: ltx_pipeline_call (or _sched) itself
+    if (sched) return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return pipeline_run(dit, vae, p, any ? &cr : nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
 }
 
 // ---- warm-up: everything a first call would otherwise do inside the caller's forward --------------------------------

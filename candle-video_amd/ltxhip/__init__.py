@@ -347,6 +347,29 @@ LTX_RESCALE_CFG, LTX_RESCALE_MIX = 0, 1
 RESCALE_FORMS = ("cfg", "mix")                   # ltx_rescale_form, by value
 
 
+class CondItemC(C.Structure):                    # ltx_cond_item (include/ltxhip_keyframes.h)
+    _fields_ = [("tokens", C.POINTER(C.c_float)), ("cond_frames", C.c_int), ("frame_index", C.c_int), ("strength", C.c_float)]
+
+
+class CondGroupC(C.Structure):                   # ltx_cond_group
+    _fields_ = [("item", C.c_int), ("item_frame", C.c_int), ("strength", C.c_float)]
+
+
+# include/ltxhip_keyframes.h (kept apart like the seven above)
+_KEYFRAME_SIGS = {
+    "ltx_cond_layout": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "ltx_cond_place": [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp],
+    "ltx_cond_noise": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp],
+    "ltx_cond_step_hold": [_vp, _i, _f, _f, _vp, _vp],
+    "ltx_pipeline_call_keyframes": [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+}
+KEYFRAME_SYMBOLS = sorted(_KEYFRAME_SIGS)
+for _name, _sig in _KEYFRAME_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
+
+
 @dataclass
 class GuidanceSchedule:
     """ltx_guidance_schedule: one (guidance_scale, stg_scale, rescale, perturbed block list) per entry; a step takes the entry whose
@@ -1299,6 +1322,92 @@ def cond_apply(latents: torch.Tensor, cond_tokens: torch.Tensor, hold, num_frame
     return lat
 
 
+# ------------------------------------------------------------------ keyframe conditioning (include/ltxhip_keyframes.h)
+@dataclass
+class ConditioningItem:
+    """ltx_cond_item: tokens [B, cond_frames*hw, C] f32 (encode_tokens of an image or clip), the PIXEL frame it sits at, its strength"""
+    tokens: Optional[torch.Tensor]
+    frame_index: int = 0
+    strength: float = 1.0
+    cond_frames: Optional[int] = None           # None: tokens.shape[1] // (h*w)
+
+
+@dataclass
+class CondLayout:
+    """ltx_cond_layout's result: E extra groups in front of the F' grid frames, G = E + F' groups of hw tokens; groups[g] =
+    (item or -1, the item's latent frame, strength); coords [G*hw, 3] of one batch row"""
+    E: int
+    G: int
+    hw: int
+    groups: List[tuple]
+    coords: torch.Tensor
+
+    def groups_c(self):
+        return (CondGroupC * self.G)(*[CondGroupC(i, f, s) for i, f, s in self.groups])
+
+
+def _items_c(items, hw: int, keep: list, need_tokens: bool):
+    arr = (CondItemC * max(len(items), 1))()
+    for k, it in enumerate(items):
+        fc, t = it.cond_frames, None
+        if it.tokens is not None:
+            t = _dev(it.tokens, torch.float32); keep.append(t)
+            if t.dim() != 3 or t.shape[1] % hw != 0 or (fc is not None and t.shape[1] != fc * hw):
+                raise LtxError(f"conditioning item {k}: tokens must be [B, cond_frames*{hw}, C]")
+            fc = t.shape[1] // hw
+        elif need_tokens or fc is None:
+            raise LtxError(f"conditioning item {k}: tokens are required")
+        arr[k] = CondItemC(C.cast(C.c_void_p(t.data_ptr() if t is not None else None), C.POINTER(C.c_float)), int(fc), int(it.frame_index), float(it.strength))
+    return arr
+
+
+def cond_layout(items: Sequence[ConditioningItem], height: int, width: int, num_frames: int, frame_rate: int = 25,
+                ts_ratio: int = 8, sp_ratio: int = 32) -> CondLayout:
+    """ltx_cond_layout: where the items go (host only; an item needs tokens or cond_frames).  Raises LtxError on every refusal."""
+    hw = (height // sp_ratio) * (width // sp_ratio)
+    keep = []
+    arr = _items_c(items, max(hw, 1), keep, False)
+    E, G = C.c_int(0), C.c_int(0)
+    _check(lib.ltx_cond_layout(arr, len(items), height, width, num_frames, frame_rate, ts_ratio, sp_ratio, C.byref(E), C.byref(G), None, 0, None))
+    groups = (CondGroupC * G.value)()
+    coords = torch.empty(G.value * hw, 3, dtype=torch.float32)
+    _check(lib.ltx_cond_layout(arr, len(items), height, width, num_frames, frame_rate, ts_ratio, sp_ratio, C.byref(E), C.byref(G), groups, G.value,
+                               C.c_void_p(coords.data_ptr())))
+    return CondLayout(E.value, G.value, hw, [(g.item, g.item_frame, g.strength) for g in groups], coords)
+
+
+def cond_place(latents: torch.Tensor, items: Sequence[ConditioningItem], layout: CondLayout) -> torch.Tensor:
+    """ltx_cond_place on a copy: latents [B, G*hw, C] f32 (the caller's noise); a placed group becomes a + s*(b - a)"""
+    lat = _dev(latents, torch.float32).clone()
+    if lat.dim() != 3 or lat.shape[1] != layout.G * layout.hw:
+        raise LtxError(f"cond_place: latents must be [B, {layout.G * layout.hw}, C]")
+    keep = []
+    arr = _items_c(items, layout.hw, keep, True)
+    for k, t in enumerate(keep):
+        if t.shape[0] != lat.shape[0] or t.shape[2] != lat.shape[2] or t.device != lat.device:
+            raise LtxError(f"cond_place: item {k} must agree with latents in B, C and device")
+    _check(lib.ltx_cond_place(_ptr(lat), arr, len(items), layout.groups_c(), layout.G, lat.shape[0], layout.hw, lat.shape[2], _stream()))
+    return lat
+
+
+def cond_noise(latents: torch.Tensor, clean: torch.Tensor, noise: torch.Tensor, layout: CondLayout, scale: float, sigma: float) -> torch.Tensor:
+    """ltx_cond_noise on a copy: the groups of full strength become clean + scale*sigma^2*noise; all three [B, G*hw, C] f32"""
+    lat = _dev(latents, torch.float32).clone()
+    cl, nz = _dev(clean, torch.float32), _dev(noise, torch.float32)
+    if lat.dim() != 3 or lat.shape[1] != layout.G * layout.hw or cl.shape != lat.shape or nz.shape != lat.shape:
+        raise LtxError(f"cond_noise: latents, clean and noise must be [B, {layout.G * layout.hw}, C]")
+    _check(lib.ltx_cond_noise(_ptr(lat), _ptr(cl), _ptr(nz), layout.groups_c(), layout.G, lat.shape[0], layout.hw, lat.shape[2], float(scale), float(sigma), _stream()))
+    return lat
+
+
+def cond_step_hold(layout: CondLayout, sigma: float, timestep: float = 0.0):
+    """ltx_cond_step_hold: ([G] 1 = the group keeps its bits on a step of `sigma`, [G] what the model sees at scheduler timestep `timestep`)"""
+    hold = (C.c_ubyte * layout.G)()
+    tm = (C.c_float * layout.G)()
+    _check(lib.ltx_cond_step_hold(layout.groups_c(), layout.G, float(sigma), float(timestep), hold, tm))
+    return list(hold), list(tm)
+
+
 # ------------------------------------------------------------------ pipeline
 @dataclass
 class PipelineCall:
@@ -1332,8 +1441,14 @@ class LtxPipeline:
     def call(self, args: PipelineCall, latents: torch.Tensor, prompt_embeds: torch.Tensor, prompt_attention_mask: torch.Tensor,
              negative_prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_attention_mask: Optional[torch.Tensor] = None,
              decode_noise: Optional[torch.Tensor] = None, step_noise: Optional[torch.Tensor] = None,
-             interrupt=None, on_step=None, hold=None, schedule: Optional["GuidanceSchedule"] = None):
+             interrupt=None, on_step=None, hold=None, schedule: Optional["GuidanceSchedule"] = None,
+             conditioning_items: Optional[Sequence["ConditioningItem"]] = None, image_cond_noise_scale: float = 0.0,
+             cond_noise: Optional[torch.Tensor] = None):
         """Returns (final_latents [B,S,C] f32, video [B,3,frames,H,W] f32 or None).
+        conditioning_items: keyframe conditioning (ltx_pipeline_call_keyframes, with `schedule` or without; not with `hold`) - `latents`
+        is the caller's noise for the EXTENDED sequence [B, G*hw, C] of cond_layout(conditioning_items, ...), step_noise covers it too,
+        the returned latents are the extended ones (the grid tokens start at token E*hw of a row) and the video has the plain call's
+        shape.  image_cond_noise_scale > 0 with cond_noise [steps, B, G*hw, C]: the noised holds of full-strength items.
         schedule: a GuidanceSchedule (ltx_pipeline_call_sched, with `hold` or without) - the guidance of every step comes from it and
         the scalar guidance fields and skip_block_list of `args` are ignored.
         hold [B, F'] (truthy = held): image-to-video / clip continuation (ltx_pipeline_call_cond) - `latents` carries the held
@@ -1356,13 +1471,19 @@ class LtxPipeline:
         sr = self.vae.config.spatial_compression_ratio if self.vae is not None else 32
         F, H, W = (args.num_frames - 1) // tr + 1, args.height // sr, args.width // sr
         Cin = self.transformer.config.in_channels
-        _expect("latents", lat, (B, F * H * W, Cin))
+        S_seq = F * H * W
+        if conditioning_items is not None:
+            if hold is not None:
+                raise LtxError("conditioning_items and hold exclude each other (an item at frame 0 with strength 1 is a held frame)")
+            layout = cond_layout(conditioning_items, args.height, args.width, args.num_frames, args.frame_rate, tr, sr)
+            S_seq = layout.G * H * W
+        _expect("latents", lat, (B, S_seq, Cin))
         _expect("prompt_embeds", pe, (B, K, self.transformer.config.caption_channels))
         _expect("prompt_attention_mask", pm, (B, K))
         if ne is not None: _expect("negative_prompt_embeds", ne, (B, K, self.transformer.config.caption_channels))
         if nm is not None: _expect("negative_prompt_attention_mask", nm, (B, K))
         if dn is not None: _expect("decode_noise", dn, (B, Cin, F, H, W))
-        if step_noise is not None: _expect("step_noise", step_noise, (args.num_inference_steps, B, F * H * W, Cin))
+        if step_noise is not None: _expect("step_noise", step_noise, (args.num_inference_steps, B, S_seq, Cin))
         p = PipelineParamsC()
         lib.ltx_pipeline_params_default(C.byref(p))
         p.height, p.width, p.num_frames, p.frame_rate = args.height, args.width, args.num_frames, args.frame_rate
@@ -1411,7 +1532,23 @@ class LtxPipeline:
                 video = torch.empty(B, (F - 1) * tr + 1, H * sr, W * sr, 3, dtype=torch.uint8, device=lat.device)
             else:
                 video = torch.empty(B, 3, (F - 1) * tr + 1, H * sr, W * sr, dtype=torch.float32, device=lat.device)
-        if schedule is not None:
+        if conditioning_items is not None:
+            items_c = _items_c(conditioning_items, H * W, keep, True)
+            for k, t in enumerate(keep[-len(conditioning_items):] if conditioning_items else []):
+                if t.shape[0] != B or t.shape[2] != Cin or t.device != lat.device:
+                    raise LtxError(f"conditioning item {k}: tokens must be [{B}, cond_frames*{H * W}, {Cin}] on the latents' device")
+            cn = None
+            if image_cond_noise_scale > 0.0:
+                if cond_noise is None:
+                    raise LtxError("image_cond_noise_scale > 0 needs cond_noise [steps, B, S_ext, C]")
+                cn = _dev(cond_noise, torch.float32); keep.append(cn)
+                _expect("cond_noise", cn, (args.num_inference_steps, B, S_seq, Cin))
+            sched = schedule.to_c(keep) if schedule is not None else None
+            _check(lib.ltx_pipeline_call_keyframes(self.transformer._h, self.vae._h if self.vae is not None else None, C.byref(p),
+                                                   C.byref(sched) if sched is not None else None, items_c, len(conditioning_items),
+                                                   float(image_cond_noise_scale), _ptr(cn), _ptr(lat), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K,
+                                                   _ptr(video), _stream()))
+        elif schedule is not None:
             sched = schedule.to_c(keep)
             cond = None
             if hold is not None:

@@ -442,3 +442,46 @@ extern "C" {
                                               neg_mask: *const c_float, decode_noise: *const c_float, b: c_int, k: c_int, latents_hi_out: *mut c_float,
                                               out_video: *mut c_float, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_keyframes.h: conditioning items at any frame, strengths, noised holds ----
+
+/// `ltx_cond_item`: DEVICE f32 tokens [B, cond_frames*hw, C], the PIXEL frame the item sits at, its strength in [0, 1].
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_cond_item {
+    pub tokens: *const c_float,
+    pub cond_frames: c_int,
+    pub frame_index: c_int,
+    pub strength: c_float,
+}
+
+/// `ltx_cond_group`: one group of the extended sequence - the item that owns it (-1: none), the item's latent frame, its strength.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_cond_group {
+    pub item: c_int,
+    pub item_frame: c_int,
+    pub strength: c_float,
+}
+
+pub const KEYFRAMES_LAYOUT_LTX_COND_ITEM: (usize, usize) = (24, 8);
+pub const KEYFRAMES_LAYOUT_LTX_COND_GROUP: (usize, usize) = (12, 4);
+const _: () = assert!(size_of::<ltx_cond_item>() == KEYFRAMES_LAYOUT_LTX_COND_ITEM.0 && align_of::<ltx_cond_item>() == KEYFRAMES_LAYOUT_LTX_COND_ITEM.1);
+const _: () = assert!(size_of::<ltx_cond_group>() == KEYFRAMES_LAYOUT_LTX_COND_GROUP.0 && align_of::<ltx_cond_group>() == KEYFRAMES_LAYOUT_LTX_COND_GROUP.1);
+
+extern "C" {
+    pub fn ltx_cond_layout(items: *const ltx_cond_item, n_items: c_int, height: c_int, width: c_int, num_frames: c_int, frame_rate: c_int,
+                           ts_ratio: c_int, sp_ratio: c_int, e: *mut c_int, g: *mut c_int, groups: *mut ltx_cond_group, max_groups: c_int,
+                           coords: *mut c_float) -> c_int;
+    pub fn ltx_cond_place(latents: *mut c_float, items: *const ltx_cond_item, n_items: c_int, groups: *const ltx_cond_group, g: c_int, b: c_int,
+                          tokens_per_group: c_int, channels: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_cond_noise(latents: *mut c_float, clean: *const c_float, noise: *const c_float, groups: *const ltx_cond_group, g: c_int, b: c_int,
+                          tokens_per_group: c_int, channels: c_int, scale: c_float, sigma: c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_cond_step_hold(groups: *const ltx_cond_group, g: c_int, sigma: c_float, timestep: c_float, hold_out: *mut u8,
+                              timesteps_out: *mut c_float) -> c_int;
+    pub fn ltx_pipeline_call_keyframes(dit: *mut ltx_dit, vae: *mut ltx_vae, p: *const ltx_pipeline_params, sched: *const ltx_guidance_schedule,
+                                       items: *const ltx_cond_item, n_items: c_int, image_cond_noise_scale: c_float, cond_noise: *const c_float,
+                                       latents: *mut c_float, prompt_embeds: *const c_float, prompt_mask: *const c_float, neg_embeds: *const c_float,
+                                       neg_mask: *const c_float, decode_noise: *const c_float, b: c_int, k: c_int, out_video: *mut c_float,
+                                       stream: ltx_stream) -> c_int;
+}
