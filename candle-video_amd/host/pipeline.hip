@@ -12,6 +12,7 @@
 #include "../../include/ltxhip_guidance.h"
 #include "../../include/ltxhip_keyframes.h"
 #include "cond_plan.h"
+#include "step_plan.h"
 
 // calculate_shift (t2v_pipeline.rs:159-169), f32 arithmetic
 extern "C" float ltx_calculate_shift(int seq_len, int base_seq_len, int max_seq_len, float base_shift, float max_shift) {
@@ -207,16 +208,27 @@ extern "C" int ltx_build_video_coords(int F, int H, int W, int frame_rate, int t
     return LTX_OK;
 }
 
+// The one fill of a mix's arguments, for the five C entries below and the denoise loop.  step_noise: the stochastic update on
+// (sigma, sigma_next), null: Euler with dt; hold: the held frames, null: none; stats: the classic mix's workspace (the _ex mix has its own).
+static GuidanceArgs guidance_args(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype, float* latents, float* noise_pred_out,
+                                  int B, int64_t n, float guidance_scale, float guidance_rescale, float stg_scale, float dt, float sigma, float sigma_next,
+                                  const float* step_noise, void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems) {
+    GuidanceArgs a;
+    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
+    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
+    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale;
+    if (step_noise) { a.sigma = sigma; a.sigma_next = sigma_next; a.step_noise = step_noise; } else a.dt = dt;
+    a.stats = reinterpret_cast<double*>(stats_ws);
+    if (hold) { a.hold = hold; a.num_frames = num_frames; a.frame_elems = frame_elems; }
+    return a;
+}
+
 extern "C" int ltx_guidance_step(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype,
                                  float* latents, float* noise_pred_out, int B, int64_t n,
                                  float guidance_scale, float guidance_rescale, float stg_scale, float dt,
                                  void* stats_ws, ltx_stream stream) {
-    GuidanceArgs a;
-    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
-    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale; a.dt = dt;
-    a.stats = reinterpret_cast<double*>(stats_ws);
-    return ltx_launch_guidance_step(a, (hipStream_t)stream);
+    return ltx_launch_guidance_step(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
+                                                  dt, 0.0f, 0.0f, nullptr, stats_ws, nullptr, 1, 0), (hipStream_t)stream);
 }
 
 extern "C" int ltx_guidance_step_stochastic(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype,
@@ -225,13 +237,8 @@ extern "C" int ltx_guidance_step_stochastic(const void* text, const void* uncond
                                             float sigma, float sigma_next, const float* step_noise,
                                             void* stats_ws, ltx_stream stream) {
     if (!step_noise || !latents) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic: latents and step_noise are required");
-    GuidanceArgs a;
-    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
-    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale;
-    a.sigma = sigma; a.sigma_next = sigma_next; a.step_noise = step_noise;
-    a.stats = reinterpret_cast<double*>(stats_ws);
-    return ltx_launch_guidance_step(a, (hipStream_t)stream);
+    return ltx_launch_guidance_step(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
+                                                  0.0f, sigma, sigma_next, step_noise, stats_ws, nullptr, 1, 0), (hipStream_t)stream);
 }
 
 // ---- held frames (include/ltxhip_cond.h) ----
@@ -240,13 +247,8 @@ extern "C" int ltx_guidance_step_held(const void* text, const void* uncond, cons
                                       float guidance_scale, float guidance_rescale, float stg_scale, float dt,
                                       void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems, ltx_stream stream) {
     if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_held: hold is required");
-    GuidanceArgs a;
-    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
-    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale; a.dt = dt;
-    a.stats = reinterpret_cast<double*>(stats_ws);
-    a.hold = hold; a.num_frames = num_frames; a.frame_elems = frame_elems;
-    return ltx_launch_guidance_step_held(a, (hipStream_t)stream);
+    return ltx_launch_guidance_step_held(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
+                                                       dt, 0.0f, 0.0f, nullptr, stats_ws, hold, num_frames, frame_elems), (hipStream_t)stream);
 }
 
 extern "C" int ltx_guidance_step_stochastic_held(const void* text, const void* uncond, const void* perturbed, ltx_dtype pred_dtype,
@@ -256,14 +258,8 @@ extern "C" int ltx_guidance_step_stochastic_held(const void* text, const void* u
                                                  void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems, ltx_stream stream) {
     if (!step_noise || !latents) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic_held: latents and step_noise are required");
     if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic_held: hold is required");
-    GuidanceArgs a;
-    a.text = text; a.uncond = uncond; a.pert = perturbed; a.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    a.latents = latents; a.noise_out = noise_pred_out; a.B = B; a.n_per_batch = n;
-    a.guidance_scale = guidance_scale; a.guidance_rescale = guidance_rescale; a.stg_scale = stg_scale;
-    a.sigma = sigma; a.sigma_next = sigma_next; a.step_noise = step_noise;
-    a.stats = reinterpret_cast<double*>(stats_ws);
-    a.hold = hold; a.num_frames = num_frames; a.frame_elems = frame_elems;
-    return ltx_launch_guidance_step_held(a, (hipStream_t)stream);
+    return ltx_launch_guidance_step_held(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
+                                                       0.0f, sigma, sigma_next, step_noise, stats_ws, hold, num_frames, frame_elems), (hipStream_t)stream);
 }
 
 // ---- per-step guidance schedules, CFG-star, the two rescale forms (include/ltxhip_guidance.h) ----
@@ -322,11 +318,8 @@ extern "C" int ltx_guidance_step_ex(const void* text, const void* uncond, const 
     if (stg_scale < 0.0f) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_ex: negative stg_scale");
     if (pred_dtype != LTX_F32 && pred_dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_ex: bad dtype");
     GuidanceExArgs a;
-    a.g.text = text; a.g.uncond = uncond; a.g.pert = perturbed; a.g.pred_dtype = pred_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32;
-    a.g.latents = latents; a.g.noise_out = noise_pred_out; a.g.B = B; a.g.n_per_batch = n;
-    a.g.guidance_scale = guidance_scale; a.g.guidance_rescale = guidance_rescale; a.g.stg_scale = stg_scale;
-    if (step_noise) { a.g.sigma = sigma; a.g.sigma_next = sigma_next; a.g.step_noise = step_noise; } else a.g.dt = dt;
-    if (hold) { a.g.hold = hold; a.g.num_frames = num_frames; a.g.frame_elems = frame_elems; }
+    a.g = guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
+                        dt, sigma, sigma_next, step_noise, nullptr, hold, num_frames, frame_elems);
     a.cfg_star = cfg_star; a.rescale_form = rescale_form; a.ws = ws; a.scalars_out = scalars_out;
     return ltx_launch_guidance_step_ex(a, (hipStream_t)stream);
 }
@@ -374,9 +367,9 @@ namespace {
 // Device scratch of the denoise loop, kept per (thread, device) across calls: per-call hipMalloc/hipFree (an implicit
 // device sync each) and the coords rebuild + blocking upload cost ~1 ms per video for nothing.
 struct PipeCache {
-    DevBuf p_text, p_uncond, p_pert, stats, coords, hold, gws;
+    DevBuf stats, coords, hold, gws;
     DevBuf kf_coords, kf_clean, kf_grid;                // a keyframe call: its own coordinates (never the geometry-keyed ones), the placed latents, the stripped grid
-    DevBuf g_lat, g_emb, g_mask, g_pred, g_coords;      // the guidance branches of a step as one forward: inputs / predictions of all branches
+    DevBuf g_lat, g_emb, g_mask, g_pred, g_coords;      // the branch slots of a step (BranchBatch below): inputs of a batched forward / every prediction
     int coords_key[6] = {-1, -1, -1, -1, -1, -1};      // B, F, H, W, frame_rate, ratios packed
 };
 PipeCache& pipe_cache(int device) {
@@ -384,7 +377,6 @@ PipeCache& pipe_cache(int device) {
     return caches[device];
 }
 struct PipeScratch {
-    void *p_text = nullptr, *p_uncond = nullptr, *p_pert = nullptr, *coords = nullptr, *stats = nullptr;   // borrowed from PipeCache
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> step_ev;        // three per denoise step (start, after the forwards, after the update); every
                                             // event is owned exactly once and pushed here the moment it exists
@@ -415,17 +407,6 @@ int ltx_pipeline_schedule(const ltx_pipeline_params* p, int S, std::vector<float
     return ltx_sched_set_timesteps(sig_in.data(), N, mu, 1, 1.0f, p->shift_terminal, p->use_shift_terminal, sig->data(), ts->data());
 }
 
-// A schedule resolved against the call's sigmas (include/ltxhip_guidance.h): what each step's guidance is.
-struct StepGuidance {
-    const ltx_guidance_schedule* sc = nullptr;
-    std::vector<int> entry;                                 // entry_of_step [N]
-    float g(int i) const { return sc->guidance_scale[entry[i]]; }
-    float s(int i) const { return sc->stg_scale[entry[i]]; }
-    float r(int i) const { return sc->rescale[entry[i]]; }
-    const int* skip(int i) const { return sc->skip_blocks + sc->skip_offsets[entry[i]]; }      // (never read when n_skip is 0)
-    int n_skip(int i) const { return sc->skip_offsets[entry[i] + 1] - sc->skip_offsets[entry[i]]; }
-};
-
 // A conditioned run (include/ltxhip_cond.h, ltxhip_keyframes.h): the sequence is G groups of h * w tokens per batch row, E extra ones
 // in front of the F' grid frames.  ltx_pipeline_call_cond fills it with the grid alone and one hold row; a keyframe call with its layout.
 struct CondRun {
@@ -439,30 +420,72 @@ struct CondRun {
     std::vector<int> hard;                   // ... and the groups they cover
 };
 
-// cr: null - ltx_pipeline_call
-// plan: null - the scalars of `p` on every step; else the branches, scales and perturbed blocks are the step's own (ltx_pipeline_call_sched)
-static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const StepGuidance* plan,
-                        float* latents, const float* prompt_embeds, const float* prompt_mask,
-                        const float* neg_embeds, const float* neg_mask, const float* decode_noise,
-                        int B, int K, float* out_video, ltx_stream stream) {
-    if (!dit || !p || !latents || !prompt_embeds || !prompt_mask) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: null argument");
-    if (!p->output_latent && (!vae || !out_video)) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: decode requested without vae/out_video");
+// The latent geometry of a call (t2v_pipeline.rs:743-745): the VAE's compression ratios, (8, 32) without one.  A ratio below 1 leaves
+// its extents 0 (the callers that take a ratio from outside refuse it).
+struct LatentGeom { int ts_ratio = 8, sp_ratio = 32, F = 0, H = 0, W = 0; };
+static int latent_geom(ltx_vae* vae, const ltx_pipeline_params* p, LatentGeom* g) {
+    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); g->ts_ratio = vc.temporal_compression_ratio; g->sp_ratio = vc.spatial_compression_ratio; }
+    if (g->ts_ratio >= 1) g->F = (p->num_frames - 1) / g->ts_ratio + 1;
+    if (g->sp_ratio >= 1) { g->H = p->height / g->sp_ratio; g->W = p->width / g->sp_ratio; }
+    return LTX_OK;
+}
+static bool any_held(const unsigned char* hold, int B, int F) {
+    for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) if (hold[j]) return true;
+    return false;
+}
+
+// what every pipeline entry hands through to the loop
+struct PipeIO { float* latents; const float *prompt_embeds, *prompt_mask, *neg_embeds, *neg_mask, *decode_noise; int B, K; float* out_video; ltx_stream stream; };
+
+// The branch slots of host/step_plan.h on the device, B rows each: slot 0 negative prompt, slot 1 prompt, slot 2 prompt (perturbed).
+// Every prediction lies in its slot of g_pred, whichever way its forward ran.  A step whose branches run as ONE forward (:860-940: up to
+// three B-row forwards on the same latents) reads the slots [slot0, slot0 + nbr) of g_lat / g_emb / g_mask / g_coords: branch rows are
+// independent, every plan of a GEMM shape returns the same bits, and a row that skips a layer keeps its row partials (dit.hip) - so each
+// branch's prediction is, bit for bit, the separate forward's WHERE B * S and nbr * B * S rows take the same kernels and K partition
+// (above 512 rows per branch: C2 / C3 / C5; at a few hundred tokens the split-K factor, the one-row-per-block norms and the deferred ff2
+// depend on the row count and the two forms agree to rounding only: tests/test_gpu_c3.py), at 2.5 instead of 3 rounds of the chip per
+// attention launch and fewer one-round grids (one C3 step 61.8 -> 58.1 ms).  guidance_batch=0: the reference's three calls.
+// The DiT's text context is keyed by (embeddings, mask, rows): one key for an unscheduled call, at most the four it keeps under a
+// schedule (DESIGN.md enumerates them).  Every pointer is fixed in front of the loop (rope_key compares the coordinates' in the caching scope).
+struct BranchBatch {
+    PipeCache& pc; int B; int64_t n; size_t emb_n, mask_n, coords_n;         // elements of one slot
+    const float* src_emb[3]; const float* src_mask[3];                       // the caller's tensors of each slot
+    float* pred(int slot) const { return pc.g_pred.as<float>() + (size_t)slot * B * n; }
+    const float* emb(int slot) const { return pc.g_emb.as<float>() + (size_t)slot * emb_n; }
+    const float* mask(int slot) const { return pc.g_mask.as<float>() + (size_t)slot * mask_n; }
+    const float* coords(int slot) const { return pc.g_coords.as<float>() + (size_t)slot * coords_n; }
+    // sizes the buffers; with a batched step in the plan, the inputs of the slots some step runs (coords: DEVICE [B, S, 3])
+    int stage(const StepPlan& plan, const float* coords_dev, hipStream_t s) {
+        LTX_TRY(pc.g_pred.ensure((size_t)3 * B * n * sizeof(float)));
+        if (!plan.any_batched) return LTX_OK;
+        LTX_TRY(pc.g_lat.ensure((size_t)3 * B * n * sizeof(float))); LTX_TRY(pc.g_emb.ensure(3 * emb_n * sizeof(float)));
+        LTX_TRY(pc.g_mask.ensure(3 * mask_n * sizeof(float))); LTX_TRY(pc.g_coords.ensure(3 * coords_n * sizeof(float)));
+        const bool present[3] = {plan.any_cfg, true, plan.any_stg};
+        for (int k = 0; k < 3; ++k) {
+            if (!present[k]) continue;
+            HIP_TRY(hipMemcpyAsync(pc.g_emb.as<float>() + (size_t)k * emb_n, src_emb[k], emb_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(pc.g_mask.as<float>() + (size_t)k * mask_n, src_mask[k], mask_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(pc.g_coords.as<float>() + (size_t)k * coords_n, coords_dev, coords_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        return LTX_OK;
+    }
+};
+
+// cr: null - no conditioning; plan: the branches, scales and perturbed blocks of every step (host/step_plan.h)
+static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const StepPlan& plan, const PipeIO& io) {
+    float* const latents = io.latents; const int B = io.B, K = io.K;
+    if (!dit || !p || !latents || !io.prompt_embeds || !io.prompt_mask) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: null argument");
+    if (!p->output_latent && (!vae || !io.out_video)) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: decode requested without vae/out_video");
     // check_inputs (:313-365)
     if (p->height % 32 != 0 || p->width % 32 != 0) LTX_FAIL(LTX_ERR_ARG, "`height` and `width` must be divisible by 32");
     if (p->num_inference_steps < 1) LTX_FAIL(LTX_ERR_ARG, "num_inference_steps must be >= 1");
-    // :304-310; under a schedule: whether ANY step has the branch (the steps decide for themselves below)
-    bool do_cfg = p->guidance_scale > 1.0f, do_stg = p->stg_scale > 0.0f;
-    if (plan) {
-        do_cfg = do_stg = false;
-        for (int i = 0; i < p->num_inference_steps; ++i) { do_cfg = do_cfg || plan->g(i) > 1.0f; do_stg = do_stg || plan->s(i) > 0.0f; }
-    }
-    if (do_cfg && (!neg_embeds || !neg_mask)) LTX_FAIL(LTX_ERR_ARG, "classifier-free guidance needs negative embeddings and mask");
+    // :304-310: whether ANY step has the branch (the steps decide for themselves below)
+    if (plan.any_cfg && (!io.neg_embeds || !io.neg_mask)) LTX_FAIL(LTX_ERR_ARG, "classifier-free guidance needs negative embeddings and mask");
     if (p->stochastic_sampling && !p->step_noise) LTX_FAIL(LTX_ERR_ARG, "stochastic_sampling needs step_noise [steps,B,S*C]");
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)io.stream;
     ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
-    int ts_ratio = 8, sp_ratio = 32;
-    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; sp_ratio = vc.spatial_compression_ratio; }
-    const int F = (p->num_frames - 1) / ts_ratio + 1, H = p->height / sp_ratio, W = p->width / sp_ratio;   // :743-745
+    LatentGeom lg; LTX_TRY(latent_geom(vae, p, &lg));
+    const int F = lg.F, H = lg.H, W = lg.W;
     const int G = cr ? cr->G : F, E = cr ? cr->E : 0;                      // groups of the sequence the model sees; the grid is its last F
     const int S = G * H * W, C = dc.in_channels, L = dc.num_layers;
     const int64_t n = (int64_t)S * C;
@@ -470,12 +493,8 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
                (cr->hold_rows != 1 && cr->hold_rows != p->num_inference_steps) || (E > 0 && !cr->coords)))
         LTX_FAIL(LTX_ERR_ARG, "pipeline: inconsistent conditioning description");
 
-    // skip blocks: permanent iff STG is off (:691-697)
-    if (plan) LTX_TRY(ltx_dit_set_skip_blocks(dit, nullptr, 0));      // a schedule never skips a block for good
-    else if (p->skip_block_list) {
-        if (!do_stg) LTX_TRY(ltx_dit_set_skip_blocks(dit, p->skip_block_list, p->n_skip_blocks));
-        else LTX_TRY(ltx_dit_set_skip_blocks(dit, nullptr, 0));
-    }
+    // skip blocks: permanent iff STG is off (:691-697); a schedule never skips a block for good
+    if (plan.set_skip) LTX_TRY(ltx_dit_set_skip_blocks(dit, plan.perm_skip, plan.n_perm_skip));
     // sigmas / mu / timesteps (:750-791)
     const int N = p->num_inference_steps;
     std::vector<float> sig; std::vector<int64_t> ts;
@@ -484,96 +503,37 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     PipeScratch sc;
     int cur_dev = 0; HIP_TRY(hipGetDevice(&cur_dev));
     PipeCache& pc = pipe_cache(cur_dev);
-    const size_t pred_bytes = (size_t)B * n * sizeof(float);
-    LTX_TRY(pc.p_text.ensure(pred_bytes)); sc.p_text = pc.p_text.p;
-    if (do_cfg) { LTX_TRY(pc.p_uncond.ensure(pred_bytes)); sc.p_uncond = pc.p_uncond.p; }
-    if (do_stg) { LTX_TRY(pc.p_pert.ensure(pred_bytes)); sc.p_pert = pc.p_pert.p; }
-    LTX_TRY(pc.stats.ensure(64 * B)); sc.stats = pc.stats.p;
-    if (plan) LTX_TRY(pc.gws.ensure(ltx_guidance_ex_ws_bytes(B, n)));
+    const bool classic = plan.mix == STEP_MIX_CLASSIC;
+    LTX_TRY(pc.stats.ensure(64 * B));
+    if (!classic) LTX_TRY(pc.gws.ensure(ltx_guidance_ex_ws_bytes(B, n)));
     if (cr) {                                        // device copy for the update kernels (the model's per-group timesteps are built on the host)
         LTX_TRY(pc.hold.ensure(cr->hold.size()));
         HIP_TRY(hipMemcpyAsync(pc.hold.p, cr->hold.data(), cr->hold.size(), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));            // (once per call, in front of the loop)
     }
+    auto upload_coords = [&](DevBuf& buf, const float* row) -> int {      // one batch row's HOST [S, 3] -> DEVICE [B, S, 3]
+        std::vector<float> all((size_t)B * S * 3);
+        for (int b = 0; b < B; ++b) std::memcpy(all.data() + (size_t)b * S * 3, row, sizeof(float) * S * 3);
+        LTX_TRY(buf.ensure(all.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(buf.p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return LTX_OK;
+    };
+    const int key[6] = {B, F, H, W, p->frame_rate, lg.ts_ratio * 1000 + lg.sp_ratio};
     if (cr && cr->coords) {
         // a layout's own coordinates: a buffer of their own, written on every call - the geometry-keyed one below is neither read nor
         // re-keyed, and the pointer is stable for the whole call (the DiT's rope_key compares it inside the caching scope)
-        std::vector<float> all((size_t)B * S * 3);
-        for (int b = 0; b < B; ++b) std::memcpy(all.data() + (size_t)b * S * 3, cr->coords, sizeof(float) * S * 3);
-        LTX_TRY(pc.kf_coords.ensure(all.size() * sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(pc.kf_coords.p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        sc.coords = pc.kf_coords.p;
-    } else {
-        // video_coords [B,S,3] (:798-847): rebuilt only when the geometry changes
-        const int key[6] = {B, F, H, W, p->frame_rate, ts_ratio * 1000 + sp_ratio};
-        LTX_TRY(pc.coords.ensure((size_t)B * S * 3 * sizeof(float)));
-        if (std::memcmp(key, pc.coords_key, sizeof(key)) != 0) {
-            std::vector<float> vc((size_t)S * 3), all((size_t)B * S * 3);
-            LTX_TRY(ltx_build_video_coords(F, H, W, p->frame_rate, ts_ratio, sp_ratio, vc.data()));
-            for (int b = 0; b < B; ++b) std::memcpy(all.data() + (size_t)b * S * 3, vc.data(), sizeof(float) * S * 3);
-            HIP_TRY(hipMemcpyAsync(pc.coords.p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            std::memcpy(pc.coords_key, key, sizeof(key));
-        }
-        sc.coords = pc.coords.p;
+        LTX_TRY(upload_coords(pc.kf_coords, cr->coords));
+    } else if (std::memcmp(key, pc.coords_key, sizeof(key)) != 0) {      // video_coords [B,S,3] (:798-847): rebuilt only when the geometry changes
+        std::vector<float> vc((size_t)S * 3);
+        LTX_TRY(ltx_build_video_coords(F, H, W, p->frame_rate, lg.ts_ratio, lg.sp_ratio, vc.data()));
+        LTX_TRY(upload_coords(pc.coords, vc.data()));
+        std::memcpy(pc.coords_key, key, sizeof(key));
     }
-    // The guidance branches of a step (:860-940: up to three B-row forwards on the same latents - negative prompt, prompt, prompt with
-    // the STG blocks skipped) as ONE forward of nbr * B rows where that fits the DiT's 8-row pass: branch rows are independent, every
-    // plan of a GEMM shape returns the same bits, and a row that skips a layer keeps its row partials (dit.hip) - so each branch's
-    // prediction is, bit for bit, the separate forward's WHERE B * S and nbr * B * S rows take the same kernels and K partition
-    // (above 512 rows per branch: C2 / C3 / C5; at a few hundred tokens the split-K factor, the one-row-per-block norms and the
-    // deferred ff2 depend on the row count and the two forms agree to rounding only: tests/test_gpu_c3.py), at 2.5 instead of 3
-    // rounds of the chip per attention launch and fewer one-round grids (one C3 step 61.8 -> 58.1 ms).  guidance_batch=0: the
-    // reference's three calls.
-    const int nbr = 1 + (do_cfg ? 1 : 0) + (do_stg ? 1 : 0);
-    const bool gbatch = !plan && nbr > 1 && nbr * B <= 8 && ltx_opt().guidance_batch;      // (a schedule: per step, below)
-    const int Dt = dc.caption_channels;
-    std::vector<float> g_slm;
-    if (gbatch) {
-        const int GB = nbr * B;
-        LTX_TRY(pc.g_lat.ensure((size_t)GB * n * sizeof(float))); LTX_TRY(pc.g_pred.ensure((size_t)GB * n * sizeof(float)));
-        LTX_TRY(pc.g_emb.ensure((size_t)GB * K * Dt * sizeof(float))); LTX_TRY(pc.g_mask.ensure((size_t)GB * K * sizeof(float)));
-        LTX_TRY(pc.g_coords.ensure((size_t)GB * S * 3 * sizeof(float)));
-        int r = 0;                                   // branch order: uncond, text, perturbed (the reference's call order)
-        auto put = [&](const float* e, const float* mk) -> int {
-            HIP_TRY(hipMemcpyAsync(pc.g_emb.as<float>() + (size_t)r * B * K * Dt, e, (size_t)B * K * Dt * sizeof(float), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(pc.g_mask.as<float>() + (size_t)r * B * K, mk, (size_t)B * K * sizeof(float), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(pc.g_coords.as<float>() + (size_t)r * B * S * 3, sc.coords, (size_t)B * S * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-            ++r; return LTX_OK;
-        };
-        if (do_cfg) { sc.p_uncond = pc.g_pred.as<float>() + (size_t)r * B * n; LTX_TRY(put(neg_embeds, neg_mask)); }
-        sc.p_text = pc.g_pred.as<float>() + (size_t)r * B * n; LTX_TRY(put(prompt_embeds, prompt_mask));
-        if (do_stg) {
-            sc.p_pert = pc.g_pred.as<float>() + (size_t)r * B * n;
-            g_slm.assign((size_t)L * GB, 0.0f);
-            for (int i = 0; i < p->n_skip_blocks; ++i) { const int li = p->skip_block_list[i]; if (li >= 0 && li < L) for (int b = 0; b < B; ++b) g_slm[(size_t)li * GB + r * B + b] = 1.0f; }
-            LTX_TRY(put(prompt_embeds, prompt_mask));
-        }
-    }
-    // Under a schedule the branches differ from step to step.  The inputs of all three lie in the order above, B rows each - slot 0
-    // negative prompt, slot 1 prompt, slot 2 prompt again - so every composition is a contiguous run of slots: uncond + text slots
-    // 0-1, text + perturbed slots 1-2, all three 0-2 (text alone is no batch: the caller's own tensors).  The DiT's text context is
-    // keyed by (embeddings, mask, rows): these four are exactly the four entries it keeps (text_context, dit.hip), each computed once
-    // per call.  Whether a step's branches fit the 8-row pass is judged per step.
-    bool sched_gb = false;
-    if (plan && ltx_opt().guidance_batch)
-        for (int i = 0; i < N; ++i) { const int nb = 1 + (plan->g(i) > 1.0f ? 1 : 0) + (plan->s(i) > 0.0f ? 1 : 0); sched_gb = sched_gb || (nb > 1 && nb * B <= 8); }
-    if (sched_gb) {
-        const int GB = 3 * B;
-        LTX_TRY(pc.g_lat.ensure((size_t)GB * n * sizeof(float))); LTX_TRY(pc.g_pred.ensure((size_t)GB * n * sizeof(float)));
-        LTX_TRY(pc.g_emb.ensure((size_t)GB * K * Dt * sizeof(float))); LTX_TRY(pc.g_mask.ensure((size_t)GB * K * sizeof(float)));
-        LTX_TRY(pc.g_coords.ensure((size_t)GB * S * 3 * sizeof(float)));
-        auto put = [&](int slot, const float* e, const float* mk) -> int {
-            HIP_TRY(hipMemcpyAsync(pc.g_emb.as<float>() + (size_t)slot * B * K * Dt, e, (size_t)B * K * Dt * sizeof(float), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(pc.g_mask.as<float>() + (size_t)slot * B * K, mk, (size_t)B * K * sizeof(float), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(pc.g_coords.as<float>() + (size_t)slot * B * S * 3, sc.coords, (size_t)B * S * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-            return LTX_OK;
-        };
-        if (do_cfg) LTX_TRY(put(0, neg_embeds, neg_mask));
-        LTX_TRY(put(1, prompt_embeds, prompt_mask));
-        if (do_stg) LTX_TRY(put(2, prompt_embeds, prompt_mask));
-    }
+    const float* coords = (cr && cr->coords ? pc.kf_coords : pc.coords).as<float>();
+    BranchBatch bb{pc, B, n, (size_t)B * K * dc.caption_channels, (size_t)B * K, (size_t)B * S * 3,
+                   {io.neg_embeds, io.prompt_embeds, io.prompt_embeds}, {io.neg_mask, io.prompt_mask, io.prompt_mask}};
+    LTX_TRY(bb.stage(plan, coords, s));
     for (auto& e : sc.ev) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipEventRecord(sc.ev[0], s));
     const int64_t group_elems = (int64_t)H * W * C;
@@ -583,18 +543,13 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
         LTX_TRY(pc.kf_clean.ensure((size_t)B * n * sizeof(float)));
         HIP_TRY(hipMemcpyAsync(pc.kf_clean.p, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    std::vector<float> stg_mask;
-    if (do_stg && !plan) {                           // :911-923
-        stg_mask.assign((size_t)L * B, 0.0f);
-        for (int i = 0; i < p->n_skip_blocks; ++i) { int li = p->skip_block_list[i]; if (li >= 0 && li < L) for (int b = 0; b < B; ++b) stg_mask[(size_t)li * B + b] = 1.0f; }
-    }
-    const float* coords = reinterpret_cast<const float*>(sc.coords);
     struct CtxScope { ltx_dit* d; ~CtxScope() { (void)ltx_dit_context_cache(d, 0); } } ctx_scope{dit};
     LTX_TRY(ltx_dit_context_cache(dit, 1));     // embeddings/masks are step-invariant inside one call
     // denoising loop (:860-994)
     const bool hooked = p->interrupt != nullptr || p->on_step != nullptr;
     bool stopped = false; int steps_run = 0;
     std::vector<float> tframes;                             // held frames: the step's timesteps per (row of the forward, latent frame)
+    std::vector<float> slm;                                 // the step's skip mask [L, rows of the forward] (:911-923)
     std::vector<hipEvent_t> done_ev;                        // e2 of every executed step (owned by sc.step_ev)
     for (int i = 0; i < N; ++i) {
         // interrupt / per-step hook (:861-865).  The loop only ENQUEUES work: the host stays at most one step ahead of the device
@@ -609,15 +564,10 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
         hipEvent_t e0, e1, e2;
         LTX_TRY(sc.new_event(&e0)); LTX_TRY(sc.new_event(&e1)); LTX_TRY(sc.new_event(&e2));
         HIP_TRY(hipEventRecord(e0, s));
-        // held frames: the model sees timestep 0 for their tokens and t_i for the rest, in every guidance branch
-        // the branches of THIS step (a schedule: uncond iff g > 1, perturbed iff s > 0)
-        bool cfg_i = do_cfg, stg_i = do_stg, gb_i = gbatch; int nbr_i = nbr;
-        if (plan) {
-            cfg_i = plan->g(i) > 1.0f; stg_i = plan->s(i) > 0.0f; nbr_i = 1 + (cfg_i ? 1 : 0) + (stg_i ? 1 : 0);
-            gb_i = sched_gb && nbr_i > 1 && nbr_i * B <= 8;
-        }
-        if (cr) {
-            tframes.resize((size_t)(gb_i ? nbr_i : 1) * B * G);
+        const StepEntry& st = plan.steps[(size_t)i];        // the branches of THIS step (uncond iff g > 1, perturbed iff s > 0)
+        const int frows = st.batched ? st.rows : B;         // rows of one forward of this step
+        if (cr) {                                    // held frames: the model sees timestep 0 for their tokens and t_i for the rest, in every guidance branch
+            tframes.resize((size_t)frows * G);
             for (size_t r = 0; r < tframes.size() / ((size_t)B * G); ++r)
                 for (size_t j = 0; j < (size_t)B * G; ++j) tframes[r * B * G + j] = std::fmin((float)ts[i], cr->tcap[j]);
         }
@@ -626,57 +576,27 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             LTX_TRY(ltx_launch_cond_noise(latents, pc.kf_clean.as<float>(), cr->cond_noise + (size_t)i * B * n, cr->hard.data(), (int)cr->hard.size(), B, G, group_elems, kn, s));
         }
         const unsigned char* hold_i = cr ? pc.hold.as<unsigned char>() + (cr->hold_rows > 1 ? (size_t)i * B * G : 0) : nullptr;
-        auto forward = [&](const void* x, const void* emb, const float* mk, int rows, const float* vc, const float* slm, void* pred) -> int {
-            if (cr) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, G, H, W, nullptr, vc, slm, LTX_F32, pred, s);
-            return ltx_dit_forward(dit, x, emb, tvals, mk, rows, S, K, F, H, W, nullptr, vc, slm, LTX_F32, pred, s);
+        auto forward = [&](const void* x, const void* emb, const float* mk, int rows, const float* vc, const float* skip, void* pred) -> int {
+            if (cr) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, G, H, W, nullptr, vc, skip, LTX_F32, pred, s);
+            return ltx_dit_forward(dit, x, emb, tvals, mk, rows, S, K, F, H, W, nullptr, vc, skip, LTX_F32, pred, s);
         };
-        void *pt = sc.p_text, *pu = sc.p_uncond, *pp = sc.p_pert;
-        auto skip_rows = [&](std::vector<float>& m, int rows, int row0) {      // ones on the step's block list for rows [row0, row0 + B) of [L, rows]
-            m.assign((size_t)L * rows, 0.0f);
-            for (int k = 0; k < plan->n_skip(i); ++k) for (int b = 0; b < B; ++b) m[(size_t)plan->skip(i)[k] * rows + row0 + b] = 1.0f;
-        };
-        if (plan && gb_i) {
-            const int r0 = cfg_i ? 0 : 1, rows = nbr_i * B;                      // the step's slots: [r0, r0 + nbr_i)
-            for (int r = 0; r < nbr_i; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (stg_i) skip_rows(g_slm, rows, (nbr_i - 1) * B);
-            LTX_TRY(forward(pc.g_lat.p, pc.g_emb.as<float>() + (size_t)r0 * B * K * Dt, pc.g_mask.as<float>() + (size_t)r0 * B * K, rows,
-                            pc.g_coords.as<float>() + (size_t)r0 * B * S * 3, stg_i ? g_slm.data() : nullptr, pc.g_pred.as<float>() + (size_t)r0 * B * n));
-            pu = pc.g_pred.as<float>(); pt = pc.g_pred.as<float>() + (size_t)B * n; pp = pc.g_pred.as<float>() + (size_t)2 * B * n;
-        } else if (plan) {
-            if (cfg_i) LTX_TRY(forward(latents, neg_embeds, neg_mask, B, coords, nullptr, pu));
-            LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, nullptr, pt));
-            if (stg_i) { skip_rows(stg_mask, B, 0); LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, stg_mask.data(), pp)); }
-        } else if (gbatch) {
-            for (int r = 0; r < nbr; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            LTX_TRY(forward(pc.g_lat.p, pc.g_emb.p, pc.g_mask.as<float>(), nbr * B, pc.g_coords.as<float>(), do_stg ? g_slm.data() : nullptr, pc.g_pred.p));
+        if (st.stg) step_skip_rows(L, frows, st.batched ? (st.nbr - 1) * B : 0, B, st.guide.skip, st.guide.n_skip, &slm);      // (the perturbed branch: the last rows)
+        if (st.batched) {
+            for (int r = 0; r < st.nbr; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            LTX_TRY(forward(pc.g_lat.p, bb.emb(st.slot0), bb.mask(st.slot0), st.rows, bb.coords(st.slot0), st.stg ? slm.data() : nullptr, bb.pred(st.slot0)));
         } else {
-            if (do_cfg) LTX_TRY(forward(latents, neg_embeds, neg_mask, B, coords, nullptr, sc.p_uncond));
-            LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, nullptr, sc.p_text));
-            if (do_stg) LTX_TRY(forward(latents, prompt_embeds, prompt_mask, B, coords, stg_mask.data(), sc.p_pert));
+            for (int k = st.slot0; k < st.slot0 + st.nbr; ++k) LTX_TRY(forward(latents, bb.src_emb[k], bb.src_mask[k], B, coords, k == 2 ? slm.data() : nullptr, bb.pred(k)));
         }
         HIP_TRY(hipEventRecord(e1, s));
-        // guidance mix (:941-962) + scheduler.step (:987; scheduler.rs:544-581): dt = sigma_next - sigma
-        const float dts = sig[i + 1] - sig[i];
-        if (plan) {                                  // the mix of include/ltxhip_guidance.h on the branches that ran
-            GuidanceExArgs ge;
-            GuidanceArgs& ga = ge.g;
-            ga.text = pt; ga.uncond = cfg_i ? pu : nullptr; ga.pert = stg_i ? pp : nullptr; ga.pred_dtype = LTX_DT_F32;
-            ga.latents = latents; ga.B = B; ga.n_per_batch = n;
-            ga.guidance_scale = plan->g(i); ga.guidance_rescale = plan->r(i); ga.stg_scale = plan->s(i);
-            if (p->stochastic_sampling) { ga.sigma = sig[i]; ga.sigma_next = sig[i + 1]; ga.step_noise = p->step_noise + (size_t)i * B * n; }
-            else ga.dt = dts;
-            if (cr) { ga.hold = hold_i; ga.num_frames = G; ga.frame_elems = group_elems; }
-            ge.cfg_star = plan->sc->cfg_star; ge.rescale_form = plan->sc->rescale_form; ge.ws = pc.gws.p;
+        // guidance mix (:941-962) on the branches that ran + scheduler.step (:987; scheduler.rs:544-581): dt = sigma_next - sigma; held groups keep their bits
+        GuidanceExArgs ge;
+        ge.g = guidance_args(bb.pred(1), st.cfg ? bb.pred(0) : nullptr, st.stg ? bb.pred(2) : nullptr, LTX_F32, latents, nullptr, B, n,
+                             st.guide.g, st.guide.r, st.guide.s, sig[i + 1] - sig[i], sig[i], sig[i + 1],
+                             p->stochastic_sampling ? p->step_noise + (size_t)i * B * n : nullptr, classic ? pc.stats.p : nullptr, hold_i, G, group_elems);
+        if (classic) LTX_TRY(ltx_launch_guidance_step(ge.g, s));
+        else {                                       // the mix of include/ltxhip_guidance.h
+            ge.cfg_star = plan.cfg_star; ge.rescale_form = plan.rescale_form; ge.ws = pc.gws.p;
             LTX_TRY(ltx_launch_guidance_step_ex(ge, s));
-        } else {
-            GuidanceArgs ga;
-            ga.text = sc.p_text; ga.uncond = do_cfg ? sc.p_uncond : nullptr; ga.pert = do_stg ? sc.p_pert : nullptr; ga.pred_dtype = LTX_DT_F32;
-            ga.latents = latents; ga.B = B; ga.n_per_batch = n; ga.stats = reinterpret_cast<double*>(sc.stats);
-            ga.guidance_scale = p->guidance_scale; ga.guidance_rescale = p->guidance_rescale; ga.stg_scale = p->stg_scale;
-            if (p->stochastic_sampling) { ga.sigma = sig[i]; ga.sigma_next = sig[i + 1]; ga.step_noise = p->step_noise + (size_t)i * B * n; }
-            else ga.dt = dts;
-            if (cr) { ga.hold = hold_i; ga.num_frames = G; ga.frame_elems = group_elems; }      // held groups keep their bits
-            LTX_TRY(ltx_launch_guidance_step(ga, s));
         }
         HIP_TRY(hipEventRecord(e2, s));
         done_ev.push_back(e2);
@@ -697,7 +617,7 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             HIP_TRY(hipMemcpy2DAsync(pc.kf_grid.p, row, grid, (size_t)n * sizeof(float), row, (size_t)B, hipMemcpyDeviceToDevice, s));
             grid = pc.kf_grid.as<float>();
         }
-        LTX_TRY(ltx_vae_decode_tokens(vae, grid, tc ? decode_noise : nullptr, nsc, tc ? tdec : nullptr, B, F, H, W, p->tiling, p->postprocess, out_video, s));
+        LTX_TRY(ltx_vae_decode_tokens(vae, grid, tc ? io.decode_noise : nullptr, nsc, tc ? tdec : nullptr, B, F, H, W, p->tiling, p->postprocess, io.out_video, s));
     }
     HIP_TRY(hipEventRecord(sc.ev[2], s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -712,11 +632,22 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     return LTX_OK;
 }
 
+// the unscheduled call: the constant plan of the scalars of `p`
+static int pipeline_run_params(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const PipeIO& io) {
+    StepPlan plan;
+    if (p) {
+        StepGuide g; g.g = p->guidance_scale; g.s = p->stg_scale; g.r = p->guidance_rescale;
+        g.skip = p->skip_block_list; g.n_skip = p->skip_block_list ? p->n_skip_blocks : 0;
+        step_plan_constant(p->num_inference_steps, io.B, g, ltx_opt().guidance_batch != 0, &plan);
+    }
+    return pipeline_run(dit, vae, p, cr, plan, io);
+}
+
 extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p,
                                  float* latents, const float* prompt_embeds, const float* prompt_mask,
                                  const float* neg_embeds, const float* neg_mask, const float* decode_noise,
                                  int B, int K, float* out_video, ltx_stream stream) {
-    return pipeline_run(dit, vae, p, nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return pipeline_run_params(dit, vae, p, nullptr, {latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream});
 }
 
 // the held frames of include/ltxhip_cond.h as a conditioned run: the grid alone, one hold row, timestep 0 on a held frame
@@ -733,43 +664,32 @@ extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipe
                                       int B, int K, float* out_video, ltx_stream stream) {
     if (!cond || !cond->hold) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cond: conditioning with a hold mask is required");
     if (!p || B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cond: null argument");
-    int ts_ratio = 8;
-    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; }
-    const int F = (p->num_frames - 1) / ts_ratio + 1;
-    bool any = false;
-    for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0); ++j) any = any || cond->hold[j] != 0;
+    LatentGeom lg; LTX_TRY(latent_geom(vae, p, &lg));
+    const bool any = any_held(cond->hold, B, lg.F);
     CondRun cr;
-    if (any) cond_run_from_hold(cond->hold, B, F, &cr);
+    if (any) cond_run_from_hold(cond->hold, B, lg.F, &cr);
     // nothing held: ltx_pipeline_call itself
-    return pipeline_run(dit, vae, p, any ? &cr : nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    return pipeline_run_params(dit, vae, p, any ? &cr : nullptr, {latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream});
 }
 
 // ---- the pipeline calls under a guidance schedule (include/ltxhip_guidance.h) ----
 // cr: the conditioned run or null; sig: the call's sigmas (ltx_pipeline_schedule at the grid's tokens)
 static int pipeline_run_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched, const CondRun* cr,
-                              const std::vector<float>& sig, float* latents, const float* prompt_embeds, const float* prompt_mask,
-                              const float* neg_embeds, const float* neg_mask, const float* decode_noise,
-                              int B, int K, float* out_video, ltx_stream stream) {
+                              const std::vector<float>& sig, const PipeIO& io) {
     const int N = p->num_inference_steps;
-    StepGuidance plan; plan.sc = sched; plan.entry.assign(N, 0);
-    LTX_TRY(ltx_guidance_schedule_resolve(sched, sig.data(), N, plan.entry.data()));
-    // The same values on every step, no CFG-star, the reference's rescale: the unscheduled call on those values, its kernels and bits.
-    // (An entry with s == 0 perturbs nothing and skips nothing: its list is not handed on, and the handle's own list is cleared.)
-    bool constant = !sched->cfg_star && sched->rescale_form == LTX_RESCALE_CFG;
-    for (int i = 1; i < N && constant; ++i) {
-        constant = plan.g(i) == plan.g(0) && plan.s(i) == plan.s(0) && plan.r(i) == plan.r(0);
-        if (constant && plan.s(0) > 0.0f && plan.entry[i] != plan.entry[0])
-            constant = plan.n_skip(i) == plan.n_skip(0) && (plan.n_skip(0) == 0 || !std::memcmp(plan.skip(i), plan.skip(0), sizeof(int) * plan.n_skip(0)));
+    std::vector<int> entry((size_t)N, 0);
+    LTX_TRY(ltx_guidance_schedule_resolve(sched, sig.data(), N, entry.data()));
+    std::vector<StepGuide> guides((size_t)N);
+    for (int i = 0; i < N; ++i) {
+        const int j = entry[(size_t)i];
+        StepGuide& g = guides[(size_t)i];
+        g.g = sched->guidance_scale[j]; g.s = sched->stg_scale[j]; g.r = sched->rescale[j];
+        g.n_skip = sched->skip_offsets[j + 1] - sched->skip_offsets[j];
+        g.skip = g.n_skip > 0 ? sched->skip_blocks + sched->skip_offsets[j] : nullptr;
     }
-    if (constant) {
-        static const int none = 0;
-        ltx_pipeline_params q = *p;
-        q.guidance_scale = plan.g(0); q.stg_scale = plan.s(0); q.guidance_rescale = plan.r(0);
-        const bool stg = plan.s(0) > 0.0f && plan.n_skip(0) > 0;
-        q.skip_block_list = stg ? plan.skip(0) : &none; q.n_skip_blocks = stg ? plan.n_skip(0) : 0;
-        return pipeline_run(dit, vae, &q, cr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
-    }
-    return pipeline_run(dit, vae, p, cr, &plan, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    StepPlan plan;
+    step_plan_scheduled(guides.data(), N, io.B, sched->cfg_star, sched->rescale_form, ltx_opt().guidance_batch != 0, &plan);
+    return pipeline_run(dit, vae, p, cr, plan, io);
 }
 
 extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched,
@@ -781,16 +701,14 @@ extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pip
     ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
     LTX_TRY(guidance_schedule_check(sched, dc.num_layers));
     // the sigmas the denoise loop will run (the same geometry rule and the same builder)
-    int ts_ratio = 8, sp_ratio = 32;
-    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; sp_ratio = vc.spatial_compression_ratio; }
-    if (ts_ratio < 1 || sp_ratio < 1 || p->num_frames < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_sched: bad geometry");
-    const int F = (p->num_frames - 1) / ts_ratio + 1, S = F * (p->height / sp_ratio) * (p->width / sp_ratio);
+    LatentGeom lg; LTX_TRY(latent_geom(vae, p, &lg));
+    if (lg.ts_ratio < 1 || lg.sp_ratio < 1 || p->num_frames < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_sched: bad geometry");
     std::vector<float> sig; std::vector<int64_t> ts;
-    LTX_TRY(ltx_pipeline_schedule(p, S, &sig, &ts));
-    CondRun cr; bool any = false;
-    if (cond) for (size_t j = 0; j < (size_t)B * (F > 0 ? F : 0) && !any; ++j) any = cond->hold[j] != 0;
-    if (any) cond_run_from_hold(cond->hold, B, F, &cr);
-    return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    LTX_TRY(ltx_pipeline_schedule(p, lg.F * lg.H * lg.W, &sig, &ts));
+    const bool any = cond && any_held(cond->hold, B, lg.F);
+    CondRun cr;
+    if (any) cond_run_from_hold(cond->hold, B, lg.F, &cr);
+    return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, {latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream});
 }
 
 // ---- keyframe conditioning (include/ltxhip_keyframes.h): the layout is host/cond_plan.h's, these entries hand it on ----
@@ -872,10 +790,9 @@ extern "C" int ltx_pipeline_call_keyframes(ltx_dit* dit, ltx_vae* vae, const ltx
     if (image_cond_noise_scale > 0.0f && !cond_noise) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_keyframes: image_cond_noise_scale " + std::to_string(image_cond_noise_scale) + " needs cond_noise [steps, B, S_ext*C]");
     ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
     if (sched) LTX_TRY(guidance_schedule_check(sched, dc.num_layers));
-    int ts_ratio = 8, sp_ratio = 32;
-    if (vae) { ltx_vae_config vc; LTX_TRY(ltx_vae_get_config(vae, &vc)); ts_ratio = vc.temporal_compression_ratio; sp_ratio = vc.spatial_compression_ratio; }
+    LatentGeom lg; LTX_TRY(latent_geom(vae, p, &lg));
     CondPlan plan;
-    LTX_TRY(cond_plan_from_items(items, n_items, p->height, p->width, p->num_frames, p->frame_rate, ts_ratio, sp_ratio, &plan));
+    LTX_TRY(cond_plan_from_items(items, n_items, p->height, p->width, p->num_frames, p->frame_rate, lg.ts_ratio, lg.sp_ratio, &plan));
     std::vector<float> sig; std::vector<int64_t> ts;
     LTX_TRY(ltx_pipeline_schedule(p, plan.Fl * plan.hw, &sig, &ts));
     const int N = p->num_inference_steps, G = plan.G;
@@ -902,8 +819,9 @@ extern "C" int ltx_pipeline_call_keyframes(ltx_dit* dit, ltx_vae* vae, const ltx
         }
     }
     // no item owns a group: ltx_pipeline_call (or _sched) itself
-    if (sched) return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
-    return pipeline_run(dit, vae, p, any ? &cr : nullptr, nullptr, latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream);
+    const PipeIO io{latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream};
+    if (sched) return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, io);
+    return pipeline_run_params(dit, vae, p, any ? &cr : nullptr, io);
 }
 
 // ---- warm-up: everything a first call would otherwise do inside the caller's forward --------------------------------

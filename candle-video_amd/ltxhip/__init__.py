@@ -1484,45 +1484,11 @@ class LtxPipeline:
         if nm is not None: _expect("negative_prompt_attention_mask", nm, (B, K))
         if dn is not None: _expect("decode_noise", dn, (B, Cin, F, H, W))
         if step_noise is not None: _expect("step_noise", step_noise, (args.num_inference_steps, B, S_seq, Cin))
-        p = PipelineParamsC()
-        lib.ltx_pipeline_params_default(C.byref(p))
-        p.height, p.width, p.num_frames, p.frame_rate = args.height, args.width, args.num_frames, args.frame_rate
-        p.num_inference_steps = args.num_inference_steps
         keep = []
-        if args.sigmas is not None:
-            s = _floats(args.sigmas); keep.append(s)
-            p.sigmas = C.cast(s, C.POINTER(C.c_float))
-        p.guidance_scale, p.guidance_rescale, p.stg_scale = args.guidance_scale, args.guidance_rescale, args.stg_scale
-        if args.skip_block_list is not None:
-            sb = (C.c_int * max(len(args.skip_block_list), 1))(*args.skip_block_list); keep.append(sb)
-            p.skip_block_list = C.cast(sb, C.POINTER(C.c_int))
-            p.n_skip_blocks = len(args.skip_block_list)
-        p.decode_timestep, p.decode_noise_scale = args.decode_timestep, args.decode_noise_scale
-        p.output_latent, p.postprocess = int(args.output_latent), (2 if args.output_rgb8 else int(args.postprocess))
-        p.shift_terminal = args.shift_terminal if args.shift_terminal is not None else 0.0
-        p.use_shift_terminal = int(args.shift_terminal is not None)
-        if args.stochastic_sampling:
-            if step_noise is None:
-                raise LtxError("stochastic_sampling needs step_noise [steps,B,S,C]")
-            sn = _dev(step_noise, torch.float32); keep.append(sn)
-            p.stochastic_sampling = 1
-            p.step_noise = C.cast(C.c_void_p(sn.data_ptr()), C.POINTER(C.c_float))
-        tl = self.vae._tiling() if self.vae is not None else None
-        if tl is not None:
-            keep.append(tl)
-            p.tiling = C.pointer(tl)
+        p = _params_c(args, self.vae, keep, step_noise)
         if interrupt is not None:
             p.interrupt = C.pointer(interrupt)
-        hook_exc = []
-        if on_step is not None:
-            def _hook(_user, step, num_steps, timestep):
-                try:
-                    return 1 if on_step(step, num_steps, timestep) else 0
-                except BaseException as exc:                  # never unwind through the C frame: stop the loop, re-raise after the call
-                    hook_exc.append(exc)
-                    return 1
-            cb = StepFn(_hook); keep.append(cb)
-            p.on_step = C.cast(cb, C.c_void_p)
+        hook_exc = _step_hook(on_step, keep, p)
         video = None
         if not args.output_latent:
             if self.vae is None:
@@ -1693,10 +1659,8 @@ def latent_renoise(tokens: torch.Tensor, noise: torch.Tensor, sigma: float) -> t
     return t
 
 
-def _params_c(args: "PipelineCall", vae, keep: list) -> "PipelineParamsC":
-    """PipelineCall -> ltx_pipeline_params (deterministic scheduler; the buffers it points at are appended to `keep`)"""
-    if args.stochastic_sampling:
-        raise LtxError("the multi-scale call runs the deterministic scheduler")
+def _params_c(args: "PipelineCall", vae, keep: list, step_noise: Optional[torch.Tensor] = None) -> "PipelineParamsC":
+    """PipelineCall -> ltx_pipeline_params (the buffers it points at are appended to `keep`)"""
     p = PipelineParamsC()
     lib.ltx_pipeline_params_default(C.byref(p))
     p.height, p.width, p.num_frames, p.frame_rate = args.height, args.width, args.num_frames, args.frame_rate
@@ -1713,6 +1677,12 @@ def _params_c(args: "PipelineCall", vae, keep: list) -> "PipelineParamsC":
     p.output_latent, p.postprocess = int(args.output_latent), (2 if args.output_rgb8 else int(args.postprocess))
     p.shift_terminal = args.shift_terminal if args.shift_terminal is not None else 0.0
     p.use_shift_terminal = int(args.shift_terminal is not None)
+    if args.stochastic_sampling:
+        if step_noise is None:
+            raise LtxError("stochastic_sampling needs step_noise [steps,B,S,C]")
+        sn = _dev(step_noise, torch.float32); keep.append(sn)
+        p.stochastic_sampling = 1
+        p.step_noise = C.cast(C.c_void_p(sn.data_ptr()), C.POINTER(C.c_float))
     tl = vae._tiling() if vae is not None else None
     if tl is not None:
         keep.append(tl)
@@ -1720,8 +1690,27 @@ def _params_c(args: "PipelineCall", vae, keep: list) -> "PipelineParamsC":
     return p
 
 
+def _step_hook(on_step, keep: list, *params) -> list:
+    """on_step(step, num_steps, timestep) as the per-step hook of every params struct given -> the list an exception of the hook lands in
+    (it never unwinds through the C frame: the loop stops, the caller re-raises after the call)"""
+    hook_exc = []
+    if on_step is not None:
+        def _hook(_user, step, num_steps, timestep):
+            try:
+                return 1 if on_step(step, num_steps, timestep) else 0
+            except BaseException as exc:
+                hook_exc.append(exc)
+                return 1
+        cb = StepFn(_hook); keep.append(cb)
+        for p in params:
+            p.on_step = C.cast(cb, C.c_void_p)
+    return hook_exc
+
+
 def pipeline_first_sigma(args: "PipelineCall", S: int) -> float:
     """the first sigma LtxPipeline.call(args) runs at S latent tokens (ltx_pipeline_first_sigma)"""
+    if args.stochastic_sampling:
+        raise LtxError("the multi-scale call runs the deterministic scheduler")
     keep = []
     p = _params_c(args, None, keep)
     out = C.c_float(0.0)
@@ -1769,22 +1758,14 @@ class LtxMultiScalePipeline:
         if ne is not None: _expect("negative_prompt_embeds", ne, (B, K, self.transformer.config.caption_channels))
         if nm is not None: _expect("negative_prompt_attention_mask", nm, (B, K))
         if dn is not None: _expect("decode_noise", dn, (B, Cin, Fo, Ho, Wo))
+        if first.stochastic_sampling or second.stochastic_sampling:
+            raise LtxError("the multi-scale call runs the deterministic scheduler")
         keep = []
         p1, p2 = _params_c(first, self.vae, keep), _params_c(second, self.vae, keep)
-        hook_exc = []
         for p in (p1, p2):
             if interrupt is not None:
                 p.interrupt = C.pointer(interrupt)
-        if on_step is not None:
-            def _hook(_user, step, num_steps, timestep):
-                try:
-                    return 1 if on_step(step, num_steps, timestep) else 0
-                except BaseException as exc:                  # never unwind through the C frame
-                    hook_exc.append(exc)
-                    return 1
-            cb = StepFn(_hook); keep.append(cb)
-            p1.on_step = C.cast(cb, C.c_void_p)
-            p2.on_step = C.cast(cb, C.c_void_p)
+        hook_exc = _step_hook(on_step, keep, p1, p2)
         hi = torch.empty(B, S_hi, Cin, dtype=torch.float32, device=lo.device)
         video = None
         if not second.output_latent:
