@@ -209,7 +209,7 @@ struct QkNormRopeArgs {
     const float* cos = nullptr; const float* sin = nullptr;  // f32 [rows, D/2] or null (no RoPE)
     float out_scale0 = 1.f;       // extra factor on segment 0's output (q): lets attention fold scale*log2(e) into Q
 };
-int ltx_launch_qknorm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t s);
+int ltx_launch_qknorm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t s);      // (qknorm_rope.hip, as the route and the rope table below)
 // The same for the q/k pass (probe: ltx_op_qknorm_route): the decision reads dtype, rows and D alone
 enum QkNormRoute { QKNORM_REFUSED = 0, QKNORM_BLOCK, QKNORM_FUSED4, QKNORM_FUSED8, QKNORM_CACHED, QKNORM_REREAD };
 QkNormRoute ltx_qknorm_route(int dtype, int64_t rows, int D, const char** why);

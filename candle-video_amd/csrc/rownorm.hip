@@ -6,67 +6,32 @@
 //                        and rmsnorm_channels_first + maybe_apply_scale_shift + SiLU of the VAE
 //                        resnet (vae.rs:148-153, 711-739, 755-800) on channels-last rows.
 //                 LN   = LayerNormNoParams (ltx_transformer.rs:72-79) + final modulation (:1149-1161).
-//  qknorm_rope  : q/k RMSNorm with weight over the FULL inner dim (ltx_transformer.rs:671-672)
-//                 fused with apply_rotary_emb (:314-339), in place, for 1 or 2 segments of a fused
-//                 QKV row.
-//  rope_table   : LtxVideoRotaryPosEmbed::forward (:436-524) -> half-width cos/sin tables.
+//  (the q/k pass and the rotary tables: qknorm_rope.hip)
 //
-// Mapping: LPR lanes per row (power of two, >= 16-B chunks per row, <= 64), 64/LPR rows per wave,
-// 4 waves per block; every lane moves 16 B per access.  The row lives in registers between the
-// statistics pass and the write pass (one HBM read, one HBM write), and every lane issues all of
+// Mapping: LPR lanes per row (pick_lpr), 64/LPR rows per wave, 4 waves per block; every lane moves 16 B per access.  The row
+// lives in registers between the statistics pass and the write pass (one HBM read, one HBM write), and every lane issues all of
 // its loads before the first reduction (memory-level parallelism instead of a dependent loop):
 //   WIDE   rows (> LPR chunks): up to NSLOT chunks of ONE row per lane;
 //   NARROW rows (<= LPR chunks, e.g. the VAE's 128..1024-channel voxels): NSLOT different rows per
 //          lane group, one chunk each.
 // Rows that do not fit NSLOT chunks per lane fall back to a re-reading variant (second read hits L2).
+// Every kernel is the same four pieces (norm_common.h and below): the row statistics (add_sum / add_sqdev, reduced by group_sum or
+// block_sum), one of the forms of 1 / rms (rinv_div; rinv_rsq for NARROW), the chunk's operands (load_chunk_operands) and its
+// finish (finish_chunk_regs; finish_chunk = both).  The presum kernels take the statistic from presum_load / presum_rinv instead.
 #include <type_traits>
 #include "common.h"
 #include "kernels.h"
 #include "gemm_common.h"
+#include "norm_common.h"
 #include "options.h"
 
 namespace {
 
-constexpr int NSLOT = 8;
-
-__device__ __forceinline__ float group_sum(float v, int lpr) {
-    for (int o = lpr >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ void finish_chunk(const RowNormArgs& a, const float* f_in, float mean, float rinv, int c, const float* sc,
-                                             const float* sh, T* y, bool active) {
-    constexpr int CH = ElemTraits<T>::CHUNK;
-    const T* w = reinterpret_cast<const T*>(a.weight);
-    float f[CH], wv[CH], scv[CH], shv[CH];
-    if (w) { Chunk16 wc; wc.u = *reinterpret_cast<const u32x4*>(w + c * CH); chunk_to_f32<T>(wc, wv); }
-    if (sc) {
-#pragma unroll
-        for (int q = 0; q < CH / 4; ++q) {
-            f32x4 a4 = *reinterpret_cast<const f32x4*>(sc + c * CH + 4 * q), b4 = *reinterpret_cast<const f32x4*>(sh + c * CH + 4 * q);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { scv[4 * q + i] = a4[i]; shv[4 * q + i] = b4[i]; }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-        float n = (f_in[i] - mean) * rinv;
-        if (w) n *= wv[i];
-        if (sc) n = n * (1.0f + scv[i]) + shv[i];
-        if (a.act == 1) n = silu_f(n);
-        f[i] = n;
-    }
-    Chunk16 o; f32_to_chunk<T>(f, o);
-    if (active) *reinterpret_cast<u32x4*>(y + c * CH) = o.u;
-}
-
-// Same, with the per-channel operands (weight, scale, shift of ONE chunk) already in registers: the NARROW mapping
-// keeps a lane on the same chunk for all of its rows, so they are loaded once instead of once per row
-// (64 B of modulation per 16 B of data through the L1/TA path otherwise).
+// The finish of a chunk, operands (weight, scale, shift of ONE chunk) in registers: (f - mean) * rinv [* w] [* (1 + scale) + shift]
+// [silu], rounded and stored at dst.  NT: streaming store.
 template <typename T, bool NT = false>
-__device__ __forceinline__ void finish_chunk_regs(const RowNormArgs& a, const float* f_in, float mean, float rinv, int c, bool has_w, bool has_mod,
-                                                  const float* wv, const float* scv, const float* shv, T* y, bool active) {
+__device__ __forceinline__ void finish_chunk_regs(const float* f_in, float mean, float rinv, bool has_w, bool has_mod, bool silu,
+                                                  const float* wv, const float* scv, const float* shv, T* dst, bool active) {
     constexpr int CH = ElemTraits<T>::CHUNK;
     float f[CH];
 #pragma unroll
@@ -74,16 +39,24 @@ __device__ __forceinline__ void finish_chunk_regs(const RowNormArgs& a, const fl
         float n = (f_in[i] - mean) * rinv;
         if (has_w) n *= wv[i];
         if (has_mod) n = n * (1.0f + scv[i]) + shv[i];
-        if (a.act == 1) n = silu_f(n);
+        if (silu) n = silu_f(n);
         f[i] = n;
     }
     Chunk16 o; f32_to_chunk<T>(f, o);
     if (active) {
-        if constexpr (NT) __builtin_nontemporal_store(o.u, reinterpret_cast<u32x4*>(y + c * CH));
-        else *reinterpret_cast<u32x4*>(y + c * CH) = o.u;
+        if constexpr (NT) __builtin_nontemporal_store(o.u, reinterpret_cast<u32x4*>(dst));
+        else *reinterpret_cast<u32x4*>(dst) = o.u;
     }
 }
 
+template <typename T, bool NT = false>
+__device__ __forceinline__ void finish_chunk_regs(const Chunk16& v, float mean, float rinv, bool has_w, bool has_mod, bool silu,
+                                                  const float* wv, const float* scv, const float* shv, T* dst, bool active) {
+    float f[ElemTraits<T>::CHUNK]; chunk_to_f32<T>(v, f);
+    finish_chunk_regs<T, NT>(f, mean, rinv, has_w, has_mod, silu, wv, scv, shv, dst, active);
+}
+
+// the operands of chunk c for batch element b: the weight's, and scale / shift from b's rows
 template <typename T>
 __device__ __forceinline__ void load_chunk_operands(const RowNormArgs& a, int c, int64_t b, float* wv, float* scv, float* shv) {
     constexpr int CH = ElemTraits<T>::CHUNK;
@@ -98,6 +71,51 @@ __device__ __forceinline__ void load_chunk_operands(const RowNormArgs& a, int c,
             for (int i = 0; i < 4; ++i) { scv[4 * q + i] = a4[i]; shv[4 * q + i] = b4[i]; }
         }
     }
+}
+
+// Load the chunk's operands, finish it.  The mappings that keep a lane on one chunk for several rows (NARROW, the presum kernels)
+// load once, call finish_chunk_regs per row and load again only for a row of another batch element: 64 B of modulation per 16 B
+// of data through the L1/TA path otherwise.
+template <typename T>
+__device__ __forceinline__ void finish_chunk(const RowNormArgs& a, const float* f_in, float mean, float rinv, int c, int64_t b, T* y, bool active) {
+    constexpr int CH = ElemTraits<T>::CHUNK;
+    float wv[CH], scv[CH], shv[CH];
+    load_chunk_operands<T>(a, c, b, wv, scv, shv);
+    finish_chunk_regs<T>(f_in, mean, rinv, a.weight != nullptr, a.scale != nullptr, a.act == 1, wv, scv, shv, y + c * CH, active);
+}
+
+template <typename T>
+__device__ __forceinline__ void finish_chunk(const RowNormArgs& a, const Chunk16& v, float mean, float rinv, int c, int64_t b, T* y, bool active) {
+    float f[ElemTraits<T>::CHUNK]; chunk_to_f32<T>(v, f);
+    finish_chunk<T>(a, f, mean, rinv, c, b, y, active);
+}
+
+// RowNormArgs::presum: n partial sums of squares per row, written by the GEMM before it.
+// up to 16 of a row's, loaded without a branch: a group of four past n re-reads the last one and is zeroed
+__device__ __forceinline__ void presum_load(const float* presum, int64_t row, int n, f32x4 (&t)[4]) {
+    const float* ps = presum + row * n;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const bool in = 4 * q < n;
+        const f32x4 u = *reinterpret_cast<const f32x4*>(ps + (in ? 4 * q : n - 4));
+        t[q] = in ? u : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+// 1 / rms from them, added in ascending order (groups past n add 0.0f, which changes no bit of a non-negative sum).  PAST16: rows
+// of more than 16 partials (wider than the DiT's) take the rest from memory in a loop.
+template <bool PAST16>
+__device__ __forceinline__ float presum_rinv(const float* presum, int64_t row, int n, const f32x4 (&t)[4], int D, float eps) {
+    float ss = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { ss += t[q][0]; ss += t[q][1]; ss += t[q][2]; ss += t[q][3]; }
+    if (PAST16 && n > 16) {
+        const float* ps = presum + row * n;                   // (formed here, behind the test: it would stay live from the loads on)
+        for (int g4 = 16; g4 < n; g4 += 4) {
+            const f32x4 u = *reinterpret_cast<const f32x4*>(ps + g4);
+            ss += u[0]; ss += u[1]; ss += u[2]; ss += u[3];
+        }
+    }
+    return rinv_div(ss, 1.0f / (float)D, eps);
 }
 
 // RowNormArgs::parts: chunk c of a row that arrives as the K-range sums of the linear layer before it - finished with the layer's
@@ -190,6 +208,8 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const RowNormArgs a, int l
         for (int i = 0; i < NSLOT; ++i) {
             const int64_t row = row0 + (int64_t)i * rpw;
             const bool active = row < a.rows;
+            // (this loop keeps the parent's text - the row expanded once, the sums written out: through add_sum / add_sqdev and
+            // the chunk form of the finish the same arithmetic was scheduled 3 - 6 % slower on the VAE's rows, 92.9 against 87.7 us)
             float f[CH]; chunk_to_f32<T>(v[i], f);
             float mean = 0.f;
             if (a.kind == 1) {
@@ -204,16 +224,10 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const RowNormArgs a, int l
                 for (int j = 0; j < CH; ++j) { float d = f[j] - mean; ss += d * d; }
             }
             ss = group_sum(ss, lpr);
-            const float rinv = __builtin_amdgcn_rsqf(ss * invD + a.eps);
+            const float rinv = rinv_rsq(ss, invD, a.eps);
             if (has) {
-                if (row < b0_end) {
-                    finish_chunk_regs<T>(a, f, mean, rinv, sub, a.weight != nullptr, a.scale != nullptr, wv, scv, shv, yp + i * ys, active);
-                } else if (active) {                                                     // a row of a later batch (rare)
-                    const int64_t b = row / a.rows_per_batch;
-                    const float* sc = a.scale ? a.scale + b * a.mod_stride : nullptr;
-                    const float* sh = a.shift ? a.shift + b * a.mod_stride : nullptr;
-                    finish_chunk<T>(a, f, mean, rinv, sub, sc, sh, yp + i * ys, active);
-                }
+                if (row < b0_end) finish_chunk_regs<T>(f, mean, rinv, a.weight != nullptr, a.scale != nullptr, a.act == 1, wv, scv, shv, yp + i * ys + sub * CH, active);
+                else if (active) finish_chunk<T>(a, f, mean, rinv, sub, row / a.rows_per_batch, yp + i * ys, active);      // a row of a later batch (rare)
             }
         }
     } else {
@@ -223,8 +237,7 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const RowNormArgs a, int l
         const T* x = reinterpret_cast<const T*>(a.x) + rr * a.ldx;
         T* y = reinterpret_cast<T*>(a.y) + rr * a.ldy;
         const int64_t b = rr / a.rows_per_batch;
-        const float* sc = a.scale ? a.scale + b * a.mod_stride : nullptr;
-        const float* sh = a.shift ? a.shift + b * a.mod_stride : nullptr;
+        auto chunk = [&](int c) { Chunk16 v; v.u = *reinterpret_cast<const u32x4*>(x + c * CH); return v; };
         if constexpr (MODE == 0) {
             Chunk16 v[NSLOT];
 #pragma unroll
@@ -232,70 +245,39 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const RowNormArgs a, int l
                 int c = sub + i * lpr;
                 v[i].u = (u32x4){0u, 0u, 0u, 0u};
                 if constexpr (DEFER != 0) { if (c < nch) v[i] = deferred_chunk<T, DEFER == 4 ? 4 : 0>(a, rr, b, c, active); }
-                else if (c < nch) v[i].u = *reinterpret_cast<const u32x4*>(x + c * CH);
+                else if (c < nch) v[i] = chunk(c);
             }
             float mean = 0.f;
-            if (a.kind == 1) {
-                float s = 0.f;
-#pragma unroll
-                for (int i = 0; i < NSLOT; ++i) { float f[CH]; chunk_to_f32<T>(v[i], f);
-#pragma unroll
-                    for (int j = 0; j < CH; ++j) s += f[j]; }
-                mean = group_sum(s, lpr) * invD;
-            }
-            float ss = 0.f;
-#pragma unroll
-            for (int i = 0; i < NSLOT; ++i) {
-                if (sub + i * lpr < nch) {
-                    float f[CH]; chunk_to_f32<T>(v[i], f);
-#pragma unroll
-                    for (int j = 0; j < CH; ++j) { float d = f[j] - mean; ss += d * d; }
-                }
-            }
-            ss = group_sum(ss, lpr);
-            const float rinv = 1.0f / sqrtf(ss * invD + a.eps);
+            if (a.kind == 1) mean = group_sum(cached_sum<T>(v), lpr) * invD;
+            const float rinv = rinv_div(group_sum(cached_sqdev<T>(v, mean, sub, lpr, nch), lpr), invD, a.eps);
 #pragma unroll
             for (int i = 0; i < NSLOT; ++i) {
                 int c = sub + i * lpr;
-                if (c < nch) { float f[CH]; chunk_to_f32<T>(v[i], f); finish_chunk<T>(a, f, mean, rinv, c, sc, sh, y, active); }
+                if (c < nch) finish_chunk<T>(a, v[i], mean, rinv, c, b, y, active);
             }
         } else {
             float mean = 0.f;
             if (a.kind == 1) {
                 float s = 0.f;
-                for (int c = sub; c < nch; c += lpr) {
-                    Chunk16 v; v.u = *reinterpret_cast<const u32x4*>(x + c * CH);
-                    float f[CH]; chunk_to_f32<T>(v, f);
-#pragma unroll
-                    for (int i = 0; i < CH; ++i) s += f[i];
-                }
+                for (int c = sub; c < nch; c += lpr) s = add_sum<T>(chunk(c), s);
                 mean = group_sum(s, lpr) * invD;
             }
             float ss = 0.f;
-            for (int c = sub; c < nch; c += lpr) {
-                Chunk16 v; v.u = *reinterpret_cast<const u32x4*>(x + c * CH);
-                float f[CH]; chunk_to_f32<T>(v, f);
-#pragma unroll
-                for (int i = 0; i < CH; ++i) { float d = f[i] - mean; ss += d * d; }
-            }
-            ss = group_sum(ss, lpr);
-            const float rinv = 1.0f / sqrtf(ss * invD + a.eps);
-            for (int c = sub; c < nch; c += lpr) {
-                Chunk16 v; v.u = *reinterpret_cast<const u32x4*>(x + c * CH);
-                float f[CH]; chunk_to_f32<T>(v, f);
-                finish_chunk<T>(a, f, mean, rinv, c, sc, sh, y, active);
-            }
+            for (int c = sub; c < nch; c += lpr) ss = add_sqdev<T>(chunk(c), mean, ss);
+            const float rinv = rinv_div(group_sum(ss, lpr), invD, a.eps);
+            for (int c = sub; c < nch; c += lpr) finish_chunk<T>(a, chunk(c), mean, rinv, c, b, y, active);
         }
     }
 }
 
-// Wide rows, several per wave, software-pipelined (round 4).  The one-row-per-wave form (MODE 0 above) has every wave of the launch
-// resident at once and therefore in the same phase: the chip first reads the whole matrix, then writes the whole result - 41 MB
-// of the DiT's [4992, 2048] pass take 12.7 us where a pure elementwise map of the same bytes takes 6.6 us (tools/norm_probe.py).
-// Here a wave walks R rows (row = wave + k * waves) with the loads of the next PD rows in flight while it reduces, modulates and
-// stores the current one, so reads and writes overlap; each lane keeps the modulation operands of its NS chunks in registers when
-// all rows of the wave share a batch element (they do for B = 1; otherwise they are re-loaded per row).  Per row the arithmetic is
-// MODE 0's, expression for expression: same bits.
+#ifdef LTX_EXPERIMENTS
+// Wide rows, several per wave, software-pipelined (round 4; measured negative, lab notes R4.4).  The one-row-per-wave form (MODE 0
+// above) has every wave of the launch resident at once and therefore in the same phase: the chip first reads the whole matrix, then
+// writes the whole result - 41 MB of the DiT's [4992, 2048] pass take 12.7 us where a pure elementwise map of the same bytes takes
+// 6.6 us (tools/archive/norm_probe.py).  Here a wave walks R rows (row = wave + k * waves) with the loads of the next PD rows in
+// flight while it reduces, modulates and stores the current one, so reads and writes overlap; each lane keeps the modulation
+// operands of its NS chunks in registers when all rows of the wave share a batch element (they do for B = 1; otherwise they are
+// re-loaded per row).  Per row the statistics and the finish are MODE 0's calls.
 template <typename T, int NS, int R, int PD>
 __global__ __launch_bounds__(256) void rownorm_rows_kernel(const RowNormArgs a, int total_waves) {
     constexpr int CH = ElemTraits<T>::CHUNK;
@@ -323,7 +305,8 @@ __global__ __launch_bounds__(256) void rownorm_rows_kernel(const RowNormArgs a, 
     const bool one_batch = last_row / a.rows_per_batch == b_first;
     float wv[NS][CH], scv[NS][CH], shv[NS][CH];
 #pragma unroll
-    for (int i = 0; i < NS; ++i) if (lane + i * 64 < nch) load_chunk_operands<T>(a, lane + i * 64, b_first, wv[i], scv[i], shv[i]);
+    for (int i = 0; i < NS; ++i)
+        if (lane + i * 64 < nch) load_chunk_operands<T>(a, lane + i * 64, b_first, wv[i], scv[i], shv[i]);
 #pragma unroll
     for (int k = 0; k < PD; ++k) load_row(k, v[k]);
 #pragma unroll
@@ -333,47 +316,25 @@ __global__ __launch_bounds__(256) void rownorm_rows_kernel(const RowNormArgs a, 
         const int64_t row = row_of(k);
         const bool active = row < a.rows;
         float mean = 0.f;
-        if (a.kind == 1) {
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) { float f[CH]; chunk_to_f32<T>(cur[i], f);
-#pragma unroll
-                for (int j = 0; j < CH; ++j) s += f[j]; }
-            mean = group_sum(s, 64) * invD;
-        }
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            if (lane + i * 64 < nch) {
-                float f[CH]; chunk_to_f32<T>(cur[i], f);
-#pragma unroll
-                for (int j = 0; j < CH; ++j) { float d = f[j] - mean; ss += d * d; }
-            }
-        }
-        ss = group_sum(ss, 64);
-        const float rinv = 1.0f / sqrtf(ss * invD + a.eps);
+        if (a.kind == 1) mean = group_sum(cached_sum<T>(cur), 64) * invD;
+        const float rinv = rinv_div(group_sum(cached_sqdev<T>(cur, mean, lane, 64, nch), 64), invD, a.eps);
         T* y = reinterpret_cast<T*>(a.y) + (active ? row : a.rows - 1) * a.ldy;
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
             const int c = lane + i * 64;
             if (c >= nch) continue;
             asm volatile("" : "+v"(cur[i].u));              // (keeps the f32 expansion of the statistics from living on: registers)
-            float f[CH]; chunk_to_f32<T>(cur[i], f);
-            if (one_batch) finish_chunk_regs<T>(a, f, mean, rinv, c, a.weight != nullptr, a.scale != nullptr, wv[i], scv[i], shv[i], y, active);
-            else {
-                const int64_t b = (active ? row : a.rows - 1) / a.rows_per_batch;
-                const float* sc = a.scale ? a.scale + b * a.mod_stride : nullptr;
-                const float* sh = a.shift ? a.shift + b * a.mod_stride : nullptr;
-                finish_chunk<T>(a, f, mean, rinv, c, sc, sh, y, active);
-            }
+            if (!one_batch && active) load_chunk_operands<T>(a, c, row / a.rows_per_batch, wv[i], scv[i], shv[i]);
+            finish_chunk_regs<T>(cur[i], mean, rinv, a.weight != nullptr, a.scale != nullptr, a.act == 1, wv[i], scv[i], shv[i], y + c * CH, active);
         }
     }
 }
+#endif
 
 // RMS norm (+ weight, modulation, activation) of rows whose sums of squares are already known (RowNormArgs::presum, the
 // by-product of the GEMM that wrote x): one thread per 16-byte chunk, no reduction, no wave waiting for a row - where the
 // one-row-per-wave kernel takes 12.6 us for the DiT's [4992, 2048] pass, a pure map of the same bytes takes 6.5 us
-// (tools/norm_probe.py).  rinv is formed exactly as in rownorm_kernel; the partials are summed in ascending order.
+// (tools/archive/norm_probe.py).  1 / rms: presum_rinv.
 template <typename T, int R, bool WIDE, bool NT = false>       // WIDE: nch >= 64 (a wave lies inside one row group); NT: streaming hints on x and y
 __global__ __launch_bounds__(256) void rownorm_presum_kernel(const RowNormArgs a, int nch, int rpb) {
     // block = rpb * R whole rows: thread (sub, c) owns 16-byte chunk c of rows row0 + sub * R .. + R - 1 (nch a power of two
@@ -397,116 +358,69 @@ __global__ __launch_bounds__(256) void rownorm_presum_kernel(const RowNormArgs a
         if constexpr (NT) v[r].u = __builtin_nontemporal_load(xp); else v[r].u = *xp;
     }
     // 1 / rms of the R rows of this thread: lanes 0 .. R-1 of the wave each sum one row's partials (a wave lies inside one sub
-    // when nch >= 64; for narrower rows every lane does its own rows' sums).  Ascending order; groups past presum_n add 0.0f,
-    // which changes no bit of a non-negative sum.
+    // when nch >= 64; for narrower rows every lane does its own rows' sums).
     float rinv[R];
-    auto partials_of = [&](int64_t row, f32x4 (&t)[4]) {
-        const float* ps = a.presum + (row < a.rows ? row : a.rows - 1) * a.presum_n;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {                         // no branch: a group past presum_n re-reads the last one and is zeroed
-            const bool in = 4 * q < a.presum_n;
-            const f32x4 u = *reinterpret_cast<const f32x4*>(ps + (in ? 4 * q : a.presum_n - 4));
-            t[q] = in ? u : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto rinv_from = [&](int64_t row, const f32x4 (&t)[4]) {
-        float ss = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { ss += t[q][0]; ss += t[q][1]; ss += t[q][2]; ss += t[q][3]; }
-        if (a.presum_n > 16) {                                // wider rows than the DiT's: the rest in a loop
-            const float* ps = a.presum + (row < a.rows ? row : a.rows - 1) * a.presum_n;
-            for (int g4 = 16; g4 < a.presum_n; g4 += 4) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(ps + g4);
-                ss += u[0]; ss += u[1]; ss += u[2]; ss += u[3];
-            }
-        }
-        return 1.0f / sqrtf(ss * (1.0f / (float)a.D) + a.eps);
-    };
+    auto in_rows = [&](int64_t row) { return row < a.rows ? row : a.rows - 1; };
     f32x4 pt[WIDE ? 1 : R][4];
-    if constexpr (WIDE) { if (lane < R) partials_of(row0 + lane, pt[0]); }
+    if constexpr (WIDE) { if (lane < R) presum_load(a.presum, in_rows(row0 + lane), a.presum_n, pt[0]); }
     else {
 #pragma unroll
-        for (int r = 0; r < R; ++r) partials_of(row0 + r, pt[r]);
+        for (int r = 0; r < R; ++r) presum_load(a.presum, in_rows(row0 + r), a.presum_n, pt[r]);
     }
     const uint32_t b0 = (uint32_t)row0 / (uint32_t)a.rows_per_batch;
     const int64_t last = row0 + R - 1 < a.rows ? row0 + R - 1 : a.rows - 1;
     const bool one_batch = (uint32_t)last / (uint32_t)a.rows_per_batch == b0;
     float wv[CH], scv[CH], shv[CH];
-    load_chunk_operands<T>(a, c, (int64_t)b0, wv, scv, shv);
+    load_chunk_operands<T>(a, c, b0, wv, scv, shv);
     if constexpr (WIDE) {
         float mine = 0.f;
-        if (lane < R) mine = rinv_from(row0 + lane, pt[0]);
+        if (lane < R) mine = presum_rinv<true>(a.presum, in_rows(row0 + lane), a.presum_n, pt[0], a.D, a.eps);
 #pragma unroll
         for (int r = 0; r < R; ++r) rinv[r] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), r));
     } else {
 #pragma unroll
-        for (int r = 0; r < R; ++r) rinv[r] = rinv_from(row0 + r, pt[r]);
+        for (int r = 0; r < R; ++r) rinv[r] = presum_rinv<true>(a.presum, in_rows(row0 + r), a.presum_n, pt[r], a.D, a.eps);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int64_t row = row0 + r;
         const bool active = row < a.rows;
-        float f[CH]; chunk_to_f32<T>(v[r], f);
         T* y = reinterpret_cast<T*>(a.y) + (active ? row : a.rows - 1) * a.ldy;
-        if (one_batch) finish_chunk_regs<T, NT>(a, f, 0.f, rinv[r], c, a.weight != nullptr, a.scale != nullptr, wv, scv, shv, y, active);
-        else if (active) {
-            const uint32_t b = (uint32_t)row / (uint32_t)a.rows_per_batch;
-            finish_chunk<T>(a, f, 0.f, rinv[r], c, a.scale ? a.scale + (int64_t)b * a.mod_stride : nullptr, a.shift ? a.shift + (int64_t)b * a.mod_stride : nullptr, y, true);
-        }
+        if (!one_batch && active && r > 0) load_chunk_operands<T>(a, c, (uint32_t)row / (uint32_t)a.rows_per_batch, wv, scv, shv);      // (rare: the row's own batch element)
+        finish_chunk_regs<T, NT>(v[r], 0.f, rinv[r], a.weight != nullptr, a.scale != nullptr, a.act == 1, wv, scv, shv, y + c * CH, active);
     }
 }
 
 // The DiT's case of the map above with nothing left to decide at run time: bf16, a row of nch chunks
-// (nch = 64 / 128 / 256), modulation present, no weight, no activation, groups of R rows inside one batch element, no ragged tail.
-// rownorm_presum_kernel serves every combination and runs ~550 instructions per wave at 20 000 waves per pass - as many issue
-// cycles as the pass has memory time (a bare copy of the same bytes in the same geometry: 7.5 us; that kernel: 10.4-11.6,
-// tools/norm_diag.py).  Same expressions in the same order: same bits (tests/test_gpu_q2fold.py).
+// (nch = 64 / 128 / 256), modulation present, no weight, no activation, groups of R rows inside one batch element, no ragged tail,
+// at most 16 partials.  rownorm_presum_kernel serves every combination and runs ~550 instructions per wave at 20 000 waves per
+// pass - as many issue cycles as the pass has memory time (a bare copy of the same bytes in the same geometry: 7.5 us; that
+// kernel: 10.4-11.6, tools/archive/norm_diag.py).  The same presum_load / presum_rinv / finish_chunk_regs: same bits
+// (tests/test_gpu_q2fold.py).
 template <int R>
 __global__ __launch_bounds__(256) void rownorm_presum_lean_kernel(const RowNormArgs a, int nch, int rpb) {
     const int lane = threadIdx.x & 63;
     const int sub = threadIdx.x / nch, c = threadIdx.x - sub * nch;
     const uint32_t row0 = ((uint32_t)blockIdx.x * (uint32_t)rpb + (uint32_t)sub) * R;
     const bf16_t* x = reinterpret_cast<const bf16_t*>(a.x) + (int64_t)row0 * a.ldx + c * 8;
-    u32x4 v[R];
+    Chunk16 v[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) v[r] = *reinterpret_cast<const u32x4*>(x + (int64_t)r * a.ldx);
+    for (int r = 0; r < R; ++r) v[r].u = *reinterpret_cast<const u32x4*>(x + (int64_t)r * a.ldx);
     f32x4 pt[4];
-    if (lane < R) {
-        const float* ps = a.presum + (int64_t)(row0 + lane) * a.presum_n;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool in = 4 * q < a.presum_n;
-            const f32x4 u = *reinterpret_cast<const f32x4*>(ps + (in ? 4 * q : a.presum_n - 4));
-            pt[q] = in ? u : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    }
+    if (lane < R) presum_load(a.presum, row0 + lane, a.presum_n, pt);
     const uint32_t b = row0 / (uint32_t)a.rows_per_batch;
     const float* sc = a.scale + (int64_t)b * a.mod_stride + c * 8; const float* sh = a.shift + (int64_t)b * a.mod_stride + c * 8;
     const f32x4 s0 = *reinterpret_cast<const f32x4*>(sc), s1 = *reinterpret_cast<const f32x4*>(sc + 4);
     const f32x4 h0 = *reinterpret_cast<const f32x4*>(sh), h1 = *reinterpret_cast<const f32x4*>(sh + 4);
     float mine = 0.f;
-    if (lane < R) {
-        float ss = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { ss += pt[q][0]; ss += pt[q][1]; ss += pt[q][2]; ss += pt[q][3]; }
-        mine = 1.0f / sqrtf(ss * (1.0f / (float)a.D) + a.eps);
-    }
+    if (lane < R) mine = presum_rinv<false>(a.presum, row0 + lane, a.presum_n, pt, a.D, a.eps);
     const float scv[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
     const float shv[8] = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
     bf16_t* y = reinterpret_cast<bf16_t*>(a.y) + (int64_t)row0 * a.ldy + c * 8;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const float rinv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), r));
-        Chunk16 ch; ch.u = v[r];
-        float f[8]; chunk_to_f32<bf16_t>(ch, f);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            float n = (f[i] - 0.f) * rinv;
-            n = n * (1.0f + scv[i]) + shv[i];
-            f[i] = n;
-        }
-        Chunk16 o; f32_to_chunk<bf16_t>(f, o);
-        *reinterpret_cast<u32x4*>(y + (int64_t)r * a.ldy) = o.u;
+        finish_chunk_regs<bf16_t>(v[r], 0.f, rinv, false, true, false, nullptr, scv, shv, y + (int64_t)r * a.ldy, true);
     }
 }
 
@@ -538,199 +452,6 @@ extern "C" int ltx_dbg_norm_diag(const void* x, void* y, long long nchunks, int 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #endif
-
-// CACHED: the (<= NSLOT chunks per lane) segment stays in registers between the two passes
-template <typename T, bool CACHED>
-__global__ __launch_bounds__(256) void qknorm_rope_kernel(const QkNormRopeArgs a, int lpr) {
-    constexpr int CH = ElemTraits<T>::CHUNK;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rpw = 64 / lpr;
-    const int64_t row = ((int64_t)blockIdx.x * 4 + wave) * rpw + lane / lpr;
-    const int sub = lane % lpr;
-    const bool active = row < a.rows;
-    const int64_t rr = active ? row : a.rows - 1;
-    const int nch = a.D / CH;
-    const float* cs = a.cos ? a.cos + rr * (a.D / 2) : nullptr;
-    const float* sn = a.sin ? a.sin + rr * (a.D / 2) : nullptr;
-    auto finish = [&](Chunk16 v, int c, float rinv, const T* w, const T* wb, T* x) {
-        float f[CH]; chunk_to_f32<T>(v, f);
-        Chunk16 wc; wc.u = *reinterpret_cast<const u32x4*>(w + c * CH);
-        float wv[CH]; chunk_to_f32<T>(wc, wv);
-#pragma unroll
-        for (int i = 0; i < CH; ++i) f[i] = f[i] * rinv * wv[i];
-        if (wb) {                                          // a consumer's weight folded in (QkNormRopeArgs::w0b)
-            Chunk16 wc2; wc2.u = *reinterpret_cast<const u32x4*>(wb + c * CH);
-            float wv2[CH]; chunk_to_f32<T>(wc2, wv2);
-#pragma unroll
-            for (int i = 0; i < CH; ++i) f[i] *= wv2[i];
-        }
-        if (cs) {
-            float co[CH / 2], si[CH / 2];
-            if constexpr (CH == 8) {
-                f32x4 c4 = *reinterpret_cast<const f32x4*>(cs + c * 4), s4 = *reinterpret_cast<const f32x4*>(sn + c * 4);
-#pragma unroll
-                for (int p = 0; p < 4; ++p) { co[p] = c4[p]; si[p] = s4[p]; }
-            } else {
-#pragma unroll
-                for (int p = 0; p < CH / 2; ++p) { co[p] = cs[c * (CH / 2) + p]; si[p] = sn[c * (CH / 2) + p]; }
-            }
-#pragma unroll
-            for (int p = 0; p < CH / 2; ++p) {
-                float re = f[2 * p], im = f[2 * p + 1];
-                f[2 * p] = re * co[p] - im * si[p];          // x*cos + (-x_imag)*sin
-                f[2 * p + 1] = im * co[p] + re * si[p];      // x*cos + ( x_real)*sin
-            }
-        }
-        Chunk16 o; f32_to_chunk<T>(f, o);
-        if (active) *reinterpret_cast<u32x4*>(x + c * CH) = o.u;
-    };
-    for (int seg = 0; seg < a.nseg; ++seg) {
-        T* x = reinterpret_cast<T*>(a.x) + rr * a.ld + (int64_t)seg * (a.seg_stride ? a.seg_stride : a.D);
-        const T* w = reinterpret_cast<const T*>(seg == 0 ? a.w0 : a.w1);
-        const T* wb = seg == 0 ? reinterpret_cast<const T*>(a.w0b) : nullptr;
-        const float oscale = seg == 0 ? a.out_scale0 : 1.0f;
-        if constexpr (CACHED) {
-            Chunk16 v[NSLOT];
-#pragma unroll
-            for (int i = 0; i < NSLOT; ++i) {
-                int c = sub + i * lpr;
-                v[i].u = (u32x4){0u, 0u, 0u, 0u};
-                if (c < nch) v[i].u = *reinterpret_cast<const u32x4*>(x + c * CH);
-            }
-            float ss = 0.f;
-#pragma unroll
-            for (int i = 0; i < NSLOT; ++i) { float f[CH]; chunk_to_f32<T>(v[i], f);
-#pragma unroll
-                for (int j = 0; j < CH; ++j) ss += f[j] * f[j]; }
-            ss = group_sum(ss, lpr);
-            const float rinv = oscale / sqrtf(ss / (float)a.D + a.eps);
-#pragma unroll
-            for (int i = 0; i < NSLOT; ++i) { int c = sub + i * lpr; if (c < nch) finish(v[i], c, rinv, w, wb, x); }
-        } else {
-            float ss = 0.f;
-            for (int c = sub; c < nch; c += lpr) {
-                Chunk16 v; v.u = *reinterpret_cast<const u32x4*>(x + c * CH);
-                float f[CH]; chunk_to_f32<T>(v, f);
-#pragma unroll
-                for (int i = 0; i < CH; ++i) ss += f[i] * f[i];
-            }
-            ss = group_sum(ss, lpr);
-            const float rinv = oscale / sqrtf(ss / (float)a.D + a.eps);
-            for (int c = sub; c < nch; c += lpr) { Chunk16 v; v.u = *reinterpret_cast<const u32x4*>(x + c * CH); finish(v, c, rinv, w, wb, x); }
-        }
-    }
-}
-
-// Fast path of the kernel above for rows of <= NS*lpr chunks (the DiT's 2048-wide q/k: 4 chunks per lane): the cos/sin
-// chunks of a lane are loaded ONCE and reused by both segments (q and k share the table), and the loads of every
-// segment are issued before the first reduction (memory-level parallelism; the slow kernel read the tables twice and
-// serialised the segments).
-template <typename T, int NS, int OCC = 5>      // OCC: blocks per CU the register allocation must allow (NS = 4: 94 registers, five)
-__global__ __launch_bounds__(256, OCC) void qknorm_rope_fused_kernel(const QkNormRopeArgs a, int lpr) {
-    constexpr int CH = ElemTraits<T>::CHUNK;
-    static_assert(CH == 8, "bf16 rows only");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rpw = 64 / lpr;
-    const int64_t row = ((int64_t)blockIdx.x * 4 + wave) * rpw + lane / lpr;
-    const int sub = lane % lpr;
-    const bool active = row < a.rows;
-    const int64_t rr = active ? row : a.rows - 1;
-    const int nch = a.D / CH;
-    const bool rope = a.cos != nullptr;
-    const float* cs = rope ? a.cos + rr * (a.D / 2) : nullptr;
-    const float* sn = rope ? a.sin + rr * (a.D / 2) : nullptr;
-    T* x0 = reinterpret_cast<T*>(a.x) + rr * a.ld;
-    const int64_t sst = a.seg_stride ? a.seg_stride : a.D;
-    Chunk16 v[2][NS];
-    f32x4 co[NS], si[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int c = sub + i * lpr;
-        const bool in = c < nch;
-        v[0][i].u = (u32x4){0u, 0u, 0u, 0u}; v[1][i].u = (u32x4){0u, 0u, 0u, 0u};
-        if (in) v[0][i].u = *reinterpret_cast<const u32x4*>(x0 + c * CH);
-        if (in && a.nseg == 2) v[1][i].u = *reinterpret_cast<const u32x4*>(x0 + sst + c * CH);
-        if (in && rope) { co[i] = *reinterpret_cast<const f32x4*>(cs + c * 4); si[i] = *reinterpret_cast<const f32x4*>(sn + c * 4); }
-    }
-    // both row statistics first, then chunk-major: chunk i of q and of k are finished together with ONE copy of its cos / sin
-    // in registers, which then die (seg-major order kept all four table chunks and both rows alive: 118 VGPRs = 4 waves per SIMD
-    // = 4096 wave slots for the DiT's 4992 row-waves, i.e. a second, mostly empty round; chunk-major fits 5 per SIMD)
-    float rinv[2] = {0.f, 0.f};
-#pragma unroll
-    for (int seg = 0; seg < 2; ++seg) {
-        if (seg >= a.nseg) break;
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) { float f[CH]; chunk_to_f32<T>(v[seg][i], f);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) ss += f[j] * f[j]; }
-        ss = group_sum(ss, lpr);
-        rinv[seg] = (seg == 0 ? a.out_scale0 : 1.0f) / sqrtf(ss / (float)a.D + a.eps);
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int c = sub + i * lpr;
-        if (c >= nch) continue;
-#pragma unroll
-        for (int seg = 0; seg < 2; ++seg) {
-            if (seg >= a.nseg) break;
-            const T* w = reinterpret_cast<const T*>(seg == 0 ? a.w0 : a.w1);
-            // (opaque copy: without it the f32 expansion of all eight chunks made for the row statistics is kept alive - 64 registers)
-            asm volatile("" : "+v"(v[seg][i].u));
-            float f[CH]; chunk_to_f32<T>(v[seg][i], f);
-            Chunk16 wc; wc.u = *reinterpret_cast<const u32x4*>(w + c * CH);
-            float wv[CH]; chunk_to_f32<T>(wc, wv);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) f[j] = f[j] * rinv[seg] * wv[j];
-            if (seg == 0 && a.w0b) {                       // a consumer's weight folded in (QkNormRopeArgs::w0b)
-                Chunk16 wc2; wc2.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(a.w0b) + c * CH);
-                float wv2[CH]; chunk_to_f32<T>(wc2, wv2);
-#pragma unroll
-                for (int j = 0; j < CH; ++j) f[j] *= wv2[j];
-            }
-            if (rope) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float re = f[2 * p], im = f[2 * p + 1];
-                    f[2 * p] = re * co[i][p] - im * si[i][p];
-                    f[2 * p + 1] = im * co[i][p] + re * si[i][p];
-                }
-            }
-            Chunk16 o; f32_to_chunk<T>(f, o);
-            if (active) *reinterpret_cast<u32x4*>(x0 + seg * sst + c * CH) = o.u;
-            __builtin_amdgcn_sched_barrier(0);             // one (chunk, segment) at a time: the scheduler's interleave of all eight costs 30 registers
-        }
-    }
-}
-
-__global__ void rope_table_kernel(const RopeTableArgs a) {
-    const int half = a.D / 2;
-    const int64_t S = (int64_t)a.F * a.H * a.W;
-    const int64_t total = (int64_t)a.B * S * half;
-    const int rem_pairs = (a.D % 6) / 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % half);
-        const int64_t row = i / half;
-        float co = 1.0f, si = 0.0f;
-        if (p >= rem_pairs) {
-            const int fi = p - rem_pairs;
-            const int step = fi / 3, ax = fi - step * 3;
-            float g;
-            if (a.use_coords) {
-                g = a.coords[row * 3 + ax] * a.gscale[ax];
-            } else {
-                const int64_t s = row % S;
-                const int w = (int)(s % a.W); const int64_t t1 = s / a.W;
-                const int h = (int)(t1 % a.H); const int f = (int)(t1 / a.H);
-                const float idx = ax == 0 ? (float)f : (ax == 1 ? (float)h : (float)w);
-                g = idx * a.gscale[ax];
-            }
-            const float ang = a.freqs[step] * (g * 2.0f - 1.0f);
-            co = cosf(ang); si = sinf(ang);
-        }
-        a.cos[i] = co; a.sin[i] = si;
-    }
-}
 
 // Canonical per-row partial sums of squares (GemmArgs::rowsq) of a stored matrix: one f32 per (row, 128-column group) =
 // sequential sum over the group's 32 four-column leaves (ltx_rowsq_leaf), ascending.  The stand-alone form of what
@@ -771,8 +492,8 @@ __global__ __launch_bounds__(256) void rowsq_kernel(const T* x, int64_t rows, in
 // Few rows (C1's 384 tokens, the 128 text rows of T5): ONE ROW PER BLOCK, a chunk (two beyond 2048 columns) per thread.  With a wave per
 // row such a pass is 384 waves on 256 CUs, each walking a dependent chain of four chunks (and, finishing deferred K ranges, 1 KiB of
 // loads per lane): pure latency - 7.0 us plain, 14.6 us with four ranges.  Four waves per row quarter the chain and put 4 x the loads
-// in flight.  Row statistic: lane butterfly, then the four wave sums in wave order - the plain and the deferred form share it, so
-// finishing the ranges here returns the bits of in-launch reduction + this norm (tests/test_gpu_defer.py).
+// in flight.  Row statistic: block_sum - the plain and the deferred form share it, so finishing the ranges here returns the bits of
+// in-launch reduction + this norm (tests/test_gpu_defer.py).
 template <typename T, int DEFER>          // DEFER: 0 no; 1: a.nparts ranges; 4: four ranges (unrolled)
 __global__ __launch_bounds__(256) void rownorm_block_kernel(const RowNormArgs a) {
     constexpr int CH = ElemTraits<T>::CHUNK, NC = 2;
@@ -784,8 +505,6 @@ __global__ __launch_bounds__(256) void rownorm_block_kernel(const RowNormArgs a)
     const T* x = reinterpret_cast<const T*>(a.x) + row * a.ldx;
     T* y = reinterpret_cast<T*>(a.y) + row * a.ldy;
     const int64_t b = row / a.rows_per_batch;
-    const float* sc = a.scale ? a.scale + b * a.mod_stride : nullptr;
-    const float* sh = a.shift ? a.shift + b * a.mod_stride : nullptr;
     Chunk16 v[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
@@ -796,45 +515,15 @@ __global__ __launch_bounds__(256) void rownorm_block_kernel(const RowNormArgs a)
             else v[i].u = *reinterpret_cast<const u32x4*>(x + c * CH);
         }
     }
-    auto block_sum = [&](float t, int slot) {
-        t = group_sum(t, 64);
-        if (lane == 0) red[slot][wave] = t;
-        __syncthreads();
-        return ((red[slot][0] + red[slot][1]) + red[slot][2]) + red[slot][3];
-    };
     float mean = 0.f;
-    if (a.kind == 1) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) { float f[CH]; chunk_to_f32<T>(v[i], f);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) t += f[j]; }
-        mean = block_sum(t, 0) * invD;
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        if (tid + i * 256 < nch) {
-            float f[CH]; chunk_to_f32<T>(v[i], f);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) { const float d = f[j] - mean; ss += d * d; }
-        }
-    }
-    ss = block_sum(ss, 1);
-    const float rinv = 1.0f / sqrtf(ss * invD + a.eps);
+    if (a.kind == 1) mean = block_sum(cached_sum<T>(v), red, lane, wave) * invD;
+    const float rinv = rinv_div(block_sum(cached_sqdev<T>(v, mean, tid, 256, nch), red + 1, lane, wave), invD, a.eps);
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
         const int c = tid + i * 256;
-        if (c < nch) { float f[CH]; chunk_to_f32<T>(v[i], f); finish_chunk<T>(a, f, mean, rinv, c, sc, sh, y, true); }
+        if (c < nch) finish_chunk<T>(a, v[i], mean, rinv, c, b, y, true);
     }
 }
-
-int pick_lpr(int nch) {
-    int lpr = 1;
-    while (lpr < nch && lpr < 64) lpr <<= 1;
-    return lpr;
-}
-
 // The launches of ltx_rownorm_route's answers: nothing is decided here.
 template <typename T>
 void launch_rownorm_t(const RowNormArgs& a, const NormDecision& d, int lpr, int nch, hipStream_t s) {
@@ -865,14 +554,16 @@ void launch_rownorm_t(const RowNormArgs& a, const NormDecision& d, int lpr, int 
     case NORM_WIDE_DEFER4: LTX_LAUNCH_TIMED((rownorm_kernel<T, 0, 4>), wave_grid, dim3(256), 0, s, a, lpr); break;
     case NORM_WIDE_DEFER: LTX_LAUNCH_TIMED((rownorm_kernel<T, 0, 1>), wave_grid, dim3(256), 0, s, a, lpr); break;
     case NORM_WIDE: {
-        // LTX_ROWNORM_OCC=n (experiment): at most n blocks per CU, by asking for 160 KiB / n of LDS the kernel never touches -
-        // several generations of blocks instead of one, so that the stores of one overlap the loads of the next
         int shm = 0;
+#ifdef LTX_EXPERIMENTS
+        // x_rownorm_occ=n: at most n blocks per CU, by asking for 160 KiB / n of LDS the kernel never touches - several
+        // generations of blocks instead of one, so that the stores of one overlap the loads of the next
         { const int n = ltx_exp("rownorm_occ", 0); if (n >= 1 && n <= 8) shm = 163840 / n - 1024; }
         if (shm > 65536) {
             static std::atomic<unsigned long long> occ_devs{0};
             (void)ltx_set_max_dyn_smem(occ_devs, reinterpret_cast<const void*>(&rownorm_kernel<T, 0>), 163840);
         }
+#endif
         LTX_LAUNCH_TIMED((rownorm_kernel<T, 0>), wave_grid, dim3(256), shm, s, a, lpr);
         break;
     }
@@ -893,9 +584,11 @@ void launch_presum(const RowNormArgs& a, const NormDecision& d, int dtype, int n
     const dim3 grid4((unsigned)cdiv64(a.rows, (int64_t)rpb * 4));
     if (d.route == NORM_PRESUM_LEAN) LTX_LAUNCH_TIMED((rownorm_presum_lean_kernel<4>), grid4, dim3(256), 0, s, a, nch, rpb);
     else if (dtype != LTX_DT_BF16) launch_presum_r<float, 4>(a, d, nch, rpb, s);
+#ifdef LTX_EXPERIMENTS     // x_norm_nt, x_norm_presum_r = 2 / 8: measured, not faster (the shipped decision never sets presum_nt or another presum_r)
     else if (d.presum_nt) LTX_LAUNCH_TIMED((rownorm_presum_kernel<bf16_t, 4, true, true>), grid4, dim3(256), 0, s, a, nch, rpb);
     else if (d.presum_r == 2) launch_presum_r<bf16_t, 2>(a, d, nch, rpb, s);
     else if (d.presum_r == 8) launch_presum_r<bf16_t, 8>(a, d, nch, rpb, s);
+#endif
     else launch_presum_r<bf16_t, 4>(a, d, nch, rpb, s);
 }
 
@@ -977,135 +670,6 @@ int ltx_launch_rownorm(const RowNormArgs& a, int dtype, hipStream_t s) {
     LTX_CHECK_LAUNCH();
     return LTX_OK;
 }
-
-namespace {
-// Few rows (C1's 384 tokens; the text rows of the cached cross-attention keys): one row per block, a chunk (two beyond 2048 columns)
-// per thread and segment - the arithmetic of qknorm_rope_fused_kernel, the row statistics summed lane butterfly first, then the four
-// wave sums in wave order (see rownorm_block_kernel): 6.6 -> ~4 us per launch at 384 rows.
-template <typename T>
-__global__ __launch_bounds__(256) void qknorm_rope_block_kernel(const QkNormRopeArgs a) {
-    constexpr int CH = ElemTraits<T>::CHUNK, NC = 2;
-    static_assert(CH == 8, "bf16 rows only");
-    __shared__ float red[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t row = blockIdx.x;
-    const int nch = a.D / CH;
-    const bool rope = a.cos != nullptr;
-    const float* cs = rope ? a.cos + row * (a.D / 2) : nullptr;
-    const float* sn = rope ? a.sin + row * (a.D / 2) : nullptr;
-    T* x0 = reinterpret_cast<T*>(a.x) + row * a.ld;
-    const int64_t sst = a.seg_stride ? a.seg_stride : a.D;
-    Chunk16 v[2][NC];
-    f32x4 co[NC], si[NC];
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        const int c = tid + i * 256;
-        const bool in = c < nch;
-        v[0][i].u = (u32x4){0u, 0u, 0u, 0u}; v[1][i].u = (u32x4){0u, 0u, 0u, 0u};
-        if (in) v[0][i].u = *reinterpret_cast<const u32x4*>(x0 + c * CH);
-        if (in && a.nseg == 2) v[1][i].u = *reinterpret_cast<const u32x4*>(x0 + sst + c * CH);
-        if (in && rope) { co[i] = *reinterpret_cast<const f32x4*>(cs + c * 4); si[i] = *reinterpret_cast<const f32x4*>(sn + c * 4); }
-    }
-    float ss[2] = {0.f, 0.f};
-#pragma unroll
-    for (int seg = 0; seg < 2; ++seg) {
-#pragma unroll
-        for (int i = 0; i < NC; ++i) { float f[CH]; chunk_to_f32<T>(v[seg][i], f);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) ss[seg] += f[j] * f[j]; }
-        ss[seg] = group_sum(ss[seg], 64);
-        if (lane == 0) red[seg][wave] = ss[seg];
-    }
-    __syncthreads();
-    float rinv[2];
-#pragma unroll
-    for (int seg = 0; seg < 2; ++seg) {
-        const float t = ((red[seg][0] + red[seg][1]) + red[seg][2]) + red[seg][3];
-        rinv[seg] = (seg == 0 ? a.out_scale0 : 1.0f) / sqrtf(t / (float)a.D + a.eps);
-    }
-#pragma unroll
-    for (int i = 0; i < NC; ++i) {
-        const int c = tid + i * 256;
-        if (c >= nch) continue;
-#pragma unroll
-        for (int seg = 0; seg < 2; ++seg) {
-            if (seg >= a.nseg) break;
-            const T* w = reinterpret_cast<const T*>(seg == 0 ? a.w0 : a.w1);
-            float f[CH]; chunk_to_f32<T>(v[seg][i], f);
-            Chunk16 wc; wc.u = *reinterpret_cast<const u32x4*>(w + c * CH);
-            float wv[CH]; chunk_to_f32<T>(wc, wv);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) f[j] = f[j] * rinv[seg] * wv[j];
-            if (seg == 0 && a.w0b) {
-                Chunk16 wc2; wc2.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(a.w0b) + c * CH);
-                float wv2[CH]; chunk_to_f32<T>(wc2, wv2);
-#pragma unroll
-                for (int j = 0; j < CH; ++j) f[j] *= wv2[j];
-            }
-            if (rope) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float re = f[2 * p], im = f[2 * p + 1];
-                    f[2 * p] = re * co[i][p] - im * si[i][p];
-                    f[2 * p + 1] = im * co[i][p] + re * si[i][p];
-                }
-            }
-            Chunk16 o; f32_to_chunk<T>(f, o);
-            *reinterpret_cast<u32x4*>(x0 + seg * sst + c * CH) = o.u;
-        }
-    }
-}
-}  // namespace
-
-// The one place where the q/k pass's kernel is chosen (kernels.h).
-QkNormRoute ltx_qknorm_route(int dtype, int64_t rows, int D, const char** why) {
-    const int ch = dtype == LTX_DT_BF16 ? 8 : 4;
-    if (D < ch || D % ch != 0) { if (why) *why = "qknorm: D/ld must be multiples of the 16-byte chunk"; return QKNORM_REFUSED; }
-    const int nch = D / ch, lpr = pick_lpr(nch);
-    const bool cached = nch <= NSLOT * lpr;
-    if (dtype == LTX_DT_BF16) {
-        if (rows <= 512 && nch > 64 && nch <= 512) return QKNORM_BLOCK;              // few wide rows: one row per block
-        if (nch <= 4 * lpr) return QKNORM_FUSED4;
-        // the 13B model's 4096-wide rows: eight chunks per lane, the table still read once for q and k (LTX_QKNORM_FUSED8=0: the two-pass kernel)
-        if (nch <= 8 * lpr && ltx_exp("qknorm_fused8", 1)) return QKNORM_FUSED8;
-    }
-    return cached ? QKNORM_CACHED : QKNORM_REREAD;
-}
-
-const char* ltx_qknorm_route_name(QkNormRoute r) {
-    static const char* const names[] = {"refused", "block", "fused4", "fused8", "cached", "reread"};
-    return names[r];
-}
-
-int ltx_launch_qknorm_rope(const QkNormRopeArgs& a, int dtype, hipStream_t s) {
-    const int ch = dtype == LTX_DT_BF16 ? 8 : 4;
-    if (a.rows <= 0) return LTX_OK;
-    if (a.D % ch != 0 || a.ld % ch != 0) LTX_FAIL(LTX_ERR_ARG, "qknorm: D/ld must be multiples of the 16-byte chunk");
-    if (a.nseg < 1 || a.nseg > 2 || !a.w0 || (a.nseg == 2 && !a.w1)) LTX_FAIL(LTX_ERR_ARG, "qknorm: bad segments/weights");
-    const char* why = nullptr;
-    const QkNormRoute route = ltx_qknorm_route(dtype, a.rows, a.D, &why);
-    if (route == QKNORM_REFUSED) LTX_FAIL(LTX_ERR_ARG, why);
-    const int nch = a.D / ch, lpr = pick_lpr(nch);
-    const int64_t rows_per_block = 4 * (64 / lpr);
-    dim3 grid((unsigned)cdiv64(a.rows, rows_per_block)), block(256);
-    const bool bf16 = dtype == LTX_DT_BF16;
-    switch (route) {
-    case QKNORM_BLOCK: hipLaunchKernelGGL((qknorm_rope_block_kernel<bf16_t>), dim3((unsigned)a.rows), block, 0, s, a); break;
-    case QKNORM_FUSED4: hipLaunchKernelGGL((qknorm_rope_fused_kernel<bf16_t, 4>), grid, block, 0, s, a, lpr); break;
-    case QKNORM_FUSED8: hipLaunchKernelGGL((qknorm_rope_fused_kernel<bf16_t, 8, 2>), grid, block, 0, s, a, lpr); break;
-    case QKNORM_CACHED:
-        if (bf16) hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t, true>), grid, block, 0, s, a, lpr);
-        else hipLaunchKernelGGL((qknorm_rope_kernel<float, true>), grid, block, 0, s, a, lpr);
-        break;
-    default:
-        if (bf16) hipLaunchKernelGGL((qknorm_rope_kernel<bf16_t, false>), grid, block, 0, s, a, lpr);
-        else hipLaunchKernelGGL((qknorm_rope_kernel<float, false>), grid, block, 0, s, a, lpr);
-        break;
-    }
-    LTX_CHECK_LAUNCH();
-    return LTX_OK;
-}
-
 int ltx_launch_rowsq(const void* x, int dtype, int64_t rows, int N, int ld, float* out, hipStream_t s) {
     if (rows <= 0 || N <= 0) return LTX_OK;
     if (!x || !out || N % 4 != 0 || ld % 4 != 0 || ((uintptr_t)x & 7)) LTX_FAIL(LTX_ERR_ARG, "rowsq: N and ld must be multiples of 4 and x 8-byte aligned");
@@ -1159,15 +723,6 @@ int ltx_launch_shift_gemv(const void* W, const void* bias, const float* shift, i
         LTX_FAIL(LTX_ERR_ARG, "shift_gemv: bf16 weights [N, K] with K % 8 == 0, f32 shift rows 16-byte aligned, 1..8 batch rows");
     hipLaunchKernelGGL(shift_gemv_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(W), reinterpret_cast<const bf16_t*>(bias),
                        shift, shift_stride, B, N, K, cvec, cvec_stride);
-    LTX_CHECK_LAUNCH();
-    return LTX_OK;
-}
-
-int ltx_launch_rope_table(const RopeTableArgs& a, hipStream_t s) {
-    if (a.D % 2 != 0 || a.D < 6) LTX_FAIL(LTX_ERR_ARG, "rope: dim must be even and >= 6");
-    const int64_t total = (int64_t)a.B * a.F * a.H * a.W * (a.D / 2);
-    int64_t blocks = cdiv64(total, 256); if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
     LTX_CHECK_LAUNCH();
     return LTX_OK;
 }
