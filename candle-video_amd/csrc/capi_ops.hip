@@ -3,6 +3,7 @@
 #include "../../include/ltxhip_ops.h"
 #include "../../include/ltxhip_upsampler_st.h"
 #include "../../include/ltxhip_stg.h"
+#include "../../include/ltxhip_stepcache.h"
 
 static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
 
@@ -475,4 +476,24 @@ extern "C" int ltx_op_dit_plan(int heads, int head_dim, int model_dtype, int io_
     const int64_t v[LTX_DIT_PLAN_FIELDS] = {p.M, p.MK, p.NB, p.Sg, p.seg, p.ldqkv, p.fold_q2, p.presum, p.nfold, p.defer_ff2, p.ff2_parts, p.dense_qkv, p.fold_q};
     for (int i = 0; i < LTX_DIT_PLAN_FIELDS; ++i) out[i] = v[i];
     return LTX_OK;
+}
+
+// ---- the step cache's kernels on their own (include/ltxhip_stepcache.h) ----
+extern "C" size_t ltx_op_step_measure_ws_bytes(int64_t rows, int D, ltx_dtype dtype) {
+    return (size_t)ltx_step_measure_blocks(rows, D, dtc((int)dtype)) * 2 * sizeof(double);
+}
+extern "C" int ltx_op_step_measure(const void* h, void* prev, const float* shift, const float* scale, int mod_stride, int64_t rows, int D,
+                                   int64_t rows_per_batch, float eps, ltx_dtype dtype, int first, void* ws, double* sums, ltx_stream stream) {
+    if (!h || !prev || !shift || !scale || !ws || !sums) LTX_FAIL(LTX_ERR_ARG, "ltx_op_step_measure: null tensor");
+    if (dtype != LTX_F32 && dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_op_step_measure: bad dtype");
+    if (rows < 1 || rows_per_batch < 1 || mod_stride < D) LTX_FAIL(LTX_ERR_ARG, "ltx_op_step_measure: rows and rows_per_batch must be at least 1 and mod_stride at least D");
+    StepMeasureArgs a;
+    a.h = h; a.prev = prev; a.shift = shift; a.scale = scale; a.mod_stride = mod_stride; a.rows = rows; a.D = D; a.rows_per_batch = rows_per_batch;
+    a.eps = eps; a.first = first != 0; a.part = reinterpret_cast<double*>(ws);
+    LTX_TRY(ltx_launch_step_measure(a, dtc((int)dtype), (hipStream_t)stream));
+    return ltx_launch_step_measure_finish(a.part, ltx_step_measure_blocks(rows, D, dtc((int)dtype)), sums, (hipStream_t)stream);
+}
+extern "C" int ltx_op_step_residual(const void* h, void* r, int64_t rows, int D, ltx_dtype dtype, ltx_stream stream) {
+    if (dtype != LTX_F32 && dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_op_step_residual: bad dtype");
+    return ltx_launch_step_residual(h, r, rows, D, dtc((int)dtype), (hipStream_t)stream);
 }

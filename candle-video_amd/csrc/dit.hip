@@ -10,6 +10,8 @@
 #include "options.h"
 #include "../../include/ltxhip_cond.h"
 #include "../../include/ltxhip_stg.h"
+#include "../../include/ltxhip_stepcache.h"
+#include "../host/step_cache.h"
 #include "lora.h"
 
 struct DitBlock {
@@ -87,8 +89,11 @@ struct ltx_dit {
     struct { bool valid = false; const float* coords = nullptr; float rs[3] = {0, 0, 0}; bool has_rs = false; int B = 0, S = 0, F = 0, H = 0, W = 0; hipStream_t stream = nullptr; } rope_key;
     // every cache that is a function of the weights (wcache keeps its allocations; wfold_off and the GEMM plans are not touched):
     // the scaled-weight copies, the text contexts (k / v projections and vo = V Wo2^T, DitCtx), the norm fold's per-timestep vectors.
-    // A cache added to the forward is added HERE and to release_caches.
+    // A cache added to the forward is added HERE and to release_caches.  Caches that live outside the handle (ltx_step_cache: its
+    // residuals are block outputs) compare weights_epoch instead.
+    uint64_t weights_epoch = 0;
     void invalidate_weight_derived() {
+        ++weights_epoch;
         for (auto& e : wcache) e.valid = false;
         for (auto& e : ctxs) e.valid = false;
         for (auto& e : tcache) e.cfold_valid = false;
@@ -115,6 +120,30 @@ struct ltx_dit {
         release_caches();
     }
 };
+
+// The step cache (include/ltxhip_stepcache.h): the previous measurement of block 0's modulated input, the block residuals per cache
+// row, and the policy's two words of state (host/step_cache.h).
+struct ltx_step_cache {
+    ltx_dit* dit = nullptr;
+    struct Row { bool valid = false; int S = 0; uint64_t epoch = 0; };
+    std::vector<Row> rows;
+    DevBuf prev, resid, parts, sums;      // [B * S, D] model dtype; [rows][resid_S][D] model dtype; f64 pairs; f64 [2]
+    int64_t prev_rows = 0; int resid_S = 0;
+    double* host = nullptr;               // pinned [2]
+    hipStream_t stream = nullptr; bool used = false;      // the stream of the last launch that touched the buffers
+    StepCacheState st;
+    void forget() { st = StepCacheState(); for (auto& r : rows) r.valid = false; }
+    void* resid_row(int row) const { return (char*)resid.p + (size_t)row * resid_S * dit->D * ltx_dt_size(dit->dtype); }
+    // null: row holds a residual for S under the present weights; else why not
+    const char* row_unusable(int row, int S) const {
+        const Row& r = rows[(size_t)row];
+        if (!r.valid) return "holds no residual (never computed, or the cache was reset)";
+        if (r.S != S) return "holds the residual of another sequence length";
+        if (r.epoch != dit->weights_epoch) return "holds a residual of other weights (the adapters changed)";
+        return nullptr;
+    }
+};
+struct StepCacheUse { ltx_step_cache* c = nullptr; int row0 = 0; bool reuse = false; };      // a forward through cache rows [row0, row0 + B)
 
 namespace {
 
@@ -837,7 +866,7 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
 int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float* timestep, int G,
                    const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
                    const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
-                   ltx_dtype io_dtype, void* out, ltx_stream stream) {
+                   ltx_dtype io_dtype, void* out, ltx_stream stream, const StepCacheUse* sc = nullptr) {
     if (B < 1 || B > 8) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: internal batch chunk must be 1..8");
     if (S < 1 || K < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: empty sequence");
     if (!video_coords && (int64_t)num_frames * height * width != S)
@@ -858,22 +887,44 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
         {&m->temb, nte * 6 * D * esz}, {&m->cosb, rope}, {&m->sinb, rope}, {&m->bias, MK * sizeof(float)}, {&m->outT, M * c.out_channels * esz},
         {&m->rsq, p.fold_q2 ? part : 0}, {&m->hsq, p.presum ? part : 0}, {&m->parts, p.defer_ff2 ? (size_t)p.ff2_parts * M * D * sizeof(float) : 0}, {&m->orig, skip_layer_mask ? MD : 0}};
     for (const auto& w : ws) LTX_TRY(w.first->ensure(w.second));
+    const bool reuse = sc && sc->reuse;
+    if (reuse) {
+        for (int b = 0; b < B; ++b)
+            if (const char* why = sc->c->row_unusable(sc->row0 + b, S))
+                LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_cached: reuse asked of cache row " + std::to_string(sc->row0 + b) + ", which " + why);
+    } else if (sc) {      // the residuals are laid out for one sequence length: another one starts the cache's rows afresh
+        ltx_step_cache* k = sc->c;
+        if (k->resid_S != S) { for (auto& r : k->rows) r.valid = false; k->resid_S = S; }
+        LTX_TRY(k->resid.ensure(k->rows.size() * (size_t)S * D * esz));
+        for (int b = 0; b < B; ++b) k->rows[(size_t)sc->row0 + b].valid = false;
+    }
 
     // inputs -> model dtype (:1045-1047)
     LTX_TRY(ltx_launch_cast(hidden, p.iodt, m->xin.p, dt, p.M * c.in_channels, s));
-    LTX_TRY(ltx_linear(m->proj_in, m->xin.p, c.in_channels, m->h.p, D, (int)p.M, dt, EPI_BIAS, s));
+    // a re-used step: h = proj_in(x) + (h_after_blocks - h_after_proj_in) of the rows' last computed forward, in the projection's epilogue
+    if (reuse) LTX_TRY(ltx_linear(m->proj_in, m->xin.p, c.in_channels, m->h.p, D, (int)p.M, dt, EPI_RESID, s, sc->c->resid_row(sc->row0), D));
+    else LTX_TRY(ltx_linear(m->proj_in, m->xin.p, c.in_channels, m->h.p, D, (int)p.M, dt, EPI_BIAS, s));
+    if (sc && !reuse) HIP_TRY(hipMemcpyAsync(sc->c->resid_row(sc->row0), m->h.p, MD, hipMemcpyDeviceToDevice, s));
 
     DitLayerIn in; in.skip_layer_mask = skip_layer_mask;
-    LTX_TRY(G == 1 ? time_tables(m, p, timestep, B, s, &in.tab) : group_tables(m, p, timestep, s, &in.tab));
-    LTX_TRY(scaled_weights(m, p, timestep, in.tab.ada, s, &in.we));
+    // a re-used step reads the final norm's table alone: the norm fold's per-timestep vectors (two weight streams per layer) are the
+    // blocks' and are not built for it
+    DitPlan pt = p; if (reuse) pt.nfold = false;
+    LTX_TRY(G == 1 ? time_tables(m, pt, timestep, B, s, &in.tab) : group_tables(m, pt, timestep, s, &in.tab));
     DitCtx* ctx = nullptr;
-    LTX_TRY(text_context(m, p, enc, enc_mask, s, &ctx)); in.ctx = ctx;
-    in.fold_vo = ctx->fold_vo;
-    LTX_TRY(rope_tables(m, p, num_frames, height, width, rope_scale, video_coords, s));
-
     DitCarry st;
-    for (int l = 0; l < L; ++l)
-        if (block_runs(m, skip_layer_mask, B, l)) LTX_TRY(dit_block(m, p, l, in, st, s));
+    if (!reuse) {
+        LTX_TRY(scaled_weights(m, p, timestep, in.tab.ada, s, &in.we));
+        LTX_TRY(text_context(m, p, enc, enc_mask, s, &ctx)); in.ctx = ctx;
+        in.fold_vo = ctx->fold_vo;
+        LTX_TRY(rope_tables(m, p, num_frames, height, width, rope_scale, video_coords, s));
+
+        for (int l = 0; l < L; ++l)
+            if (block_runs(m, skip_layer_mask, B, l)) LTX_TRY(dit_block(m, p, l, in, st, s));
+    }
+    // the block residual of a computed step: once h is complete - with a deferred ff2 that is behind the final norm, which finishes the rows
+    const bool resid_late = sc && !reuse && st.pending;
+    if (sc && !reuse && !resid_late) LTX_TRY(ltx_launch_step_residual(m->h.p, sc->c->resid_row(sc->row0), p.M, D, dt, s));
 
     // final LayerNorm (no affine) + modulation (:1126-1161), proj_out (:1163)
     RowNormArgs rn; rn.x = m->h.p; rn.y = m->n.p; rn.rows = p.M; rn.D = D; rn.ldx = D; rn.ldy = D;
@@ -881,10 +932,13 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
     rn.rows_per_batch = p.Sg; rn.mod_stride = D;
     st.take_pending(rn, m, p);
     LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+    if (resid_late) LTX_TRY(ltx_launch_step_residual(m->h.p, sc->c->resid_row(sc->row0), p.M, D, dt, s));
+    if (sc && !reuse)
+        for (int b = 0; b < B; ++b) sc->c->rows[(size_t)sc->row0 + b] = {true, S, m->weights_epoch};
     void* dst = p.iodt == dt ? out : m->outT.p;
     LTX_TRY(ltx_linear(m->proj_out, m->n.p, D, dst, c.out_channels, (int)p.M, dt, EPI_BIAS, s));
     if (p.iodt != dt) LTX_TRY(ltx_launch_cast(m->outT.p, dt, out, p.iodt, p.M * c.out_channels, s));
-    if (!m->ctx_mode) ctx->valid = false;
+    if (ctx && !m->ctx_mode) ctx->valid = false;
     return LTX_OK;
 }
 
@@ -896,7 +950,7 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
 int dit_forward_chunks(ltx_dit* m, const void* hidden, const void* enc, const float* timestep, int F,
                        const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
                        const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
-                       ltx_dtype io_dtype, void* out, ltx_stream stream) {
+                       ltx_dtype io_dtype, void* out, ltx_stream stream, const StepCacheUse* sc = nullptr) {
     const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
     const int L = m->cfg.num_layers;
     if (skip_layer_mask && m->stg_mode != LTX_STG_TRANSFORMER_BLOCK)      // the attention modes replace an operand of to_out: there is nothing to blend
@@ -921,10 +975,11 @@ int dit_forward_chunks(ltx_dit* m, const void* hidden, const void* enc, const fl
             for (int b = 0; b < bc; ++b) for (int f = 1; f < F; ++f) uniform = uniform && memcmp(&tc[(size_t)b * F + f], &tc[(size_t)b * F], sizeof(float)) == 0;
             if (uniform) { for (int b = 0; b < bc; ++b) t_row[b] = tc[(size_t)b * F]; tc = t_row; } else G = F;
         }
-        LTX_TRY(dit_forward_b8(m, (const char*)hidden + (size_t)b0 * S * m->cfg.in_channels * esz, (const char*)enc + (size_t)b0 * K * m->cfg.caption_channels * esz,
+        StepCacheUse use; if (sc) { use = *sc; use.row0 += b0; }
+        LTX_TRY(dit_forward_b8(m, (const char*)hidden + (size_t)b0 * S * m->cfg.in_channels * esz, enc ? (const char*)enc + (size_t)b0 * K * m->cfg.caption_channels * esz : nullptr,
                                tc, G, enc_mask ? enc_mask + (size_t)b0 * K : nullptr, bc, S, K, num_frames, height, width, rope_scale,
                                video_coords ? video_coords + (size_t)b0 * S * 3 : nullptr, slm, io_dtype,
-                               (char*)out + (size_t)b0 * S * m->cfg.out_channels * esz, stream));
+                               (char*)out + (size_t)b0 * S * m->cfg.out_channels * esz, stream, sc ? &use : nullptr));
     }
     return LTX_OK;
 }
@@ -958,6 +1013,157 @@ extern "C" int ltx_dit_context_cache(ltx_dit* m, int enable) {
     m->rope_key.valid = false;
     m->ctx_mode = enable != 0;
     return LTX_OK;
+}
+
+// ---- step cache (include/ltxhip_stepcache.h) ----
+extern "C" void ltx_step_cache_params_default(ltx_step_cache_params* p) {
+    if (!p) return;
+    const StepCachePolicy d;
+    p->rel_l1_thresh = d.thresh; for (int k = 0; k < 5; ++k) p->coeff[k] = d.coeff[k];
+    p->pattern = nullptr; p->n_pattern = 0;
+}
+
+extern "C" int ltx_step_cache_create(ltx_dit* dit, int rows, ltx_step_cache** out) {
+    if (!dit || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_create: null argument");
+    *out = nullptr;
+    if (rows < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_create: rows must be at least 1, got " + std::to_string(rows));
+    if (!ltx_step_measure_blocks(1, dit->D, dit->dtype))
+        LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_step_cache_create: inner dim " + std::to_string(dit->D) + " is not a multiple of 128 the measure kernel serves");
+    HIP_TRY(hipSetDevice(dit->device));
+    ltx_step_cache* c = new ltx_step_cache();
+    c->dit = dit; c->rows.resize((size_t)rows);
+    int rc = c->sums.ensure(2 * sizeof(double));
+    if (rc == LTX_OK && hipHostMalloc((void**)&c->host, 2 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); ltx_set_error("ltx_step_cache_create: hipHostMalloc of the result pair"); rc = LTX_ERR_HIP;
+    }
+    if (rc != LTX_OK) { c->sums.release(); delete c; return rc; }
+    *out = c;
+    return LTX_OK;
+}
+
+extern "C" void ltx_step_cache_destroy(ltx_step_cache* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->dit->device);
+    if (c->used) (void)hipStreamSynchronize(c->stream);      // (launches enqueued on it may still read the buffers)
+    c->prev.release(); c->resid.release(); c->parts.release(); c->sums.release();
+    if (c->host) (void)hipHostFree(c->host);
+    delete c;
+}
+
+extern "C" int ltx_step_cache_reset(ltx_step_cache* c) {
+    if (!c) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_reset: null handle");
+    c->forget();
+    return LTX_OK;
+}
+
+static int step_cache_policy_of(const ltx_step_cache_params* params, const char* who, StepCachePolicy* pol) {
+    if (!params) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null step cache parameters");
+    pol->thresh = params->rel_l1_thresh; for (int k = 0; k < 5; ++k) pol->coeff[k] = params->coeff[k];
+    pol->pattern = params->pattern; pol->n_pattern = params->n_pattern;
+    if (const char* why = step_cache_policy_error(*pol)) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": " + why);
+    return LTX_OK;
+}
+// (host/pipeline.hip checks a call's parameters before it touches the device; declared in model_util.h)
+int ltx_step_cache_params_check(const ltx_step_cache_params* params, const char* who) { StepCachePolicy pol; return step_cache_policy_of(params, who, &pol); }
+
+extern "C" int ltx_step_cache_decide(ltx_step_cache* c, ltx_dit* m, const void* hidden, const float* timestep, int frames,
+                                     int B, int S, int num_frames, int height, int width, ltx_dtype io_dtype,
+                                     int step, int n_steps, const ltx_step_cache_params* params, int* reuse, float* distance, ltx_stream stream) {
+    if (!c || !m || !hidden || !timestep || !reuse) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_decide: null argument");
+    if (c->dit != m) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_decide: the cache was created for another model handle");
+    if (B < 1 || S < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_decide: batch and sequence must be at least 1");
+    if (n_steps < 1 || step < 0 || step >= n_steps) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_decide: step " + std::to_string(step) + " outside 0.." + std::to_string(n_steps - 1));
+    if (io_dtype != LTX_F32 && io_dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_decide: bad dtype");
+    if (frames && (num_frames < 1 || height < 1 || width < 1 || (int64_t)num_frames * height * width != S))
+        LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_decide: with per-frame timesteps S must equal num_frames*height*width");
+    StepCachePolicy pol;
+    LTX_TRY(step_cache_policy_of(params, "ltx_step_cache_decide", &pol));
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ltx_dit_config& cfg = m->cfg;
+    const int dt = m->dtype, D = m->D, F = frames ? num_frames : 0;
+    const size_t esz = ltx_dt_size(dt), iosz = io_dtype == LTX_BF16 ? 2 : 4;
+    const int64_t M = (int64_t)B * S;
+    LTX_TRY(c->prev.ensure((size_t)M * D * esz));
+    c->stream = s; c->used = true;
+    if (c->prev_rows != M) { c->st.have_prev = false; c->prev_rows = M; }      // another geometry: nothing to be a distance from
+    const bool first = !c->st.have_prev;
+    int64_t nblk = 0;
+    for (int b0 = 0; b0 < B; b0 += 8) nblk += ltx_step_measure_blocks((int64_t)(B - b0 < 8 ? B - b0 : 8) * S, D, dt);
+    LTX_TRY(c->parts.ensure((size_t)nblk * 2 * sizeof(double)));
+    float t_row[8];
+    int64_t blk0 = 0;
+    for (int b0 = 0; b0 < B; b0 += 8) {      // the chunks of dit_forward_chunks, with its collapse of rows whose frames share one timestep
+        const int bc = B - b0 < 8 ? B - b0 : 8;
+        const float* tc = timestep + (size_t)b0 * (F ? F : 1);
+        int G = 1;
+        if (F) {
+            bool uniform = true;
+            for (int b = 0; b < bc; ++b) for (int f = 1; f < F; ++f) uniform = uniform && memcmp(&tc[(size_t)b * F + f], &tc[(size_t)b * F], sizeof(float)) == 0;
+            if (uniform) { for (int b = 0; b < bc; ++b) t_row[b] = tc[(size_t)b * F]; tc = t_row; } else G = F;
+        }
+        DitPlan p = ltx_dit_plan(cfg, dt, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, bc, S, 1, G, false);
+        p.nfold = false;                                        // (the tables alone: the norm fold's vectors are the forward's to build)
+        const size_t nte = p.NB == p.B ? (size_t)p.B : 8;
+        const std::pair<DevBuf*, size_t> ws[] = {
+            {&m->xin, p.M * cfg.in_channels * esz}, {&m->h, p.M * D * esz}, {&m->tproj, nte * 256 * esz}, {&m->e1, nte * D * esz}, {&m->emb, nte * D * esz},
+            {&m->embs, nte * D * esz}, {&m->temb, nte * 6 * D * esz}};
+        for (const auto& w : ws) LTX_TRY(w.first->ensure(w.second));
+        LTX_TRY(ltx_launch_cast((const char*)hidden + (size_t)b0 * S * cfg.in_channels * iosz, p.iodt, m->xin.p, dt, p.M * cfg.in_channels, s));
+        LTX_TRY(ltx_linear(m->proj_in, m->xin.p, cfg.in_channels, m->h.p, D, (int)p.M, dt, EPI_BIAS, s));
+        DitTables tab;
+        LTX_TRY(G == 1 ? time_tables(m, p, tc, bc, s, &tab) : group_tables(m, p, tc, s, &tab));
+        StepMeasureArgs a;      // block 0's shift_msa / scale_msa: rows 0 and 1 of its table
+        a.h = m->h.p; a.prev = (char*)c->prev.p + (size_t)b0 * S * D * esz; a.shift = tab.ada; a.scale = tab.ada + D; a.mod_stride = 6 * D;
+        a.rows = p.M; a.D = D; a.rows_per_batch = p.Sg; a.eps = cfg.norm_eps; a.first = first ? 1 : 0; a.part = c->parts.as<double>() + 2 * blk0;
+        LTX_TRY(ltx_launch_step_measure(a, dt, s));
+        blk0 += ltx_step_measure_blocks(p.M, D, dt);
+    }
+    LTX_TRY(ltx_launch_step_measure_finish(c->parts.as<double>(), nblk, c->sums.as<double>(), s));
+    HIP_TRY(hipMemcpyAsync(c->host, c->sums.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));                           // the one wait of a step: the decision is the host's
+    const double num = c->host[0], den = c->host[1];
+    *reuse = step_cache_decide(&c->st, pol, step, n_steps, num, den, true);
+    if (distance) *distance = first ? 0.0f : (float)(num / den);
+    return LTX_OK;
+}
+
+extern "C" int ltx_step_cache_require(ltx_step_cache* c, const ltx_dit* m, int row0, int nrows, int S, int* reuse) {
+    if (!c || !m || !reuse) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_require: null argument");
+    if (c->dit != m) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_require: the cache was created for another model handle");
+    if (row0 < 0 || nrows < 1 || (size_t)row0 + (size_t)nrows > c->rows.size())
+        LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_require: rows " + std::to_string(row0) + ".." + std::to_string(row0 + nrows - 1) + " outside the cache's " + std::to_string(c->rows.size()));
+    if (!*reuse) return LTX_OK;
+    for (int r = row0; r < row0 + nrows; ++r)
+        if (c->row_unusable(r, S)) { *reuse = step_cache_demote(&c->st, *reuse, false); break; }
+    return LTX_OK;
+}
+
+extern "C" int ltx_dit_forward_cached(ltx_dit* m, ltx_step_cache* c, int row0, int reuse, int frames,
+                                      const void* hidden, const void* enc, const float* timestep, const float* enc_mask,
+                                      int B, int S, int K, int num_frames, int height, int width,
+                                      const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
+                                      ltx_dtype io_dtype, void* out, ltx_stream stream) {
+    if (!m || !c || !hidden || !timestep || !out || (!reuse && !enc)) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_cached: null argument");
+    if (c->dit != m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_cached: the cache was created for another model handle");
+    if (B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_cached: batch must be at least 1");
+    if (row0 < 0 || (size_t)row0 + (size_t)B > c->rows.size())
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_cached: rows " + std::to_string(row0) + ".." + std::to_string(row0 + B - 1) + " outside the cache's " + std::to_string(c->rows.size()));
+    if (frames && (num_frames < 1 || height < 1 || width < 1 || (int64_t)num_frames * height * width != S))
+        LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward_cached: with per-frame timesteps S must equal num_frames*height*width (tokens in pack order)");
+    const StepCacheUse use{c, row0, reuse != 0};
+    c->stream = (hipStream_t)stream; c->used = true;
+    return dit_forward_chunks(m, hidden, enc, timestep, frames ? num_frames : 0, enc_mask, B, S, K, num_frames, height, width, rope_scale, video_coords,
+                              reuse ? nullptr : skip_layer_mask, io_dtype, out, stream, &use);
+}
+
+extern "C" int ltx_step_cache_read_residual(const ltx_step_cache* c, int row, float* dst, ltx_stream stream) {
+    if (!c || !dst) LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_read_residual: null argument");
+    if (row < 0 || (size_t)row >= c->rows.size() || !c->rows[(size_t)row].valid)
+        LTX_FAIL(LTX_ERR_ARG, "ltx_step_cache_read_residual: row " + std::to_string(row) + " holds no residual");
+    HIP_TRY(hipSetDevice(c->dit->device));
+    const_cast<ltx_step_cache*>(c)->stream = (hipStream_t)stream;
+    return ltx_launch_cast(c->resid_row(row), c->dit->dtype, dst, LTX_DT_F32, (int64_t)c->resid_S * c->dit->D, (hipStream_t)stream);
 }
 
 // ---- LoRA adapters (include/ltxhip_lora.h) ----

@@ -199,6 +199,21 @@ NormRouteArgs ltx_rownorm_route_args(const RowNormArgs& a, int dtype);
 NormDecision ltx_rownorm_route(const NormRouteArgs& r);
 const char* ltx_rownorm_route_name(NormRoute r);      // "narrow", "block", "wide", "reread", "presum", "presum_lean", "wide_defer", ... ; "refused"
 
+// ---------------- step cache (stepcache.hip; include/ltxhip_stepcache.h) ----------------
+// One pass over h and prev [rows, D] (T): m = round_T(rms_norm(h, eps) * (1 + scale[g]) + shift[g]), g = row / rows_per_batch (f32 tables,
+// row stride mod_stride - RowNormArgs' indexing), written over prev; the block's sum |m - prev| and sum |prev| (f64) go to
+// part[2 * block], part[2 * block + 1].  first: prev is not read and both sums are 0.  D: a multiple of 128 that fits 16 chunks a lane.
+struct StepMeasureArgs {
+    const void* h = nullptr; void* prev = nullptr;
+    const float* shift = nullptr; const float* scale = nullptr; int mod_stride = 0;
+    int64_t rows = 0; int D = 0; int64_t rows_per_batch = 1; float eps = 1e-6f; int first = 0;
+    double* part = nullptr;       // ltx_step_measure_blocks(rows, D, dtype) pairs
+};
+int64_t ltx_step_measure_blocks(int64_t rows, int D, int dtype);      // blocks (= partial pairs) of the launch; 0: the shape is not served
+int ltx_launch_step_measure(const StepMeasureArgs& a, int dtype, hipStream_t s);
+int ltx_launch_step_measure_finish(const double* part, int64_t nblk, double* sums, hipStream_t s);      // sums[0 .. 2) = the pairs added in one fixed tree
+int ltx_launch_step_residual(const void* h, void* r, int64_t rows, int D, int dtype, hipStream_t s);     // r = h - r in place, 16-byte accesses
+
 struct QkNormRopeArgs {
     void* x = nullptr;            // in place, nseg segments of width D at x + j*D in each row
     int64_t rows = 0; int D = 0; int ld = 0; int nseg = 1;

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "../../include/ltxhip.h"
+#include "../../include/ltxhip_stepcache.h"
 
 // thread-local "the last failure on this thread was an out-of-memory hipMalloc" (DevBuf::ensure); cleared by the reader
 void ltx_note_oom();
@@ -95,6 +96,9 @@ struct DitPlan {
     bool fold_q = false;          // self-attention q leaves its norm multiplied by scale * log2(e)
 };
 DitPlan ltx_dit_plan(const ltx_dit_config& c, int dt, int iodt, int B, int S, int K, int G, bool skip_mask);
+
+// the caller's step cache parameters (include/ltxhip_stepcache.h) checked before anything touches the device; `who` leads the message (dit.hip)
+int ltx_step_cache_params_check(const ltx_step_cache_params* params, const char* who);
 
 // sigmas [N + 1] and truncated timesteps [N] of ltx_pipeline_call(p) at S latent tokens (host/pipeline.hip)
 int ltx_pipeline_schedule(const ltx_pipeline_params* p, int S, std::vector<float>* sig, std::vector<int64_t>* ts);

@@ -11,6 +11,7 @@
 #include "../../include/ltxhip_cond.h"
 #include "../../include/ltxhip_guidance.h"
 #include "../../include/ltxhip_keyframes.h"
+#include "../../include/ltxhip_stepcache.h"
 #include "cond_plan.h"
 #include "step_plan.h"
 
@@ -471,8 +472,13 @@ struct BranchBatch {
     }
 };
 
-// cr: null - no conditioning; plan: the branches, scales and perturbed blocks of every step (host/step_plan.h)
-static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const StepPlan& plan, const PipeIO& io) {
+// The step cache of a call (include/ltxhip_stepcache.h): the caller's parameters and where the decisions go.  Null in pipeline_run: not
+// one launch or wait of the loop changes.
+struct PipeStepCache { const ltx_step_cache_params* params; unsigned char* reused_out; float* distance_out; };
+
+// cr: null - no conditioning; plan: the branches, scales and perturbed blocks of every step (host/step_plan.h); scd: the step cache or null
+static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const StepPlan& plan, const PipeIO& io,
+                        const PipeStepCache* scd = nullptr) {
     float* const latents = io.latents; const int B = io.B, K = io.K;
     if (!dit || !p || !latents || !io.prompt_embeds || !io.prompt_mask) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: null argument");
     if (!p->output_latent && (!vae || !io.out_video)) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call: decode requested without vae/out_video");
@@ -545,6 +551,12 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
     }
     struct CtxScope { ltx_dit* d; ~CtxScope() { (void)ltx_dit_context_cache(d, 0); } } ctx_scope{dit};
     LTX_TRY(ltx_dit_context_cache(dit, 1));     // embeddings/masks are step-invariant inside one call
+    // the step cache: 3 * B rows, one set per branch slot of host/step_plan.h; it lives for this call
+    struct CacheScope { ltx_step_cache* c = nullptr; ~CacheScope() { ltx_step_cache_destroy(c); } } cache;
+    if (scd) {
+        LTX_TRY(ltx_step_cache_create(dit, 3 * B, &cache.c));
+        for (int i = 0; i < N; ++i) { if (scd->reused_out) scd->reused_out[i] = 0; if (scd->distance_out) scd->distance_out[i] = 0.0f; }
+    }
     // denoising loop (:860-994)
     const bool hooked = p->interrupt != nullptr || p->on_step != nullptr;
     bool stopped = false; int steps_run = 0;
@@ -576,16 +588,25 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
             LTX_TRY(ltx_launch_cond_noise(latents, pc.kf_clean.as<float>(), cr->cond_noise + (size_t)i * B * n, cr->hard.data(), (int)cr->hard.size(), B, G, group_elems, kn, s));
         }
         const unsigned char* hold_i = cr ? pc.hold.as<unsigned char>() + (cr->hold_rows > 1 ? (size_t)i * B * G : 0) : nullptr;
-        auto forward = [&](const void* x, const void* emb, const float* mk, int rows, const float* vc, const float* skip, void* pred) -> int {
+        int reuse = 0;
+        if (scd) {                                   // one measurement of the B videos and one decision for every branch of the step
+            float dist = 0.0f;
+            LTX_TRY(ltx_step_cache_decide(cache.c, dit, latents, cr ? tframes.data() : tvals, cr ? G : 0, B, S, cr ? G : F, H, W, LTX_F32, i, N, scd->params, &reuse, &dist, s));
+            LTX_TRY(ltx_step_cache_require(cache.c, dit, st.slot0 * B, st.nbr * B, S, &reuse));      // (a branch the steps before did not run)
+            if (scd->reused_out) scd->reused_out[i] = (unsigned char)reuse;
+            if (scd->distance_out) scd->distance_out[i] = dist;
+        }
+        auto forward = [&](const void* x, const void* emb, const float* mk, int rows, const float* vc, const float* skip, void* pred, int slot) -> int {
+            if (scd) return ltx_dit_forward_cached(dit, cache.c, slot * B, reuse, cr ? G : 0, x, emb, cr ? tframes.data() : tvals, mk, rows, S, K, cr ? G : F, H, W, nullptr, vc, skip, LTX_F32, pred, s);
             if (cr) return ltx_dit_forward_frames(dit, x, emb, tframes.data(), mk, rows, S, K, G, H, W, nullptr, vc, skip, LTX_F32, pred, s);
             return ltx_dit_forward(dit, x, emb, tvals, mk, rows, S, K, F, H, W, nullptr, vc, skip, LTX_F32, pred, s);
         };
         if (st.stg) step_skip_rows(L, frows, st.batched ? (st.nbr - 1) * B : 0, B, st.guide.skip, st.guide.n_skip, &slm);      // (the perturbed branch: the last rows)
         if (st.batched) {
             for (int r = 0; r < st.nbr; ++r) HIP_TRY(hipMemcpyAsync(pc.g_lat.as<float>() + (size_t)r * B * n, latents, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            LTX_TRY(forward(pc.g_lat.p, bb.emb(st.slot0), bb.mask(st.slot0), st.rows, bb.coords(st.slot0), st.stg ? slm.data() : nullptr, bb.pred(st.slot0)));
+            LTX_TRY(forward(pc.g_lat.p, bb.emb(st.slot0), bb.mask(st.slot0), st.rows, bb.coords(st.slot0), st.stg ? slm.data() : nullptr, bb.pred(st.slot0), st.slot0));
         } else {
-            for (int k = st.slot0; k < st.slot0 + st.nbr; ++k) LTX_TRY(forward(latents, bb.src_emb[k], bb.src_mask[k], B, coords, k == 2 ? slm.data() : nullptr, bb.pred(k)));
+            for (int k = st.slot0; k < st.slot0 + st.nbr; ++k) LTX_TRY(forward(latents, bb.src_emb[k], bb.src_mask[k], B, coords, k == 2 ? slm.data() : nullptr, bb.pred(k), k));
         }
         HIP_TRY(hipEventRecord(e1, s));
         // guidance mix (:941-962) on the branches that ran + scheduler.step (:987; scheduler.rs:544-581): dt = sigma_next - sigma; held groups keep their bits
@@ -633,14 +654,14 @@ static int pipeline_run(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p
 }
 
 // the unscheduled call: the constant plan of the scalars of `p`
-static int pipeline_run_params(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const PipeIO& io) {
+static int pipeline_run_params(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const CondRun* cr, const PipeIO& io, const PipeStepCache* scd = nullptr) {
     StepPlan plan;
     if (p) {
         StepGuide g; g.g = p->guidance_scale; g.s = p->stg_scale; g.r = p->guidance_rescale;
         g.skip = p->skip_block_list; g.n_skip = p->skip_block_list ? p->n_skip_blocks : 0;
         step_plan_constant(p->num_inference_steps, io.B, g, ltx_opt().guidance_batch != 0, &plan);
     }
-    return pipeline_run(dit, vae, p, cr, plan, io);
+    return pipeline_run(dit, vae, p, cr, plan, io, scd);
 }
 
 extern "C" int ltx_pipeline_call(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p,
@@ -675,7 +696,7 @@ extern "C" int ltx_pipeline_call_cond(ltx_dit* dit, ltx_vae* vae, const ltx_pipe
 // ---- the pipeline calls under a guidance schedule (include/ltxhip_guidance.h) ----
 // cr: the conditioned run or null; sig: the call's sigmas (ltx_pipeline_schedule at the grid's tokens)
 static int pipeline_run_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched, const CondRun* cr,
-                              const std::vector<float>& sig, const PipeIO& io) {
+                              const std::vector<float>& sig, const PipeIO& io, const PipeStepCache* scd = nullptr) {
     const int N = p->num_inference_steps;
     std::vector<int> entry((size_t)N, 0);
     LTX_TRY(ltx_guidance_schedule_resolve(sched, sig.data(), N, entry.data()));
@@ -689,7 +710,7 @@ static int pipeline_run_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_par
     }
     StepPlan plan;
     step_plan_scheduled(guides.data(), N, io.B, sched->cfg_star, sched->rescale_form, ltx_opt().guidance_batch != 0, &plan);
-    return pipeline_run(dit, vae, p, cr, plan, io);
+    return pipeline_run(dit, vae, p, cr, plan, io, scd);
 }
 
 extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched,
@@ -709,6 +730,31 @@ extern "C" int ltx_pipeline_call_sched(ltx_dit* dit, ltx_vae* vae, const ltx_pip
     CondRun cr;
     if (any) cond_run_from_hold(cond->hold, B, lg.F, &cr);
     return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, {latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream});
+}
+
+// ---- the step cache (include/ltxhip_stepcache.h): ltx_pipeline_call / _cond / _sched with one decision per step ----
+extern "C" int ltx_pipeline_call_cached(ltx_dit* dit, ltx_vae* vae, const ltx_pipeline_params* p, const ltx_guidance_schedule* sched,
+                                        const ltx_conditioning* cond, const ltx_step_cache_params* cache_params,
+                                        float* latents, const float* prompt_embeds, const float* prompt_mask,
+                                        const float* neg_embeds, const float* neg_mask, const float* decode_noise,
+                                        int B, int K, float* out_video, ltx_stream stream,
+                                        unsigned char* reused_out, float* distance_out) {
+    if (!dit || !p || B < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cached: null argument");
+    if (cond && !cond->hold) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cached: conditioning without a hold mask");
+    LTX_TRY(ltx_step_cache_params_check(cache_params, "ltx_pipeline_call_cached"));
+    LatentGeom lg; LTX_TRY(latent_geom(vae, p, &lg));
+    if (lg.ts_ratio < 1 || lg.sp_ratio < 1 || p->num_frames < 1) LTX_FAIL(LTX_ERR_ARG, "ltx_pipeline_call_cached: bad geometry");
+    const bool any = cond && any_held(cond->hold, B, lg.F);
+    CondRun cr;
+    if (any) cond_run_from_hold(cond->hold, B, lg.F, &cr);
+    const PipeStepCache scd{cache_params, reused_out, distance_out};
+    const PipeIO io{latents, prompt_embeds, prompt_mask, neg_embeds, neg_mask, decode_noise, B, K, out_video, stream};
+    if (!sched) return pipeline_run_params(dit, vae, p, any ? &cr : nullptr, io, &scd);
+    ltx_dit_config dc; LTX_TRY(ltx_dit_get_config(dit, &dc));
+    LTX_TRY(guidance_schedule_check(sched, dc.num_layers));
+    std::vector<float> sig; std::vector<int64_t> ts;
+    LTX_TRY(ltx_pipeline_schedule(p, lg.F * lg.H * lg.W, &sig, &ts));
+    return pipeline_run_sched(dit, vae, p, sched, any ? &cr : nullptr, sig, io, &scd);
 }
 
 // ---- keyframe conditioning (include/ltxhip_keyframes.h): the layout is host/cond_plan.h's, these entries hand it on ----

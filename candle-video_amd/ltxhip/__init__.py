@@ -370,6 +370,53 @@ for _name, _sig in _KEYFRAME_SIGS.items():
     _fn.restype = C.c_int
 
 
+class StepCacheParamsC(C.Structure):             # ltx_step_cache_params (include/ltxhip_stepcache.h)
+    _fields_ = [("rel_l1_thresh", C.c_float), ("coeff", C.c_float * 5), ("pattern", C.POINTER(C.c_ubyte)), ("n_pattern", C.c_int)]
+
+
+# include/ltxhip_stepcache.h (kept apart like the eight above)
+_STEPCACHE_SIGS = {
+    "ltx_step_cache_params_default": [_vp], "ltx_step_cache_create": [_vp, _i, _vp], "ltx_step_cache_destroy": [_vp], "ltx_step_cache_reset": [_vp],
+    "ltx_step_cache_decide": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "ltx_step_cache_require": [_vp, _vp, _i, _i, _i, _vp],
+    "ltx_dit_forward_cached": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
+    "ltx_step_cache_read_residual": [_vp, _i, _vp, _vp],
+    "ltx_pipeline_call_cached": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "ltx_op_step_measure_ws_bytes": [_i64, _i, _i],
+    "ltx_op_step_measure": [_vp, _vp, _vp, _vp, _i, _i64, _i, _i64, _f, _i, _i, _vp, _vp, _vp],
+    "ltx_op_step_residual": [_vp, _vp, _i64, _i, _i, _vp],
+}
+STEPCACHE_SYMBOLS = sorted(_STEPCACHE_SIGS)
+for _name, _sig in _STEPCACHE_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = None if _name in ("ltx_step_cache_params_default", "ltx_step_cache_destroy") else C.c_size_t if _name == "ltx_op_step_measure_ws_bytes" else C.c_int
+STEP_COMPUTE, STEP_REUSE = 1, 2                  # values of a step cache pattern (0: decide)
+
+
+@dataclass
+class StepCacheParams:
+    """ltx_step_cache_params: reuse the block residual while the accumulated poly(distance) stays below rel_l1_thresh (0: never);
+    coeff = (c0 .. c4), highest power first - a published fit for the checkpoint goes here; pattern: per step 0 decide, 1 compute,
+    2 reuse.  The rule is spelled out in include/ltxhip_stepcache.h."""
+    rel_l1_thresh: float = 0.0
+    coeff: Sequence[float] = (0.0, 0.0, 0.0, 1.0, 0.0)
+    pattern: Optional[Sequence[int]] = None
+
+    def to_c(self, keep: list) -> StepCacheParamsC:
+        if len(self.coeff) != 5:
+            raise LtxError("StepCacheParams: coeff has five values (c0 .. c4)")
+        c = StepCacheParamsC()
+        c.rel_l1_thresh = float(self.rel_l1_thresh)
+        c.coeff = (C.c_float * 5)(*[float(v) for v in self.coeff])
+        if self.pattern is not None and len(self.pattern) > 0:
+            if any(int(v) < 0 or int(v) > 255 for v in self.pattern):
+                raise LtxError("StepCacheParams: pattern values are 0 (decide), 1 (compute) or 2 (reuse)")
+            pt = (C.c_ubyte * len(self.pattern))(*[int(v) for v in self.pattern]); keep.append(pt)
+            c.pattern, c.n_pattern = C.cast(pt, C.POINTER(C.c_ubyte)), len(self.pattern)
+        return c
+
+
 @dataclass
 class GuidanceSchedule:
     """ltx_guidance_schedule: one (guidance_scale, stg_scale, rescale, perturbed block list) per entry; a step takes the entry whose
@@ -1544,6 +1591,136 @@ class LtxPipeline:
         return lat, video
 
 
+# ------------------------------------------------------------------ step cache (include/ltxhip_stepcache.h)
+class StepCache:
+    """ltx_step_cache: `rows` cache rows for forwards of `model` (the pipeline call uses 3 * B, one set per guidance branch)"""
+
+    def __init__(self, model: LtxVideoTransformer3DModel, rows: int):
+        self.model = model
+        self.rows = rows
+        self._h = C.c_void_p()
+        _check(lib.ltx_step_cache_create(model._h, int(rows), C.byref(self._h)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:
+            lib.ltx_step_cache_destroy(h)
+            self._h = None
+
+    def reset(self):
+        _check(lib.ltx_step_cache_reset(self._h))
+
+    def decide(self, hidden_states: torch.Tensor, timestep, num_frames: int, height: int, width: int, step: int, n_steps: int,
+               params: StepCacheParams, frames: bool = False):
+        """the measurement and the decision of a step for hidden_states [B, S, C] -> (reuse, distance); frames: timestep [B, num_frames]"""
+        io = hidden_states.dtype if hidden_states.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        h = _dev(hidden_states, io)
+        B, S, _ = h.shape
+        t = torch.as_tensor(timestep, dtype=torch.float32).detach().flatten().cpu().tolist()
+        if len(t) != B * (num_frames if frames else 1):
+            raise LtxError(f"timestep must have {B}{' x ' + str(num_frames) if frames else ''} entries")
+        keep = []
+        pc = params.to_c(keep)
+        reuse, dist = C.c_int(0), C.c_float(0.0)
+        _check(lib.ltx_step_cache_decide(self._h, self.model._h, _ptr(h), _floats(t), int(frames), B, S, num_frames, height, width, _dt(io),
+                                         int(step), int(n_steps), C.byref(pc), C.byref(reuse), C.byref(dist), _stream()))
+        return bool(reuse.value), dist.value
+
+    def require(self, row0: int, nrows: int, S: int, reuse: bool) -> bool:
+        """reuse, demoted to compute when one of the rows holds no residual for S (ltx_step_cache_require)"""
+        r = C.c_int(int(reuse))
+        _check(lib.ltx_step_cache_require(self._h, self.model._h, int(row0), int(nrows), int(S), C.byref(r)))
+        return bool(r.value)
+
+    def read_residual(self, row: int, S: int) -> torch.Tensor:
+        """the residual of a cache row as f32 [S, D]"""
+        D = self.model.config.num_attention_heads * self.model.config.attention_head_dim
+        out = torch.empty(S, D, dtype=torch.float32, device="cuda")
+        _check(lib.ltx_step_cache_read_residual(self._h, int(row), _ptr(out), _stream()))
+        return out
+
+
+def dit_forward_cached(model: LtxVideoTransformer3DModel, cache: StepCache, row0: int, reuse: bool, hidden_states: torch.Tensor,
+                       encoder_hidden_states: Optional[torch.Tensor], timestep, encoder_attention_mask: Optional[torch.Tensor],
+                       num_frames: int, height: int, width: int, rope_interpolation_scale=None, video_coords: Optional[torch.Tensor] = None,
+                       skip_layer_mask: Optional[torch.Tensor] = None, frames: bool = False, K: Optional[int] = None) -> torch.Tensor:
+    """model.forward (frames: model.forward_frames, timestep [B, num_frames]) through cache rows [row0, row0 + B)
+    (ltx_dit_forward_cached).  reuse: the blocks are not run; encoder_hidden_states may then be None (K: its token count)."""
+    io = hidden_states.dtype if hidden_states.dtype in (torch.float32, torch.bfloat16) else torch.float32
+    h = _dev(hidden_states, io)
+    e = _dev(encoder_hidden_states, io) if encoder_hidden_states is not None else None
+    B, S, _ = h.shape
+    K = e.shape[1] if e is not None else int(K or 1)
+    t = torch.as_tensor(timestep, dtype=torch.float32).detach().flatten().cpu().tolist()
+    if len(t) != B * (num_frames if frames else 1):
+        raise LtxError(f"timestep must have {B}{' x ' + str(num_frames) if frames else ''} entries")
+    m = _dev(encoder_attention_mask, torch.float32) if encoder_attention_mask is not None else None
+    vc = _dev(video_coords, torch.float32) if video_coords is not None else None
+    if getattr(model, "_ctx_cache", False) and ((e is not None and e.data_ptr() != encoder_hidden_states.data_ptr()) or (m is not None and m.data_ptr() != encoder_attention_mask.data_ptr())
+                                                or (vc is not None and vc.data_ptr() != video_coords.data_ptr())):
+        raise LtxError("context_cache(True) needs encoder_hidden_states / encoder_attention_mask / video_coords that are already contiguous "
+                       "device tensors of the dtype the call uses: a temporary copy has no stable identity")
+    slm = _floats(skip_layer_mask.detach().float().cpu().flatten().tolist()) if skip_layer_mask is not None else None
+    rs = _floats(rope_interpolation_scale) if rope_interpolation_scale is not None else None
+    out = torch.empty(B, S, model.config.out_channels, dtype=io, device=h.device)
+    _check(lib.ltx_dit_forward_cached(model._h, cache._h, int(row0), int(bool(reuse)), int(frames), _ptr(h), _ptr(e), _floats(t), _ptr(m), B, S, K,
+                                      num_frames, height, width, rs, _ptr(vc), slm, _dt(io), _ptr(out), _stream()))
+    return out
+
+
+def pipeline_call_cached(pipe: "LtxPipeline", args: PipelineCall, params: StepCacheParams, latents: torch.Tensor, prompt_embeds: torch.Tensor,
+                         prompt_attention_mask: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor] = None,
+                         negative_prompt_attention_mask: Optional[torch.Tensor] = None, decode_noise: Optional[torch.Tensor] = None,
+                         step_noise: Optional[torch.Tensor] = None, hold=None, schedule: Optional["GuidanceSchedule"] = None):
+    """LtxPipeline.call (plain, with `hold`, with `schedule`) under the step cache (ltx_pipeline_call_cached)
+    -> (latents, video or None, reused [N] list of bool, distance [N] list of float).  pipe.last_timing_ms is updated."""
+    lat = _dev(latents, torch.float32).clone()
+    pe = _dev(prompt_embeds, torch.float32)
+    pm = _dev(prompt_attention_mask, torch.float32)
+    ne = _dev(negative_prompt_embeds, torch.float32) if negative_prompt_embeds is not None else None
+    nm = _dev(negative_prompt_attention_mask, torch.float32) if negative_prompt_attention_mask is not None else None
+    dn = _dev(decode_noise, torch.float32) if decode_noise is not None else None
+    if pe.dim() != 3 or lat.dim() != 3:
+        raise LtxError("latents must be [B, F*H*W, in_channels] and prompt_embeds [B, K, caption_channels]")
+    B, K = pe.shape[0], pe.shape[1]
+    tr = pipe.vae.config.temporal_compression_ratio if pipe.vae is not None else 8
+    sr = pipe.vae.config.spatial_compression_ratio if pipe.vae is not None else 32
+    F, H, W = (args.num_frames - 1) // tr + 1, args.height // sr, args.width // sr
+    Cin, Ccap = pipe.transformer.config.in_channels, pipe.transformer.config.caption_channels
+    _expect("latents", lat, (B, F * H * W, Cin))
+    _expect("prompt_embeds", pe, (B, K, Ccap))
+    _expect("prompt_attention_mask", pm, (B, K))
+    if ne is not None: _expect("negative_prompt_embeds", ne, (B, K, Ccap))
+    if nm is not None: _expect("negative_prompt_attention_mask", nm, (B, K))
+    if dn is not None: _expect("decode_noise", dn, (B, Cin, F, H, W))
+    if step_noise is not None: _expect("step_noise", step_noise, (args.num_inference_steps, B, F * H * W, Cin))
+    keep = []
+    p = _params_c(args, pipe.vae, keep, step_noise)
+    pc = params.to_c(keep)
+    video = None
+    if not args.output_latent:
+        if pipe.vae is None:
+            raise LtxError("decode requested but the pipeline has no VAE")
+        if args.output_rgb8:
+            video = torch.empty(B, (F - 1) * tr + 1, H * sr, W * sr, 3, dtype=torch.uint8, device=lat.device)
+        else:
+            video = torch.empty(B, 3, (F - 1) * tr + 1, H * sr, W * sr, dtype=torch.float32, device=lat.device)
+    sched = schedule.to_c(keep) if schedule is not None else None
+    cond = None
+    if hold is not None:
+        hh = _hold_host(hold, B, F); keep.append(hh)
+        cond = ConditioningC(C.cast(hh, C.POINTER(C.c_ubyte)))
+    N = args.num_inference_steps
+    reused, dist = (C.c_ubyte * max(N, 1))(), (C.c_float * max(N, 1))()
+    _check(lib.ltx_pipeline_call_cached(pipe.transformer._h, pipe.vae._h if pipe.vae is not None else None, C.byref(p),
+                                        C.byref(sched) if sched is not None else None, C.byref(cond) if cond is not None else None, C.byref(pc),
+                                        _ptr(lat), _ptr(pe), _ptr(pm), _ptr(ne), _ptr(nm), _ptr(dn), B, K, _ptr(video), _stream(), reused, dist))
+    ms = (C.c_float * 4)()
+    _check(lib.ltx_pipeline_last_timing(ms))
+    pipe.last_timing_ms = tuple(ms)
+    return lat, video, [bool(v) for v in reused][:N], list(dist)[:N]
+
+
 # ------------------------------------------------------------------ latent upsampler + two-pass call (include/ltxhip_upsampler.h)
 @dataclass
 class LatentUpsamplerConfig:
@@ -2220,6 +2397,24 @@ class ops:
         _check(lib.ltx_op_rownorm(_ptr(x.contiguous()), _ptr(y), C.c_int64(rows), D, kind, C.c_float(eps), _ptr(weight),
                                   _ptr(scale), _ptr(shift), C.c_int64(rows_per_batch), ms, act, _dt(x.dtype), _stream()))
         return y
+
+    @staticmethod
+    def step_measure(h, prev, shift, scale, rows_per_batch, eps=1e-6, first=False):
+        """ltx_op_step_measure: prev [rows, D] is overwritten with the modulated rows of h -> sums f64 [2] on the device
+        (sum |m - prev|, sum |prev|); shift / scale f32 [groups, mod_stride]"""
+        rows, D = h.shape
+        ws = torch.empty(max(int(lib.ltx_op_step_measure_ws_bytes(C.c_int64(rows), D, _dt(h.dtype))), 16), dtype=torch.uint8, device=h.device)
+        sums = torch.empty(2, dtype=torch.float64, device=h.device)
+        _check(lib.ltx_op_step_measure(_ptr(h), _ptr(prev), _ptr(shift), _ptr(scale), shift.stride(0), C.c_int64(rows), D, C.c_int64(rows_per_batch),
+                                       C.c_float(eps), _dt(h.dtype), int(first), _ptr(ws), _ptr(sums), _stream()))
+        return sums
+
+    @staticmethod
+    def step_residual(h, r):
+        """ltx_op_step_residual: r = h - r in place"""
+        rows, D = h.shape
+        _check(lib.ltx_op_step_residual(_ptr(h), _ptr(r), C.c_int64(rows), D, _dt(h.dtype), _stream()))
+        return r
 
     @staticmethod
     def linear_deferred(x, w):

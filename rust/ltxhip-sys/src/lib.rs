@@ -485,3 +485,51 @@ extern "C" {
                                        neg_mask: *const c_float, decode_noise: *const c_float, b: c_int, k: c_int, out_video: *mut c_float,
                                        stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_stepcache.h: timestep-aware step caching (re-use of the block residual on steps that barely moved) ----
+
+/// Opaque step cache handle (`ltx_step_cache`): the previous measurement, the block residuals per cache row, the policy's state.
+#[repr(C)]
+pub struct ltx_step_cache {
+    _private: [u8; 0],
+}
+
+/// `ltx_step_cache_params`: reuse while the accumulated poly(distance) stays below `rel_l1_thresh`; `pattern` HOST u8 per step
+/// (0 decide, 1 compute, 2 reuse) or null.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ltx_step_cache_params {
+    pub rel_l1_thresh: c_float,
+    pub coeff: [c_float; 5],
+    pub pattern: *const u8,
+    pub n_pattern: c_int,
+}
+
+pub const STEPCACHE_LAYOUT_LTX_STEP_CACHE_PARAMS: (usize, usize) = (40, 8);
+const _: () = assert!(size_of::<ltx_step_cache_params>() == STEPCACHE_LAYOUT_LTX_STEP_CACHE_PARAMS.0 && align_of::<ltx_step_cache_params>() == STEPCACHE_LAYOUT_LTX_STEP_CACHE_PARAMS.1);
+
+extern "C" {
+    pub fn ltx_step_cache_params_default(p: *mut ltx_step_cache_params);
+    pub fn ltx_step_cache_create(dit: *mut ltx_dit, rows: c_int, out: *mut *mut ltx_step_cache) -> c_int;
+    pub fn ltx_step_cache_destroy(cache: *mut ltx_step_cache);
+    pub fn ltx_step_cache_reset(cache: *mut ltx_step_cache) -> c_int;
+    pub fn ltx_step_cache_decide(cache: *mut ltx_step_cache, dit: *mut ltx_dit, hidden: *const c_void, timestep: *const c_float, frames: c_int,
+                                 b: c_int, s: c_int, num_frames: c_int, height: c_int, width: c_int, io_dtype: c_int, step: c_int, n_steps: c_int,
+                                 params: *const ltx_step_cache_params, reuse: *mut c_int, distance: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_step_cache_require(cache: *mut ltx_step_cache, dit: *const ltx_dit, row0: c_int, nrows: c_int, s: c_int, reuse: *mut c_int) -> c_int;
+    pub fn ltx_dit_forward_cached(dit: *mut ltx_dit, cache: *mut ltx_step_cache, row0: c_int, reuse: c_int, frames: c_int, hidden: *const c_void,
+                                  enc: *const c_void, timestep: *const c_float, enc_mask: *const c_float, b: c_int, s: c_int, k: c_int,
+                                  num_frames: c_int, height: c_int, width: c_int, rope_scale: *const c_float, video_coords: *const c_float,
+                                  skip_layer_mask: *const c_float, io_dtype: c_int, out: *mut c_void, stream: ltx_stream) -> c_int;
+    pub fn ltx_step_cache_read_residual(cache: *const ltx_step_cache, row: c_int, dst: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_pipeline_call_cached(dit: *mut ltx_dit, vae: *mut ltx_vae, p: *const ltx_pipeline_params, sched: *const ltx_guidance_schedule,
+                                    cond: *const ltx_conditioning, cache_params: *const ltx_step_cache_params, latents: *mut c_float,
+                                    prompt_embeds: *const c_float, prompt_mask: *const c_float, neg_embeds: *const c_float, neg_mask: *const c_float,
+                                    decode_noise: *const c_float, b: c_int, k: c_int, out_video: *mut c_float, stream: ltx_stream,
+                                    reused_out: *mut u8, distance_out: *mut c_float) -> c_int;
+    pub fn ltx_op_step_measure_ws_bytes(rows: i64, d: c_int, dtype: c_int) -> usize;
+    pub fn ltx_op_step_measure(h: *const c_void, prev: *mut c_void, shift: *const c_float, scale: *const c_float, mod_stride: c_int, rows: i64,
+                               d: c_int, rows_per_batch: i64, eps: c_float, dtype: c_int, first: c_int, ws: *mut c_void, sums: *mut f64,
+                               stream: ltx_stream) -> c_int;
+    pub fn ltx_op_step_residual(h: *const c_void, r: *mut c_void, rows: i64, d: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
+}
