@@ -4,6 +4,7 @@
 #include "../../include/ltxhip_upsampler_st.h"
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
+#include "../../include/ltxhip_int8.h"
 
 static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
 
@@ -496,4 +497,30 @@ extern "C" int ltx_op_step_measure(const void* h, void* prev, const float* shift
 extern "C" int ltx_op_step_residual(const void* h, void* r, int64_t rows, int D, ltx_dtype dtype, ltx_stream stream) {
     if (dtype != LTX_F32 && dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_op_step_residual: bad dtype");
     return ltx_launch_step_residual(h, r, rows, D, dtc((int)dtype), (hipStream_t)stream);
+}
+
+// ---- the int8 (W8A8) kernels on their own (include/ltxhip_int8.h) ----
+extern "C" int ltx_op_quant_rows_i8(const void* x, int64_t rows, int D, int ld, void* q, float* scale, ltx_stream stream) {
+    return ltx_launch_quant_rows_i8(x, rows, D, ld, q, scale, (hipStream_t)stream);
+}
+extern "C" int ltx_op_rownorm_quant_i8(const void* h, int64_t rows, int D, int ld, float eps, const float* shift, const float* scale, int mod_stride,
+                                       int64_t rows_per_batch, void* q, float* row_scale, ltx_stream stream) {
+    RowNormArgs a; a.x = h; a.y = q; a.rows = rows; a.D = D; a.ldx = ld; a.ldy = D; a.kind = 0; a.eps = eps; a.shift = shift; a.scale = scale;
+    a.mod_stride = mod_stride; a.rows_per_batch = rows_per_batch;
+    return ltx_launch_rownorm_quant_i8(a, row_scale, (hipStream_t)stream);
+}
+extern "C" int ltx_op_gemm_i8(const void* a_q, const float* a_scale, const void* w_q, const float* w_scale, const void* bias, void* y,
+                              int M, int N, int K, int epi, const void* resid, const float* gate, int rows_per_batch, int seg_width, int tile,
+                              ltx_stream stream) {
+    if (epi < 0 || epi > 3) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_i8: epi must be 0..3");
+    if (seg_width < 0 || (seg_width > 0 && ((seg_width & (seg_width - 1)) || N % seg_width || epi != 0)))
+        LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_i8: seg_width must be a power of two dividing N, with epi 0");
+    GemmArgs g; g.A = a_q; g.W = w_q; g.C = y; g.bias = bias; g.resid = resid; g.gate = gate;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; g.gate_stride = N;
+    if (seg_width > 0) { g.ldc = seg_width; g.c_seg_shift = __builtin_ctz((unsigned)seg_width); g.c_seg_stride = (int64_t)M * seg_width; }
+    return ltx_launch_gemm_i8(g, a_scale, w_scale, epi, tile, (hipStream_t)stream);
+}
+extern "C" int ltx_op_gemm_i8_raw(const void* a_q, const void* w_q, int* acc, int M, int N, int K, int tile, ltx_stream stream) {
+    GemmArgs g; g.A = a_q; g.W = w_q; g.C = acc; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
+    return ltx_launch_gemm_i8(g, nullptr, nullptr, EPI_I8_RAW, tile, (hipStream_t)stream);
 }

@@ -11,6 +11,7 @@
 #include "../../include/ltxhip_cond.h"
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
+#include "../../include/ltxhip_int8.h"
 #include "../host/step_cache.h"
 #include "lora.h"
 
@@ -98,6 +99,7 @@ struct ltx_dit {
         for (auto& e : ctxs) e.valid = false;
         for (auto& e : tcache) e.cfold_valid = false;
         for (auto& e : gcache) e.cfold_valid = false;
+        i8_stale = true;
     }
     void release_scaled_weights() { for (auto& e : wcache) e.release(); }      // norm_fold=2 gave up: the copies are never read again
     void release_caches() { auto all = [](auto& c) { for (auto& e : c) e.release(); c.clear(); }; all(ctxs); all(tcache); all(wcache); all(gcache); }
@@ -108,6 +110,23 @@ struct ltx_dit {
     struct LoraSlots { void* base[7] = {nullptr}; void* merged[7] = {nullptr}; };
     std::vector<LoraSlots> lora_w;
     int n_adapters = 0;
+    // INT8 (W8A8) block linears (include/ltxhip_int8.h; ltx_dit_set_int8_linears below).  Per block the mask of its int8 layers and, per
+    // kind (bit order: qkv1, o1, ff1, ff2), the int8 copy [out, in] of the weight the forward would otherwise read and its per-channel
+    // scales.  A weight-derived cache: invalidate_weight_derived marks the copies stale, the next forward (or set) re-makes them.
+    struct I8Slots { void* w[4] = {nullptr}; float* sw[4] = {nullptr}; };
+    std::vector<unsigned char> i8_mask;
+    std::vector<I8Slots> i8_w;
+    bool i8_any = false, i8_stale = false;
+    DevBuf a8, a8s;                  // a quantised activation [M, 4D] int8 and its row scales [M] f32
+    void free_int8(std::vector<void*>* later = nullptr, int l = -1, int k = -1) {      // every copy, or block l's kind k; later: collect instead of freeing
+        for (size_t i = 0; i < i8_w.size(); ++i)
+            for (int j = 0; j < 4; ++j) {
+                if ((l >= 0 && (int)i != l) || (k >= 0 && j != k)) continue;
+                void* ps[2] = {i8_w[i].w[j], i8_w[i].sw[j]};
+                for (void* p : ps) if (p) { if (later) later->push_back(p); else (void)hipFree(p); }
+                i8_w[i].w[j] = nullptr; i8_w[i].sw[j] = nullptr;
+            }
+    }
     // workspaces
     DevBuf xin, encin, h, n, qkv, attn, ff, c1, encp, kv2, tproj, e1, emb, embs, temb, ada, adaf, cosb, sinb, bias, orig, orig_hsq, outT, rsq, hsq, parts;
     void free_all() {
@@ -115,6 +134,8 @@ struct ltx_dit {
         owned.clear();
         for (auto& ls : lora_w) for (void*& p : ls.merged) if (p) { (void)hipFree(p); p = nullptr; }
         lora_w.clear();
+        free_int8(); i8_w.clear(); i8_mask.clear(); i8_any = false;
+        a8.release(); a8s.release();
         DevBuf* bs[] = {&xin, &encin, &h, &n, &qkv, &attn, &ff, &c1, &encp, &kv2, &tproj, &e1, &emb, &embs, &temb, &ada, &adaf, &cosb, &sinb, &bias, &orig, &orig_hsq, &outT, &rsq, &hsq, &parts};
         for (DevBuf* b : bs) b->release();
         release_caches();
@@ -301,6 +322,72 @@ extern "C" int ltx_dit_get_stg_mode(const ltx_dit* m, ltx_stg_mode* out) {
 extern "C" int ltx_dit_get_config(const ltx_dit* m, ltx_dit_config* out) {
     if (!m || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_config: null argument");
     *out = m->cfg;
+    return LTX_OK;
+}
+
+// ---- INT8 (W8A8) block linears (include/ltxhip_int8.h) ----
+namespace {
+constexpr int kI8Slot[4] = {0, 1, 5, 6};      // dit_slot's index of mask bit i: qkv1, o1, ff1, ff2
+// (re-)quantise every selected weight from the pointer the forward reads (LinearW::w: the base, or the LoRA-merged copy)
+int int8_quantise(ltx_dit* m, hipStream_t s) {
+    for (size_t l = 0; l < m->i8_mask.size(); ++l)
+        for (int k = 0; k < 4; ++k) {
+            if (!(m->i8_mask[l] >> k & 1)) continue;
+            const LinearW* lw = dit_slot(m->blocks[l], kI8Slot[k]);
+            LTX_TRY(ltx_launch_quant_rows_i8(lw->w, lw->out, lw->in, lw->in, m->i8_w[l].w[k], m->i8_w[l].sw[k], s));
+        }
+    m->i8_stale = false;
+    return LTX_OK;
+}
+}  // namespace
+
+extern "C" int ltx_dit_set_int8_linears(ltx_dit* m, const unsigned char* block_masks, unsigned char mask, ltx_stream stream) {
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_int8_linears: null handle");
+    const int L = m->cfg.num_layers;
+    if (mask & ~LTX_I8_ALL) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_int8_linears: mask " + std::to_string((int)mask) + " has bits outside LTX_I8_ALL");
+    for (int l = 0; block_masks && l < L; ++l)
+        if (block_masks[l] & ~LTX_I8_ALL) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_int8_linears: block_masks[" + std::to_string(l) + "] has bits outside LTX_I8_ALL");
+    std::vector<unsigned char> want((size_t)L);
+    bool any = false;
+    for (int l = 0; l < L; ++l) { want[l] = block_masks ? (unsigned char)(block_masks[l] & mask) : mask; any = any || want[l]; }
+    if (any && m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_linears: the int8 layers take a bf16 model (this handle is f32)");
+    if (any && (m->D % 16 != 0 || m->D > 4096)) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_linears: the inner dimension must be a multiple of 16, at most 4096");
+    HIP_TRY(hipSetDevice(m->device));
+    m->i8_mask.resize((size_t)L, 0); m->i8_w.resize((size_t)L);
+    // new copies first: nothing changes before every one of them exists
+    std::vector<std::pair<int, int>> fresh;
+    for (int l = 0; l < L; ++l)
+        for (int k = 0; k < 4; ++k) {
+            if (!(want[l] >> k & 1) || m->i8_w[l].w[k]) continue;
+            const LinearW* lw = dit_slot(m->blocks[l], kI8Slot[k]);
+            void* w = nullptr; void* sw = nullptr;
+            hipError_t e = hipMalloc(&w, (size_t)lw->out * lw->in);
+            if (e == hipSuccess) e = hipMalloc(&sw, (size_t)lw->out * sizeof(float));
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                if (w) (void)hipFree(w);
+                for (const auto& f : fresh) m->free_int8(nullptr, f.first, f.second);
+                LTX_FAIL(LTX_ERR_HIP, std::string("ltx_dit_set_int8_linears: hipMalloc of an int8 weight: ") + hipGetErrorString(e) + " (the handle is unchanged)");
+            }
+            m->i8_w[l].w[k] = w; m->i8_w[l].sw[k] = reinterpret_cast<float*>(sw); fresh.emplace_back(l, k);
+        }
+    std::vector<void*> unused;
+    for (int l = 0; l < L; ++l)
+        for (int k = 0; k < 4; ++k)
+            if (!(want[l] >> k & 1)) m->free_int8(&unused, l, k);
+    m->i8_mask = want; m->i8_any = any;
+    const int rc = any ? int8_quantise(m, (hipStream_t)stream) : LTX_OK;
+    if (!any) { m->i8_stale = false; }
+    if (!unused.empty()) {                                       // forwards enqueued earlier may still read them
+        (void)hipDeviceSynchronize();
+        for (void* p : unused) (void)hipFree(p);
+    }
+    if (!any) { m->a8.release(); m->a8s.release(); }
+    return rc;
+}
+extern "C" int ltx_dit_get_int8_linears(const ltx_dit* m, unsigned char* block_masks_out) {
+    if (!m || !block_masks_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_linears: null argument");
+    for (int l = 0; l < m->cfg.num_layers; ++l) block_masks_out[l] = (size_t)l < m->i8_mask.size() ? m->i8_mask[(size_t)l] : 0;
     return LTX_OK;
 }
 
@@ -752,11 +839,22 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     rn.kind = 0; rn.eps = c.norm_eps; rn.shift = ada; rn.scale = ada + D; rn.rows_per_batch = p.Sg; rn.mod_stride = 6 * D;
     if (p.presum && st.hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
     const bool fold1 = p.nfold && st.hsq_valid && (wf || st.hs_valid);      // the layer that wrote h left its row partials and h (.) (1 + scale_msa) in m->n (or the factor is in the weights): no pass
-    if (!fold1) { st.take_pending(rn, m, p); LTX_TRY(ltx_launch_rownorm(rn, dt, s)); }
+    // The block's int8 layers (ltxhip_int8.h; the forward's plan then has no norm fold, no row partials and no deferred ff2): the
+    // layer's pass-form call with A = the quantised activation in m->a8 / m->a8s and W = the layer's int8 copy
+    const unsigned i8 = m->i8_any ? m->i8_mask[(size_t)l] : 0u;
+    auto gemm_int8 = [&](int kind, GemmArgs g, int epi) {
+        g.A = m->a8.p; g.lda = g.K; g.W = m->i8_w[(size_t)l].w[kind]; g.rowsq = nullptr;
+        return ltx_launch_gemm_i8(g, m->a8s.as<float>(), m->i8_w[(size_t)l].sw[kind], epi, -1, s);
+    };
+    auto norm_int8 = [&]() { RowNormArgs rq = rn; rq.y = m->a8.p; rq.ldy = D; return ltx_launch_rownorm_quant_i8(rq, m->a8s.as<float>(), s); };      // rn's norm, quantised from f32
+    const bool qkv8 = (i8 & LTX_I8_QKV) != 0;
+    if (qkv8) LTX_TRY(norm_int8());
+    else if (!fold1) { st.take_pending(rn, m, p); LTX_TRY(ltx_launch_rownorm(rn, dt, s)); }
     st.hs_valid = false;
     rn.parts = nullptr; rn.nparts = 0; rn.x_out = nullptr; rn.d_bias = nullptr; rn.d_gate = nullptr;
     // self attention
-    LTX_TRY(ltx_launch_gemm(gemm_qkv1(p, fold1 ? fold_in_form : kPass, b, x), dt, EPI_BIAS, s));
+    if (qkv8) LTX_TRY(gemm_int8(0, gemm_qkv1(p, kPass, b, x), EPI_BIAS));
+    else LTX_TRY(ltx_launch_gemm(gemm_qkv1(p, fold1 ? fold_in_form : kPass, b, x), dt, EPI_BIAS, s));
     const float attn_scale = 1.0f / std::sqrt((float)hd);
     QkNormRopeArgs qa; qa.x = m->qkv.p; qa.rows = M; qa.D = D; qa.ld = p.ldqkv; qa.seg_stride = p.seg; qa.nseg = 2; qa.w0 = b.nq1; qa.w1 = b.nk1;
     qa.eps = 1e-5f; qa.cos = m->cosb.as<float>(); qa.sin = m->sinb.as<float>();
@@ -784,9 +882,9 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
             return ltx_launch_attention(ar, dt, s);
         }));
         if (m->stg_mode == LTX_STG_ATTENTION_VALUES) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, at.v, p.ldqkv, pert, B, S, D, dt, s));      // to_out(v): v with its bias, before the head split
-        else if (!fold1) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, m->n.p, D, pert, B, S, D, dt, s));      // to_out(n): the norm pass above left n whole in m->n
+        else if (!fold1 && !qkv8) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, m->n.p, D, pert, B, S, D, dt, s));      // to_out(n): the norm pass above left n whole in m->n
         else
-            // norm fold: n is never materialised (m->n holds h (.) (1 + scale_msa), or the factor rides on the weights), but h is still
+            // norm fold, or an int8 q | k | v: n is never materialised in bf16 (m->n holds h (.) (1 + scale_msa), the factor rides on the weights, or n went straight to int8), but h is still
             // the block's input here: the row norm over the perturbed batch rows alone, straight into their rows of m->attn
             LTX_TRY(for_runs(true, [&](int b0, int b1) {
                 RowNormArgs rp = rn; rp.presum = nullptr; rp.presum_n = 0;
@@ -797,7 +895,12 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
             }));
     }
     // h = h + gate_msa * to_out(attn)     (gate_msa = row 2)
-    LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, p.Sg));
+    if (i8 & LTX_I8_TO_OUT) {
+        GemmArgs g = gemm_base(p, b.o1, m->attn.p, D, m->h.p, D);
+        g.resid = m->h.p; g.ldr = D; g.gate = ada + 2 * D; g.gate_stride = 6 * D; g.rows_per_batch = p.Sg;
+        LTX_TRY(ltx_launch_quant_rows_i8(m->attn.p, M, D, D, m->a8.p, m->a8s.as<float>(), s));
+        LTX_TRY(gemm_int8(1, g, EPI_GATE_RESID));
+    } else LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, p.Sg));
     st.hsq_valid = false;
     // cross attention (no pre-norm, no RoPE, q/k RMSNorm, additive key bias)
     const DitCtx* ctx = in.ctx;
@@ -832,15 +935,21 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         rn.shift = ada + 3 * D; rn.scale = ada + 4 * D;
         rn.presum = nullptr; rn.presum_n = 0;
         if (p.presum && st.hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
-        LTX_TRY(ltx_launch_rownorm(rn, dt, s));
-        LTX_TRY(linear_of(b.ff1, gemm_ff1(p, kPass, b, x), dt, EPI_GELU, s));
+        if (i8 & LTX_I8_FF1) { LTX_TRY(norm_int8()); LTX_TRY(gemm_int8(2, gemm_ff1(p, kPass, b, x), EPI_GELU)); }
+        else {
+            LTX_TRY(ltx_launch_rownorm(rn, dt, s));
+            LTX_TRY(linear_of(b.ff1, gemm_ff1(p, kPass, b, x), dt, EPI_GELU, s));
+        }
     }
     st.hs_valid = false;
     if (p.defer_ff2) {
         LTX_TRY(ltx_launch_gemm(gemm_ff2(p, kDefer, b, x), dt, EPI_BIAS, s));
         st.pending = true; st.pend_gate = ada + 5 * D; st.pend_bias = b.ff2.b;
     } else if (ln >= 0) { LTX_TRY(ltx_launch_gemm(gemm_ff2(p, kFold1, b, x), dt, EPI_GATE_RESID, s)); st.hs_valid = true; }
-    else LTX_TRY(linear_of(b.ff2, gemm_ff2(p, kPass, b, x), dt, EPI_GATE_RESID, s));
+    else if (i8 & LTX_I8_FF2) {
+        LTX_TRY(ltx_launch_quant_rows_i8(m->ff.p, M, 4 * D, 4 * D, m->a8.p, m->a8s.as<float>(), s));
+        LTX_TRY(gemm_int8(3, gemm_ff2(p, kPass, b, x), EPI_GATE_RESID));
+    } else LTX_TRY(linear_of(b.ff2, gemm_ff2(p, kPass, b, x), dt, EPI_GATE_RESID, s));
     st.hsq_valid = p.presum;
     if (!any) return LTX_OK;
     LTX_TRY(ltx_launch_skip_blend(m->h.p, m->orig.p, mv, S, D, dt, s));
@@ -875,7 +984,11 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
     if (G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: the modulation groups must divide the sequence");
     hipStream_t s = (hipStream_t)stream;
     const ltx_dit_config& c = m->cfg;
-    const DitPlan p = ltx_dit_plan(c, m->dtype, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, S, K, G, skip_layer_mask != nullptr);
+    DitPlan plan = ltx_dit_plan(c, m->dtype, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, S, K, G, skip_layer_mask != nullptr);
+    // a handle with int8 layers (ltxhip_int8.h) runs its copy of the plan without the fusions whose launches pair bf16 producers with
+    // bf16 consumers: no norm fold, no row partials for the norms, no deferred ff2 (fold_q2, fold_vo, dense_qkv and fold_q stay)
+    if (m->i8_any) { plan.nfold = false; plan.presum = false; plan.defer_ff2 = false; plan.ff2_parts = 0; }
+    const DitPlan p = plan;
     const int dt = p.dt, D = p.D, L = c.num_layers;
     const int64_t M = p.M, MK = p.MK; const size_t esz = ltx_dt_size(dt);
     // the workspaces, sized for the plan; nothing is launched before every one of them exists
@@ -885,7 +998,8 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
         {&m->xin, M * c.in_channels * esz}, {&m->encin, MK * c.caption_channels * esz}, {&m->h, MD}, {&m->n, MD}, {&m->qkv, 3 * MD}, {&m->attn, MD}, {&m->ff, 4 * MD},
         {&m->c1, KD}, {&m->encp, KD}, {&m->kv2, 2 * KD}, {&m->tproj, nte * 256 * esz}, {&m->e1, nte * D * esz}, {&m->emb, nte * D * esz}, {&m->embs, nte * D * esz},
         {&m->temb, nte * 6 * D * esz}, {&m->cosb, rope}, {&m->sinb, rope}, {&m->bias, MK * sizeof(float)}, {&m->outT, M * c.out_channels * esz},
-        {&m->rsq, p.fold_q2 ? part : 0}, {&m->hsq, p.presum ? part : 0}, {&m->parts, p.defer_ff2 ? (size_t)p.ff2_parts * M * D * sizeof(float) : 0}, {&m->orig, skip_layer_mask ? MD : 0}};
+        {&m->rsq, p.fold_q2 ? part : 0}, {&m->hsq, p.presum ? part : 0}, {&m->parts, p.defer_ff2 ? (size_t)p.ff2_parts * M * D * sizeof(float) : 0}, {&m->orig, skip_layer_mask ? MD : 0},
+        {&m->a8, m->i8_any ? (size_t)M * 4 * D : 0}, {&m->a8s, m->i8_any ? (size_t)M * sizeof(float) : 0}};
     for (const auto& w : ws) LTX_TRY(w.first->ensure(w.second));
     const bool reuse = sc && sc->reuse;
     if (reuse) {
@@ -918,6 +1032,7 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
         LTX_TRY(text_context(m, p, enc, enc_mask, s, &ctx)); in.ctx = ctx;
         in.fold_vo = ctx->fold_vo;
         LTX_TRY(rope_tables(m, p, num_frames, height, width, rope_scale, video_coords, s));
+        if (m->i8_any && m->i8_stale) LTX_TRY(int8_quantise(m, s));      // the weights changed since the copies were made (adapters)
 
         for (int l = 0; l < L; ++l)
             if (block_runs(m, skip_layer_mask, B, l)) LTX_TRY(dit_block(m, p, l, in, st, s));

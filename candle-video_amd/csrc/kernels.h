@@ -13,7 +13,8 @@ enum { LTX_PROF_GEMM = 0, LTX_PROF_CONV = 1, LTX_PROF_ATTN_SELF = 2, LTX_PROF_AT
 bool ltx_prof_begin(int kind, double work, hipStream_t s, void** token);   // work: algorithmic flops (or bytes for ROWNORM)
 void ltx_prof_end(void* token, hipStream_t s);
 // which KERNEL served the launch being timed (set by the launcher that actually enqueues it; read by ltx_prof_end)
-enum { LTX_PROFK_GEMM128 = 0, LTX_PROFK_GEMM_BIG = 1, LTX_PROFK_GEMM_P8 = 2, LTX_PROFK_CONV_HALO = 3, LTX_PROFK_GEMM_ASM = 4, LTX_PROFK_GEMM_ASM16 = 5, LTX_PROFK_GEMM_RING = 6, LTX_PROFK_N = 7 };
+enum { LTX_PROFK_GEMM128 = 0, LTX_PROFK_GEMM_BIG = 1, LTX_PROFK_GEMM_P8 = 2, LTX_PROFK_CONV_HALO = 3, LTX_PROFK_GEMM_ASM = 4, LTX_PROFK_GEMM_ASM16 = 5, LTX_PROFK_GEMM_RING = 6,
+       LTX_PROFK_GEMM_I8 = 7, LTX_PROFK_QUANT_ROWS_I8 = 8, LTX_PROFK_ROWNORM_QUANT_I8 = 9, LTX_PROFK_N = 10 };      // (the int8 kernels: class GEMM, ROWNORM, ROWNORM)
 void ltx_prof_kernel(int which);
 // Kernel-level start / stop events for the launch being timed (the dispatch packet's own timestamps, what rocprofv3's kernel
 // trace reports): stream-level hipEventRecord brackets also count the dispatch latency and the end-of-kernel release that the
@@ -198,6 +199,18 @@ struct NormDecision {
 NormRouteArgs ltx_rownorm_route_args(const RowNormArgs& a, int dtype);
 NormDecision ltx_rownorm_route(const NormRouteArgs& r);
 const char* ltx_rownorm_route_name(NormRoute r);      // "narrow", "block", "wide", "reread", "presum", "presum_lean", "wide_defer", ... ; "refused"
+
+// ---------------- int8 (W8A8) linear layers (quant_i8.hip, gemm_i8.hip; include/ltxhip_int8.h states the arithmetic) ----------------
+// x [rows, D] bf16 (row stride ld) -> q int8 [rows, D] dense, scale f32 [rows]; D % 16 == 0, D <= 16384
+int ltx_launch_quant_rows_i8(const void* x, int64_t rows, int D, int ld, void* q, float* scale, hipStream_t s);
+// the modulated RMS norm of a (x, D, ldx, eps, shift, scale, mod_stride, rows_per_batch: RowNormArgs' fields; kind 0, no weight, no
+// activation) quantised from its f32 value: a.y int8 [rows, D] dense, row_scale f32 [rows]; D % 16 == 0, D <= 4096
+int ltx_launch_rownorm_quant_i8(const RowNormArgs& a, float* row_scale, hipStream_t s);
+// g: A int8 [M, lda], W int8 [N, K], C bf16 (EPI_BIAS / GELU / GATE_RESID / RESID with GemmArgs' bias, resid, gate, c_seg_*) or, epi ==
+// EPI_I8_RAW, int32 [M, ldc] unscaled (sa, sw not read).  tile: -1 the shape rule, 0 256x256, 1 256x128, 2 128x128.
+constexpr int EPI_I8_RAW = 100;
+int ltx_launch_gemm_i8(const GemmArgs& g, const float* sa, const float* sw, int epi, int tile, hipStream_t s);
+int ltx_gemm_i8_pick_tile(int M, int N);
 
 // ---------------- step cache (stepcache.hip; include/ltxhip_stepcache.h) ----------------
 // One pass over h and prev [rows, D] (T): m = round_T(rms_norm(h, eps) * (1 + scale[g]) + shift[g]), g = row / rows_per_batch (f32 tables,

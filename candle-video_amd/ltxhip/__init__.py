@@ -394,6 +394,45 @@ for _name, _sig in _STEPCACHE_SIGS.items():
 STEP_COMPUTE, STEP_REUSE = 1, 2                  # values of a step cache pattern (0: decide)
 
 
+# include/ltxhip_int8.h (kept apart like the nine above)
+_INT8_SIGS = {
+    "ltx_dit_set_int8_linears": [_vp, _vp, C.c_ubyte, _vp], "ltx_dit_get_int8_linears": [_vp, _vp],
+    "ltx_op_quant_rows_i8": [_vp, _i64, _i, _i, _vp, _vp, _vp],
+    "ltx_op_rownorm_quant_i8": [_vp, _i64, _i, _i, _f, _vp, _vp, _i, _i64, _vp, _vp, _vp],
+    "ltx_op_gemm_i8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
+    "ltx_op_gemm_i8_raw": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
+}
+INT8_SYMBOLS = sorted(_INT8_SIGS)
+for _name, _sig in _INT8_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
+LTX_I8_QKV, LTX_I8_TO_OUT, LTX_I8_FF1, LTX_I8_FF2, LTX_I8_ALL = 1, 2, 4, 8, 15
+INT8_LINEARS = ("qkv", "to_out", "ff1", "ff2")   # the mask bits of ltx_dit_set_int8_linears, lowest first
+GEMM_I8_TILES = ("256x256", "256x128", "128x128")
+
+
+def int8_mask(mask_or_names) -> int:
+    """the LTX_I8_* mask of an int, a name of INT8_LINEARS, 'all' / 'none', or a sequence of names"""
+    if mask_or_names is None:
+        return 0
+    if isinstance(mask_or_names, int):
+        m = mask_or_names
+    else:
+        names = [mask_or_names] if isinstance(mask_or_names, str) else list(mask_or_names)
+        m = 0
+        for n in names:
+            if n == "all":
+                m |= LTX_I8_ALL
+            elif n in INT8_LINEARS:
+                m |= 1 << INT8_LINEARS.index(n)
+            elif n != "none":
+                raise LtxError(f"int8 linears: unknown name {n!r} (one of {INT8_LINEARS}, 'all', 'none')")
+    if m < 0 or m > LTX_I8_ALL:
+        raise LtxError(f"int8 linears: mask {m} has bits outside LTX_I8_ALL ({LTX_I8_ALL})")
+    return m
+
+
 @dataclass
 class StepCacheParams:
     """ltx_step_cache_params: reuse the block residual while the accumulated poly(distance) stays below rel_l1_thresh (0: never);
@@ -668,6 +707,27 @@ class LtxVideoTransformer3DModel:
         out = C.c_int(0)
         _check(lib.ltx_dit_get_stg_mode(self._h, C.byref(out)))
         return STG_MODES[out.value]
+
+    # ---- INT8 (W8A8) block linears (include/ltxhip_int8.h): handle state, so every forward and LtxPipeline.call run on whatever is set
+    def set_int8_linears(self, mask_or_names=0, block_masks: Optional[Sequence] = None):
+        """run the named block linears - 'qkv', 'to_out', 'ff1', 'ff2', 'all', or an LTX_I8_* mask - on the int8 MFMA; block_masks: one
+        entry per block (same forms), and-ed with the mask (zeros keep a block in bf16).  0 / 'none' frees the int8 copies.  A bf16
+        model only.  Enqueued on the current stream; set_adapters afterwards is fine (the copies follow the merged weights)."""
+        m = int8_mask(mask_or_names)
+        arr = None
+        if block_masks is not None:
+            bm = [int8_mask(v) for v in block_masks]
+            if len(bm) != self.config.num_layers:
+                raise LtxError(f"set_int8_linears: block_masks has {len(bm)} entries for {self.config.num_layers} blocks")
+            arr = (C.c_ubyte * len(bm))(*bm)
+        _check(lib.ltx_dit_set_int8_linears(self._h, arr, m, _stream()))
+
+    @property
+    def int8_linears(self) -> List[int]:
+        """the LTX_I8_* mask of every block"""
+        out = (C.c_ubyte * self.config.num_layers)()
+        _check(lib.ltx_dit_get_int8_linears(self._h, out))
+        return list(out)
 
     # ---- LoRA adapters (include/ltxhip_lora.h): handle state, so LtxPipeline.call runs on whatever is set
     def set_adapters(self, loras: Sequence["LtxLora"] = (), scales: Optional[Sequence[float]] = None):
@@ -2416,6 +2476,49 @@ class ops:
         _check(lib.ltx_op_step_residual(_ptr(h), _ptr(r), C.c_int64(rows), D, _dt(h.dtype), _stream()))
         return r
 
+    # ---- the int8 (W8A8) kernels (include/ltxhip_int8.h)
+    @staticmethod
+    def quant_rows_i8(x):
+        """x [rows, D] bf16 (any row stride, unit column stride) -> (q int8 [rows, D], scale f32 [rows])"""
+        if x.dim() != 2 or x.stride(1) != 1:
+            x = x.contiguous()
+        rows, D = x.shape
+        q = torch.empty(rows, D, dtype=torch.int8, device=x.device)
+        sc = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _check(lib.ltx_op_quant_rows_i8(_ptr(x), C.c_int64(rows), D, x.stride(0) if rows > 1 else D, _ptr(q), _ptr(sc), _stream()))
+        return q, sc
+
+    @staticmethod
+    def rownorm_quant_i8(h, shift, scale, rows_per_batch, eps=1e-6):
+        """q, row_scale of the modulated RMS norm of h [rows, D] bf16; shift / scale f32 [groups, mod_stride]"""
+        rows, D = h.shape
+        h = h.contiguous()
+        q = torch.empty(rows, D, dtype=torch.int8, device=h.device)
+        sc = torch.empty(rows, dtype=torch.float32, device=h.device)
+        _check(lib.ltx_op_rownorm_quant_i8(_ptr(h), C.c_int64(rows), D, D, C.c_float(eps), _ptr(shift), _ptr(scale), shift.stride(0),
+                                           C.c_int64(rows_per_batch), _ptr(q), _ptr(sc), _stream()))
+        return q, sc
+
+    @staticmethod
+    def gemm_i8(a_q, a_scale, w_q, w_scale, bias=None, epi=0, resid=None, gate=None, rows_per_batch=1, seg_width=0, tile=-1):
+        """y bf16 = epi((float(a_q w_q^T) * a_scale[m]) * w_scale[n] + bias); seg_width: N / seg_width dense [M, seg_width] matrices;
+        tile: -1 the shape rule, or an index into GEMM_I8_TILES"""
+        M, K = a_q.shape
+        N = w_q.shape[0]
+        y = torch.empty((N // seg_width, M, seg_width) if seg_width else (M, N), dtype=torch.bfloat16, device=a_q.device)
+        _check(lib.ltx_op_gemm_i8(_ptr(a_q.contiguous()), _ptr(a_scale), _ptr(w_q.contiguous()), _ptr(w_scale), _ptr(bias), _ptr(y), M, N, K, epi,
+                                  _ptr(resid), _ptr(gate), rows_per_batch, seg_width, tile, _stream()))
+        return y
+
+    @staticmethod
+    def gemm_i8_raw(a_q, w_q, tile=-1):
+        """the int32 accumulators a_q w_q^T [M, N], unscaled"""
+        M, K = a_q.shape
+        N = w_q.shape[0]
+        acc = torch.empty(M, N, dtype=torch.int32, device=a_q.device)
+        _check(lib.ltx_op_gemm_i8_raw(_ptr(a_q.contiguous()), _ptr(w_q.contiguous()), _ptr(acc), M, N, K, tile, _stream()))
+        return acc
+
     @staticmethod
     def linear_deferred(x, w):
         """x @ w^T as UN-reduced K ranges (the library's shape rule): parts [P, M, N] f32 (bf16 layers of at most 512 rows)"""
@@ -2672,7 +2775,8 @@ def prof_report(kind: int):
     return ms.value, work.value, cnt.value
 
 
-PROF_KERNELS = ("gemm_kernel (128 x 128)", "gemm_big_kernel", "gemm_p8_kernel", "conv_halo_kernel", "gemm_asm_kernel (32x32x16)", "gemm_asm16_kernel", "gemm_ring_kernel")
+PROF_KERNELS = ("gemm_kernel (128 x 128)", "gemm_big_kernel", "gemm_p8_kernel", "conv_halo_kernel", "gemm_asm_kernel (32x32x16)", "gemm_asm16_kernel", "gemm_ring_kernel",
+                "gemm_i8_kernel", "quant_rows_i8_kernel", "rownorm_quant_i8_kernel")      # (the last two are timed in class 4, the row norms)
 
 
 def prof_report_kernel(kind: int, kernel: int):

@@ -224,6 +224,26 @@ impl HipDit {
         check(unsafe { sys::ltx_dit_get_stg_mode(self.h, &mut mode) })?;
         Ok(mode)
     }
+
+    /// Run the block linears named by `mask` (`sys::LTX_I8_*`) in INT8 (W8A8, include/ltxhip_int8.h); `block_masks`, one entry per
+    /// block, is and-ed with it (zeros keep a block in bf16).  Mask 0 frees the int8 copies.  Handle state: every later forward and
+    /// pipeline call on this handle obeys it; adapters set afterwards are followed.  A bf16 model only.
+    pub fn set_int8_linears(&mut self, mask: u8, block_masks: Option<&[u8]>) -> Result<()> {
+        if let Some(bm) = block_masks {
+            if bm.len() != self.cfg.num_layers {
+                candle_core::bail!("set_int8_linears: {} block masks for {} blocks", bm.len(), self.cfg.num_layers);
+            }
+        }
+        let p = block_masks.map_or(std::ptr::null(), |b| b.as_ptr());
+        check(unsafe { sys::ltx_dit_set_int8_linears(self.h, p, mask, std::ptr::null_mut()) })
+    }
+
+    /// The `sys::LTX_I8_*` mask of every block.
+    pub fn int8_linears(&self) -> Result<Vec<u8>> {
+        let mut out = vec![0u8; self.cfg.num_layers];
+        check(unsafe { sys::ltx_dit_get_int8_linears(self.h, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
 }
 
 impl Drop for HipDit {

@@ -533,3 +533,24 @@ extern "C" {
                                stream: ltx_stream) -> c_int;
     pub fn ltx_op_step_residual(h: *const c_void, r: *mut c_void, rows: i64, d: c_int, dtype: c_int, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_int8.h: opt-in INT8 (W8A8) block linears on the int8 MFMA ----
+
+/// Mask bits of `ltx_dit_set_int8_linears`: attn1's fused q | k | v, attn1.to_out, ff.net.0.proj, ff.net.2.
+pub const LTX_I8_QKV: u8 = 1;
+pub const LTX_I8_TO_OUT: u8 = 2;
+pub const LTX_I8_FF1: u8 = 4;
+pub const LTX_I8_FF2: u8 = 8;
+pub const LTX_I8_ALL: u8 = 15;
+
+extern "C" {
+    pub fn ltx_dit_set_int8_linears(m: *mut ltx_dit, block_masks: *const u8, mask: u8, stream: ltx_stream) -> c_int;
+    pub fn ltx_dit_get_int8_linears(m: *const ltx_dit, block_masks_out: *mut u8) -> c_int;
+    pub fn ltx_op_quant_rows_i8(x: *const c_void, rows: i64, d: c_int, ld: c_int, q: *mut c_void, scale: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_rownorm_quant_i8(h: *const c_void, rows: i64, d: c_int, ld: c_int, eps: c_float, shift: *const c_float, scale: *const c_float,
+                                   mod_stride: c_int, rows_per_batch: i64, q: *mut c_void, row_scale: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_gemm_i8(a_q: *const c_void, a_scale: *const c_float, w_q: *const c_void, w_scale: *const c_float, bias: *const c_void, y: *mut c_void,
+                          m: c_int, n: c_int, k: c_int, epi: c_int, resid: *const c_void, gate: *const c_float, rows_per_batch: c_int, seg_width: c_int,
+                          tile: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_gemm_i8_raw(a_q: *const c_void, w_q: *const c_void, acc: *mut c_int, m: c_int, n: c_int, k: c_int, tile: c_int, stream: ltx_stream) -> c_int;
+}
