@@ -5,6 +5,7 @@
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
 #include "../../include/ltxhip_int8.h"
+#include "../../include/ltxhip_int8_attn.h"
 
 static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
 
@@ -523,4 +524,28 @@ extern "C" int ltx_op_gemm_i8(const void* a_q, const float* a_scale, const void*
 extern "C" int ltx_op_gemm_i8_raw(const void* a_q, const void* w_q, int* acc, int M, int N, int K, int tile, ltx_stream stream) {
     GemmArgs g; g.A = a_q; g.W = w_q; g.C = acc; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
     return ltx_launch_gemm_i8(g, nullptr, nullptr, EPI_I8_RAW, tile, (hipStream_t)stream);
+}
+
+// ---- the int8 Q K^T attention kernels on their own (include/ltxhip_int8_attn.h) ----
+extern "C" int ltx_op_kmean(const void* k, int B, int Sk, int D, int ldk, float* mean, ltx_stream stream) {
+    LTX_TRY(ltx_kmean_check(k, B, Sk, D, ldk, mean));
+    hipStream_t s = (hipStream_t)stream;
+    void* part = nullptr;      // the per-block partials live for this call only (the DiT keeps its own)
+    if (hipMalloc(&part, ltx_kmean_ws_bytes(B, Sk, D)) != hipSuccess) LTX_FAIL(LTX_ERR_HIP, "ltx_op_kmean: hipMalloc of the partial sums");
+    const int rc = ltx_launch_kmean(k, B, Sk, D, ldk, (float*)part, mean, s);
+    const hipError_t e = hipStreamSynchronize(s);
+    (void)hipFree(part);
+    if (rc != LTX_OK) return rc;
+    if (e != hipSuccess) { ltx_set_error(hipGetErrorString(e)); return LTX_ERR_HIP; }
+    return LTX_OK;
+}
+extern "C" int ltx_op_quant_qk_i8(const void* q, const void* k, const float* mean, int B, int Sq, int Sk, int heads, int hd, int ldq, int ldk,
+                                  void* q8, float* qs, void* k8, float* ks, ltx_stream stream) {
+    return ltx_launch_quant_qk_i8(q, k, mean, B, Sq, Sk, heads, hd, ldq, ldk, q8, qs, k8, ks, (hipStream_t)stream);
+}
+extern "C" int ltx_op_attention_i8(const void* q8, const float* qs, const void* k8, const float* ks, const void* v, void* o,
+                                   int B, int Sq, int Sk, int heads, int hd, int ldv, int ldo, ltx_stream stream) {
+    AttnI8Args a; a.q8 = q8; a.qs = qs; a.k8 = k8; a.ks = ks; a.v = v; a.o = o; a.ldv = ldv; a.ldo = ldo;
+    a.B = B; a.Sq = Sq; a.Sk = Sk; a.heads = heads; a.hd = hd;
+    return ltx_launch_attention_i8(a, (hipStream_t)stream);
 }

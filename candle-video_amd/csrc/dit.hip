@@ -12,6 +12,7 @@
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
 #include "../../include/ltxhip_int8.h"
+#include "../../include/ltxhip_int8_attn.h"
 #include "../host/step_cache.h"
 #include "lora.h"
 
@@ -118,6 +119,12 @@ struct ltx_dit {
     std::vector<I8Slots> i8_w;
     bool i8_any = false, i8_stale = false;
     DevBuf a8, a8s;                  // a quantised activation [M, 4D] int8 and its row scales [M] f32
+    // INT8 Q K^T self-attention (include/ltxhip_int8_attn.h; ltx_dit_set_int8_attention below): per block a flag, and the operands of
+    // one block's attention - nothing here is derived from the weights
+    std::vector<unsigned char> i8a_flag;
+    bool i8a_any = false;
+    DevBuf q8, k8, q8s, k8s, kmean, kpart;      // int8 [M, D] twice; f32 [B, heads, S], [B, heads, ceil(S / 64)], [B, D], kmean's partials
+    void free_int8_attention() { for (DevBuf* b : {&q8, &k8, &q8s, &k8s, &kmean, &kpart}) b->release(); }
     void free_int8(std::vector<void*>* later = nullptr, int l = -1, int k = -1) {      // every copy, or block l's kind k; later: collect instead of freeing
         for (size_t i = 0; i < i8_w.size(); ++i)
             for (int j = 0; j < 4; ++j) {
@@ -136,6 +143,7 @@ struct ltx_dit {
         lora_w.clear();
         free_int8(); i8_w.clear(); i8_mask.clear(); i8_any = false;
         a8.release(); a8s.release();
+        free_int8_attention(); i8a_flag.clear(); i8a_any = false;
         DevBuf* bs[] = {&xin, &encin, &h, &n, &qkv, &attn, &ff, &c1, &encp, &kv2, &tproj, &e1, &emb, &embs, &temb, &ada, &adaf, &cosb, &sinb, &bias, &orig, &orig_hsq, &outT, &rsq, &hsq, &parts};
         for (DevBuf* b : bs) b->release();
         release_caches();
@@ -388,6 +396,31 @@ extern "C" int ltx_dit_set_int8_linears(ltx_dit* m, const unsigned char* block_m
 extern "C" int ltx_dit_get_int8_linears(const ltx_dit* m, unsigned char* block_masks_out) {
     if (!m || !block_masks_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_linears: null argument");
     for (int l = 0; l < m->cfg.num_layers; ++l) block_masks_out[l] = (size_t)l < m->i8_mask.size() ? m->i8_mask[(size_t)l] : 0;
+    return LTX_OK;
+}
+
+// ---- INT8 Q K^T self-attention (include/ltxhip_int8_attn.h) ----
+extern "C" int ltx_dit_set_int8_attention(ltx_dit* m, const unsigned char* block_flags, int on, ltx_stream stream) {
+    (void)stream;
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_int8_attention: null handle");
+    const int L = m->cfg.num_layers, hd = m->cfg.attention_head_dim;
+    std::vector<unsigned char> want((size_t)L);
+    bool any = false;
+    for (int l = 0; l < L; ++l) { want[l] = (on != 0 && (!block_flags || block_flags[l] != 0)) ? 1 : 0; any = any || want[l]; }
+    if (any && m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: the int8 attention takes a bf16 model (this handle is f32)");
+    if (any && hd != 64 && hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: head_dim must be 64 or 128 (this handle has " + std::to_string(hd) + ")");
+    HIP_TRY(hipSetDevice(m->device));
+    const bool had = m->i8a_any;
+    m->i8a_flag = want; m->i8a_any = any;
+    if (had && !any) {                                           // forwards enqueued earlier may still read the operands
+        (void)hipDeviceSynchronize();
+        m->free_int8_attention();
+    }
+    return LTX_OK;
+}
+extern "C" int ltx_dit_get_int8_attention(const ltx_dit* m, unsigned char* block_flags_out) {
+    if (!m || !block_flags_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_attention: null argument");
+    for (int l = 0; l < m->cfg.num_layers; ++l) block_flags_out[l] = (size_t)l < m->i8a_flag.size() ? m->i8a_flag[(size_t)l] : 0;
     return LTX_OK;
 }
 
@@ -858,12 +891,27 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     const float attn_scale = 1.0f / std::sqrt((float)hd);
     QkNormRopeArgs qa; qa.x = m->qkv.p; qa.rows = M; qa.D = D; qa.ld = p.ldqkv; qa.seg_stride = p.seg; qa.nseg = 2; qa.w0 = b.nq1; qa.w1 = b.nk1;
     qa.eps = 1e-5f; qa.cos = m->cosb.as<float>(); qa.sin = m->sinb.as<float>();
-    if (p.fold_q) qa.out_scale0 = attn_scale * 1.4426950408889634f;
+    // a block with int8 attention (ltxhip_int8_attn.h) takes the prescaled q whatever the plan says: its scores are in log2 units
+    const bool attn8 = m->i8a_any && m->i8a_flag[(size_t)l] != 0;
+    if (p.fold_q || attn8) qa.out_scale0 = attn_scale * 1.4426950408889634f;
     LTX_TRY(ltx_launch_qknorm_rope(qa, dt, s));
     AttnArgs at; at.q = m->qkv.p; at.k = (char*)m->qkv.p + (size_t)p.seg * esz; at.v = (char*)m->qkv.p + (size_t)2 * p.seg * esz; at.o = m->attn.p;
     at.ldq = at.ldk = at.ldv = p.ldqkv; at.ldo = D; at.B = B; at.Sq = S; at.Sk = S; at.heads = H; at.hd = hd; at.scale = attn_scale;
     at.q_prescaled = p.fold_q ? 1 : 0;
-    if (!stg_attn) LTX_TRY(ltx_launch_attention(at, dt, s));
+    // self-attention of the batch rows [b0, b1): the bf16 launch, or - int8 attention - the mean of K, the two quantisations and the
+    // int8 Q K^T kernel (batch rows never interact in any of them: a run of rows gets the bits of the whole-batch call)
+    auto self_attention = [&](int b0, int b1) -> int {
+        AttnArgs ar = at; ar.B = b1 - b0;
+        const size_t in_off = (size_t)b0 * S * p.ldqkv * esz;
+        ar.q = (const char*)at.q + in_off; ar.k = (const char*)at.k + in_off; ar.v = (const char*)at.v + in_off; ar.o = (char*)at.o + (size_t)b0 * S * D * esz;
+        if (!attn8) return ltx_launch_attention(ar, dt, s);
+        LTX_TRY(ltx_launch_kmean(ar.k, ar.B, S, D, p.ldqkv, m->kpart.as<float>(), m->kmean.as<float>(), s));
+        LTX_TRY(ltx_launch_quant_qk_i8(ar.q, ar.k, m->kmean.as<float>(), ar.B, S, S, H, hd, p.ldqkv, p.ldqkv, m->q8.p, m->q8s.as<float>(), m->k8.p, m->k8s.as<float>(), s));
+        AttnI8Args a8; a8.q8 = m->q8.p; a8.qs = m->q8s.as<float>(); a8.k8 = m->k8.p; a8.ks = m->k8s.as<float>(); a8.v = ar.v; a8.o = ar.o;
+        a8.ldv = p.ldqkv; a8.ldo = D; a8.B = ar.B; a8.Sq = S; a8.Sk = S; a8.heads = H; a8.hd = hd;
+        return ltx_launch_attention_i8(a8, s);
+    };
+    if (!stg_attn) LTX_TRY(self_attention(0, B));
     else {
         auto for_runs = [&](bool perturbed, auto&& fn) -> int {      // fn(b0, b1) for every maximal run [b0, b1) of batch rows that are / are not perturbed
             for (int b0 = 0; b0 < B; ++b0) {
@@ -875,12 +923,7 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         };
         // attention for the runs of unperturbed batch rows only (one launch per run, none if every row is perturbed): batch rows never
         // interact, so those rows get the bits of the whole-batch launch
-        LTX_TRY(for_runs(false, [&](int b0, int b1) {
-            AttnArgs ar = at; ar.B = b1 - b0;
-            const size_t in_off = (size_t)b0 * S * p.ldqkv * esz;
-            ar.q = (const char*)at.q + in_off; ar.k = (const char*)at.k + in_off; ar.v = (const char*)at.v + in_off; ar.o = (char*)at.o + (size_t)b0 * S * D * esz;
-            return ltx_launch_attention(ar, dt, s);
-        }));
+        LTX_TRY(for_runs(false, self_attention));
         if (m->stg_mode == LTX_STG_ATTENTION_VALUES) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, at.v, p.ldqkv, pert, B, S, D, dt, s));      // to_out(v): v with its bias, before the head split
         else if (!fold1 && !qkv8) LTX_TRY(ltx_launch_stg_fill(m->attn.p, D, m->n.p, D, pert, B, S, D, dt, s));      // to_out(n): the norm pass above left n whole in m->n
         else
@@ -999,7 +1042,10 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
         {&m->c1, KD}, {&m->encp, KD}, {&m->kv2, 2 * KD}, {&m->tproj, nte * 256 * esz}, {&m->e1, nte * D * esz}, {&m->emb, nte * D * esz}, {&m->embs, nte * D * esz},
         {&m->temb, nte * 6 * D * esz}, {&m->cosb, rope}, {&m->sinb, rope}, {&m->bias, MK * sizeof(float)}, {&m->outT, M * c.out_channels * esz},
         {&m->rsq, p.fold_q2 ? part : 0}, {&m->hsq, p.presum ? part : 0}, {&m->parts, p.defer_ff2 ? (size_t)p.ff2_parts * M * D * sizeof(float) : 0}, {&m->orig, skip_layer_mask ? MD : 0},
-        {&m->a8, m->i8_any ? (size_t)M * 4 * D : 0}, {&m->a8s, m->i8_any ? (size_t)M * sizeof(float) : 0}};
+        {&m->a8, m->i8_any ? (size_t)M * 4 * D : 0}, {&m->a8s, m->i8_any ? (size_t)M * sizeof(float) : 0},
+        {&m->q8, m->i8a_any ? (size_t)M * D : 0}, {&m->k8, m->i8a_any ? (size_t)M * D : 0}, {&m->q8s, m->i8a_any ? (size_t)M * c.num_attention_heads * sizeof(float) : 0},
+        {&m->k8s, m->i8a_any ? (size_t)B * c.num_attention_heads * ((S + 63) / 64) * sizeof(float) : 0}, {&m->kmean, m->i8a_any ? (size_t)B * D * sizeof(float) : 0},
+        {&m->kpart, m->i8a_any ? ltx_kmean_ws_bytes(B, S, D) : 0}};
     for (const auto& w : ws) LTX_TRY(w.first->ensure(w.second));
     const bool reuse = sc && sc->reuse;
     if (reuse) {

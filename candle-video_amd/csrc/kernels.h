@@ -212,6 +212,26 @@ constexpr int EPI_I8_RAW = 100;
 int ltx_launch_gemm_i8(const GemmArgs& g, const float* sa, const float* sw, int epi, int tile, hipStream_t s);
 int ltx_gemm_i8_pick_tile(int M, int N);
 
+// ---------------- int8 Q K^T self-attention (quant_qk_i8.hip, attn_i8.hip; include/ltxhip_int8_attn.h states the arithmetic) ----------------
+// mean[b][c] = (1 / Sk) sum_j k[b][j][c]; k bf16 [B, Sk, D] with row stride ldk, mean f32 [B, D].  part: f32 workspace of
+// ltx_kmean_ws_bytes(B, Sk, D) bytes (one partial row per block of 64 keys).  D % 8 == 0.
+size_t ltx_kmean_ws_bytes(int B, int Sk, int D);
+int ltx_kmean_check(const void* k, int B, int Sk, int D, int ldk, const float* mean);      // the launcher's refusals that need no workspace
+int ltx_launch_kmean(const void* k, int B, int Sk, int D, int ldk, float* part, float* mean, hipStream_t s);
+// q bf16 [B, Sq, heads * hd] (row stride ldq) -> q8 int8 [B, Sq, D] dense, qs f32 [B, heads, Sq]: one scale per (token, head);
+// k bf16 [B, Sk, D] (row stride ldk) minus mean f32 [B, D] -> k8 int8 [B, Sk, D] dense, ks f32 [B, heads, ceil(Sk / 64)]: one scale per
+// (head, block of 64 keys).  hd 64 or 128.  One launch.
+int ltx_launch_quant_qk_i8(const void* q, const void* k, const float* mean, int B, int Sq, int Sk, int heads, int hd, int ldq, int ldk,
+                           void* q8, float* qs, void* k8, float* ks, hipStream_t s);
+struct AttnI8Args {
+    const void* q8 = nullptr; const float* qs = nullptr; const void* k8 = nullptr; const float* ks = nullptr;      // the outputs of quant_qk_i8
+    const void* v = nullptr; void* o = nullptr;      // bf16, row strides ldv / ldo elements
+    int ldv = 0, ldo = 0;
+    int B = 1, Sq = 0, Sk = 0, heads = 0, hd = 0;
+    int xcd_heads = 0, wide_o = 0;                   // set by the launcher (AttnArgs' fields)
+};
+int ltx_launch_attention_i8(const AttnI8Args& a, hipStream_t s);      // profiler class: self-attention, 4 B heads Sq Sk hd flops
+
 // ---------------- step cache (stepcache.hip; include/ltxhip_stepcache.h) ----------------
 // One pass over h and prev [rows, D] (T): m = round_T(rms_norm(h, eps) * (1 + scale[g]) + shift[g]), g = row / rows_per_batch (f32 tables,
 // row stride mod_stride - RowNormArgs' indexing), written over prev; the block's sum |m - prev| and sum |prev| (f64) go to

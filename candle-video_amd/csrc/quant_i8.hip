@@ -13,29 +13,9 @@
 #include "common.h"
 #include "kernels.h"
 #include "norm_common.h"
+#include "quant_common.h"
 
 namespace {
-
-__device__ __forceinline__ float group_max(float v, int lpr) {
-    for (int o = lpr >> 1; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float absmax8(const float* f, float m) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(f[j]));
-    return m;
-}
-// q = clamp(rintf(x * inv), -127, 127), eight of them packed low byte first
-__device__ __forceinline__ u32x2 quant8(const float* f, float inv) {
-    uint32_t w[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float r = fminf(fmaxf(rintf(f[j] * inv), -127.0f), 127.0f);
-        w[j >> 2] |= ((uint32_t)(int)r & 255u) << (8 * (j & 3));
-    }
-    return (u32x2){w[0], w[1]};
-}
-__device__ __forceinline__ float inv_of(float amax) { return amax > 0.f ? 127.0f / amax : 0.f; }
 
 // one lane group (lpr lanes) per row, 64 / lpr rows per wave, four waves per block
 __global__ __launch_bounds__(256) void quant_rows_i8_kernel(const bf16_t* __restrict__ x, unsigned char* __restrict__ q, float* __restrict__ scale,

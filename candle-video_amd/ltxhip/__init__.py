@@ -407,6 +407,18 @@ for _name, _sig in _INT8_SIGS.items():
     _fn = getattr(lib, _name)
     _fn.argtypes = _sig
     _fn.restype = C.c_int
+# include/ltxhip_int8_attn.h (kept apart like the ten above)
+_INT8_ATTN_SIGS = {
+    "ltx_dit_set_int8_attention": [_vp, _vp, _i, _vp], "ltx_dit_get_int8_attention": [_vp, _vp],
+    "ltx_op_kmean": [_vp, _i, _i, _i, _i, _vp, _vp],
+    "ltx_op_quant_qk_i8": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ltx_op_attention_i8": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+}
+INT8_ATTN_SYMBOLS = sorted(_INT8_ATTN_SIGS)
+for _name, _sig in _INT8_ATTN_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
 LTX_I8_QKV, LTX_I8_TO_OUT, LTX_I8_FF1, LTX_I8_FF2, LTX_I8_ALL = 1, 2, 4, 8, 15
 INT8_LINEARS = ("qkv", "to_out", "ff1", "ff2")   # the mask bits of ltx_dit_set_int8_linears, lowest first
 GEMM_I8_TILES = ("256x256", "256x128", "128x128")
@@ -727,6 +739,24 @@ class LtxVideoTransformer3DModel:
         """the LTX_I8_* mask of every block"""
         out = (C.c_ubyte * self.config.num_layers)()
         _check(lib.ltx_dit_get_int8_linears(self._h, out))
+        return list(out)
+
+    # ---- INT8 Q K^T self-attention (include/ltxhip_int8_attn.h): handle state, independent of the int8 linears
+    def set_int8_attention(self, on=True, block_flags: Optional[Sequence] = None):
+        """run attn1's score product of every block (or of the blocks with a truthy block_flags entry) on the int8 MFMA, K smoothed by
+        its per-channel mean; on=False clears every flag and frees the operand buffers.  A bf16 model with head_dim 64 or 128."""
+        arr = None
+        if block_flags is not None:
+            if len(block_flags) != self.config.num_layers:
+                raise LtxError(f"set_int8_attention: block_flags has {len(block_flags)} entries for {self.config.num_layers} blocks")
+            arr = (C.c_ubyte * len(block_flags))(*[1 if v else 0 for v in block_flags])
+        _check(lib.ltx_dit_set_int8_attention(self._h, arr, 1 if on else 0, _stream()))
+
+    @property
+    def int8_attention(self) -> List[int]:
+        """0 / 1 per block"""
+        out = (C.c_ubyte * self.config.num_layers)()
+        _check(lib.ltx_dit_get_int8_attention(self._h, out))
         return list(out)
 
     # ---- LoRA adapters (include/ltxhip_lora.h): handle state, so LtxPipeline.call runs on whatever is set
@@ -2518,6 +2548,43 @@ class ops:
         acc = torch.empty(M, N, dtype=torch.int32, device=a_q.device)
         _check(lib.ltx_op_gemm_i8_raw(_ptr(a_q.contiguous()), _ptr(w_q.contiguous()), _ptr(acc), M, N, K, tile, _stream()))
         return acc
+
+    # ---- the int8 Q K^T attention kernels (include/ltxhip_int8_attn.h); q, k, v [B, S, heads * hd] bf16 with unit column stride (views
+    # of a wider row, e.g. slices of a fused q | k | v tensor, keep their row stride)
+    @staticmethod
+    def kmean(k):
+        """mean f32 [B, D] of k [B, Sk, D] over the keys"""
+        B, Sk, D = k.shape
+        if k.stride(2) != 1 or k.stride(0) != Sk * k.stride(1):
+            k = k.contiguous()
+        mean = torch.empty(B, D, dtype=torch.float32, device=k.device)
+        _check(lib.ltx_op_kmean(_ptr(k), B, Sk, D, k.stride(1), _ptr(mean), _stream()))
+        return mean
+
+    @staticmethod
+    def quant_qk_i8(q, k, mean, heads):
+        """-> (q8 int8 [B, Sq, D], qs f32 [B, heads, Sq], k8 int8 [B, Sk, D], ks f32 [B, heads, ceil(Sk / 64)]); q already carries
+        scale * log2(e); mean f32 [B, D] is subtracted from k"""
+        B, Sq, D = q.shape
+        Sk = k.shape[1]
+        q, k = [t if t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) else t.contiguous() for t in (q, k)]
+        q8 = torch.empty(B, Sq, D, dtype=torch.int8, device=q.device); k8 = torch.empty(B, Sk, D, dtype=torch.int8, device=q.device)
+        qs = torch.empty(B, heads, Sq, dtype=torch.float32, device=q.device); ks = torch.empty(B, heads, (Sk + 63) // 64, dtype=torch.float32, device=q.device)
+        _check(lib.ltx_op_quant_qk_i8(_ptr(q), _ptr(k), _ptr(mean.contiguous()), B, Sq, Sk, heads, D // heads, q.stride(1), k.stride(1),
+                                      _ptr(q8), _ptr(qs), _ptr(k8), _ptr(ks), _stream()))
+        return q8, qs, k8, ks
+
+    @staticmethod
+    def attention_i8(q8, qs, k8, ks, v, heads):
+        """o bf16 [B, Sq, D] = softmax2((q8 k8^T) * qs * ks) v per head, the operands of quant_qk_i8"""
+        B, Sq, D = q8.shape
+        Sk = k8.shape[1]
+        if v.stride(2) != 1 or v.stride(0) != Sk * v.stride(1):
+            v = v.contiguous()
+        o = torch.empty(B, Sq, D, dtype=torch.bfloat16, device=q8.device)
+        _check(lib.ltx_op_attention_i8(_ptr(q8.contiguous()), _ptr(qs.contiguous()), _ptr(k8.contiguous()), _ptr(ks.contiguous()), _ptr(v), _ptr(o),
+                                       B, Sq, Sk, heads, D // heads, v.stride(1), D, _stream()))
+        return o
 
     @staticmethod
     def linear_deferred(x, w):

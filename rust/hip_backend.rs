@@ -244,6 +244,19 @@ impl HipDit {
         check(unsafe { sys::ltx_dit_get_int8_linears(self.h, out.as_mut_ptr()) })?;
         Ok(out)
     }
+
+    /// Run attn1's score product on the int8 MFMA with K smoothed by its per-channel mean (include/ltxhip_int8_attn.h) in every
+    /// block, or in the blocks whose `block_flags` entry is non-zero; `on = false` clears every flag.  Handle state, independent of
+    /// `set_int8_linears`.  A bf16 model with head_dim 64 or 128.
+    pub fn set_int8_attention(&mut self, on: bool, block_flags: Option<&[u8]>) -> Result<()> {
+        if let Some(bf) = block_flags {
+            if bf.len() != self.cfg.num_layers {
+                candle_core::bail!("set_int8_attention: {} block flags for {} blocks", bf.len(), self.cfg.num_layers);
+            }
+        }
+        let p = block_flags.map_or(std::ptr::null(), |b| b.as_ptr());
+        check(unsafe { sys::ltx_dit_set_int8_attention(self.h, p, on as i32, std::ptr::null_mut()) })
+    }
 }
 
 impl Drop for HipDit {

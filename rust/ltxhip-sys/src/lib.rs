@@ -554,3 +554,15 @@ extern "C" {
                           tile: c_int, stream: ltx_stream) -> c_int;
     pub fn ltx_op_gemm_i8_raw(a_q: *const c_void, w_q: *const c_void, acc: *mut c_int, m: c_int, n: c_int, k: c_int, tile: c_int, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_int8_attn.h: opt-in INT8 Q K^T self-attention on the int8 MFMA ----
+
+extern "C" {
+    pub fn ltx_dit_set_int8_attention(m: *mut ltx_dit, block_flags: *const u8, on: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_dit_get_int8_attention(m: *const ltx_dit, block_flags_out: *mut u8) -> c_int;
+    pub fn ltx_op_kmean(k: *const c_void, b: c_int, sk: c_int, d: c_int, ldk: c_int, mean: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_quant_qk_i8(q: *const c_void, k: *const c_void, mean: *const c_float, b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int,
+                              ldq: c_int, ldk: c_int, q8: *mut c_void, qs: *mut c_float, k8: *mut c_void, ks: *mut c_float, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_attention_i8(q8: *const c_void, qs: *const c_float, k8: *const c_void, ks: *const c_float, v: *const c_void, o: *mut c_void,
+                               b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int, ldv: c_int, ldo: c_int, stream: ltx_stream) -> c_int;
+}
