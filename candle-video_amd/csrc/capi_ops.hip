@@ -5,9 +5,13 @@
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
 #include "../../include/ltxhip_int8.h"
+#include "../../include/ltxhip_fp8.h"
 #include "../../include/ltxhip_int8_attn.h"
 
-static inline int dtc(int d) { return d == 1 ? LTX_DT_BF16 : LTX_DT_F32; }
+// The ops' dtype argument -> LTX_DT_*.  The one place every op's dtype passes: LTX_F8_E4M3 (a source dtype, ltxhip_fp8.h) is refused
+// here with LTX_ERR_ARG - the enclosing entry point returns - instead of being read as four bytes per element.
+#define dtc(d) ({ const int _dt = (int)(d); if (_dt == LTX_F8_E4M3) LTX_FAIL(LTX_ERR_ARG, std::string(__func__) + ": LTX_F8_E4M3 describes source tensors only (dtype: 0 = f32, 1 = bf16)"); \
+                  _dt == 1 ? LTX_DT_BF16 : LTX_DT_F32; })
 
 extern "C" int ltx_op_linear(const void* x, const void* w, const void* bias, void* y, int M, int N, int K, int dtype, int epi,
                              const void* resid, const float* gate, int rows_per_batch, ltx_stream stream) {
@@ -462,6 +466,10 @@ extern "C" int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B
         }
         if (flags & LTX_ROUTE_PN) { g.pn_on = 1; g.pn_eps = 1e-6f; g.pn_act = 1; }
     }
+    if (flags & LTX_ROUTE_W_FP8) {      // W is e4m3 bytes (ltxhip_fp8.h)
+        if (dtype != 1) LTX_FAIL(LTX_ERR_ARG, "gemm: fp8 weights take bf16 activations");
+        g.w_fp8 = 1;
+    }
     GemmRoute r;
     LTX_TRY(ltx_gemm_route(g, dtc(dtype), epi, nullptr, false, &r));
     if (const char* why = ltx_gemm_route_refusal(g, r)) LTX_FAIL(LTX_ERR_ARG, why);
@@ -482,7 +490,8 @@ extern "C" int ltx_op_dit_plan(int heads, int head_dim, int model_dtype, int io_
 
 // ---- the step cache's kernels on their own (include/ltxhip_stepcache.h) ----
 extern "C" size_t ltx_op_step_measure_ws_bytes(int64_t rows, int D, ltx_dtype dtype) {
-    return (size_t)ltx_step_measure_blocks(rows, D, dtc((int)dtype)) * 2 * sizeof(double);
+    if (dtype != LTX_F32 && dtype != LTX_BF16) return 0;      // (no workspace: ltx_op_step_measure refuses the dtype)
+    return (size_t)ltx_step_measure_blocks(rows, D, dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32) * 2 * sizeof(double);
 }
 extern "C" int ltx_op_step_measure(const void* h, void* prev, const float* shift, const float* scale, int mod_stride, int64_t rows, int D,
                                    int64_t rows_per_batch, float eps, ltx_dtype dtype, int first, void* ws, double* sums, ltx_stream stream) {
@@ -524,6 +533,25 @@ extern "C" int ltx_op_gemm_i8(const void* a_q, const float* a_scale, const void*
 extern "C" int ltx_op_gemm_i8_raw(const void* a_q, const void* w_q, int* acc, int M, int N, int K, int tile, ltx_stream stream) {
     GemmArgs g; g.A = a_q; g.W = w_q; g.C = acc; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
     return ltx_launch_gemm_i8(g, nullptr, nullptr, EPI_I8_RAW, tile, (hipStream_t)stream);
+}
+
+// ---- the fp8 (e4m3) kernels on their own (include/ltxhip_fp8.h) ----
+extern "C" int ltx_op_cast_fp8(const void* x, int64_t rows, int D, int ld, void* q, ltx_stream stream) {
+    return ltx_launch_cast_fp8(x, rows, D, ld, q, (hipStream_t)stream);
+}
+extern "C" int ltx_op_widen_fp8(const void* q, int64_t n, ltx_dtype dst_dtype, void* y, ltx_stream stream) {
+    if (dst_dtype != LTX_F32 && dst_dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_op_widen_fp8: dst_dtype must be LTX_F32 or LTX_BF16");
+    return ltx_launch_widen_fp8(q, n, y, dtc((int)dst_dtype), (hipStream_t)stream);
+}
+extern "C" int ltx_op_gemm_w8(const void* a, const void* w, const float* w_scale, const void* bias, void* y, int M, int N, int K, int epi,
+                              const void* resid, const float* gate, int rows_per_batch, int seg_width, int tile, ltx_stream stream) {
+    if (epi < 0 || epi > 3) LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_w8: epi must be 0..3");
+    if (seg_width < 0 || (seg_width > 0 && ((seg_width & (seg_width - 1)) || N % seg_width || epi != 0)))
+        LTX_FAIL(LTX_ERR_ARG, "ltx_op_gemm_w8: seg_width must be a power of two dividing N, with epi 0");
+    GemmArgs g; g.A = a; g.W = w; g.w_fp8 = 1; g.w_scale = w_scale; g.C = y; g.bias = bias; g.resid = resid; g.gate = gate;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.ldr = N; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; g.gate_stride = N;
+    if (seg_width > 0) { g.ldc = seg_width; g.c_seg_shift = __builtin_ctz((unsigned)seg_width); g.c_seg_stride = (int64_t)M * seg_width; }
+    return ltx_launch_gemm_w8(g, epi, tile, (hipStream_t)stream);
 }
 
 // ---- the int8 Q K^T attention kernels on their own (include/ltxhip_int8_attn.h) ----

@@ -13,6 +13,7 @@
 #include "../../include/ltxhip_stepcache.h"
 #include "../../include/ltxhip_int8.h"
 #include "../../include/ltxhip_int8_attn.h"
+#include "../../include/ltxhip_fp8.h"
 #include "../host/step_cache.h"
 #include "lora.h"
 
@@ -124,6 +125,10 @@ struct ltx_dit {
     std::vector<unsigned char> i8a_flag;
     bool i8a_any = false;
     DevBuf q8, k8, q8s, k8s, kmean, kpart;      // int8 [M, D] twice; f32 [B, heads, S], [B, heads, ceil(S / 64)], [B, D], kmean's partials
+    // fp8-resident block linears (include/ltxhip_fp8.h): fixed at creation - per block the LTX_F8_* mask of the kinds whose LinearW holds
+    // the checkpoint's own e4m3 bytes (w8) and no bf16 matrix
+    std::vector<unsigned char> f8_mask;
+    bool f8_any = false;
     void free_int8_attention() { for (DevBuf* b : {&q8, &k8, &q8s, &k8s, &kmean, &kpart}) b->release(); }
     void free_int8(std::vector<void*>* later = nullptr, int l = -1, int k = -1) {      // every copy, or block l's kind k; later: collect instead of freeing
         for (size_t i = 0; i < i8_w.size(); ++i)
@@ -176,7 +181,24 @@ struct StepCacheUse { ltx_step_cache* c = nullptr; int row0 = 0; bool reuse = fa
 
 namespace {
 
-int own_linear(ltx_dit* m, const WeightMap& wm, const std::string& prefix, int in, int out, LinearW* l) {
+// an F8_E4M3 source that a bf16 handle keeps as it is (ltxhip_fp8.h): the shapes gemm_w8 serves
+bool stays_fp8(const ltx_dit* m, const ltx_weight* w, int in, int out) { return w && w->dtype == LTX_F8_E4M3 && m->dtype == LTX_DT_BF16 && in % 16 == 0 && out % 4 == 0; }
+int upload_fp8(const ltx_weight* w, void* dst, int64_t numel, const std::string& name) {
+    if (ltx_numel(w) != numel) LTX_FAIL(LTX_ERR_ARG, "weight '" + name + "': expected " + std::to_string(numel) + " elements, got " + std::to_string(ltx_numel(w)));
+    HIP_TRY(hipMemcpy(dst, w->data, (size_t)numel, w->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    return LTX_OK;
+}
+// keep_f8: one of the four kinds gemm_w8 serves - an fp8 source stays fp8 (l->w8; l->w null), the bias is widened as always
+int own_linear(ltx_dit* m, const WeightMap& wm, const std::string& prefix, int in, int out, LinearW* l, bool keep_f8 = false) {
+    const ltx_weight* w = wm.find(prefix + ".weight");
+    if (keep_f8 && stays_fp8(m, w, in, out)) {
+        l->in = in; l->out = out;
+        HIP_TRY(hipMalloc(&l->w8, (size_t)in * out + 16)); m->owned.push_back(l->w8);
+        LTX_TRY(upload_fp8(w, l->w8, (int64_t)in * out, prefix + ".weight"));
+        LTX_TRY(ltx_load_tensor(wm, prefix + ".bias", out, m->dtype, &l->b, /*optional=*/true));
+        if (l->b) m->owned.push_back(l->b);
+        return LTX_OK;
+    }
     LTX_TRY(ltx_load_linear(wm, prefix, in, out, m->dtype, l));
     m->owned.push_back(l->w); if (l->b) m->owned.push_back(l->b);
     return LTX_OK;
@@ -187,17 +209,21 @@ int own_tensor(ltx_dit* m, const WeightMap& wm, const std::string& name, int64_t
     return LTX_OK;
 }
 // fused [sum(out_i), in] linear from several reference linears sharing the same input
-int own_fused(ltx_dit* m, const WeightMap& wm, const std::vector<std::string>& prefixes, int in, int out_each, LinearW* l) {
+// keep_f8: the fused matrix stays fp8 only if EVERY part's source is fp8 (else all parts are widened)
+int own_fused(ltx_dit* m, const WeightMap& wm, const std::vector<std::string>& prefixes, int in, int out_each, LinearW* l, bool keep_f8 = false) {
     const int n = (int)prefixes.size();
     const size_t esz = ltx_dt_size(m->dtype);
     l->in = in; l->out = out_each * n;
-    HIP_TRY(hipMalloc(&l->w, (size_t)l->out * in * esz)); m->owned.push_back(l->w);
+    for (int i = 0; i < n; ++i) keep_f8 = keep_f8 && stays_fp8(m, wm.find(prefixes[i] + ".weight"), in, out_each);
+    if (keep_f8) { HIP_TRY(hipMalloc(&l->w8, (size_t)l->out * in + 16)); m->owned.push_back(l->w8); }
+    else { HIP_TRY(hipMalloc(&l->w, (size_t)l->out * in * esz)); m->owned.push_back(l->w); }
     bool has_bias = wm.find(prefixes[0] + ".bias") != nullptr;
     if (has_bias) { HIP_TRY(hipMalloc(&l->b, (size_t)l->out * esz)); m->owned.push_back(l->b); }
     for (int i = 0; i < n; ++i) {
         const ltx_weight* w = wm.find(prefixes[i] + ".weight");
         if (!w) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight '" + prefixes[i] + ".weight'");
-        LTX_TRY(ltx_upload_cast(w, (char*)l->w + (size_t)i * out_each * in * esz, m->dtype, (int64_t)out_each * in, prefixes[i] + ".weight"));
+        if (keep_f8) LTX_TRY(upload_fp8(w, (char*)l->w8 + (size_t)i * out_each * in, (int64_t)out_each * in, prefixes[i] + ".weight"));
+        else LTX_TRY(ltx_upload_cast(w, (char*)l->w + (size_t)i * out_each * in * esz, m->dtype, (int64_t)out_each * in, prefixes[i] + ".weight"));
         if (has_bias) {
             const ltx_weight* b = wm.find(prefixes[i] + ".bias");
             if (!b) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight '" + prefixes[i] + ".bias'");
@@ -225,8 +251,8 @@ int build(ltx_dit* m, const ltx_weight* weights, size_t n_weights) {
     for (int i = 0; i < L; ++i) {
         const std::string p = "transformer_blocks." + std::to_string(i) + ".";
         DitBlock& b = m->blocks[i];
-        LTX_TRY(own_fused(m, wm, {p + "attn1.to_q", p + "attn1.to_k", p + "attn1.to_v"}, D, D, &b.qkv1));
-        LTX_TRY(own_linear(m, wm, p + "attn1.to_out.0", D, D, &b.o1));
+        LTX_TRY(own_fused(m, wm, {p + "attn1.to_q", p + "attn1.to_k", p + "attn1.to_v"}, D, D, &b.qkv1, /*keep_f8=*/true));
+        LTX_TRY(own_linear(m, wm, p + "attn1.to_out.0", D, D, &b.o1, /*keep_f8=*/true));
         LTX_TRY(own_tensor(m, wm, p + "attn1.norm_q.weight", D, &b.nq1));
         LTX_TRY(own_tensor(m, wm, p + "attn1.norm_k.weight", D, &b.nk1));
         LTX_TRY(own_linear(m, wm, p + "attn2.to_q", D, D, &b.q2));
@@ -234,8 +260,8 @@ int build(ltx_dit* m, const ltx_weight* weights, size_t n_weights) {
         LTX_TRY(own_linear(m, wm, p + "attn2.to_out.0", D, D, &b.o2));
         LTX_TRY(own_tensor(m, wm, p + "attn2.norm_q.weight", D, &b.nq2));
         LTX_TRY(own_tensor(m, wm, p + "attn2.norm_k.weight", D, &b.nk2));
-        LTX_TRY(own_linear(m, wm, p + "ff.net.0.proj", D, 4 * D, &b.ff1));
-        LTX_TRY(own_linear(m, wm, p + "ff.net.2", 4 * D, D, &b.ff2));
+        LTX_TRY(own_linear(m, wm, p + "ff.net.0.proj", D, 4 * D, &b.ff1, /*keep_f8=*/true));
+        LTX_TRY(own_linear(m, wm, p + "ff.net.2", 4 * D, D, &b.ff2, /*keep_f8=*/true));
         const ltx_weight* t = wm.find(p + "scale_shift_table");
         if (!t) LTX_FAIL(LTX_ERR_MISSING_WEIGHT, "missing weight '" + p + "scale_shift_table'");
         LTX_TRY(ltx_upload_cast(t, (char*)m->sst_blocks + (size_t)i * 6 * D * esz, m->dtype, 6 * (int64_t)D, p + "scale_shift_table"));
@@ -269,6 +295,8 @@ LinearW* dit_slot(DitBlock& b, int slot) {
     LinearW* const ws[7] = {&b.qkv1, &b.o1, &b.q2, &b.kv2, &b.o2, &b.ff1, &b.ff2};
     return ws[slot];
 }
+constexpr int kI8Slot[4] = {0, 1, 5, 6};      // dit_slot's index of bit i of the LTX_I8_* / LTX_F8_* masks: qkv1, o1, ff1, ff2
+constexpr const char* kKindName[4] = {"attn1 q | k | v", "attn1.to_out", "ff.net.0.proj", "ff.net.2"};
 constexpr int kLoraSlot[kLoraLinears] = {0, 0, 0, 1, 2, 3, 3, 4, 5, 6}, kLoraPart[kLoraLinears] = {0, 1, 2, 0, 0, 0, 1, 0, 0, 0};
 constexpr int kSlotParts[7] = {3, 1, 1, 2, 1, 1, 1}, kSlotFirst[7] = {0, 3, 4, 5, 7, 8, 9};
 
@@ -278,6 +306,7 @@ extern "C" int ltx_dit_create(const ltx_dit_config* cfg, const ltx_weight* weigh
                               ltx_dtype model_dtype, int device, ltx_dit** out) {
     if (!cfg || !weights || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_create: null argument");
     *out = nullptr;
+    LTX_REFUSE_F8(model_dtype, "ltx_dit_create");
     const int hd = cfg->attention_head_dim;
     if (hd != 16 && hd != 32 && hd != 64 && hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "attention_head_dim must be 16/32/64/128");
     const int D = cfg->num_attention_heads * hd;
@@ -294,6 +323,10 @@ extern "C" int ltx_dit_create(const ltx_dit_config* cfg, const ltx_weight* weigh
     m->lora_w.resize(m->blocks.size());
     for (size_t l = 0; l < m->blocks.size(); ++l)
         for (int slot = 0; slot < 7; ++slot) m->lora_w[l].base[slot] = dit_slot(m->blocks[l], slot)->w;
+    m->f8_mask.assign(m->blocks.size(), 0);
+    for (size_t l = 0; l < m->blocks.size(); ++l)
+        for (int k = 0; k < 4; ++k)
+            if (dit_slot(m->blocks[l], kI8Slot[k])->w8) { m->f8_mask[l] |= (unsigned char)(1 << k); m->f8_any = true; }
     *out = m;
     return LTX_OK;
 }
@@ -335,7 +368,6 @@ extern "C" int ltx_dit_get_config(const ltx_dit* m, ltx_dit_config* out) {
 
 // ---- INT8 (W8A8) block linears (include/ltxhip_int8.h) ----
 namespace {
-constexpr int kI8Slot[4] = {0, 1, 5, 6};      // dit_slot's index of mask bit i: qkv1, o1, ff1, ff2
 // (re-)quantise every selected weight from the pointer the forward reads (LinearW::w: the base, or the LoRA-merged copy)
 int int8_quantise(ltx_dit* m, hipStream_t s) {
     for (size_t l = 0; l < m->i8_mask.size(); ++l)
@@ -359,6 +391,10 @@ extern "C" int ltx_dit_set_int8_linears(ltx_dit* m, const unsigned char* block_m
     bool any = false;
     for (int l = 0; l < L; ++l) { want[l] = block_masks ? (unsigned char)(block_masks[l] & mask) : mask; any = any || want[l]; }
     if (any && m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_linears: the int8 layers take a bf16 model (this handle is f32)");
+    for (int l = 0; l < L && m->f8_any; ++l)      // the quantise pass reads bf16 rows: an fp8-resident layer has none (ltxhip_fp8.h)
+        for (int k = 0; k < 4; ++k)
+            if ((want[l] & m->f8_mask[(size_t)l]) >> k & 1)
+                LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_linears: block " + std::to_string(l) + "'s " + kKindName[k] + " is fp8-resident (the handle is unchanged)");
     if (any && (m->D % 16 != 0 || m->D > 4096)) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_linears: the inner dimension must be a multiple of 16, at most 4096");
     HIP_TRY(hipSetDevice(m->device));
     m->i8_mask.resize((size_t)L, 0); m->i8_w.resize((size_t)L);
@@ -396,6 +432,13 @@ extern "C" int ltx_dit_set_int8_linears(ltx_dit* m, const unsigned char* block_m
 extern "C" int ltx_dit_get_int8_linears(const ltx_dit* m, unsigned char* block_masks_out) {
     if (!m || !block_masks_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_linears: null argument");
     for (int l = 0; l < m->cfg.num_layers; ++l) block_masks_out[l] = (size_t)l < m->i8_mask.size() ? m->i8_mask[(size_t)l] : 0;
+    return LTX_OK;
+}
+
+// ---- fp8-resident block linears (include/ltxhip_fp8.h) ----
+extern "C" int ltx_dit_get_fp8_linears(const ltx_dit* m, unsigned char* block_masks_out) {
+    if (!m || !block_masks_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_fp8_linears: null argument");
+    for (int l = 0; l < m->cfg.num_layers; ++l) block_masks_out[l] = m->f8_mask[(size_t)l];
     return LTX_OK;
 }
 
@@ -439,7 +482,7 @@ struct DitOperands {          // the handle's workspaces and one layer's table r
     float eps;
 };
 GemmArgs gemm_base(const DitPlan& p, const LinearW& w, const void* A, int lda, void* C, int ldc) {
-    GemmArgs g; g.A = A; g.W = w.w; g.C = C; g.bias = w.b; g.M = (int)p.M; g.N = w.out; g.K = w.in; g.lda = lda; g.ldc = ldc;
+    GemmArgs g; g.A = A; g.W = w.w8 ? w.w8 : w.w; g.w_fp8 = w.w8 != nullptr; g.w_scale = w.sw; g.C = C; g.bias = w.b; g.M = (int)p.M; g.N = w.out; g.K = w.in; g.lda = lda; g.ldc = ldc;
     return g;
 }
 // a consumer of the norm fold: out = epi(r_m * acc + cvec), r_m from the producer's row partials; form 2 reads h through the scaled weights
@@ -1030,7 +1073,9 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
     DitPlan plan = ltx_dit_plan(c, m->dtype, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, S, K, G, skip_layer_mask != nullptr);
     // a handle with int8 layers (ltxhip_int8.h) runs its copy of the plan without the fusions whose launches pair bf16 producers with
     // bf16 consumers: no norm fold, no row partials for the norms, no deferred ff2 (fold_q2, fold_vo, dense_qkv and fold_q stay)
-    if (m->i8_any) { plan.nfold = false; plan.presum = false; plan.defer_ff2 = false; plan.ff2_parts = 0; }
+    // ... and so does a handle with fp8-resident layers (ltxhip_fp8.h): those launches read bf16 weights (the scaled copies, the
+    // per-timestep vectors, the fold and ring kernels); a block's fp8 layer is its pass-form call, which the route sends to gemm_w8
+    if (m->i8_any || m->f8_any) { plan.nfold = false; plan.presum = false; plan.defer_ff2 = false; plan.ff2_parts = 0; }
     const DitPlan p = plan;
     const int dt = p.dt, D = p.D, L = c.num_layers;
     const int64_t M = p.M, MK = p.MK; const size_t esz = ltx_dt_size(dt);
@@ -1112,6 +1157,7 @@ int dit_forward_chunks(ltx_dit* m, const void* hidden, const void* enc, const fl
                        const float* enc_mask, int B, int S, int K, int num_frames, int height, int width,
                        const float* rope_scale, const float* video_coords, const float* skip_layer_mask,
                        ltx_dtype io_dtype, void* out, ltx_stream stream, const StepCacheUse* sc = nullptr) {
+    LTX_REFUSE_F8(io_dtype, "ltx_dit_forward");
     const size_t esz = io_dtype == LTX_BF16 ? 2 : 4;
     const int L = m->cfg.num_layers;
     if (skip_layer_mask && m->stg_mode != LTX_STG_TRANSFORMER_BLOCK)      // the attention modes replace an operand of to_out: there is nothing to blend
@@ -1345,6 +1391,12 @@ extern "C" int ltx_dit_set_adapters(ltx_dit* m, const ltx_lora* const* loras, co
             LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_adapters: adapter " + std::to_string(i) + " was built for another configuration (inner dim " +
                                   std::to_string(l->cfg.num_attention_heads * l->cfg.attention_head_dim) + ", " + std::to_string(l->cfg.num_layers) + " layers), dtype or device");
     }
+    for (int i = 0; i < n && m->f8_any; ++i)      // the merge kernel reads a bf16 base: an fp8-resident layer has none (ltxhip_fp8.h)
+        for (const LoraEntry& e : loras[i]->entries)
+            for (int k = 0; k < 4; ++k)
+                if (kLoraSlot[e.which] == kI8Slot[k] && (m->f8_mask[(size_t)e.block] >> k & 1))
+                    LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_adapters: adapter " + std::to_string(i) + " targets block " + std::to_string(e.block) + "'s " + kKindName[k] +
+                                                  ", which is fp8-resident (the handle is unchanged)");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t esz = ltx_dt_size(m->dtype);
@@ -1411,6 +1463,10 @@ extern "C" int ltx_dit_read_linear(const ltx_dit* m, int block, int which, void*
         LTX_FAIL(LTX_ERR_ARG, "ltx_dit_read_linear: block 0.." + std::to_string(m->cfg.num_layers - 1) + ", which 0..9");
     HIP_TRY(hipSetDevice(m->device));
     const LinearW* lw = dit_slot(const_cast<DitBlock&>(m->blocks[block]), kLoraSlot[which]);
+    if (lw->w8) {      // fp8-resident: the part, widened to bf16 (one convert launch; exact)
+        const int64_t numel = (int64_t)(lw->out / kSlotParts[kLoraSlot[which]]) * lw->in;
+        return ltx_launch_widen_fp8((const char*)lw->w8 + (size_t)kLoraPart[which] * numel, numel, out_dev, m->dtype, (hipStream_t)stream);
+    }
     const size_t bytes = (size_t)(lw->out / kSlotParts[kLoraSlot[which]]) * lw->in * ltx_dt_size(m->dtype);
     HIP_TRY(hipMemcpyAsync(out_dev, (const char*)lw->w + (size_t)kLoraPart[which] * bytes, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LTX_OK;

@@ -202,6 +202,10 @@ int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s) {
     GemmRoute r;
     LTX_TRY(ltx_gemm_route(g, dtype, epi, s, true, &r));
     if (const char* why = ltx_gemm_route_refusal(g, r)) LTX_FAIL(LTX_ERR_ARG, why);
+    if (r.kind == LTX_ROUTE_W8) {      // fp8 weights: gemm_w8.hip's own checks, profiler bracket and launch
+        if (dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_ARG, "gemm: fp8 weights take bf16 activations");
+        return ltx_launch_gemm_w8(g, epi, r.plan.idx, s);
+    }
     t_rowsq_done = false;
     void* tok = nullptr;
     ltx_prof_begin(g.conv ? LTX_PROF_CONV : LTX_PROF_GEMM, 2.0 * g.M * (double)g.N * g.K * (g.conv ? g.ntaps : 1), s, &tok);

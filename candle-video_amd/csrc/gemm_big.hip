@@ -877,18 +877,24 @@ int choose_plan(const GemmArgs& g, int epi, hipStream_t s, bool measure, GemmPla
 
 // ---- the route of a call (kernels.h) ---------------------------------------------------------------------------------
 int ltx_gemm_route_kind(const GemmArgs& g, int dtype, int epi) {
+    if (g.w_fp8) return LTX_ROUTE_W8;      // fp8 weights: one kernel reads them (gemm_w8.hip)
     if (ltx_gemm_asm_eligible(g, dtype, epi)) return LTX_ROUTE_ASM32;
     return ltx_gemm_big_eligible(g, dtype) ? LTX_ROUTE_PLAN : LTX_ROUTE_GEMM128;
 }
 int ltx_gemm_route(const GemmArgs& g, int dtype, int epi, hipStream_t s, bool measure, GemmRoute* r) {
     r->kind = ltx_gemm_route_kind(g, dtype, epi); r->plan = GemmPlan{};
     if (r->kind == LTX_ROUTE_PLAN) LTX_TRY(choose_plan(g, epi, s, measure, &r->plan));
+    if (r->kind == LTX_ROUTE_W8) r->plan.idx = ltx_gemm_w8_pick_tile(g.M, g.N);      // (fam stays -1: no plan family, the tile of the shape rule)
     return LTX_OK;
 }
-const char* ltx_gemm_route_name(const GemmRoute& r) { return r.kind == LTX_ROUTE_PLAN ? plan_name(r.plan) : (r.kind == LTX_ROUTE_ASM32 ? "asm32" : "gemm128"); }
+const char* ltx_gemm_route_name(const GemmRoute& r) {
+    if (r.kind == LTX_ROUTE_W8) return ltx_gemm_w8_tile_name(r.plan.idx);
+    return r.kind == LTX_ROUTE_PLAN ? plan_name(r.plan) : (r.kind == LTX_ROUTE_ASM32 ? "asm32" : "gemm128");
+}
 // Operands that only one family reads, on a route that is not that family's: the reason, else null
 const char* ltx_gemm_route_refusal(const GemmArgs& g, const GemmRoute& r) {
     const int fam = r.kind == LTX_ROUTE_PLAN ? r.plan.fam : -1;
+    if (r.kind == LTX_ROUTE_W8 && (g.conv || g.rowsq || g.Wp)) return "gemm: fp8 weights (w_fp8) serve plain linear calls only (no conv, no row partials, no packed copy)";
     if (g.defer_parts && fam != kPlanRing) return "gemm: defer_parts set on a call that is not routed to the ring tiles (ask ltx_gemm_defer_ok first)";
     if ((g.C2 || g.rs_sq) && fam != kPlanAsm16) return "gemm: norm-fold arguments (C2 / rs_sq) on a call that is not routed to gemm_asm16 (ask ltx_gemm_fold_ok first)";
     // (any route: gemm.hip's 128 x 128 kernel - f32, convs below 16 voxels, gemm_off=big - and the 32x32x16 kernel do not read pn_on either)

@@ -94,6 +94,7 @@ int ltx_launch_gguf_dequant(const void* blocks_dev, int ggml_type, int64_t numel
 
 extern "C" int ltx_gguf_dequantize(int ggml_type, const void* blocks, int on_device, int64_t numel, ltx_dtype dst_dtype, void* dst, ltx_stream stream) {
     if (!blocks || !dst) LTX_FAIL(LTX_ERR_ARG, "ltx_gguf_dequantize: null argument");
+    if (dst_dtype != LTX_F32 && dst_dtype != LTX_BF16) LTX_FAIL(LTX_ERR_ARG, "ltx_gguf_dequantize: dst_dtype must be LTX_F32 or LTX_BF16");
     int be = 0, bb = 0;
     if (ltx_gguf_type_info(ggml_type, &be, &bb) != LTX_OK) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_gguf_dequantize: ggml type " + std::to_string(ggml_type) + " is not read");
     if (numel <= 0 || numel % be) LTX_FAIL(LTX_ERR_ARG, "ltx_gguf_dequantize: element count is not a multiple of the block size");

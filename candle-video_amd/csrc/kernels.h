@@ -14,7 +14,8 @@ bool ltx_prof_begin(int kind, double work, hipStream_t s, void** token);   // wo
 void ltx_prof_end(void* token, hipStream_t s);
 // which KERNEL served the launch being timed (set by the launcher that actually enqueues it; read by ltx_prof_end)
 enum { LTX_PROFK_GEMM128 = 0, LTX_PROFK_GEMM_BIG = 1, LTX_PROFK_GEMM_P8 = 2, LTX_PROFK_CONV_HALO = 3, LTX_PROFK_GEMM_ASM = 4, LTX_PROFK_GEMM_ASM16 = 5, LTX_PROFK_GEMM_RING = 6,
-       LTX_PROFK_GEMM_I8 = 7, LTX_PROFK_QUANT_ROWS_I8 = 8, LTX_PROFK_ROWNORM_QUANT_I8 = 9, LTX_PROFK_N = 10 };      // (the int8 kernels: class GEMM, ROWNORM, ROWNORM)
+       LTX_PROFK_GEMM_I8 = 7, LTX_PROFK_QUANT_ROWS_I8 = 8, LTX_PROFK_ROWNORM_QUANT_I8 = 9,      // (the int8 kernels: class GEMM, ROWNORM, ROWNORM)
+       LTX_PROFK_GEMM_W8 = 10, LTX_PROFK_N = 11 };
 void ltx_prof_kernel(int which);
 // Kernel-level start / stop events for the launch being timed (the dispatch packet's own timestamps, what rocprofv3's kernel
 // trace reports): stream-level hipEventRecord brackets also count the dispatch latency and the end-of-kernel release that the
@@ -87,6 +88,9 @@ struct GemmArgs {
     // zero padded - a tile's K-step is then 4-KiB blocks and a block's whole K range one contiguous stream, instead of 128-byte
     // pieces of rows K * 2 bytes apart (ltx_pack_ring_weights; same values; measured neutral: opt-in, LTX_RING_PACK=1)
     const void* Wp = nullptr;
+    // W is fp8 (e4m3) bytes [N, K] (gemm_w8.hip; include/ltxhip_fp8.h): the call goes to that kernel, out = epi(acc * w_scale[n] + bias[n]);
+    // w_scale f32 [N] or null (= 1).  bf16 activations and outputs, a plain linear call (the epilogues 0..3, the segmented output).
+    int w_fp8 = 0; const float* w_scale = nullptr;
     int xcd_remap = 0;            // gemm_big: give each XCD a contiguous run of tiles
     int group_m = 0;              // gemm_big: tile order inside that run: columns of group_m row-tiles (0/1: row-major)
     int wide_epi = 0;             // gemm_big (set by its launcher): result tile through LDS, 16-byte row-contiguous stores
@@ -109,7 +113,7 @@ int ltx_launch_gemm(const GemmArgs& g, int dtype, int epi, hipStream_t s);
 // (experiment builds) or a plan - a kernel family and a tile of it (gemm_big.hip's plan table).
 enum PlanFamily { kPlanBig, kPlanP8, kPlanHalo, kPlanAsm16, kPlanAsm16Conv, kPlanRing };
 struct GemmPlan { int fam = -1, idx = 0; bool ok() const { return fam >= 0; } };
-enum { LTX_ROUTE_GEMM128 = 0, LTX_ROUTE_ASM32 = 1, LTX_ROUTE_PLAN = 2 };
+enum { LTX_ROUTE_GEMM128 = 0, LTX_ROUTE_ASM32 = 1, LTX_ROUTE_PLAN = 2, LTX_ROUTE_W8 = 3 };      // W8: GemmArgs::w_fp8 (gemm_w8.hip; its tile is a shape rule)
 struct GemmRoute { int kind = LTX_ROUTE_GEMM128; GemmPlan plan; };      // plan: empty where no family honours the call's operands
 int ltx_gemm_route_kind(const GemmArgs& g, int dtype, int epi);          // the static predicates alone: no plan is chosen
 // the whole decision; measure: a shape without a cached plan may be measured on s (otherwise s is not used)
@@ -231,6 +235,17 @@ struct AttnI8Args {
     int xcd_heads = 0, wide_o = 0;                   // set by the launcher (AttnArgs' fields)
 };
 int ltx_launch_attention_i8(const AttnI8Args& a, hipStream_t s);      // profiler class: self-attention, 4 B heads Sq Sk hd flops
+
+// ---------------- fp8 (e4m3) weights (gemm_w8.hip; include/ltxhip_fp8.h states the arithmetic) ----------------
+// g: A bf16 [M, lda], W fp8 [N, K], g.w_scale f32 [N] or null, C bf16 (EPI_BIAS / GELU / GATE_RESID / RESID with GemmArgs' bias, resid,
+// gate, c_seg_*).  tile: -1 the shape rule, 0 256x256, 1 256x128, 2 128x128.  ltx_launch_gemm sends a call with g.w_fp8 here.
+int ltx_launch_gemm_w8(const GemmArgs& g, int epi, int tile, hipStream_t s);
+int ltx_gemm_w8_pick_tile(int M, int N);
+const char* ltx_gemm_w8_tile_name(int tile);      // "w8:256x256", ...
+// x bf16 [rows, D] (row stride ld) -> q fp8 [rows, D] dense, round to nearest even, saturating at +-448; D % 16 == 0
+int ltx_launch_cast_fp8(const void* x, int64_t rows, int D, int ld, void* q, hipStream_t s);
+// q fp8 [n] -> y [n] of dst_dtype (LTX_DT_*), exact
+int ltx_launch_widen_fp8(const void* q, int64_t n, void* y, int dst_dtype, hipStream_t s);
 
 // ---------------- step cache (stepcache.hip; include/ltxhip_stepcache.h) ----------------
 // One pass over h and prev [rows, D] (T): m = round_T(rms_norm(h, eps) * (1 + scale[g]) + shift[g]), g = row / rows_per_batch (f32 tables,

@@ -11,6 +11,11 @@
 #include "../../include/ltxhip.h"
 #include "../../include/ltxhip_stepcache.h"
 
+// LTX_F8_E4M3 is a source dtype only: every entry point that takes a model dtype or an I/O dtype refuses it
+#define LTX_REFUSE_F8(dt, who) do { if ((int)(dt) == LTX_F8_E4M3) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": LTX_F8_E4M3 describes source tensors only (model and I/O dtypes: LTX_F32 or LTX_BF16)"); } while (0)
+// bytes of one element of a source tensor (ltx_weight::dtype)
+static inline size_t ltx_src_size(int dtype) { return dtype == LTX_F8_E4M3 ? 1 : (dtype == LTX_BF16 ? 2 : 4); }
+
 // thread-local "the last failure on this thread was an out-of-memory hipMalloc" (DevBuf::ensure); cleared by the reader
 void ltx_note_oom();
 bool ltx_take_oom();
@@ -37,6 +42,9 @@ struct DevBuf {
 
 struct LinearW {
     void* w = nullptr;   // [out, in] model dtype
+    // fp8-resident (include/ltxhip_fp8.h; bf16 handles, the DiT's block linears whose source is F8_E4M3): the matrix as found, [out, in]
+    // bytes, and w is null - no bf16 copy exists.  sw: one f32 factor per output channel or null (= 1; no loader sets one yet)
+    void* w8 = nullptr; float* sw = nullptr;
     void* b = nullptr;   // [out] model dtype or null
     int in = 0, out = 0;
     // tile-contiguous second copy for gemm_ring.hip (GemmArgs::Wp), made by ltx_linear on the first call with at most 512 rows
@@ -57,7 +65,7 @@ static inline int64_t ltx_numel(const ltx_weight* w) {
     return n;
 }
 
-// Copy weight `w` (host or device, any dtype) into device memory `dst` as `dst_dtype` (no layout change).
+// Copy weight `w` (host or device, any dtype) into device memory `dst` as `dst_dtype` (no layout change; an F8_E4M3 source is widened, exactly).
 int ltx_upload_cast(const ltx_weight* w, void* dst, int dst_dtype, int64_t expect_numel, const std::string& name);
 // Allocate + upload a tensor by name; fails with LTX_ERR_MISSING_WEIGHT when absent (unless optional).
 int ltx_load_tensor(const WeightMap& wm, const std::string& name, int64_t numel, int dtype, void** out, bool optional = false);

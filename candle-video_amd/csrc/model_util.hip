@@ -4,7 +4,7 @@
 int ltx_stage_src(const ltx_weight* w, const void** dev_src, void** temp_to_free) {
     *temp_to_free = nullptr;
     if (w->on_device) { *dev_src = w->data; return LTX_OK; }
-    size_t bytes = (size_t)ltx_numel(w) * ltx_dt_size(w->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32);
+    size_t bytes = (size_t)ltx_numel(w) * ltx_src_size(w->dtype);
     void* tmp = nullptr;
     HIP_TRY(hipMalloc(&tmp, bytes ? bytes : 16));
     hipError_t e = hipMemcpy(tmp, w->data, bytes, hipMemcpyHostToDevice);
@@ -18,7 +18,8 @@ int ltx_upload_cast(const ltx_weight* w, void* dst, int dst_dtype, int64_t expec
         LTX_FAIL(LTX_ERR_ARG, "weight '" + name + "': expected " + std::to_string(expect_numel) + " elements, got " + std::to_string(ltx_numel(w)));
     const void* src = nullptr; void* tmp = nullptr;
     LTX_TRY(ltx_stage_src(w, &src, &tmp));
-    int rc = ltx_launch_cast(src, w->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, dst, dst_dtype, expect_numel, 0);
+    int rc = w->dtype == LTX_F8_E4M3 ? ltx_launch_widen_fp8(src, expect_numel, dst, dst_dtype, 0)
+                                     : ltx_launch_cast(src, w->dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, dst, dst_dtype, expect_numel, 0);
     hipError_t e = hipDeviceSynchronize();
     if (tmp) (void)hipFree(tmp);
     if (rc != LTX_OK) return rc;
@@ -51,13 +52,13 @@ int ltx_load_linear(const WeightMap& wm, const std::string& prefix, int in, int 
 int ltx_linear(const LinearW& l, const void* x, int lda, void* y, int ldc, int M, int dtype, int epi, hipStream_t s,
                const void* resid, int ldr, const float* gate, int gate_stride, int rows_per_batch, float* rowsq) {
     GemmArgs g;
-    g.A = x; g.W = l.w; g.C = y; g.bias = l.b; g.resid = resid; g.gate = gate;
+    g.A = x; g.W = l.w8 ? l.w8 : l.w; g.w_fp8 = l.w8 != nullptr; g.w_scale = l.sw; g.C = y; g.bias = l.b; g.resid = resid; g.gate = gate;
     g.M = M; g.N = l.out; g.K = l.in; g.lda = lda; g.ldc = ldc; g.ldr = ldr;
     g.rows_per_batch = rows_per_batch; g.gate_stride = gate_stride; g.rowsq = rowsq;
     // Opt-in experiment (x_ring_pack=1 in an experiment build; measured: C1 654 vs 654 frames/s, T5-XXL 4.87 vs 5.08 ms - not worth a second copy
     // of the weights, docs/lab_notes.md R4.11): small-M calls hand gemm_ring.hip a tile-contiguous copy of the weights, built
     // once per layer on its first such call (+ 100 % of the layer's weight bytes).
-    if (dtype == LTX_DT_BF16 && M <= 512 && l.out >= 32 && l.out % 4 == 0 && l.in % 8 == 0) {
+    if (dtype == LTX_DT_BF16 && !l.w8 && M <= 512 && l.out >= 32 && l.out % 4 == 0 && l.in % 8 == 0) {
         const bool pack_on = ltx_exp("ring_pack", 0) == 1;      // experiment builds only
         if (pack_on && !l.wp && !l.wp_tried) {
             l.wp_tried = true;

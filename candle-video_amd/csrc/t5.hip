@@ -187,6 +187,7 @@ namespace {
 // construction in three steps, so that a loader can hand the weights over group by group (ltx_t5_create_from_gguf streams
 // one layer at a time through a small staging buffer) instead of holding the whole model twice
 int t5_begin(const ltx_t5_config* cfg, ltx_dtype model_dtype, int device, std::unique_ptr<ltx_t5>* out) {
+    LTX_REFUSE_F8(model_dtype, "ltx_t5_create");
     const int D = cfg->d_model, inner = cfg->num_heads * cfg->d_kv;
     if (cfg->num_layers < 1 || D % 8 || inner % 8 || cfg->d_ff % 8 || cfg->relative_attention_num_buckets < 4)
         LTX_FAIL(LTX_ERR_ARG, "ltx_t5_create: d_model, heads*d_kv and d_ff must be multiples of 8");
@@ -316,6 +317,7 @@ extern "C" int ltx_t5_create_from_gguf(const ltx_t5_config* cfg, const char* ggu
 extern "C" int ltx_t5_forward_masked(ltx_t5* m, const int32_t* input_ids, const float* attention_mask, int B, int S,
                                      ltx_dtype out_dtype, void* out, ltx_stream stream) {
     if (!m || !input_ids || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_t5_forward: null argument");
+    LTX_REFUSE_F8(out_dtype, "ltx_t5_forward");
     if (B < 1 || S < 1 || S > 512) LTX_FAIL(LTX_ERR_ARG, "ltx_t5_forward: need B >= 1 and 1 <= S <= 512");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;

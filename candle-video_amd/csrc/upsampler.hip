@@ -576,6 +576,7 @@ int up_create(const char* who, const ltx_upsampler_config* cfg, int sp, int tm, 
               ltx_dtype model_dtype, int device, ltx_upsampler** out) {
     if (!out) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null output");
     *out = nullptr;
+    LTX_REFUSE_F8(model_dtype, who);
     LTX_TRY(check_cfg(cfg, who));
     if (!weights && n_weights) LTX_FAIL(LTX_ERR_ARG, std::string(who) + ": null weights");
     HIP_TRY(hipSetDevice(device));
@@ -666,6 +667,7 @@ extern "C" int ltx_upsampler_get_config(const ltx_upsampler* u, ltx_upsampler_co
 extern "C" int ltx_upsampler_forward(ltx_upsampler* u, const void* latents, ltx_dtype io_dtype, int B, int F, int H, int W, void* out, ltx_stream stream) {
     LTX_TRY(check_shape("ltx_upsampler_forward", u, B, F, H, W));
     if (!latents || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_upsampler_forward: null tensor");
+    LTX_REFUSE_F8(io_dtype, "ltx_upsampler_forward");
     HIP_TRY(hipSetDevice(u->device));
     hipStream_t s = (hipStream_t)stream;
     LTX_TRY(up_ensure(u, B, F, H, W));

@@ -550,6 +550,7 @@ extern "C" int ltx_vae_create(const ltx_vae_config* cfg, const ltx_weight* weigh
                               ltx_dtype model_dtype, int device, ltx_vae** out) {
     if (!cfg || !weights || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_create: null argument");
     *out = nullptr;
+    LTX_REFUSE_F8(model_dtype, "ltx_vae_create");
     if (cfg->n_blocks < 1 || cfg->n_blocks > 4) LTX_FAIL(LTX_ERR_ARG, "n_blocks must be 1..4");
     if (cfg->patch_size != 4 || cfg->patch_size_t != 1) LTX_FAIL(LTX_ERR_UNSUPPORTED, "only patch_size=4, patch_size_t=1 are supported");
     if (cfg->latent_channels % 8 != 0) LTX_FAIL(LTX_ERR_UNSUPPORTED, "latent_channels must be a multiple of 8");
@@ -599,6 +600,7 @@ extern "C" int ltx_vae_decode(ltx_vae* v, const void* latents, ltx_dtype io_dtyp
                               float* out, ltx_stream stream) {
     LTX_TRY(check_decode_args(v, B, F, H, W));
     if (!latents || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_decode: null tensor");
+    LTX_REFUSE_F8(io_dtype, "ltx_vae_decode");
     if (B > 8) {
         const size_t in_b = (size_t)v->cfg.latent_channels * F * H * W * (io_dtype == LTX_BF16 ? 2 : 4), out_b = out_elems_per_sample(v, F, H, W);
         for (int b0 = 0; b0 < B; b0 += 8)
@@ -1002,6 +1004,7 @@ extern "C" int ltx_vae_encoder_create(const ltx_vae_encoder_config* cfg, const l
                                       ltx_dtype model_dtype, int device, ltx_vae_encoder** out) {
     if (!cfg || !weights || !out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encoder_create: null argument");
     *out = nullptr;
+    LTX_REFUSE_F8(model_dtype, "ltx_vae_encoder_create");
     if (cfg->n_blocks < 2 || cfg->n_blocks > 5) LTX_FAIL(LTX_ERR_ARG, "encoder n_blocks must be 2..5");
     if (cfg->patch_size < 1 || cfg->patch_size_t != 1) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder: only patch_size_t = 1 is supported");
     if (!cfg->is_causal) LTX_FAIL(LTX_ERR_UNSUPPORTED, "encoder: only the causal encoder (is_causal = 1) is supported");
@@ -1040,6 +1043,7 @@ extern "C" int ltx_vae_encode(ltx_vae_encoder* e, const void* video, ltx_dtype v
                               float* mean_out, float* logvar_out, ltx_stream stream) {
     LTX_TRY(check_encode_args("ltx_vae_encode", e, video, B, F, H, W));
     if (!mean_out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode: null tensor");
+    LTX_REFUSE_F8(video_dtype, "ltx_vae_encode");
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
     int oT, oH, oW;
@@ -1066,6 +1070,7 @@ extern "C" int ltx_vae_encode_tokens(ltx_vae_encoder* e, const ltx_vae* vae, con
                                      const float* eps, float* tokens_out, ltx_stream stream) {
     LTX_TRY(check_encode_args("ltx_vae_encode_tokens", e, video, B, F, H, W));
     if (!vae || !tokens_out) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode_tokens: null argument");
+    LTX_REFUSE_F8(video_dtype, "ltx_vae_encode_tokens");
     if (vae->cfg.latent_channels != e->cfg.latent_channels) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode_tokens: encoder and VAE disagree on latent_channels");
     if (vae->device != e->device) LTX_FAIL(LTX_ERR_ARG, "ltx_vae_encode_tokens: encoder and VAE live on different devices");
     HIP_TRY(hipSetDevice(e->device));

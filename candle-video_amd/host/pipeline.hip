@@ -228,6 +228,7 @@ extern "C" int ltx_guidance_step(const void* text, const void* uncond, const voi
                                  float* latents, float* noise_pred_out, int B, int64_t n,
                                  float guidance_scale, float guidance_rescale, float stg_scale, float dt,
                                  void* stats_ws, ltx_stream stream) {
+    LTX_REFUSE_F8(pred_dtype, "ltx_guidance_step");
     return ltx_launch_guidance_step(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
                                                   dt, 0.0f, 0.0f, nullptr, stats_ws, nullptr, 1, 0), (hipStream_t)stream);
 }
@@ -237,6 +238,7 @@ extern "C" int ltx_guidance_step_stochastic(const void* text, const void* uncond
                                             float guidance_scale, float guidance_rescale, float stg_scale,
                                             float sigma, float sigma_next, const float* step_noise,
                                             void* stats_ws, ltx_stream stream) {
+    LTX_REFUSE_F8(pred_dtype, "ltx_guidance_step_stochastic");
     if (!step_noise || !latents) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic: latents and step_noise are required");
     return ltx_launch_guidance_step(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
                                                   0.0f, sigma, sigma_next, step_noise, stats_ws, nullptr, 1, 0), (hipStream_t)stream);
@@ -247,6 +249,7 @@ extern "C" int ltx_guidance_step_held(const void* text, const void* uncond, cons
                                       float* latents, float* noise_pred_out, int B, int64_t n,
                                       float guidance_scale, float guidance_rescale, float stg_scale, float dt,
                                       void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems, ltx_stream stream) {
+    LTX_REFUSE_F8(pred_dtype, "ltx_guidance_step_held");
     if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_held: hold is required");
     return ltx_launch_guidance_step_held(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,
                                                        dt, 0.0f, 0.0f, nullptr, stats_ws, hold, num_frames, frame_elems), (hipStream_t)stream);
@@ -257,6 +260,7 @@ extern "C" int ltx_guidance_step_stochastic_held(const void* text, const void* u
                                                  float guidance_scale, float guidance_rescale, float stg_scale,
                                                  float sigma, float sigma_next, const float* step_noise,
                                                  void* stats_ws, const unsigned char* hold, int num_frames, int64_t frame_elems, ltx_stream stream) {
+    LTX_REFUSE_F8(pred_dtype, "ltx_guidance_step_stochastic_held");
     if (!step_noise || !latents) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic_held: latents and step_noise are required");
     if (!hold) LTX_FAIL(LTX_ERR_ARG, "ltx_guidance_step_stochastic_held: hold is required");
     return ltx_launch_guidance_step_held(guidance_args(text, uncond, perturbed, pred_dtype, latents, noise_pred_out, B, n, guidance_scale, guidance_rescale, stg_scale,

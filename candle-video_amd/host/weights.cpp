@@ -294,11 +294,12 @@ int ltx_safetensors_weight_list(const ltx_safetensors* st, const char* who, cons
         ltx_weight w; memset(&w, 0, sizeof(w));
         if (!strcmp(dtype, "F32")) w.dtype = LTX_F32;
         else if (!strcmp(dtype, "BF16")) w.dtype = LTX_BF16;
-        else LTX_FAIL(LTX_ERR_UNSUPPORTED, tensor + " is " + dtype + " (F32 and BF16 are read)");
+        else if (!strcmp(dtype, "F8_E4M3")) w.dtype = LTX_F8_E4M3;
+        else LTX_FAIL(LTX_ERR_UNSUPPORTED, tensor + " is " + dtype + " (F32, BF16 and F8_E4M3 are read)");
         if (ndim > 5) LTX_FAIL(LTX_ERR_ARG, tensor + " has more than 5 dimensions");
         int64_t numel = 1;
         for (int d = 0; d < ndim; ++d) { w.shape[d] = shape[d]; numel *= shape[d]; }
-        if ((size_t)numel * (w.dtype == LTX_BF16 ? 2 : 4) != nbytes) LTX_FAIL(LTX_ERR_ARG, tensor + ": byte count does not match its shape");
+        if ((size_t)numel * (w.dtype == LTX_F8_E4M3 ? 1 : w.dtype == LTX_BF16 ? 2 : 4) != nbytes) LTX_FAIL(LTX_ERR_ARG, tensor + ": byte count does not match its shape");
         w.name = name; w.data = data; w.ndim = ndim; w.on_device = 0;
         out->push_back(w);
     }
@@ -378,7 +379,9 @@ int gather(const char* path, int unified, int component, Loaded* L) {
                 } else continue;
             }
             int dt;
-            if (e.dtype == "F32") dt = LTX_F32; else if (e.dtype == "BF16") dt = LTX_BF16;
+            if (e.dtype == "F32") dt = LTX_F32; else if (e.dtype == "BF16") dt = LTX_BF16; else if (e.dtype == "F8_E4M3") dt = LTX_F8_E4M3;
+            else if (starts_with(e.dtype, "F8_"))      // the other 8-bit floats of an fp8 checkpoint's own tensors: say which, not "missing weight"
+                LTX_FAIL(LTX_ERR_UNSUPPORTED, "'" + f + "': tensor '" + e.name + "' is " + e.dtype + " (F32, BF16 and F8_E4M3 are read)");
             else {
                 // tensors the path never reads (e.g. an encoder stored in another dtype) must not block loading: skip
                 // them here; a needed one surfaces later as "missing weight '<name>'" from the constructor.
@@ -386,7 +389,7 @@ int gather(const char* path, int unified, int component, Loaded* L) {
             }
             if (e.shape.size() > 5) continue;
             int64_t numel = 1; for (auto d : e.shape) numel *= d;
-            if ((size_t)numel * (dt == LTX_BF16 ? 2 : 4) != e.nbytes) LTX_FAIL(LTX_ERR_ARG, "'" + f + "': tensor '" + e.name + "' has " + std::to_string(e.nbytes) + " bytes, shape says otherwise");
+            if ((size_t)numel * (dt == LTX_F8_E4M3 ? 1 : dt == LTX_BF16 ? 2 : 4) != e.nbytes) LTX_FAIL(LTX_ERR_ARG, "'" + f + "': tensor '" + e.name + "' has " + std::to_string(e.nbytes) + " bytes, shape says otherwise");
             if (seen.count(name)) continue;                                       // first shard wins (HashMap insert order is unspecified upstream)
             seen[name] = L->weights.size();
             ltx_weight w; memset(&w, 0, sizeof(w));

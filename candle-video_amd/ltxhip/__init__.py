@@ -32,6 +32,7 @@ if not os.path.exists(_LIB_PATH):
 lib = C.CDLL(_LIB_PATH)
 
 LTX_F32, LTX_BF16 = 0, 1
+LTX_F8_E4M3 = 2                                  # a SOURCE dtype only (torch.float8_e4m3fn tensors in a weight dict; include/ltxhip_fp8.h)
 
 
 class LtxError(RuntimeError):
@@ -445,6 +446,21 @@ def int8_mask(mask_or_names) -> int:
     return m
 
 
+# include/ltxhip_fp8.h (kept apart like the ones above)
+_FP8_SIGS = {
+    "ltx_dit_get_fp8_linears": [_vp, _vp],
+    "ltx_op_cast_fp8": [_vp, _i64, _i, _i, _vp, _vp], "ltx_op_widen_fp8": [_vp, _i64, _i, _vp, _vp],
+    "ltx_op_gemm_w8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
+}
+FP8_SYMBOLS = sorted(_FP8_SIGS)
+for _name, _sig in _FP8_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
+LTX_F8_QKV, LTX_F8_TO_OUT, LTX_F8_FF1, LTX_F8_FF2, LTX_F8_ALL = 1, 2, 4, 8, 15      # bits of fp8_linears, the order of INT8_LINEARS
+GEMM_W8_TILES = ("256x256", "256x128", "128x128")
+
+
 @dataclass
 class StepCacheParams:
     """ltx_step_cache_params: reuse the block residual while the accumulated poly(distance) stays below rel_l1_thresh (0: never);
@@ -552,7 +568,8 @@ def _make_weights(weights: Dict[str, torch.Tensor]):
     arr = (_Weight * len(weights))()
     keep = []
     for i, (name, t) in enumerate(weights.items()):
-        if t.dtype not in (torch.float32, torch.bfloat16):
+        f8 = t.dtype == torch.float8_e4m3fn              # passed as it is: the constructor keeps it in fp8 or widens it (ltxhip_fp8.h)
+        if not f8 and t.dtype not in (torch.float32, torch.bfloat16):
             t = t.float()
         t = t.contiguous()
         keep.append(t)
@@ -560,7 +577,7 @@ def _make_weights(weights: Dict[str, torch.Tensor]):
         keep.append(nb)
         arr[i].name = nb
         arr[i].data = t.data_ptr()
-        arr[i].dtype = _dt(t.dtype)
+        arr[i].dtype = LTX_F8_E4M3 if f8 else _dt(t.dtype)
         arr[i].ndim = t.dim()
         for j in range(t.dim()):
             arr[i].shape[j] = t.shape[j]
@@ -757,6 +774,13 @@ class LtxVideoTransformer3DModel:
         """0 / 1 per block"""
         out = (C.c_ubyte * self.config.num_layers)()
         _check(lib.ltx_dit_get_int8_attention(self._h, out))
+        return list(out)
+
+    @property
+    def fp8_linears(self) -> List[int]:
+        """the LTX_F8_* mask of every block: the kinds that stayed in fp8 (e4m3 sources of a bf16 model; include/ltxhip_fp8.h)"""
+        out = (C.c_ubyte * self.config.num_layers)()
+        _check(lib.ltx_dit_get_fp8_linears(self._h, out))
         return list(out)
 
     # ---- LoRA adapters (include/ltxhip_lora.h): handle state, so LtxPipeline.call runs on whatever is set
@@ -2586,6 +2610,36 @@ class ops:
                                        B, Sq, Sk, heads, D // heads, v.stride(1), D, _stream()))
         return o
 
+    # ---- the fp8 (e4m3) kernels (include/ltxhip_fp8.h)
+    @staticmethod
+    def cast_fp8(x):
+        """x [rows, D] bf16 (any row stride, unit column stride) -> torch.float8_e4m3fn [rows, D]: round to nearest even, saturating at +-448"""
+        if x.dim() != 2 or x.stride(1) != 1:
+            x = x.contiguous()
+        rows, D = x.shape
+        q = torch.empty(rows, D, dtype=torch.uint8, device=x.device)
+        _check(lib.ltx_op_cast_fp8(_ptr(x), C.c_int64(rows), D, x.stride(0) if rows > 1 else D, _ptr(q), _stream()))
+        return q.view(torch.float8_e4m3fn)
+
+    @staticmethod
+    def widen_fp8(q, dtype=torch.bfloat16):
+        """q torch.float8_e4m3fn (or its bytes) -> the same values in dtype (bf16 or f32), exactly"""
+        q = q.contiguous()
+        y = torch.empty(q.shape, dtype=dtype, device=q.device)
+        _check(lib.ltx_op_widen_fp8(_ptr(q), C.c_int64(q.numel()), _dt(dtype), _ptr(y), _stream()))
+        return y
+
+    @staticmethod
+    def gemm_w8(a, w, w_scale=None, bias=None, epi=0, resid=None, gate=None, rows_per_batch=1, seg_width=0, tile=-1):
+        """y bf16 = epi((a w^T) * w_scale[n] + bias): a bf16 [M, K], w torch.float8_e4m3fn (or its bytes) [N, K]; seg_width: N / seg_width
+        dense [M, seg_width] matrices; tile: -1 the shape rule, or an index into GEMM_W8_TILES"""
+        M, K = a.shape
+        N = w.shape[0]
+        y = torch.empty((N // seg_width, M, seg_width) if seg_width else (M, N), dtype=torch.bfloat16, device=a.device)
+        _check(lib.ltx_op_gemm_w8(_ptr(a.contiguous()), _ptr(w.contiguous()), _ptr(w_scale), _ptr(bias), _ptr(y), M, N, K, epi,
+                                  _ptr(resid), _ptr(gate), rows_per_batch, seg_width, tile, _stream()))
+        return y
+
     @staticmethod
     def linear_deferred(x, w):
         """x @ w^T as UN-reduced K ranges (the library's shape rule): parts [P, M, N] f32 (bf16 layers of at most 512 rows)"""
@@ -2779,11 +2833,12 @@ class ops:
         return buf.value.decode()
 
     @staticmethod
-    def gemm_route(M, N, K, conv=0, ntaps=1, B=1, T=1, H=1, W=1, epi=0, dtype=torch.bfloat16, pn=False, defer=False, fold_in=False, fold_out=False) -> str:
-        """where the GEMM dispatch sends the described call under the current options: "gemm128", "asm32" or a plan name.
+    def gemm_route(M, N, K, conv=0, ntaps=1, B=1, T=1, H=1, W=1, epi=0, dtype=torch.bfloat16, pn=False, defer=False, fold_in=False, fold_out=False, w_fp8=False) -> str:
+        """where the GEMM dispatch sends the described call under the current options: "gemm128", "asm32", a plan name or, for an fp8
+        weight (w_fp8), "w8:<tile>".
         Nothing is launched or measured; LtxError where the launch would refuse the call."""
         buf = C.create_string_buffer(32)
-        flags = (1 if pn else 0) | (2 if defer else 0) | (4 if fold_in else 0) | (8 if fold_out else 0)
+        flags = (1 if pn else 0) | (2 if defer else 0) | (4 if fold_in else 0) | (8 if fold_out else 0) | (16 if w_fp8 else 0)
         _check(lib.ltx_op_gemm_route(M, N, K, conv, ntaps, B, T, H, W, epi, _dt(dtype), flags, buf, 32))
         return buf.value.decode()
 
@@ -2843,7 +2898,8 @@ def prof_report(kind: int):
 
 
 PROF_KERNELS = ("gemm_kernel (128 x 128)", "gemm_big_kernel", "gemm_p8_kernel", "conv_halo_kernel", "gemm_asm_kernel (32x32x16)", "gemm_asm16_kernel", "gemm_ring_kernel",
-                "gemm_i8_kernel", "quant_rows_i8_kernel", "rownorm_quant_i8_kernel")      # (the last two are timed in class 4, the row norms)
+                "gemm_i8_kernel", "quant_rows_i8_kernel", "rownorm_quant_i8_kernel",      # (the last two are timed in class 4, the row norms)
+                "gemm_w8_kernel")
 
 
 def prof_report_kernel(kind: int, kernel: int):

@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-typedef enum { LTX_F32 = 0, LTX_BF16 = 1 } ltx_dtype;
+/* LTX_F8_E4M3 (OCP e4m3fn, the safetensors F8_E4M3) describes a SOURCE tensor (ltx_weight::data) only: as a model dtype or the
+ * dtype of an input / output it is refused with LTX_ERR_ARG (ltxhip_fp8.h) */
+typedef enum { LTX_F32 = 0, LTX_BF16 = 1, LTX_F8_E4M3 = 2 } ltx_dtype;
 typedef struct ltx_dit ltx_dit;
 typedef struct ltx_vae ltx_vae;
 typedef void* ltx_stream;   /* hipStream_t */

@@ -215,7 +215,8 @@ int ltx_op_gemm_plan(int M, int N, int K, int conv, int ntaps, int T, int H, int
 enum { LTX_ROUTE_PN = 1,         /* conv with the fused output norm */
        LTX_ROUTE_DEFER = 2,      /* K-range sums left to the consumer (ltx_op_linear_deferred) */
        LTX_ROUTE_FOLD_IN = 4,    /* ltx_op_linear_fold_in's operands (16 row partials) */
-       LTX_ROUTE_FOLD_OUT = 8 }; /* ltx_op_linear_fold_out's operands */
+       LTX_ROUTE_FOLD_OUT = 8,   /* ltx_op_linear_fold_out's operands */
+       LTX_ROUTE_W_FP8 = 16 };   /* W is fp8 (e4m3) bytes: ltx_op_gemm_w8's kernel, "w8:<tile>" (ltxhip_fp8.h) */
 int ltx_op_gemm_route(int M, int N, int K, int conv, int ntaps, int B, int T, int H, int W, int epi, int dtype, int flags, char* name, int cap);
 
 /* Diagnostic, read-only: the decisions of one DiT forward of B <= 8 batch rows under the current options, for a model of

@@ -61,7 +61,9 @@ int ltx_weights_resolve(const char* path, char* out, size_t cap, size_t* n_files
  *                  main.rs:461-499 does ("vae." / "model.diffusion_model." / "transformer." prefixes stripped);
  *   unified == 0 : `path` is the component's own safetensors file or directory (Diffusers layout), tensor names taken
  *                  as they are (WeightLoader::load_single / load_from_directory).
- * F32 and BF16 payloads are accepted (anything else: LTX_ERR_UNSUPPORTED naming the tensor). */
+ * F32, BF16 and F8_E4M3 payloads are accepted; F8_E4M3 tensors are widened exactly to the model dtype, except the DiT block linears
+ * that a bf16 handle keeps in fp8 (ltxhip_fp8.h).  Another 8-bit float (F8_E5M2, ...): LTX_ERR_UNSUPPORTED naming the tensor;
+ * tensors of any other dtype are not read, and a needed one surfaces as a missing weight. */
 /* AutoencoderKLLtxVideoConfig from a diffusers `vae/config.json` (serde names and aliases of vae.rs:30-66); fields the file
  * does not carry keep the value already in *cfg (serde(default) over Default::default() when the caller passed
  * ltx_vae_config_default).  Host only. */

@@ -238,6 +238,13 @@ impl HipDit {
         check(unsafe { sys::ltx_dit_set_int8_linears(self.h, p, mask, std::ptr::null_mut()) })
     }
 
+    /// The `sys::LTX_F8_*` mask of every block: the linears that stayed in fp8 (E4M3 sources of a bf16 handle, include/ltxhip_fp8.h).
+    pub fn fp8_linears(&self) -> Result<Vec<u8>> {
+        let mut out = vec![0u8; self.cfg.num_layers];
+        check(unsafe { sys::ltx_dit_get_fp8_linears(self.h, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
     /// The `sys::LTX_I8_*` mask of every block.
     pub fn int8_linears(&self) -> Result<Vec<u8>> {
         let mut out = vec![0u8; self.cfg.num_layers];

@@ -566,3 +566,23 @@ extern "C" {
     pub fn ltx_op_attention_i8(q8: *const c_void, qs: *const c_float, k8: *const c_void, ks: *const c_float, v: *const c_void, o: *mut c_void,
                                b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int, ldv: c_int, ldo: c_int, stream: ltx_stream) -> c_int;
 }
+
+// ---- include/ltxhip_fp8.h: FP8 (E4M3) checkpoints, fp8-resident block linears ----
+
+/// `ltx_dtype` of an e4m3 SOURCE tensor (`ltx_weight::dtype`); never a model or I/O dtype.
+pub const LTX_F8_E4M3: c_int = 2;
+/// Mask bits of `ltx_dit_get_fp8_linears`, the order of `LTX_I8_*`.
+pub const LTX_F8_QKV: u8 = 1;
+pub const LTX_F8_TO_OUT: u8 = 2;
+pub const LTX_F8_FF1: u8 = 4;
+pub const LTX_F8_FF2: u8 = 8;
+pub const LTX_F8_ALL: u8 = 15;
+
+extern "C" {
+    pub fn ltx_dit_get_fp8_linears(m: *const ltx_dit, block_masks_out: *mut u8) -> c_int;
+    pub fn ltx_op_cast_fp8(x: *const c_void, rows: i64, d: c_int, ld: c_int, q: *mut c_void, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_widen_fp8(q: *const c_void, n: i64, dst_dtype: c_int, y: *mut c_void, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_gemm_w8(a: *const c_void, w: *const c_void, w_scale: *const c_float, bias: *const c_void, y: *mut c_void, m: c_int, n: c_int, k: c_int,
+                          epi: c_int, resid: *const c_void, gate: *const c_float, rows_per_batch: c_int, seg_width: c_int, tile: c_int,
+                          stream: ltx_stream) -> c_int;
+}
