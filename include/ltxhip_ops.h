@@ -4,6 +4,13 @@
  * so that parity tests and micro-benchmarks can drive each one through the C ABI with plain
  * device pointers.  Each entry cites the reference code the kernel replaces
  * (FerrisMind/candle-video, src/models/ltx_video/...).  dtype: 0 = f32, 1 = bf16 (ltx_dtype).
+ *
+ * What an entry touches - held for the entries tests/test_gpu_extents.py has a case for (the linear family, the quantised GEMMs, the
+ * row passes, attention and the convolutions; not yet ltx_op_rope_table, ltx_op_downsample3d, ltx_op_ring_pack,
+ * ltx_op_xattn_fold_build): it writes every element of the tensors named as outputs below - `cols` columns of each row, rows `ld`
+ * elements apart where a stride is passed, dense otherwise - and no other byte: not the ld - cols gap behind a row, nothing in
+ * front of or behind a tensor, no input.  Its result depends on the named operand elements alone, whatever the bytes around them
+ * hold (NaN and Inf included).
  */
 #ifndef LTXHIP_OPS_H
 #define LTXHIP_OPS_H
@@ -31,6 +38,7 @@ int ltx_op_linear_packed(const void* x, const void* w, const void* w_packed, con
                          const void* resid, const float* gate, int rows_per_batch, ltx_stream stream);
 int ltx_op_linear_rowsq(const void* x, const void* w, const void* bias, void* y, float* rowsq, int M, int N, int K, int dtype, int epi,
                         const void* resid, const float* gate, int rows_per_batch, ltx_stream stream);   /* epi 0, 2, 3 as ltx_op_linear */
+/* rowsq (both entries): dense [rows, ceil(N/128)] f32, every column written; the last holds the N % 128 remaining columns' sum. */
 int ltx_op_rowsq(const void* x, int64_t rows, int N, int ld, float* rowsq, int dtype, ltx_stream stream);
 
 /* The norm fold of the DiT block (LtxVideoTransformerBlock::forward, ltx_transformer.rs:847-851, 905-909: y = h * r * (1 + sc) + sh
@@ -42,6 +50,7 @@ int ltx_op_rowsq(const void* x, int64_t rows, int N, int ld, float* rowsq, int d
  *     y2[m][n] = bf16(float(y[m][n] as stored) * (1.0f + scale2[b(m) * scale2_stride + n]))
  *   fold_in (epi 0 / 1, no bias): y = epi(r_m * (x @ w^T) + cvec[b(m) * cvec_stride + n]),
  *     r_m = 1 / sqrt(sum_g rs_sq[m * rs_n + g] / rs_D + eps); rs_n in {4, 8, 12, 16} */
+/* Written: fold_out y, y2 dense [M, N] and rowsq dense [M, ceil(N/128)]; fold_in y dense [M, N]; shift_gemv B rows of N floats, cvec_stride apart. */
 int ltx_op_linear_fold_out(const void* x, const void* w, const void* bias, void* y, void* y2, float* rowsq, const float* scale2, int scale2_stride,
                            int M, int N, int K, int epi, const void* resid, const float* gate, int rows_per_batch, ltx_stream stream);
 int ltx_op_linear_fold_in(const void* x, const void* w, void* y, const float* rs_sq, int rs_n, int rs_D, float eps, const float* cvec, int cvec_stride,
@@ -72,6 +81,7 @@ int ltx_op_rownorm_presum(const void* x, void* y, int64_t rows, int D, float eps
  * h = resid + gate_b * (((p0 + p1) + ...) + bias) (gate NULL: resid + sum + bias), rounded to the dtype, written to h_out, then
  * y = the row norm of ltx_op_rownorm on h.  Together they return the bits of ltx_op_linear(epi 2 / 3) followed by ltx_op_rownorm. */
 int ltx_op_linear_split_factor(int M, int N, int K);
+/* Written: parts dense [split_factor][M][N] f32, all of it; rownorm_deferred h_out and y dense [rows, D]. */
 int ltx_op_linear_deferred(const void* x, const void* w, float* parts, int M, int N, int K, ltx_stream stream);
 int ltx_op_rownorm_deferred(const float* parts, int nparts, const void* bias, const void* resid, const float* gate, int gate_stride, void* h_out,
                             void* y, int64_t rows, int D, int kind, float eps, const float* scale, const float* shift, int64_t rows_per_batch,
@@ -137,6 +147,7 @@ int ltx_op_attention_rowsq(const void* q, const void* k, const void* v, void* o,
  * blocks that hold them - a masked text token (bias -10000, ltx_transformer.rs:1059-1070) has softmax weight exp(s - 10000 - max)
  * = +0.0f exactly, so the result is that of ltx_op_attention.  q_rowsq may be NULL (then q is used as it is).  counts_out
  * (DEVICE int [B], may be NULL) receives the number of keys kept per batch row.  Blocks until done (temporary buffers). */
+/* Written: o (B * Sq rows of heads * hd, ldo apart) and counts_out [B]; k and v must be dense rows (ldk = ldv = heads * hd), else LTX_ERR_ARG. */
 int ltx_op_attention_compact(const void* q, const void* k, const void* v, void* o, int B, int Sq, int Sk, int heads, int hd,
                              int ldq, int ldk, int ldv, int ldo, float scale, const float* key_bias,
                              const float* q_rowsq, int q_rowsq_n, int q_rowsq_D, float q_rowsq_eps, int* counts_out, ltx_stream stream);
@@ -193,6 +204,7 @@ int ltx_op_downsample3d(const void* x, const void* w, const void* bias, int wdty
                         int B, int T, int H, int W, int Cin, int Cout, int down_type, int dtype, ltx_stream stream);
 
 /* conv_out + unpatchify(4) (vae.rs:1626-1654, 1724-1725): x [B,T,H,W,Cin] -> f32 NCTHW [B,Cout/16,T,4H,4W]. */
+/* Written: all of y, dense; weight rows past Cout (the 64-wide tile's rows 48..63 at Cout = 48) do not exist and are not read. */
 int ltx_op_conv_out_unpatchify(const void* x, const void* w, const void* bias, int wdtype, float* y,
                                int B, int T, int H, int W, int Cin, int Cout, int causal, int postprocess, int dtype, ltx_stream stream);
 
