@@ -7,6 +7,8 @@
 #include "../../include/ltxhip_int8.h"
 #include "../../include/ltxhip_fp8.h"
 #include "../../include/ltxhip_int8_attn.h"
+#include "../../include/ltxhip_sparse_attn.h"
+#include "../host/sparse_map.h"
 
 // The ops' dtype argument -> LTX_DT_*.  The one place every op's dtype passes: LTX_F8_E4M3 (a source dtype, ltxhip_fp8.h) is refused
 // here with LTX_ERR_ARG - the enclosing entry point returns - instead of being read as four bytes per element.
@@ -576,4 +578,19 @@ extern "C" int ltx_op_attention_i8(const void* q8, const float* qs, const void* 
     AttnI8Args a; a.q8 = q8; a.qs = qs; a.k8 = k8; a.ks = ks; a.v = v; a.o = o; a.ldv = ldv; a.ldo = ldo;
     a.B = B; a.Sq = Sq; a.Sk = Sk; a.heads = heads; a.hd = hd;
     return ltx_launch_attention_i8(a, (hipStream_t)stream);
+}
+
+// ---- the block-sparse attention kernel on its own and the host side of its maps (include/ltxhip_sparse_attn.h) ----
+extern "C" size_t ltx_sparse_map_words(int64_t S) { return sparse_map_words(S); }
+extern "C" int ltx_sparse_window_map(int F, int H, int W, int wf, int wh, int ww, int sink_frames, uint32_t* map_out, size_t words) {
+    std::string err;
+    if (!sparse_window_map_build(F, H, W, wf, wh, ww, sink_frames, map_out, words, &err)) LTX_FAIL(LTX_ERR_ARG, "ltx_sparse_window_map: " + err);
+    return LTX_OK;
+}
+extern "C" double ltx_sparse_map_density(const uint32_t* map, int64_t S) { return sparse_map_density(map, S); }
+extern "C" int ltx_op_attention_sparse(const void* q, const void* k, const void* v, void* o, const uint32_t* map, int map_heads,
+                                       int B, int Sq, int Sk, int heads, int hd, int ldq, int ldk, int ldv, int ldo, ltx_stream stream) {
+    AttnArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.B = B; a.Sq = Sq; a.Sk = Sk; a.heads = heads; a.hd = hd; a.q_prescaled = 1;
+    return ltx_launch_attention_sparse(a, map, map_heads, (hipStream_t)stream);
 }

@@ -14,7 +14,9 @@
 #include "../../include/ltxhip_int8.h"
 #include "../../include/ltxhip_int8_attn.h"
 #include "../../include/ltxhip_fp8.h"
+#include "../../include/ltxhip_sparse_attn.h"
 #include "../host/step_cache.h"
+#include "../host/sparse_map.h"
 #include "lora.h"
 
 struct DitBlock {
@@ -125,6 +127,12 @@ struct ltx_dit {
     std::vector<unsigned char> i8a_flag;
     bool i8a_any = false;
     DevBuf q8, k8, q8s, k8s, kmean, kpart;      // int8 [M, D] twice; f32 [B, heads, S], [B, heads, ceil(S / 64)], [B, D], kmean's partials
+    // Block-sparse self-attention (include/ltxhip_sparse_attn.h; ltx_dit_set_sparse_attention below): per block a flag, and the device
+    // copy of the block map [spa_heads][ltx_sparse_map_words(spa_S)] - nothing here is derived from the weights
+    std::vector<unsigned char> spa_flag;
+    bool spa_any = false;
+    DevBuf spa_map; int spa_heads = 0; int64_t spa_S = 0;
+    void free_sparse_attention() { spa_map.release(); spa_flag.clear(); spa_any = false; spa_heads = 0; spa_S = 0; }
     // fp8-resident block linears (include/ltxhip_fp8.h): fixed at creation - per block the LTX_F8_* mask of the kinds whose LinearW holds
     // the checkpoint's own e4m3 bytes (w8) and no bf16 matrix
     std::vector<unsigned char> f8_mask;
@@ -149,6 +157,7 @@ struct ltx_dit {
         free_int8(); i8_w.clear(); i8_mask.clear(); i8_any = false;
         a8.release(); a8s.release();
         free_int8_attention(); i8a_flag.clear(); i8a_any = false;
+        free_sparse_attention();
         DevBuf* bs[] = {&xin, &encin, &h, &n, &qkv, &attn, &ff, &c1, &encp, &kv2, &tproj, &e1, &emb, &embs, &temb, &ada, &adaf, &cosb, &sinb, &bias, &orig, &orig_hsq, &outT, &rsq, &hsq, &parts};
         for (DevBuf* b : bs) b->release();
         release_caches();
@@ -452,6 +461,9 @@ extern "C" int ltx_dit_set_int8_attention(ltx_dit* m, const unsigned char* block
     for (int l = 0; l < L; ++l) { want[l] = (on != 0 && (!block_flags || block_flags[l] != 0)) ? 1 : 0; any = any || want[l]; }
     if (any && m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: the int8 attention takes a bf16 model (this handle is f32)");
     if (any && hd != 64 && hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: head_dim must be 64 or 128 (this handle has " + std::to_string(hd) + ")");
+    for (int l = 0; l < L && m->spa_any; ++l)
+        if (want[l] && m->spa_flag[(size_t)l])
+            LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: block " + std::to_string(l) + " runs block-sparse attention (ltx_dit_set_sparse_attention); sparse int8 scores are not served (the handle is unchanged)");
     HIP_TRY(hipSetDevice(m->device));
     const bool had = m->i8a_any;
     m->i8a_flag = want; m->i8a_any = any;
@@ -464,6 +476,46 @@ extern "C" int ltx_dit_set_int8_attention(ltx_dit* m, const unsigned char* block
 extern "C" int ltx_dit_get_int8_attention(const ltx_dit* m, unsigned char* block_flags_out) {
     if (!m || !block_flags_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_attention: null argument");
     for (int l = 0; l < m->cfg.num_layers; ++l) block_flags_out[l] = (size_t)l < m->i8a_flag.size() ? m->i8a_flag[(size_t)l] : 0;
+    return LTX_OK;
+}
+
+// ---- block-sparse self-attention (include/ltxhip_sparse_attn.h) ----
+extern "C" int ltx_dit_set_sparse_attention(ltx_dit* m, const uint32_t* map, int map_heads, int64_t S, const unsigned char* block_flags, ltx_stream stream) {
+    (void)stream;
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention: null handle");
+    const int L = m->cfg.num_layers, hd = m->cfg.attention_head_dim, H = m->cfg.num_attention_heads;
+    std::vector<unsigned char> want((size_t)L);
+    bool any = false;
+    for (int l = 0; l < L; ++l) { want[l] = (map && (!block_flags || block_flags[l] != 0)) ? 1 : 0; any = any || want[l]; }
+    if (any) {
+        if (m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention: the sparse attention takes a bf16 model (this handle is f32)");
+        if (hd != 64 && hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention: head_dim must be 64 or 128 (this handle has " + std::to_string(hd) + ")");
+        if (map_heads != 1 && map_heads != H)
+            LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention: map_heads must be 1 or the handle's " + std::to_string(H) + " heads (got " + std::to_string(map_heads) + ")");
+        if (S < 1 || S > INT32_MAX) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention: S must be a token count (got " + std::to_string(S) + ")");
+        const int64_t rows = map_heads * sparse_map_nqb(S), empty = sparse_map_empty_row(map, rows, S);
+        if (empty >= 0)
+            LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention: map row " + std::to_string(empty % sparse_map_nqb(S)) + " of head " + std::to_string(empty / sparse_map_nqb(S)) + " lists no key tile (S " + std::to_string(S) + ")");
+        for (int l = 0; l < L && m->i8a_any; ++l)
+            if (want[l] && m->i8a_flag[(size_t)l])
+                LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention: block " + std::to_string(l) + " runs int8 attention (ltx_dit_set_int8_attention); sparse int8 scores are not served (the handle is unchanged)");
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    if (m->spa_any) (void)hipDeviceSynchronize();                 // forwards enqueued earlier may still read the copy
+    m->free_sparse_attention();
+    if (!any) return LTX_OK;
+    const size_t bytes = (size_t)map_heads * sparse_map_words(S) * sizeof(uint32_t);
+    LTX_TRY(m->spa_map.ensure(bytes));
+    const hipError_t e = hipMemcpy(m->spa_map.p, map, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipGetLastError(); m->free_sparse_attention(); LTX_FAIL(LTX_ERR_HIP, std::string("ltx_dit_set_sparse_attention: upload of the map: ") + hipGetErrorString(e)); }
+    m->spa_flag = want; m->spa_any = true; m->spa_heads = map_heads; m->spa_S = S;
+    return LTX_OK;
+}
+extern "C" int ltx_dit_get_sparse_attention(const ltx_dit* m, unsigned char* block_flags_out, int* map_heads_out, int64_t* S_out) {
+    if (!m || !block_flags_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_sparse_attention: null argument");
+    for (int l = 0; l < m->cfg.num_layers; ++l) block_flags_out[l] = (size_t)l < m->spa_flag.size() ? m->spa_flag[(size_t)l] : 0;
+    if (map_heads_out) *map_heads_out = m->spa_heads;
+    if (S_out) *S_out = m->spa_S;
     return LTX_OK;
 }
 
@@ -936,7 +988,8 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     qa.eps = 1e-5f; qa.cos = m->cosb.as<float>(); qa.sin = m->sinb.as<float>();
     // a block with int8 attention (ltxhip_int8_attn.h) takes the prescaled q whatever the plan says: its scores are in log2 units
     const bool attn8 = m->i8a_any && m->i8a_flag[(size_t)l] != 0;
-    if (p.fold_q || attn8) qa.out_scale0 = attn_scale * 1.4426950408889634f;
+    const bool attn_sp = m->spa_any && m->spa_flag[(size_t)l] != 0;      // ... and so does a block with sparse attention (ltxhip_sparse_attn.h)
+    if (p.fold_q || attn8 || attn_sp) qa.out_scale0 = attn_scale * 1.4426950408889634f;
     LTX_TRY(ltx_launch_qknorm_rope(qa, dt, s));
     AttnArgs at; at.q = m->qkv.p; at.k = (char*)m->qkv.p + (size_t)p.seg * esz; at.v = (char*)m->qkv.p + (size_t)2 * p.seg * esz; at.o = m->attn.p;
     at.ldq = at.ldk = at.ldv = p.ldqkv; at.ldo = D; at.B = B; at.Sq = S; at.Sk = S; at.heads = H; at.hd = hd; at.scale = attn_scale;
@@ -947,6 +1000,7 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         AttnArgs ar = at; ar.B = b1 - b0;
         const size_t in_off = (size_t)b0 * S * p.ldqkv * esz;
         ar.q = (const char*)at.q + in_off; ar.k = (const char*)at.k + in_off; ar.v = (const char*)at.v + in_off; ar.o = (char*)at.o + (size_t)b0 * S * D * esz;
+        if (attn_sp) return ltx_launch_attention_sparse(ar, m->spa_map.as<uint32_t>(), m->spa_heads, s);      // the listed key tiles only
         if (!attn8) return ltx_launch_attention(ar, dt, s);
         LTX_TRY(ltx_launch_kmean(ar.k, ar.B, S, D, p.ldqkv, m->kpart.as<float>(), m->kmean.as<float>(), s));
         LTX_TRY(ltx_launch_quant_qk_i8(ar.q, ar.k, m->kmean.as<float>(), ar.B, S, S, H, hd, p.ldqkv, p.ldqkv, m->q8.p, m->q8s.as<float>(), m->k8.p, m->k8s.as<float>(), s));
@@ -1068,6 +1122,8 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
         LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: num_frames*height*width must equal S when video_coords is absent");
     HIP_TRY(hipSetDevice(m->device));
     if (G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: the modulation groups must divide the sequence");
+    if (m->spa_any && S != m->spa_S)
+        LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_forward: the handle's sparse-attention map is for " + std::to_string(m->spa_S) + " tokens, this forward has " + std::to_string(S) + " (ltx_dit_set_sparse_attention)");
     hipStream_t s = (hipStream_t)stream;
     const ltx_dit_config& c = m->cfg;
     DitPlan plan = ltx_dit_plan(c, m->dtype, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, S, K, G, skip_layer_mask != nullptr);

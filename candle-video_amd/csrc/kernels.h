@@ -325,6 +325,9 @@ int ltx_attention_q128_prepare();   // allocate + zero the current device's over
 int ltx_launch_attention(const AttnArgs& a, int dtype, hipStream_t s);
 int ltx_launch_attention_q64(const AttnArgs& a, hipStream_t s);   // attn_q64.hip: head_dim 64, q prescaled, 64 queries per wave (caller sets xcd_heads / wide_o)
 bool ltx_attention_q64_fits(const AttnArgs& a);   // attn_q64.hip: every row offset below 2^31 (its 32-bit buffer arithmetic)
+// attn_sparse.hip (include/ltxhip_sparse_attn.h): bf16, q prescaled, no bias; map DEVICE uint32 [map_heads][ceil(Sq / 128)][ceil(ceil(Sk / 64) / 32)],
+// map_heads 1 or heads.  Refused (LTX_ERR_UNSUPPORTED) where ltx_attention_q64_fits says no.  Sets xcd_heads / wide_o itself.
+int ltx_launch_attention_sparse(const AttnArgs& a, const uint32_t* map, int map_heads, hipStream_t s);
 bool ltx_attention_prescale_ok(int hd);
 bool ltx_attention_cross64_ok(int hd, int Sk);   // shape-only: the short-key-set kernel serves the launch (k_count / bias2d / q_rowsq)
 // attn2.to_out folded into the cached text context (xattn_fold.hip).  ONE decision, read by dit.hip's text_context and by the

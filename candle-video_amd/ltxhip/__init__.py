@@ -420,9 +420,39 @@ for _name, _sig in _INT8_ATTN_SIGS.items():
     _fn = getattr(lib, _name)
     _fn.argtypes = _sig
     _fn.restype = C.c_int
+# include/ltxhip_sparse_attn.h (kept apart like the eleven above)
+_SPARSE_ATTN_SIGS = {
+    "ltx_sparse_map_words": [_i64], "ltx_sparse_window_map": [_i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t], "ltx_sparse_map_density": [_vp, _i64],
+    "ltx_dit_set_sparse_attention": [_vp, _vp, _i, _i64, _vp, _vp], "ltx_dit_get_sparse_attention": [_vp, _vp, _vp, _vp],
+    "ltx_op_attention_sparse": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+}
+SPARSE_ATTN_SYMBOLS = sorted(_SPARSE_ATTN_SIGS)
+for _name, _sig in _SPARSE_ATTN_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_size_t if _name == "ltx_sparse_map_words" else C.c_double if _name == "ltx_sparse_map_density" else C.c_int
 LTX_I8_QKV, LTX_I8_TO_OUT, LTX_I8_FF1, LTX_I8_FF2, LTX_I8_ALL = 1, 2, 4, 8, 15
 INT8_LINEARS = ("qkv", "to_out", "ff1", "ff2")   # the mask bits of ltx_dit_set_int8_linears, lowest first
 GEMM_I8_TILES = ("256x256", "256x128", "128x128")
+
+
+def sparse_window_map(F: int, H: int, W: int, wf: int, wh: int, ww: int, sink_frames: int = 0) -> torch.Tensor:
+    """the block map of a window over (frame, row, column) plus sink frames (include/ltxhip_sparse_attn.h) for the F * H * W tokens of
+    the DiT's order -> CPU int32 [ceil(S / 128), ceil(ceil(S / 64) / 32)] (the uint32 words' bits): key tile kt is bit kt & 31 of word kt >> 5"""
+    S = F * H * W
+    nqb = max((S + 127) // 128, 0)
+    words = int(lib.ltx_sparse_map_words(C.c_int64(S)))
+    out = torch.zeros(nqb, words // nqb if nqb else 0, dtype=torch.int32)
+    _check(lib.ltx_sparse_window_map(F, H, W, wf, wh, ww, sink_frames, C.c_void_p(out.data_ptr()), C.c_size_t(words)))
+    return out
+
+
+def sparse_map_density(map: torch.Tensor, S: int) -> float:
+    """listed tiles of a one-head map (CPU int32 [ceil(S / 128), NW]) divided by all of them"""
+    m = map.cpu().to(torch.int32).contiguous()
+    if m.numel() != int(lib.ltx_sparse_map_words(C.c_int64(S))):
+        raise LtxError(f"sparse_map_density: {m.numel()} words for S = {S}")
+    return float(lib.ltx_sparse_map_density(C.c_void_p(m.data_ptr()), C.c_int64(S)))
 
 
 def int8_mask(mask_or_names) -> int:
@@ -774,6 +804,33 @@ class LtxVideoTransformer3DModel:
         """0 / 1 per block"""
         out = (C.c_ubyte * self.config.num_layers)()
         _check(lib.ltx_dit_get_int8_attention(self._h, out))
+        return list(out)
+
+    # ---- block-sparse self-attention (include/ltxhip_sparse_attn.h): handle state
+    def set_sparse_attention(self, map: Optional[torch.Tensor], S: int = 0, block_flags: Optional[Sequence] = None):
+        """attn1 of every block (or of the blocks with a truthy block_flags entry) computes only the key tiles `map` lists: int32
+        [NQB, NW] (shared by the heads) or [heads, NQB, NW] for S tokens, e.g. sparse_window_map(F, H, W, ...).  None clears the
+        state.  A bf16 model with head_dim 64 or 128; forwards of another token count are refused while a block is flagged."""
+        arr = None
+        if block_flags is not None:
+            if len(block_flags) != self.config.num_layers:
+                raise LtxError(f"set_sparse_attention: block_flags has {len(block_flags)} entries for {self.config.num_layers} blocks")
+            arr = (C.c_ubyte * len(block_flags))(*[1 if v else 0 for v in block_flags])
+        if map is None:
+            _check(lib.ltx_dit_set_sparse_attention(self._h, None, 0, C.c_int64(0), arr, _stream()))
+            return
+        m = map.cpu().to(torch.int32).contiguous()
+        words = int(lib.ltx_sparse_map_words(C.c_int64(S)))
+        mh = m.shape[0] if m.dim() == 3 else 1
+        if m.dim() not in (2, 3) or m.numel() != mh * words:
+            raise LtxError(f"set_sparse_attention: a map of shape {tuple(m.shape)} for S = {S} ({words} words per head)")
+        _check(lib.ltx_dit_set_sparse_attention(self._h, C.c_void_p(m.data_ptr()), mh, C.c_int64(S), arr, _stream()))
+
+    @property
+    def sparse_attention(self) -> List[int]:
+        """0 / 1 per block"""
+        out = (C.c_ubyte * self.config.num_layers)()
+        _check(lib.ltx_dit_get_sparse_attention(self._h, out, None, None))
         return list(out)
 
     @property
@@ -2608,6 +2665,24 @@ class ops:
         o = torch.empty(B, Sq, D, dtype=torch.bfloat16, device=q8.device)
         _check(lib.ltx_op_attention_i8(_ptr(q8.contiguous()), _ptr(qs.contiguous()), _ptr(k8.contiguous()), _ptr(ks.contiguous()), _ptr(v), _ptr(o),
                                        B, Sq, Sk, heads, D // heads, v.stride(1), D, _stream()))
+        return o
+
+    # ---- the block-sparse attention kernel (include/ltxhip_sparse_attn.h)
+    @staticmethod
+    def attention_sparse(q, k, v, map, heads):
+        """o bf16 [B, Sq, D] = softmax2 over the keys of the tiles `map` lists; q already carries scale * log2(e); map DEVICE int32
+        [NQB, NW] (shared by the heads) or [heads, NQB, NW]"""
+        B, Sq, D = q.shape
+        Sk = k.shape[1]
+        q, k, v = [t if t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) else t.contiguous() for t in (q, k, v)]
+        nqb, nw = (Sq + 127) // 128, ((Sk + 63) // 64 + 31) // 32
+        mh = map.shape[0] if map.dim() == 3 else 1
+        if map.dtype != torch.int32 or tuple(map.shape[-2:]) != (nqb, nw) or map.dim() not in (2, 3):
+            raise LtxError(f"attention_sparse: map must be int32 [{nqb}, {nw}] or [heads, {nqb}, {nw}], got {map.dtype} {tuple(map.shape)}")
+        map = _dev(map).contiguous()
+        o = torch.empty(B, Sq, D, dtype=torch.bfloat16, device=q.device)
+        _check(lib.ltx_op_attention_sparse(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(map), mh, B, Sq, Sk, heads, D // heads,
+                                           q.stride(1), k.stride(1), v.stride(1), D, _stream()))
         return o
 
     # ---- the fp8 (e4m3) kernels (include/ltxhip_fp8.h)

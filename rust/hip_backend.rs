@@ -264,6 +264,26 @@ impl HipDit {
         let p = block_flags.map_or(std::ptr::null(), |b| b.as_ptr());
         check(unsafe { sys::ltx_dit_set_int8_attention(self.h, p, on as i32, std::ptr::null_mut()) })
     }
+
+    /// attn1 of every block (or of the blocks whose `block_flags` entry is non-zero) computes only the key tiles the block map lists
+    /// (include/ltxhip_sparse_attn.h): `map` holds `map_heads` (1 or the model's heads) maps of `ltx_sparse_map_words(s)` words for
+    /// `s` tokens; `None` clears the state.  A bf16 model with head_dim 64 or 128.
+    pub fn set_sparse_attention(&mut self, map: Option<&[u32]>, map_heads: usize, s: usize, block_flags: Option<&[u8]>) -> Result<()> {
+        if let Some(bf) = block_flags {
+            if bf.len() != self.cfg.num_layers {
+                candle_core::bail!("set_sparse_attention: {} block flags for {} blocks", bf.len(), self.cfg.num_layers);
+            }
+        }
+        if let Some(m) = map {
+            let words = unsafe { sys::ltx_sparse_map_words(s as i64) };
+            if m.len() != map_heads * words {
+                candle_core::bail!("set_sparse_attention: {} words for {} maps of {} words (S = {})", m.len(), map_heads, words, s);
+            }
+        }
+        let p = block_flags.map_or(std::ptr::null(), |b| b.as_ptr());
+        let mp = map.map_or(std::ptr::null(), |m| m.as_ptr());
+        check(unsafe { sys::ltx_dit_set_sparse_attention(self.h, mp, map_heads as i32, s as i64, p, std::ptr::null_mut()) })
+    }
 }
 
 impl Drop for HipDit {

@@ -567,6 +567,18 @@ extern "C" {
                                b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int, ldv: c_int, ldo: c_int, stream: ltx_stream) -> c_int;
 }
 
+// ---- include/ltxhip_sparse_attn.h: opt-in block-sparse self-attention over a block map ----
+
+extern "C" {
+    pub fn ltx_sparse_map_words(s: i64) -> usize;
+    pub fn ltx_sparse_window_map(f: c_int, h: c_int, w: c_int, wf: c_int, wh: c_int, ww: c_int, sink_frames: c_int, map_out: *mut u32, words: usize) -> c_int;
+    pub fn ltx_sparse_map_density(map: *const u32, s: i64) -> f64;
+    pub fn ltx_dit_set_sparse_attention(m: *mut ltx_dit, map: *const u32, map_heads: c_int, s: i64, block_flags: *const u8, stream: ltx_stream) -> c_int;
+    pub fn ltx_dit_get_sparse_attention(m: *const ltx_dit, block_flags_out: *mut u8, map_heads_out: *mut c_int, s_out: *mut i64) -> c_int;
+    pub fn ltx_op_attention_sparse(q: *const c_void, k: *const c_void, v: *const c_void, o: *mut c_void, map: *const u32, map_heads: c_int,
+                                   b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int, ldq: c_int, ldk: c_int, ldv: c_int, ldo: c_int, stream: ltx_stream) -> c_int;
+}
+
 // ---- include/ltxhip_fp8.h: FP8 (E4M3) checkpoints, fp8-resident block linears ----
 
 /// `ltx_dtype` of an e4m3 SOURCE tensor (`ltx_weight::dtype`); never a model or I/O dtype.
