@@ -43,7 +43,7 @@ template <int N> __device__ __forceinline__ void vm_wait() { __builtin_amdgcn_s_
 typedef const __attribute__((address_space(4))) uint32_t* map_ptr;
 
 template <int HD>
-__global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_sparse_kernel(const AttnArgs a, const uint32_t* map, int map_heads) {
+__global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_sparse_kernel(const AttnArgs a, const uint32_t* map, int map_heads, int64_t map_bstride) {
     constexpr int KROW = HD * 2, VROW = HD * 2;              // bytes per LDS row
     constexpr int CPR = KROW / 16;                           // 16-byte chunks per row
     constexpr int NKS = HD / 16;                             // k-steps over the head dim for S^T
@@ -72,7 +72,8 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_sparse_kernel(cons
     const bf16_t* V = reinterpret_cast<const bf16_t*>(a.v) + (int64_t)b * a.Sk * a.ldv + head * HD;
 
     // ---- the walk over this block's map row: scalar state (word index, the bits left of it, the next word already requested)
-    const map_ptr MR = (map_ptr)(uintptr_t)(map + ((int64_t)(map_heads > 1 ? head : 0) * nqb + qb) * nw);
+    // (map_bstride words between the maps of two batch rows - ltxhip_sparse_dynamic.h; 0: one map for the batch)
+    const map_ptr MR = (map_ptr)(uintptr_t)(map + (int64_t)b * map_bstride + ((int64_t)(map_heads > 1 ? head : 0) * nqb + qb) * nw);
     auto map_word = [&](int i) -> uint32_t {
         uint32_t x = MR[i];
         if (i == nw - 1 && (nt & 31)) x &= (1u << (nt & 31)) - 1u;      // bits at or above NKT are not tiles
@@ -280,12 +281,16 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_sparse_kernel(cons
 
 }  // namespace
 
-int ltx_launch_attention_sparse(const AttnArgs& a, const uint32_t* map, int map_heads, hipStream_t s) {
+int ltx_launch_attention_sparse(const AttnArgs& a, const uint32_t* map, int map_heads, hipStream_t s) { return ltx_launch_attention_sparse_batched(a, map, map_heads, 0, s); }
+
+int ltx_launch_attention_sparse_batched(const AttnArgs& a, const uint32_t* map, int map_heads, int64_t map_bstride, hipStream_t s) {
     if (!a.q || !a.k || !a.v || !a.o || !map) LTX_FAIL(LTX_ERR_ARG, "attention_sparse: null tensor or map");
     if (a.B < 1 || a.Sq < 1 || a.Sk < 1 || a.heads < 1) LTX_FAIL(LTX_ERR_ARG, "attention_sparse: empty problem");
     if (a.hd != 64 && a.hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "attention_sparse: head_dim must be 64 or 128 (got " + std::to_string(a.hd) + ")");
     if (map_heads != 1 && map_heads != a.heads)
         LTX_FAIL(LTX_ERR_ARG, "attention_sparse: map_heads must be 1 or heads (got " + std::to_string(map_heads) + " with " + std::to_string(a.heads) + " heads)");
+    if (map_bstride != 0 && map_bstride < (int64_t)map_heads * cdiv(a.Sq, BQ) * cdiv(cdiv(a.Sk, BKV), 32))
+        LTX_FAIL(LTX_ERR_ARG, "attention_sparse: map_batch_stride must be 0 or hold a batch row's map (got " + std::to_string(map_bstride) + " words)");
     if (a.bias || a.bias2d || a.k_count || a.p_out || a.q_rowsq) LTX_FAIL(LTX_ERR_UNSUPPORTED, "attention_sparse: no key bias, key count, row factor or P-only mode");
     const int64_t D = (int64_t)a.heads * a.hd;
     if (a.ldq < D || a.ldk < D || a.ldv < D || a.ldo < D) LTX_FAIL(LTX_ERR_ARG, "attention_sparse: ldq, ldk, ldv and ldo must hold heads * head_dim");
@@ -299,8 +304,8 @@ int ltx_launch_attention_sparse(const AttnArgs& a, const uint32_t* map, int map_
     void* tok = nullptr;
     ltx_prof_begin(LTX_PROF_ATTN_SELF, 4.0 * a.B * a.heads * (double)a.Sq * a.Sk * a.hd, s, &tok);      // the dense count: the profiler's rate shows the saving
     const dim3 grid((unsigned)(cdiv(a.Sq, BQ) * a.heads * a.B)), block(256);
-    if (a.hd == 64) LTX_LAUNCH_TIMED(attn_sparse_kernel<64>, grid, block, 0, s, ax, map, map_heads);
-    else LTX_LAUNCH_TIMED(attn_sparse_kernel<128>, grid, block, 0, s, ax, map, map_heads);
+    if (a.hd == 64) LTX_LAUNCH_TIMED(attn_sparse_kernel<64>, grid, block, 0, s, ax, map, map_heads, map_bstride);
+    else LTX_LAUNCH_TIMED(attn_sparse_kernel<128>, grid, block, 0, s, ax, map, map_heads, map_bstride);
     ltx_prof_end(tok, s);
     LTX_CHECK_LAUNCH();
     return LTX_OK;

@@ -8,6 +8,7 @@
 #include "../../include/ltxhip_fp8.h"
 #include "../../include/ltxhip_int8_attn.h"
 #include "../../include/ltxhip_sparse_attn.h"
+#include "../../include/ltxhip_sparse_dynamic.h"
 #include "../host/sparse_map.h"
 
 // The ops' dtype argument -> LTX_DT_*.  The one place every op's dtype passes: LTX_F8_E4M3 (a source dtype, ltxhip_fp8.h) is refused
@@ -593,4 +594,19 @@ extern "C" int ltx_op_attention_sparse(const void* q, const void* k, const void*
     AttnArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.B = B; a.Sq = Sq; a.Sk = Sk; a.heads = heads; a.hd = hd; a.q_prescaled = 1;
     return ltx_launch_attention_sparse(a, map, map_heads, (hipStream_t)stream);
+}
+
+// ---- the device-built maps' kernels on their own (include/ltxhip_sparse_dynamic.h) ----
+extern "C" int ltx_op_pool_qk(const void* q, const void* k, float* qbar, float* kbar, int B, int S, int heads, int hd, int ldq, int ldk, ltx_stream stream) {
+    return ltx_launch_pool_qk(q, k, qbar, kbar, B, S, heads, hd, ldq, ldk, (hipStream_t)stream);
+}
+extern "C" int ltx_op_sparse_select(const float* qbar, const float* kbar, const uint32_t* keep, int keep_heads, uint32_t* map_out, uint32_t* count_out,
+                                    int B, int S, int heads, int hd, float mass, ltx_stream stream) {
+    return ltx_launch_sparse_select(qbar, kbar, keep, keep_heads, map_out, count_out, B, S, heads, hd, mass, (hipStream_t)stream);
+}
+extern "C" int ltx_op_attention_sparse_batched(const void* q, const void* k, const void* v, void* o, const uint32_t* map, int map_heads, int64_t map_batch_stride,
+                                               int B, int Sq, int Sk, int heads, int hd, int ldq, int ldk, int ldv, int ldo, ltx_stream stream) {
+    AttnArgs a; a.q = q; a.k = k; a.v = v; a.o = o; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.B = B; a.Sq = Sq; a.Sk = Sk; a.heads = heads; a.hd = hd; a.q_prescaled = 1;
+    return ltx_launch_attention_sparse_batched(a, map, map_heads, map_batch_stride, (hipStream_t)stream);
 }

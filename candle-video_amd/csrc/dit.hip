@@ -15,6 +15,7 @@
 #include "../../include/ltxhip_int8_attn.h"
 #include "../../include/ltxhip_fp8.h"
 #include "../../include/ltxhip_sparse_attn.h"
+#include "../../include/ltxhip_sparse_dynamic.h"
 #include "../host/step_cache.h"
 #include "../host/sparse_map.h"
 #include "lora.h"
@@ -133,6 +134,20 @@ struct ltx_dit {
     bool spa_any = false;
     DevBuf spa_map; int spa_heads = 0; int64_t spa_S = 0;
     void free_sparse_attention() { spa_map.release(); spa_flag.clear(); spa_any = false; spa_heads = 0; spa_S = 0; }
+    // Device-built maps (include/ltxhip_sparse_dynamic.h; ltx_dit_set_sparse_attention_dynamic below): per block a flag, the requested
+    // mass, the optional device copy of the keep map [spd_keep_heads][ltx_sparse_map_words(spd_keep_S)], and the buffers of one block's
+    // selection - the pooled means, one map [B][heads][NQB][NW] - plus the counts of every block [L][B * heads * NQB].  spd_rows: per
+    // block the batch rows of the last forward whose attention ran (bit b), for ltx_dit_sparse_dynamic_density.  Nothing weight-derived.
+    std::vector<unsigned char> spd_flag, spd_rows;
+    bool spd_any = false;
+    float spd_mass = 0.f;
+    DevBuf spd_keep; int spd_keep_heads = 0; int64_t spd_keep_S = 0;
+    DevBuf spd_qbar, spd_kbar, spd_map, spd_count;
+    int spd_B = 0, spd_fS = 0; hipStream_t spd_stream = nullptr;      // the last forward: its batch rows, token count and stream
+    void free_sparse_dynamic() {
+        for (DevBuf* b : {&spd_keep, &spd_qbar, &spd_kbar, &spd_map, &spd_count}) b->release();
+        spd_flag.clear(); spd_rows.clear(); spd_any = false; spd_mass = 0.f; spd_keep_heads = 0; spd_keep_S = 0; spd_B = 0; spd_fS = 0; spd_stream = nullptr;
+    }
     // fp8-resident block linears (include/ltxhip_fp8.h): fixed at creation - per block the LTX_F8_* mask of the kinds whose LinearW holds
     // the checkpoint's own e4m3 bytes (w8) and no bf16 matrix
     std::vector<unsigned char> f8_mask;
@@ -158,6 +173,7 @@ struct ltx_dit {
         a8.release(); a8s.release();
         free_int8_attention(); i8a_flag.clear(); i8a_any = false;
         free_sparse_attention();
+        free_sparse_dynamic();
         DevBuf* bs[] = {&xin, &encin, &h, &n, &qkv, &attn, &ff, &c1, &encp, &kv2, &tproj, &e1, &emb, &embs, &temb, &ada, &adaf, &cosb, &sinb, &bias, &orig, &orig_hsq, &outT, &rsq, &hsq, &parts};
         for (DevBuf* b : bs) b->release();
         release_caches();
@@ -464,6 +480,9 @@ extern "C" int ltx_dit_set_int8_attention(ltx_dit* m, const unsigned char* block
     for (int l = 0; l < L && m->spa_any; ++l)
         if (want[l] && m->spa_flag[(size_t)l])
             LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: block " + std::to_string(l) + " runs block-sparse attention (ltx_dit_set_sparse_attention); sparse int8 scores are not served (the handle is unchanged)");
+    for (int l = 0; l < L && m->spd_any; ++l)
+        if (want[l] && m->spd_flag[(size_t)l])
+            LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_attention: block " + std::to_string(l) + " runs block-sparse attention with device-built maps (ltx_dit_set_sparse_attention_dynamic); sparse int8 scores are not served (the handle is unchanged)");
     HIP_TRY(hipSetDevice(m->device));
     const bool had = m->i8a_any;
     m->i8a_flag = want; m->i8a_any = any;
@@ -488,6 +507,7 @@ extern "C" int ltx_dit_set_sparse_attention(ltx_dit* m, const uint32_t* map, int
     bool any = false;
     for (int l = 0; l < L; ++l) { want[l] = (map && (!block_flags || block_flags[l] != 0)) ? 1 : 0; any = any || want[l]; }
     if (any) {
+        if (m->spd_any) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention: the handle builds its maps on the device (ltx_dit_set_sparse_attention_dynamic); clear that mode first (the handle is unchanged)");
         if (m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention: the sparse attention takes a bf16 model (this handle is f32)");
         if (hd != 64 && hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention: head_dim must be 64 or 128 (this handle has " + std::to_string(hd) + ")");
         if (map_heads != 1 && map_heads != H)
@@ -516,6 +536,74 @@ extern "C" int ltx_dit_get_sparse_attention(const ltx_dit* m, unsigned char* blo
     for (int l = 0; l < m->cfg.num_layers; ++l) block_flags_out[l] = (size_t)l < m->spa_flag.size() ? m->spa_flag[(size_t)l] : 0;
     if (map_heads_out) *map_heads_out = m->spa_heads;
     if (S_out) *S_out = m->spa_S;
+    return LTX_OK;
+}
+
+// ---- device-built maps for the block-sparse self-attention (include/ltxhip_sparse_dynamic.h) ----
+extern "C" int ltx_dit_set_sparse_attention_dynamic(ltx_dit* m, float mass, const uint32_t* keep_map, int keep_heads, int64_t keep_S,
+                                                    const unsigned char* block_flags, ltx_stream stream) {
+    (void)stream;
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention_dynamic: null handle");
+    const int L = m->cfg.num_layers, hd = m->cfg.attention_head_dim, H = m->cfg.num_attention_heads;
+    const bool clear = mass == 0.f && !block_flags;
+    if (!clear && !(mass > 0.f && mass <= 1.f)) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention_dynamic: mass must be in (0, 1] (got " + std::to_string(mass) + "); 0 with no block flags clears the mode");
+    std::vector<unsigned char> want((size_t)L);
+    bool any = false;
+    for (int l = 0; l < L; ++l) { want[l] = (!clear && (!block_flags || block_flags[l] != 0)) ? 1 : 0; any = any || want[l]; }
+    if (any) {
+        if (m->spa_any) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention_dynamic: the handle has a static map set (ltx_dit_set_sparse_attention); clear it first (the handle is unchanged)");
+        if (m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention_dynamic: the sparse attention takes a bf16 model (this handle is f32)");
+        if (hd != 64 && hd != 128) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention_dynamic: head_dim must be 64 or 128 (this handle has " + std::to_string(hd) + ")");
+        if (keep_map && keep_heads != 1 && keep_heads != H)
+            LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention_dynamic: keep_heads must be 1 or the handle's " + std::to_string(H) + " heads (got " + std::to_string(keep_heads) + ")");
+        if (keep_map && (keep_S < 1 || keep_S > LTX_SPARSE_DYNAMIC_MAX_S))
+            LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_sparse_attention_dynamic: keep_S must be a token count of at most " + std::to_string(LTX_SPARSE_DYNAMIC_MAX_S) + " (got " + std::to_string(keep_S) + ")");
+        for (int l = 0; l < L && m->i8a_any; ++l)
+            if (want[l] && m->i8a_flag[(size_t)l])
+                LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_sparse_attention_dynamic: block " + std::to_string(l) + " runs int8 attention (ltx_dit_set_int8_attention); sparse int8 scores are not served (the handle is unchanged)");
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    if (m->spd_any) (void)hipDeviceSynchronize();                 // forwards enqueued earlier may still read the buffers
+    m->free_sparse_dynamic();
+    if (!any) return LTX_OK;
+    if (keep_map) {
+        const size_t bytes = (size_t)keep_heads * sparse_map_words(keep_S) * sizeof(uint32_t);
+        LTX_TRY(m->spd_keep.ensure(bytes));
+        const hipError_t e = hipMemcpy(m->spd_keep.p, keep_map, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipGetLastError(); m->free_sparse_dynamic(); LTX_FAIL(LTX_ERR_HIP, std::string("ltx_dit_set_sparse_attention_dynamic: upload of the keep map: ") + hipGetErrorString(e)); }
+        m->spd_keep_heads = keep_heads; m->spd_keep_S = keep_S;
+    }
+    m->spd_flag = want; m->spd_rows.assign((size_t)L, 0); m->spd_any = true; m->spd_mass = mass;
+    return LTX_OK;
+}
+extern "C" int ltx_dit_get_sparse_attention_dynamic(const ltx_dit* m, unsigned char* block_flags_out, float* mass_out, int* keep_heads_out, int64_t* keep_S_out) {
+    if (!m || !block_flags_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_sparse_attention_dynamic: null argument");
+    for (int l = 0; l < m->cfg.num_layers; ++l) block_flags_out[l] = (size_t)l < m->spd_flag.size() ? m->spd_flag[(size_t)l] : 0;
+    if (mass_out) *mass_out = m->spd_mass;
+    if (keep_heads_out) *keep_heads_out = m->spd_keep_heads;
+    if (keep_S_out) *keep_S_out = m->spd_keep_S;
+    return LTX_OK;
+}
+extern "C" int ltx_dit_sparse_dynamic_density(ltx_dit* m, double* per_block_out) {
+    if (!m || !per_block_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_sparse_dynamic_density: null argument");
+    const int L = m->cfg.num_layers, H = m->cfg.num_attention_heads;
+    for (int l = 0; l < L; ++l) per_block_out[l] = -1.0;
+    if (!m->spd_any || m->spd_B < 1) return LTX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->spd_stream));
+    const int64_t nqb = sparse_map_nqb(m->spd_fS), nkt = sparse_map_nkt(m->spd_fS), per_row = (int64_t)H * nqb, per_block = m->spd_B * per_row;
+    std::vector<uint32_t> host((size_t)per_block);
+    for (int l = 0; l < L; ++l) {
+        if (!m->spd_flag[(size_t)l] || !m->spd_rows[(size_t)l]) continue;
+        HIP_TRY(hipMemcpy(host.data(), m->spd_count.as<uint32_t>() + (size_t)l * per_block, (size_t)per_block * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        int64_t n = 0, rows = 0;
+        for (int b = 0; b < m->spd_B; ++b) {
+            if (!(m->spd_rows[(size_t)l] >> b & 1)) continue;
+            ++rows;
+            for (int64_t i = 0; i < per_row; ++i) n += host[(size_t)(b * per_row + i)];
+        }
+        per_block_out[l] = (double)n / ((double)rows * (double)per_row * (double)nkt);
+    }
     return LTX_OK;
 }
 
@@ -989,7 +1077,8 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     // a block with int8 attention (ltxhip_int8_attn.h) takes the prescaled q whatever the plan says: its scores are in log2 units
     const bool attn8 = m->i8a_any && m->i8a_flag[(size_t)l] != 0;
     const bool attn_sp = m->spa_any && m->spa_flag[(size_t)l] != 0;      // ... and so does a block with sparse attention (ltxhip_sparse_attn.h)
-    if (p.fold_q || attn8 || attn_sp) qa.out_scale0 = attn_scale * 1.4426950408889634f;
+    const bool attn_dyn = m->spd_any && m->spd_flag[(size_t)l] != 0;     // ... and one whose maps are built here (ltxhip_sparse_dynamic.h)
+    if (p.fold_q || attn8 || attn_sp || attn_dyn) qa.out_scale0 = attn_scale * 1.4426950408889634f;
     LTX_TRY(ltx_launch_qknorm_rope(qa, dt, s));
     AttnArgs at; at.q = m->qkv.p; at.k = (char*)m->qkv.p + (size_t)p.seg * esz; at.v = (char*)m->qkv.p + (size_t)2 * p.seg * esz; at.o = m->attn.p;
     at.ldq = at.ldk = at.ldv = p.ldqkv; at.ldo = D; at.B = B; at.Sq = S; at.Sk = S; at.heads = H; at.hd = hd; at.scale = attn_scale;
@@ -1001,6 +1090,15 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         const size_t in_off = (size_t)b0 * S * p.ldqkv * esz;
         ar.q = (const char*)at.q + in_off; ar.k = (const char*)at.k + in_off; ar.v = (const char*)at.v + in_off; ar.o = (char*)at.o + (size_t)b0 * S * D * esz;
         if (attn_sp) return ltx_launch_attention_sparse(ar, m->spa_map.as<uint32_t>(), m->spa_heads, s);      // the listed key tiles only
+        if (attn_dyn) {      // the means of q' and k, the tiles they select per (batch row, head, query block), the listed tiles only
+            const int64_t rows = (int64_t)H * sparse_map_nqb(S);
+            uint32_t* cnt = m->spd_count.as<uint32_t>() + ((size_t)l * B + b0) * rows;
+            LTX_TRY(ltx_launch_pool_qk(ar.q, ar.k, m->spd_qbar.as<float>(), m->spd_kbar.as<float>(), ar.B, S, H, hd, p.ldqkv, p.ldqkv, s));
+            LTX_TRY(ltx_launch_sparse_select(m->spd_qbar.as<float>(), m->spd_kbar.as<float>(), m->spd_keep.as<uint32_t>(), m->spd_keep_heads,
+                                             m->spd_map.as<uint32_t>(), cnt, ar.B, S, H, hd, m->spd_mass, s));
+            for (int bb = b0; bb < b1; ++bb) m->spd_rows[(size_t)l] |= (unsigned char)(1u << bb);
+            return ltx_launch_attention_sparse_batched(ar, m->spd_map.as<uint32_t>(), H, rows * sparse_map_nw(S), s);
+        }
         if (!attn8) return ltx_launch_attention(ar, dt, s);
         LTX_TRY(ltx_launch_kmean(ar.k, ar.B, S, D, p.ldqkv, m->kpart.as<float>(), m->kmean.as<float>(), s));
         LTX_TRY(ltx_launch_quant_qk_i8(ar.q, ar.k, m->kmean.as<float>(), ar.B, S, S, H, hd, p.ldqkv, p.ldqkv, m->q8.p, m->q8s.as<float>(), m->k8.p, m->k8s.as<float>(), s));
@@ -1124,6 +1222,10 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
     if (G < 1 || S % G != 0) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_forward: the modulation groups must divide the sequence");
     if (m->spa_any && S != m->spa_S)
         LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_forward: the handle's sparse-attention map is for " + std::to_string(m->spa_S) + " tokens, this forward has " + std::to_string(S) + " (ltx_dit_set_sparse_attention)");
+    if (m->spd_any && m->spd_keep.p && S != m->spd_keep_S)
+        LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_forward: the handle's keep map is for " + std::to_string(m->spd_keep_S) + " tokens, this forward has " + std::to_string(S) + " (ltx_dit_set_sparse_attention_dynamic)");
+    if (m->spd_any && S > LTX_SPARSE_DYNAMIC_MAX_S)
+        LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_forward: device-built sparse maps serve at most " + std::to_string(LTX_SPARSE_DYNAMIC_MAX_S) + " tokens, this forward has " + std::to_string(S) + " (ltx_dit_set_sparse_attention_dynamic)");
     hipStream_t s = (hipStream_t)stream;
     const ltx_dit_config& c = m->cfg;
     DitPlan plan = ltx_dit_plan(c, m->dtype, io_dtype == LTX_BF16 ? LTX_DT_BF16 : LTX_DT_F32, B, S, K, G, skip_layer_mask != nullptr);
@@ -1146,8 +1248,12 @@ int dit_forward_b8(ltx_dit* m, const void* hidden, const void* enc, const float*
         {&m->a8, m->i8_any ? (size_t)M * 4 * D : 0}, {&m->a8s, m->i8_any ? (size_t)M * sizeof(float) : 0},
         {&m->q8, m->i8a_any ? (size_t)M * D : 0}, {&m->k8, m->i8a_any ? (size_t)M * D : 0}, {&m->q8s, m->i8a_any ? (size_t)M * c.num_attention_heads * sizeof(float) : 0},
         {&m->k8s, m->i8a_any ? (size_t)B * c.num_attention_heads * ((S + 63) / 64) * sizeof(float) : 0}, {&m->kmean, m->i8a_any ? (size_t)B * D * sizeof(float) : 0},
-        {&m->kpart, m->i8a_any ? ltx_kmean_ws_bytes(B, S, D) : 0}};
+        {&m->kpart, m->i8a_any ? ltx_kmean_ws_bytes(B, S, D) : 0},
+        {&m->spd_qbar, m->spd_any ? (size_t)B * sparse_map_nqb(S) * D * sizeof(float) : 0}, {&m->spd_kbar, m->spd_any ? (size_t)B * sparse_map_nkt(S) * D * sizeof(float) : 0},
+        {&m->spd_map, m->spd_any ? (size_t)B * c.num_attention_heads * sparse_map_words(S) * sizeof(uint32_t) : 0},
+        {&m->spd_count, m->spd_any ? (size_t)L * B * c.num_attention_heads * sparse_map_nqb(S) * sizeof(uint32_t) : 0}};
     for (const auto& w : ws) LTX_TRY(w.first->ensure(w.second));
+    if (m->spd_any) { m->spd_rows.assign((size_t)L, 0); m->spd_B = B; m->spd_fS = S; m->spd_stream = s; }      // what ltx_dit_sparse_dynamic_density reads
     const bool reuse = sc && sc->reuse;
     if (reuse) {
         for (int b = 0; b < B; ++b)

@@ -328,6 +328,14 @@ bool ltx_attention_q64_fits(const AttnArgs& a);   // attn_q64.hip: every row off
 // attn_sparse.hip (include/ltxhip_sparse_attn.h): bf16, q prescaled, no bias; map DEVICE uint32 [map_heads][ceil(Sq / 128)][ceil(ceil(Sk / 64) / 32)],
 // map_heads 1 or heads.  Refused (LTX_ERR_UNSUPPORTED) where ltx_attention_q64_fits says no.  Sets xcd_heads / wide_o itself.
 int ltx_launch_attention_sparse(const AttnArgs& a, const uint32_t* map, int map_heads, hipStream_t s);
+// ... with map_batch_stride WORDS between the maps of two batch rows (include/ltxhip_sparse_dynamic.h); 0: the launch above, bit for bit
+int ltx_launch_attention_sparse_batched(const AttnArgs& a, const uint32_t* map, int map_heads, int64_t map_batch_stride, hipStream_t s);
+// sparse_select.hip (include/ltxhip_sparse_dynamic.h): the pooled means qbar f32 [B, heads, ceil(S / 128), hd] / kbar f32 [B, heads, ceil(S / 64), hd]
+// of q' / k bf16 (row strides ldq / ldk), and the selection: map uint32 [B, heads, NQB, NW], count uint32 [B, heads, NQB]; keep DEVICE
+// [keep_heads][NQB][NW] or null.  hd 64 or 128, S <= 131072, mass in (0, 1].
+int ltx_launch_pool_qk(const void* q, const void* k, float* qbar, float* kbar, int B, int S, int heads, int hd, int ldq, int ldk, hipStream_t s);
+int ltx_launch_sparse_select(const float* qbar, const float* kbar, const uint32_t* keep, int keep_heads, uint32_t* map, uint32_t* count,
+                             int B, int S, int heads, int hd, float mass, hipStream_t s);
 bool ltx_attention_prescale_ok(int hd);
 bool ltx_attention_cross64_ok(int hd, int Sk);   // shape-only: the short-key-set kernel serves the launch (k_count / bias2d / q_rowsq)
 // attn2.to_out folded into the cached text context (xattn_fold.hip).  ONE decision, read by dit.hip's text_context and by the

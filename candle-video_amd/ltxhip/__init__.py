@@ -431,6 +431,19 @@ for _name, _sig in _SPARSE_ATTN_SIGS.items():
     _fn = getattr(lib, _name)
     _fn.argtypes = _sig
     _fn.restype = C.c_size_t if _name == "ltx_sparse_map_words" else C.c_double if _name == "ltx_sparse_map_density" else C.c_int
+# include/ltxhip_sparse_dynamic.h (kept apart like the twelve above)
+_SPARSE_DYNAMIC_SIGS = {
+    "ltx_dit_set_sparse_attention_dynamic": [_vp, _f, _vp, _i, _i64, _vp, _vp], "ltx_dit_get_sparse_attention_dynamic": [_vp, _vp, _vp, _vp, _vp],
+    "ltx_dit_sparse_dynamic_density": [_vp, _vp],
+    "ltx_op_pool_qk": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "ltx_op_sparse_select": [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "ltx_op_attention_sparse_batched": [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+}
+SPARSE_DYNAMIC_SYMBOLS = sorted(_SPARSE_DYNAMIC_SIGS)
+for _name, _sig in _SPARSE_DYNAMIC_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
 LTX_I8_QKV, LTX_I8_TO_OUT, LTX_I8_FF1, LTX_I8_FF2, LTX_I8_ALL = 1, 2, 4, 8, 15
 INT8_LINEARS = ("qkv", "to_out", "ff1", "ff2")   # the mask bits of ltx_dit_set_int8_linears, lowest first
 GEMM_I8_TILES = ("256x256", "256x128", "128x128")
@@ -831,6 +844,42 @@ class LtxVideoTransformer3DModel:
         """0 / 1 per block"""
         out = (C.c_ubyte * self.config.num_layers)()
         _check(lib.ltx_dit_get_sparse_attention(self._h, out, None, None))
+        return list(out)
+
+    # ---- device-built maps for the block-sparse self-attention (include/ltxhip_sparse_dynamic.h): handle state
+    def set_sparse_attention_dynamic(self, mass: float, keep: Optional[torch.Tensor] = None, keep_S: int = 0, block_flags: Optional[Sequence] = None):
+        """attn1 of every block (or of the blocks with a truthy block_flags entry) selects its key tiles on the device, per batch row,
+        head and 128-query block, from the pooled q and k of the forward: the shortest prefix of tiles in descending pooled softmax
+        mass that reaches `mass` in (0, 1], plus the diagonal, plus the tiles of `keep` (int32 [NQB, NW] or [heads, NQB, NW] for
+        keep_S tokens, e.g. sparse_window_map(...); with it, forwards of another token count are refused).  mass = 0 with no
+        block_flags clears the state.  A bf16 model with head_dim 64 or 128."""
+        arr = None
+        if block_flags is not None:
+            if len(block_flags) != self.config.num_layers:
+                raise LtxError(f"set_sparse_attention_dynamic: block_flags has {len(block_flags)} entries for {self.config.num_layers} blocks")
+            arr = (C.c_ubyte * len(block_flags))(*[1 if v else 0 for v in block_flags])
+        if keep is None:
+            _check(lib.ltx_dit_set_sparse_attention_dynamic(self._h, float(mass), None, 0, C.c_int64(0), arr, _stream()))
+            return
+        m = keep.cpu().to(torch.int32).contiguous()
+        words = int(lib.ltx_sparse_map_words(C.c_int64(keep_S)))
+        mh = m.shape[0] if m.dim() == 3 else 1
+        if m.dim() not in (2, 3) or m.numel() != mh * words:
+            raise LtxError(f"set_sparse_attention_dynamic: a keep map of shape {tuple(m.shape)} for S = {keep_S} ({words} words per head)")
+        _check(lib.ltx_dit_set_sparse_attention_dynamic(self._h, float(mass), C.c_void_p(m.data_ptr()), mh, C.c_int64(keep_S), arr, _stream()))
+
+    @property
+    def sparse_attention_dynamic(self):
+        """(0 / 1 per block, mass, keep_heads, keep_S)"""
+        out = (C.c_ubyte * self.config.num_layers)()
+        mass, kh, ks = C.c_float(0), C.c_int(0), C.c_int64(0)
+        _check(lib.ltx_dit_get_sparse_attention_dynamic(self._h, out, C.byref(mass), C.byref(kh), C.byref(ks)))
+        return list(out), mass.value, kh.value, ks.value
+
+    def sparse_dynamic_density(self) -> List[float]:
+        """per block the selected tiles over all tiles of the last forward (-1: not flagged, or no forward yet); waits for that forward"""
+        out = (C.c_double * self.config.num_layers)()
+        _check(lib.ltx_dit_sparse_dynamic_density(self._h, out))
         return list(out)
 
     @property
@@ -2683,6 +2732,49 @@ class ops:
         o = torch.empty(B, Sq, D, dtype=torch.bfloat16, device=q.device)
         _check(lib.ltx_op_attention_sparse(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(map), mh, B, Sq, Sk, heads, D // heads,
                                            q.stride(1), k.stride(1), v.stride(1), D, _stream()))
+        return o
+
+    # ---- the device-built maps' kernels (include/ltxhip_sparse_dynamic.h)
+    @staticmethod
+    def pool_qk(q, k, heads):
+        """-> (qbar f32 [B, heads, ceil(S / 128), hd], kbar f32 [B, heads, ceil(S / 64), hd]): the block means of q and k bf16 [B, S, D]"""
+        B, S, D = q.shape
+        q, k = [t if t.stride(2) == 1 and t.stride(0) == S * t.stride(1) else t.contiguous() for t in (q, k)]
+        qbar = torch.empty(B, heads, (S + 127) // 128, D // heads, dtype=torch.float32, device=q.device)
+        kbar = torch.empty(B, heads, (S + 63) // 64, D // heads, dtype=torch.float32, device=q.device)
+        _check(lib.ltx_op_pool_qk(_ptr(q), _ptr(k), _ptr(qbar), _ptr(kbar), B, S, heads, D // heads, q.stride(1), k.stride(1), _stream()))
+        return qbar, kbar
+
+    @staticmethod
+    def sparse_select(qbar, kbar, S, mass, keep=None):
+        """-> (map int32 [B, heads, NQB, NW], count int32 [B, heads, NQB]) from pool_qk's means; keep DEVICE int32 [NQB, NW] or [heads, NQB, NW]"""
+        B, heads, nqb, hd = qbar.shape
+        nw = ((S + 63) // 64 + 31) // 32
+        map = torch.empty(B, heads, nqb, nw, dtype=torch.int32, device=qbar.device)
+        count = torch.empty(B, heads, nqb, dtype=torch.int32, device=qbar.device)
+        kh = 0
+        if keep is not None:
+            if keep.dtype != torch.int32 or tuple(keep.shape[-2:]) != (nqb, nw) or keep.dim() not in (2, 3):
+                raise LtxError(f"sparse_select: keep must be int32 [{nqb}, {nw}] or [heads, {nqb}, {nw}], got {keep.dtype} {tuple(keep.shape)}")
+            kh = keep.shape[0] if keep.dim() == 3 else 1
+            keep = _dev(keep).contiguous()
+        _check(lib.ltx_op_sparse_select(_ptr(qbar.contiguous()), _ptr(kbar.contiguous()), _ptr(keep), kh, _ptr(map), _ptr(count), B, S, heads, hd, float(mass), _stream()))
+        return map, count
+
+    @staticmethod
+    def attention_sparse_batched(q, k, v, map, heads):
+        """attention_sparse with one map per batch row: map DEVICE int32 [B, NQB, NW] or [B, heads, NQB, NW]"""
+        B, Sq, D = q.shape
+        Sk = k.shape[1]
+        q, k, v = [t if t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1) else t.contiguous() for t in (q, k, v)]
+        nqb, nw = (Sq + 127) // 128, ((Sk + 63) // 64 + 31) // 32
+        if map.dtype != torch.int32 or tuple(map.shape[-2:]) != (nqb, nw) or map.dim() not in (3, 4) or map.shape[0] != B:
+            raise LtxError(f"attention_sparse_batched: map must be int32 [{B}, {nqb}, {nw}] or [{B}, heads, {nqb}, {nw}], got {map.dtype} {tuple(map.shape)}")
+        mh = map.shape[1] if map.dim() == 4 else 1
+        map = _dev(map).contiguous()
+        o = torch.empty(B, Sq, D, dtype=torch.bfloat16, device=q.device)
+        _check(lib.ltx_op_attention_sparse_batched(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(map), mh, C.c_int64(mh * nqb * nw), B, Sq, Sk, heads, D // heads,
+                                                   q.stride(1), k.stride(1), v.stride(1), D, _stream()))
         return o
 
     # ---- the fp8 (e4m3) kernels (include/ltxhip_fp8.h)

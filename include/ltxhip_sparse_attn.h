@@ -29,7 +29,8 @@
  *
  * Out of scope: token reordering into 3-D tiles (STA's layout - without it the spatial window saves little in row-major order and the
  * saving comes from wf); per-head pattern search; sparse int8 scores; cross-attention; a generated-assembly loop; maps per batch row;
- * keyframe, multiscale second-pass and sharded forms under a map of another S (refused, see below).
+ * keyframe, multiscale second-pass and sharded forms under a map of another S (refused, see below).  Maps chosen from the content,
+ * per batch row and head, are ltxhip_sparse_dynamic.h's: a producer on the device in front of this kernel.
  * Conventions are those of ltxhip.h (device pointers unless marked HOST, 0 = success, ltx_last_error). */
 #ifndef LTXHIP_SPARSE_ATTN_H
 #define LTXHIP_SPARSE_ATTN_H

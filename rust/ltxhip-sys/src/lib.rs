@@ -579,6 +579,19 @@ extern "C" {
                                    b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int, ldq: c_int, ldk: c_int, ldv: c_int, ldo: c_int, stream: ltx_stream) -> c_int;
 }
 
+// ---- include/ltxhip_sparse_dynamic.h: block maps built on the device from the forward's own q and k ----
+
+extern "C" {
+    pub fn ltx_dit_set_sparse_attention_dynamic(m: *mut ltx_dit, mass: f32, keep_map: *const u32, keep_heads: c_int, keep_s: i64, block_flags: *const u8, stream: ltx_stream) -> c_int;
+    pub fn ltx_dit_get_sparse_attention_dynamic(m: *const ltx_dit, block_flags_out: *mut u8, mass_out: *mut f32, keep_heads_out: *mut c_int, keep_s_out: *mut i64) -> c_int;
+    pub fn ltx_dit_sparse_dynamic_density(m: *mut ltx_dit, per_block_out: *mut f64) -> c_int;
+    pub fn ltx_op_pool_qk(q: *const c_void, k: *const c_void, qbar: *mut f32, kbar: *mut f32, b: c_int, s: c_int, heads: c_int, hd: c_int, ldq: c_int, ldk: c_int, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_sparse_select(qbar: *const f32, kbar: *const f32, keep: *const u32, keep_heads: c_int, map_out: *mut u32, count_out: *mut u32,
+                                b: c_int, s: c_int, heads: c_int, hd: c_int, mass: f32, stream: ltx_stream) -> c_int;
+    pub fn ltx_op_attention_sparse_batched(q: *const c_void, k: *const c_void, v: *const c_void, o: *mut c_void, map: *const u32, map_heads: c_int, map_batch_stride: i64,
+                                           b: c_int, sq: c_int, sk: c_int, heads: c_int, hd: c_int, ldq: c_int, ldk: c_int, ldv: c_int, ldo: c_int, stream: ltx_stream) -> c_int;
+}
+
 // ---- include/ltxhip_fp8.h: FP8 (E4M3) checkpoints, fp8-resident block linears ----
 
 /// `ltx_dtype` of an e4m3 SOURCE tensor (`ltx_weight::dtype`); never a model or I/O dtype.
