@@ -838,6 +838,119 @@ def _attention_i8(hip, A, st):
     return {"o": ov}
 
 
+# ================================================================== block-sparse attention and its device-built maps
+def sparse_qkv(g, B, Sq, Sk, D, hd):
+    return randn(g, B, Sq, D, scale=3.0 * LOG2E * hd ** -0.5), randn(g, B, Sk, D), randn(g, B, Sk, D)
+
+
+def sparse_attention_case(hd):
+    @simple(f"attention_sparse hd{hd} (B 2, Sq 200, Sk 300, heads 3) per-head map, k | v slices, o on ld = D + 8 and D + 4")
+    def fn(hip, A, st):
+        """key tile 3 is in no row of any head: its k and v rows are operands the kernel must not need.  o is stored twice: beside
+        eight other columns (16-byte stores) and beside four (ldo % 8 == 4: the 8-byte stores)"""
+        import sparse_attn_ref as SP
+        from test_gpu_int8_attn import TOL
+        from test_gpu_sparse_attn import random_bits
+        B, Sq, Sk, heads = 2, 200, 300, 3
+        D = heads * hd
+        q, k, v = sparse_qkv(gen(31 + hd), B, Sq, Sk, D, hd)
+        bits = random_bits((heads, 2, 5), 6)
+        bits[:, 0, 3] = bits[:, 1, 3] = False
+        assert bool(bits.any(-1).all()) and not bool(bits[..., 3].any())
+        map = SP.pack(bits)
+        pq, _ = A.place(q, name="q"); (pk, _), (pv, _) = A.place_fused([k, v], ["in"] * 2, names=["k", "v"])
+        pm, _ = A.place(map.view(1, -1), name="map")
+        outs = {}
+        calls = []
+        for extra in (8, 4):
+            (po, ov), (_, _) = A.place_fused([torch.empty(B * Sq, D, dtype=BF16), torch.zeros(B * Sq, extra, dtype=BF16)], ["out", "in"], names=[f"o ld D+{extra}", "beside o"])
+            outs[f"o{extra}"] = ov; calls.append((po, D + extra))
+        A.arm()
+        for po, ldo in calls:
+            hip._check(hip.lib.ltx_op_attention_sparse(pq, pk, pv, po, pm, heads, B, Sq, Sk, heads, hd, D, 2 * D, 2 * D, ldo, stream(hip)))
+        ref = SP.attention64(q, k, v, map, heads).float()
+
+        def value(o):                                                                           # test_gpu_sparse_attn's bar
+            assert E.same_bits(o["o8"], o["o4"]), "the 8-byte stores differ from the 16-byte stores"
+            e = rel_l2(o["o8"].float().view(B, Sq, D), ref)
+            assert e <= TOL, e
+        st["check"] = value
+        return outs
+    return fn
+
+
+def sparse_batched_case(hd):
+    @simple(f"attention_sparse_batched hd{hd} (B 2, S 300, heads 3) q | k | v slices, map_batch_stride > a row's map")
+    def fn(hip, A, st):
+        """the two batch rows' maps lie five filler words apart"""
+        import sparse_attn_ref as SP
+        from test_gpu_int8_attn import TOL
+        from test_gpu_sparse_attn import random_bits
+        B, S, heads = 2, 300, 3
+        D = heads * hd
+        q, k, v = sparse_qkv(gen(37 + hd), B, S, S, D, hd)
+        bits = random_bits((B, heads, 3, 5), 7)
+        map = SP.pack(bits)
+        words = heads * 3
+        assert not torch.equal(map[0], map[1])
+        (pq, _), (pk, _), (pv, _) = A.place_fused([q, k, v], ["in"] * 3, names=["q", "k", "v"])
+        pm, _ = A.place(map.view(B, words), ld=words + 5, name="maps")
+        (po, ov), (_, _) = A.place_fused([torch.empty(B * S, D, dtype=BF16), torch.zeros(B * S, 8, dtype=BF16)], ["out", "in"], names=["o", "beside o"])
+        A.arm()
+        hip._check(hip.lib.ltx_op_attention_sparse_batched(pq, pk, pv, po, pm, heads, words + 5, B, S, S, heads, hd, 3 * D, 3 * D, 3 * D, D + 8, stream(hip)))
+        ref = torch.cat([SP.attention64(q[b:b + 1], k[b:b + 1], v[b:b + 1], map[b], heads) for b in range(B)]).float()
+
+        def value(o):
+            e = rel_l2(o["o"].float().view(B, S, D), ref)
+            assert e <= TOL, e
+        st["check"] = value
+        return {"o": ov}
+    return fn
+
+
+@simple("pool_qk (B 2, S 193, heads 9, hd 64) on q | k | v slices: 72 16-byte chunks a row, k's last beside v's first")
+def _pool_qk(hip, A, st):
+    import test_gpu_sparse_select as TSS
+    B, S, heads, hd = 2, 193, 9, 64
+    D = heads * hd
+    g = gen(41)
+    q, k, v = randn(g, B, S, D), randn(g, B, S, D), randn(g, B, S, D)
+    (pq, _), (pk, _), (_, _) = A.place_fused([q, k, v], ["in"] * 3, names=["q", "k", "v"])
+    pqb, qbar = A.place(torch.empty(B * heads * 2, hd, dtype=F32), role="out", name="qbar"); pkb, kbar = A.place(torch.empty(B * heads * 4, hd, dtype=F32), role="out", name="kbar")
+    A.arm()
+    hip._check(hip.lib.ltx_op_pool_qk(pq, pk, pqb, pkb, B, S, heads, hd, 3 * D, 3 * D, stream(hip)))
+    st["check"] = lambda o: TSS.pooled_inside_the_bound(q, k, heads, o["qbar"].view(B, heads, 2, hd), o["kbar"].view(B, heads, 4, hd), st["name"])
+    return {"qbar": qbar, "kbar": kbar}
+
+
+def sparse_select_case(hd):
+    @simple(f"sparse_select hd{hd} (B 2, 4097 tokens, heads 4) with a keep map: three words a row")
+    def fn(hip, A, st):
+        """65 tiles: NW = 3 is odd, so the last ballot of a row stores ONE word.  Every word and count written, nothing behind a row's
+        third word.  The keep map holds tiles 0 and 32 in every row, so no map word can be the arena's never-written value (bit 31
+        alone); word 2 holds bit 0 or nothing"""
+        import sparse_attn_ref as SP
+        import test_gpu_sparse_select as TSS
+        S, (B, heads) = 4097, TSS.WIDE[4097]
+        qbar, kbar = [x.cpu() for x in TSS.ranked_world(S, hd)]
+        keep = torch.zeros(33, 65, dtype=torch.bool)
+        keep[:, 0] = keep[:, 32] = keep[::4, 64] = True
+        pqb, _ = A.place(qbar, name="qbar"); pkb, _ = A.place(kbar, name="kbar"); pkeep, _ = A.place(SP.pack(keep), name="keep")
+        pm, map = A.place(torch.empty(B * heads * 33, 3, dtype=torch.int32), role="out", name="map")
+        pc, count = A.place(torch.empty(1, B * heads * 33, dtype=torch.int32), role="out", name="count")
+        A.arm()
+        hip._check(hip.lib.ltx_op_sparse_select(pqb, pkb, pkeep, 1, pm, pc, B, S, heads, hd, 0.5, stream(hip)))
+        st["check"] = lambda o: TSS.selection_matches(o["map"].view(B, heads, 33, 3), o["count"].view(B, heads, 33), qbar, kbar, S, 0.5, keep, st["name"])
+        return {"map": map, "count": count}
+    return fn
+
+
+for _hd in (64, 128):
+    sparse_attention_case(_hd)
+    sparse_batched_case(_hd)
+    sparse_select_case(_hd)
+
+
 # ================================================================== convolutions (channels-last, B = 2)
 def conv_case(name, Cin, Cout, fam, dt=BF16, causal=False, resid=False, kind="conv", T=2, H=5, W=6, **opts):
     @case(name, **opts)

@@ -29,6 +29,22 @@ def hand_bits(nkt):      # per head three rows: head 0 only tile 0 / only the la
     return bits
 
 
+def rows_of(nkt, *rows):      # hand-made map rows from lists of tiles
+    bits = torch.zeros(len(rows), nkt, dtype=torch.bool)
+    for i, tiles in enumerate(rows):
+        bits[i, list(tiles)] = True
+    return bits
+
+
+# 4500 keys: 71 tiles in THREE map words, the last tile of 20 keys.  Map a, (head, block): only word 2, two empty words in front | words 0
+# and 2 around an empty one | tiles 31 and 32, neighbours across a word boundary | the ragged tile 70 alone: the masked body as the first
+# tile.  Map b: every tile | one tile a word | the last bit of a word, and the first and last of the next | every tile but word 1
+THREE_A = rows_of(71, range(64, 71), (3, 17, 66, 70), (31, 32), (70,)).view(2, 2, 71)
+THREE_B = rows_of(71, range(71), (5, 40, 69), (0, 31, 32, 63), list(range(32)) + list(range(64, 71))).view(2, 2, 71)
+# 17556 keys: 275 tiles in NINE words, the last tile of 20 keys: eight empty words, then tiles 270 .. 274 | tiles 0, 130 and 274 (the
+# word ahead is re-loaded across empty words twice) | a window of tiles 100 .. 140 plus the sink tile 0
+NINE = {"tail": rows_of(275, range(270, 275)), "far-apart": rows_of(275, (0, 130, 274)), "window": rows_of(275, [0] + list(range(100, 141)))}
+
 # (B, Sq, Sk, heads, bits): one tile, one partial query block; a ragged last key tile, a 72-row last query block, odd heads and the batch
 # stride under a per-head map; heads % 8 == 0 (XCD order) under a shared map; 34 key tiles (the walk crosses a map word, the ring
 # wraps); hand-made rows of 1, 2 and all of 5 listed tiles with Sq != Sk - at Sk = 320 as a whole last tile and at 300 as a ragged one
@@ -39,6 +55,12 @@ CASES = {
     "two-words": (1, 128, 2157, 2, random_bits((1, 34), 3)),
     "hand-made": (1, 384, 320, 2, hand_bits(5)),
     "hand-made-ragged": (1, 384, 300, 2, hand_bits(5)),
+    "three-words-a": (1, 256, 4500, 2, THREE_A),
+    "three-words-b": (1, 256, 4500, 2, THREE_B),
+    "nine-words-tail": (1, 128, 17556, 1, NINE["tail"]),
+    "nine-words-far-apart": (1, 128, 17556, 1, NINE["far-apart"]),
+    "nine-words-window": (1, 128, 17556, 1, NINE["window"]),
+    "xcd-per-head": (2, 200, 200, 16, random_bits((16, 2, 4), 5)),      # head = xcd + 8 * (j / nqb) with two heads per XCD and a batch offset
 }
 
 
@@ -75,6 +97,74 @@ def test_skipped_tiles_are_not_read_and_an_empty_row_gives_zeros(hip, hd):
     bits[1] = False                                                     # the second map row lists nothing
     o = run(hip, q, k, v, SP.pack(bits), heads)
     assert bool((o[:, 128:] == 0).all()) and rel_l2(o[:, :128], ref[:, :128]) <= TOL
+
+
+@pytest.mark.parametrize("hd", HDS)
+@pytest.mark.parametrize("name", ["three-words-a", "three-words-b"])
+def test_stale_bits_above_the_last_tile_change_nothing(hip, name, hd):
+    """every bit at or above tile 71 of the last word set: the header promises them harmless.  k and v of the tiles a head lists in
+    no row hold NaN, so a stale bit that were walked - or a tile of an empty word that were staged and multiplied - would show"""
+    B, Sq, Sk, heads, bits = CASES[name]
+    q, k, v = mk(B, Sq, Sk, heads, hd, seed=3 * Sk + hd)
+    clean = SP.pack(bits)
+    ref = SP.attention64(q, k, v, clean, heads).float().cpu()
+    unlisted = 0
+    for h in range(heads):
+        for t in (~bits[h].any(0)).nonzero().flatten().tolist():
+            k[:, 64 * t:64 * t + 64, h * hd:(h + 1) * hd] = float("nan"); v[:, 64 * t:64 * t + 64, h * hd:(h + 1) * hd] = float("nan")
+            unlisted += 1
+    assert unlisted > 0
+    stale = clean.clone()
+    stale[..., 2] |= -(1 << (71 - 64))                                  # bits 7 .. 31 of word 2
+    assert not torch.equal(stale, clean) and torch.equal(SP.expand(stale, Sq, Sk), SP.expand(clean, Sq, Sk))
+    o = run(hip, q, k, v, clean, heads)
+    assert torch.equal(run(hip, q, k, v, stale, heads), o)
+    assert torch.isfinite(o).all() and rel_l2(o, ref) <= TOL, rel_l2(o, ref)
+
+
+# tile maxima of the scores, in log2 units above tile 0's: every tile after the first rescales (the threshold is 2^5) | nothing
+# rescales after the first tile's adoption and the late tiles' p vanish | four tiles inside the threshold, then one jump, then none
+STEPS = {"ascending": [8 * t for t in range(10)], "descending": [8 * (9 - t) for t in range(10)], "flat-then-a-jump": [0] * 4 + [8] * 6}
+
+
+@pytest.mark.parametrize("hd", HDS)
+@pytest.mark.parametrize("steps", list(STEPS))
+def test_attention_sparse_lazy_rescale_branch(hip, steps, hd):
+    """the sparse counterpart of test_attention_online_softmax_rescale_branch: q' holds 0.5 in its first eight channels, k of tile t
+    holds steps[t] / 4 more there, so every score of tile t lies about steps[t] log2 units higher (the sum rounds to bf16; both sides
+    read the rounded tensor, and |q'| stays below 1, so the f64 reference is exact in the usual sense).  All ten tiles are listed."""
+    B, Sq, Sk, heads = 1, 128, 640, 1
+    q, k, v = mk(B, Sq, Sk, heads, hd, seed=29 + hd)
+    q[..., :8] = 0.5
+    k[..., :8] += (torch.tensor(STEPS[steps], dtype=torch.float32) / 4).repeat_interleave(64)[None, :, None].to(DEV)
+    map = SP.pack(torch.ones(1, 10, dtype=torch.bool))
+    o = run(hip, q, k, v, map, heads)
+    e = rel_l2(o, SP.attention64(q, k, v, map, heads).float().cpu())
+    print({"case": steps, "hd": hd, "rel_l2": round(e, 5)})
+    assert torch.isfinite(o).all() and e <= TOL, e
+
+
+@pytest.mark.parametrize("hd", HDS)
+def test_narrow_o_store_is_the_wide_store(hip, hd):
+    """the 8-byte store path (wide_o == 0) through the C entry: o as a view with ldo = D + 4, and o on ldo = D but 8 bytes off a 16-byte
+    boundary.  Both bit-equal to the 16-byte stores of the same call; the columns between the rows and the elements around o untouched"""
+    B, Sq, Sk, heads, bits = CASES["per-head"]
+    D = heads * hd
+    q, k, v = mk(B, Sq, Sk, heads, hd, seed=3 * Sk + hd)
+    map = SP.pack(bits).to(DEV)
+    wide = hip.ops.attention_sparse(q, k, v, map, heads)
+
+    def call(o_ptr, ldo):
+        hip._check(hip.lib.ltx_op_attention_sparse(q.data_ptr(), k.data_ptr(), v.data_ptr(), o_ptr, map.data_ptr(), heads, B, Sq, Sk, heads, hd,
+                                                   q.stride(1), k.stride(1), v.stride(1), ldo, hip._stream()))
+    rows = torch.full((B * Sq, D + 4), 7.0, dtype=torch.bfloat16, device=DEV)
+    assert rows.data_ptr() % 16 == 0
+    call(rows.data_ptr(), D + 4)
+    assert torch.equal(rows[:, :D].reshape(B, Sq, D), wide) and bool((rows[:, D:] == 7.0).all())
+    flat = torch.full((B * Sq * D + 8,), 7.0, dtype=torch.bfloat16, device=DEV)
+    assert flat.data_ptr() % 16 == 0
+    call(flat.data_ptr() + 8, D)
+    assert torch.equal(flat[4:-4].view(B, Sq, D), wide) and bool((flat[:4] == 7.0).all()) and bool((flat[-4:] == 7.0).all())
 
 
 # ---------------------------------------------------------------- handle level (the world and cases of test_gpu_int8's forward test)
