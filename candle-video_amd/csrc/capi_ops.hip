@@ -5,6 +5,7 @@
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
 #include "../../include/ltxhip_int8.h"
+#include "../../include/ltxhip_int8_rot.h"
 #include "../../include/ltxhip_fp8.h"
 #include "../../include/ltxhip_int8_attn.h"
 #include "../../include/ltxhip_sparse_attn.h"
@@ -521,6 +522,16 @@ extern "C" int ltx_op_rownorm_quant_i8(const void* h, int64_t rows, int D, int l
     RowNormArgs a; a.x = h; a.y = q; a.rows = rows; a.D = D; a.ldx = ld; a.ldy = D; a.kind = 0; a.eps = eps; a.shift = shift; a.scale = scale;
     a.mod_stride = mod_stride; a.rows_per_batch = rows_per_batch;
     return ltx_launch_rownorm_quant_i8(a, row_scale, (hipStream_t)stream);
+}
+// ---- the rotated quantise passes on their own (include/ltxhip_int8_rot.h) ----
+extern "C" int ltx_op_hadamard_quant_rows_i8(const void* x, int64_t rows, int D, int ld, float out_scale, void* q, float* scale, ltx_stream stream) {
+    return ltx_launch_hadamard_quant_rows_i8(x, rows, D, ld, out_scale, q, scale, (hipStream_t)stream);
+}
+extern "C" int ltx_op_rownorm_hadamard_quant_i8(const void* h, int64_t rows, int D, int ld, float eps, const float* shift, const float* scale, int mod_stride,
+                                                int64_t rows_per_batch, void* q, float* row_scale, ltx_stream stream) {
+    RowNormArgs a; a.x = h; a.y = q; a.rows = rows; a.D = D; a.ldx = ld; a.ldy = D; a.kind = 0; a.eps = eps; a.shift = shift; a.scale = scale;
+    a.mod_stride = mod_stride; a.rows_per_batch = rows_per_batch;
+    return ltx_launch_rownorm_hadamard_quant_i8(a, row_scale, (hipStream_t)stream);
 }
 extern "C" int ltx_op_gemm_i8(const void* a_q, const float* a_scale, const void* w_q, const float* w_scale, const void* bias, void* y,
                               int M, int N, int K, int epi, const void* resid, const float* gate, int rows_per_batch, int seg_width, int tile,

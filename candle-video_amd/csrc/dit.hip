@@ -12,6 +12,7 @@
 #include "../../include/ltxhip_stg.h"
 #include "../../include/ltxhip_stepcache.h"
 #include "../../include/ltxhip_int8.h"
+#include "../../include/ltxhip_int8_rot.h"
 #include "../../include/ltxhip_int8_attn.h"
 #include "../../include/ltxhip_fp8.h"
 #include "../../include/ltxhip_sparse_attn.h"
@@ -122,6 +123,9 @@ struct ltx_dit {
     std::vector<unsigned char> i8_mask;
     std::vector<I8Slots> i8_w;
     bool i8_any = false, i8_stale = false;
+    // Hadamard rotation (include/ltxhip_int8_rot.h; ltx_dit_set_int8_rotation below): the kinds whose int8 layers quantise H x against
+    // H w / in.  A layer rotates iff its bit is set here AND in its block's i8_mask; the rotated copies live in i8_w like the plain ones.
+    unsigned char i8_rot = 0;
     DevBuf a8, a8s;                  // a quantised activation [M, 4D] int8 and its row scales [M] f32
     // INT8 Q K^T self-attention (include/ltxhip_int8_attn.h; ltx_dit_set_int8_attention below): per block a flag, and the operands of
     // one block's attention - nothing here is derived from the weights
@@ -393,13 +397,16 @@ extern "C" int ltx_dit_get_config(const ltx_dit* m, ltx_dit_config* out) {
 
 // ---- INT8 (W8A8) block linears (include/ltxhip_int8.h) ----
 namespace {
-// (re-)quantise every selected weight from the pointer the forward reads (LinearW::w: the base, or the LoRA-merged copy)
-int int8_quantise(ltx_dit* m, hipStream_t s) {
+// (re-)quantise every selected weight of the kinds in `kinds` from the pointer the forward reads (LinearW::w: the base, or the
+// LoRA-merged copy); a kind in the rotation mask (ltxhip_int8_rot.h) stores H w with its scales times 1 / in.  Stale copies: all kinds.
+int int8_quantise(ltx_dit* m, hipStream_t s, unsigned kinds = LTX_I8_ALL) {
+    if (m->i8_stale) kinds = LTX_I8_ALL;
     for (size_t l = 0; l < m->i8_mask.size(); ++l)
         for (int k = 0; k < 4; ++k) {
-            if (!(m->i8_mask[l] >> k & 1)) continue;
+            if (!(m->i8_mask[l] & kinds & (1u << k))) continue;
             const LinearW* lw = dit_slot(m->blocks[l], kI8Slot[k]);
-            LTX_TRY(ltx_launch_quant_rows_i8(lw->w, lw->out, lw->in, lw->in, m->i8_w[l].w[k], m->i8_w[l].sw[k], s));
+            if (m->i8_rot >> k & 1) LTX_TRY(ltx_launch_hadamard_quant_rows_i8(lw->w, lw->out, lw->in, lw->in, 1.0f / (float)lw->in, m->i8_w[l].w[k], m->i8_w[l].sw[k], s));
+            else LTX_TRY(ltx_launch_quant_rows_i8(lw->w, lw->out, lw->in, lw->in, m->i8_w[l].w[k], m->i8_w[l].sw[k], s));
         }
     m->i8_stale = false;
     return LTX_OK;
@@ -457,6 +464,26 @@ extern "C" int ltx_dit_set_int8_linears(ltx_dit* m, const unsigned char* block_m
 extern "C" int ltx_dit_get_int8_linears(const ltx_dit* m, unsigned char* block_masks_out) {
     if (!m || !block_masks_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_linears: null argument");
     for (int l = 0; l < m->cfg.num_layers; ++l) block_masks_out[l] = (size_t)l < m->i8_mask.size() ? m->i8_mask[(size_t)l] : 0;
+    return LTX_OK;
+}
+
+// ---- Hadamard rotation of the int8 layers (include/ltxhip_int8_rot.h) ----
+extern "C" int ltx_dit_set_int8_rotation(ltx_dit* m, unsigned char mask, ltx_stream stream) {
+    if (!m) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_int8_rotation: null handle");
+    if (mask & ~LTX_I8_ALL) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_set_int8_rotation: mask " + std::to_string((int)mask) + " has bits outside LTX_I8_ALL");
+    if (mask && m->dtype != LTX_DT_BF16) LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_rotation: the int8 layers take a bf16 model (this handle is f32)");
+    if (mask && (m->D < 128 || 4 * (int64_t)m->D > 16384 || (m->D & (m->D - 1))))
+        LTX_FAIL(LTX_ERR_UNSUPPORTED, "ltx_dit_set_int8_rotation: the inner dimension D and 4 D must be powers of two in 128 .. 16384 (this handle has D = " + std::to_string(m->D) + ", 4 D = " + std::to_string(4 * (int64_t)m->D) + ")");
+    const unsigned changed = m->i8_rot ^ mask;
+    if (!changed) return LTX_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    m->i8_rot = mask;
+    // the copies of the kinds that changed are stale: re-made here, like ltx_dit_set_int8_linears makes its copies
+    return m->i8_any ? int8_quantise(m, (hipStream_t)stream, changed) : LTX_OK;
+}
+extern "C" int ltx_dit_get_int8_rotation(const ltx_dit* m, unsigned char* mask_out) {
+    if (!m || !mask_out) LTX_FAIL(LTX_ERR_ARG, "ltx_dit_get_int8_rotation: null argument");
+    *mask_out = m->i8_rot;
     return LTX_OK;
 }
 
@@ -1062,9 +1089,16 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         g.A = m->a8.p; g.lda = g.K; g.W = m->i8_w[(size_t)l].w[kind]; g.rowsq = nullptr;
         return ltx_launch_gemm_i8(g, m->a8s.as<float>(), m->i8_w[(size_t)l].sw[kind], epi, -1, s);
     };
-    auto norm_int8 = [&]() { RowNormArgs rq = rn; rq.y = m->a8.p; rq.ldy = D; return ltx_launch_rownorm_quant_i8(rq, m->a8s.as<float>(), s); };      // rn's norm, quantised from f32
+    const unsigned rot = i8 & m->i8_rot;      // the int8 layers that quantise H x against their rotated copy (ltxhip_int8_rot.h)
+    auto norm_int8 = [&](unsigned kind_bit) {      // rn's norm, quantised from f32
+        RowNormArgs rq = rn; rq.y = m->a8.p; rq.ldy = D;
+        return (rot & kind_bit) ? ltx_launch_rownorm_hadamard_quant_i8(rq, m->a8s.as<float>(), s) : ltx_launch_rownorm_quant_i8(rq, m->a8s.as<float>(), s);
+    };
+    auto quant_int8 = [&](unsigned kind_bit, const void* x, int K) {      // a stored bf16 activation [M, K]
+        return (rot & kind_bit) ? ltx_launch_hadamard_quant_rows_i8(x, M, K, K, 1.0f, m->a8.p, m->a8s.as<float>(), s) : ltx_launch_quant_rows_i8(x, M, K, K, m->a8.p, m->a8s.as<float>(), s);
+    };
     const bool qkv8 = (i8 & LTX_I8_QKV) != 0;
-    if (qkv8) LTX_TRY(norm_int8());
+    if (qkv8) LTX_TRY(norm_int8(LTX_I8_QKV));
     else if (!fold1) { st.take_pending(rn, m, p); LTX_TRY(ltx_launch_rownorm(rn, dt, s)); }
     st.hs_valid = false;
     rn.parts = nullptr; rn.nparts = 0; rn.x_out = nullptr; rn.d_bias = nullptr; rn.d_gate = nullptr;
@@ -1136,7 +1170,7 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
     if (i8 & LTX_I8_TO_OUT) {
         GemmArgs g = gemm_base(p, b.o1, m->attn.p, D, m->h.p, D);
         g.resid = m->h.p; g.ldr = D; g.gate = ada + 2 * D; g.gate_stride = 6 * D; g.rows_per_batch = p.Sg;
-        LTX_TRY(ltx_launch_quant_rows_i8(m->attn.p, M, D, D, m->a8.p, m->a8s.as<float>(), s));
+        LTX_TRY(quant_int8(LTX_I8_TO_OUT, m->attn.p, D));
         LTX_TRY(gemm_int8(1, g, EPI_GATE_RESID));
     } else LTX_TRY(ltx_linear(b.o1, m->attn.p, D, m->h.p, D, (int)M, dt, EPI_GATE_RESID, s, m->h.p, D, ada + 2 * D, 6 * D, p.Sg));
     st.hsq_valid = false;
@@ -1173,7 +1207,7 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         rn.shift = ada + 3 * D; rn.scale = ada + 4 * D;
         rn.presum = nullptr; rn.presum_n = 0;
         if (p.presum && st.hsq_valid) { rn.presum = m->hsq.as<float>(); rn.presum_n = D / 128; }
-        if (i8 & LTX_I8_FF1) { LTX_TRY(norm_int8()); LTX_TRY(gemm_int8(2, gemm_ff1(p, kPass, b, x), EPI_GELU)); }
+        if (i8 & LTX_I8_FF1) { LTX_TRY(norm_int8(LTX_I8_FF1)); LTX_TRY(gemm_int8(2, gemm_ff1(p, kPass, b, x), EPI_GELU)); }
         else {
             LTX_TRY(ltx_launch_rownorm(rn, dt, s));
             LTX_TRY(linear_of(b.ff1, gemm_ff1(p, kPass, b, x), dt, EPI_GELU, s));
@@ -1185,7 +1219,7 @@ int dit_block(ltx_dit* m, const DitPlan& p, int l, const DitLayerIn& in, DitCarr
         st.pending = true; st.pend_gate = ada + 5 * D; st.pend_bias = b.ff2.b;
     } else if (ln >= 0) { LTX_TRY(ltx_launch_gemm(gemm_ff2(p, kFold1, b, x), dt, EPI_GATE_RESID, s)); st.hs_valid = true; }
     else if (i8 & LTX_I8_FF2) {
-        LTX_TRY(ltx_launch_quant_rows_i8(m->ff.p, M, 4 * D, 4 * D, m->a8.p, m->a8s.as<float>(), s));
+        LTX_TRY(quant_int8(LTX_I8_FF2, m->ff.p, 4 * D));
         LTX_TRY(gemm_int8(3, gemm_ff2(p, kPass, b, x), EPI_GATE_RESID));
     } else LTX_TRY(linear_of(b.ff2, gemm_ff2(p, kPass, b, x), dt, EPI_GATE_RESID, s));
     st.hsq_valid = p.presum;

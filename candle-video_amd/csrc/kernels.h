@@ -15,7 +15,9 @@ void ltx_prof_end(void* token, hipStream_t s);
 // which KERNEL served the launch being timed (set by the launcher that actually enqueues it; read by ltx_prof_end)
 enum { LTX_PROFK_GEMM128 = 0, LTX_PROFK_GEMM_BIG = 1, LTX_PROFK_GEMM_P8 = 2, LTX_PROFK_CONV_HALO = 3, LTX_PROFK_GEMM_ASM = 4, LTX_PROFK_GEMM_ASM16 = 5, LTX_PROFK_GEMM_RING = 6,
        LTX_PROFK_GEMM_I8 = 7, LTX_PROFK_QUANT_ROWS_I8 = 8, LTX_PROFK_ROWNORM_QUANT_I8 = 9,      // (the int8 kernels: class GEMM, ROWNORM, ROWNORM)
-       LTX_PROFK_GEMM_W8 = 10, LTX_PROFK_N = 11 };
+       LTX_PROFK_GEMM_W8 = 10,
+       LTX_PROFK_HADAMARD_QUANT_ROWS_I8 = 11, LTX_PROFK_ROWNORM_HADAMARD_QUANT_I8 = 12,      // (quant_i8_rot.hip: class ROWNORM)
+       LTX_PROFK_N = 13 };
 void ltx_prof_kernel(int which);
 // Kernel-level start / stop events for the launch being timed (the dispatch packet's own timestamps, what rocprofv3's kernel
 // trace reports): stream-level hipEventRecord brackets also count the dispatch latency and the end-of-kernel release that the
@@ -210,6 +212,10 @@ int ltx_launch_quant_rows_i8(const void* x, int64_t rows, int D, int ld, void* q
 // the modulated RMS norm of a (x, D, ldx, eps, shift, scale, mod_stride, rows_per_batch: RowNormArgs' fields; kind 0, no weight, no
 // activation) quantised from its f32 value: a.y int8 [rows, D] dense, row_scale f32 [rows]; D % 16 == 0, D <= 4096
 int ltx_launch_rownorm_quant_i8(const RowNormArgs& a, float* row_scale, hipStream_t s);
+// the same two passes with the row rotated by the Hadamard matrix before it is quantised (quant_i8_rot.hip; include/ltxhip_int8_rot.h):
+// q = quantised H x, scale = (amax / 127) * out_scale; D a power of two, 128 .. 16384 (rows) / 128 .. 4096 (norm)
+int ltx_launch_hadamard_quant_rows_i8(const void* x, int64_t rows, int D, int ld, float out_scale, void* q, float* scale, hipStream_t s);
+int ltx_launch_rownorm_hadamard_quant_i8(const RowNormArgs& a, float* row_scale, hipStream_t s);
 // g: A int8 [M, lda], W int8 [N, K], C bf16 (EPI_BIAS / GELU / GATE_RESID / RESID with GemmArgs' bias, resid, gate, c_seg_*) or, epi ==
 // EPI_I8_RAW, int32 [M, ldc] unscaled (sa, sw not read).  tile: -1 the shape rule, 0 256x256, 1 256x128, 2 128x128.
 constexpr int EPI_I8_RAW = 100;

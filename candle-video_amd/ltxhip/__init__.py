@@ -444,6 +444,17 @@ for _name, _sig in _SPARSE_DYNAMIC_SIGS.items():
     _fn = getattr(lib, _name)
     _fn.argtypes = _sig
     _fn.restype = C.c_int
+# include/ltxhip_int8_rot.h (kept apart like the thirteen above)
+_INT8_ROT_SIGS = {
+    "ltx_dit_set_int8_rotation": [_vp, C.c_ubyte, _vp], "ltx_dit_get_int8_rotation": [_vp, _vp],
+    "ltx_op_hadamard_quant_rows_i8": [_vp, _i64, _i, _i, _f, _vp, _vp, _vp],
+    "ltx_op_rownorm_hadamard_quant_i8": [_vp, _i64, _i, _i, _f, _vp, _vp, _i, _i64, _vp, _vp, _vp],
+}
+INT8_ROT_SYMBOLS = sorted(_INT8_ROT_SIGS)
+for _name, _sig in _INT8_ROT_SIGS.items():
+    _fn = getattr(lib, _name)
+    _fn.argtypes = _sig
+    _fn.restype = C.c_int
 LTX_I8_QKV, LTX_I8_TO_OUT, LTX_I8_FF1, LTX_I8_FF2, LTX_I8_ALL = 1, 2, 4, 8, 15
 INT8_LINEARS = ("qkv", "to_out", "ff1", "ff2")   # the mask bits of ltx_dit_set_int8_linears, lowest first
 GEMM_I8_TILES = ("256x256", "256x128", "128x128")
@@ -800,6 +811,20 @@ class LtxVideoTransformer3DModel:
         out = (C.c_ubyte * self.config.num_layers)()
         _check(lib.ltx_dit_get_int8_linears(self._h, out))
         return list(out)
+
+    # ---- Hadamard rotation of the int8 linears (include/ltxhip_int8_rot.h): handle state, independent of the int8 masks
+    def set_int8_rotation(self, mask_or_names=0):
+        """the named kinds - 'qkv', 'to_out', 'ff1', 'ff2', 'all', or an LTX_I8_* mask - quantise Hadamard-rotated activations against
+        rotated int8 weight copies wherever set_int8_linears runs them in int8 (either call may come first); 0 / 'none' clears it.
+        A bf16 model whose inner dimension is a power of two, 128 .. 4096.  Enqueued on the current stream."""
+        _check(lib.ltx_dit_set_int8_rotation(self._h, int8_mask(mask_or_names), _stream()))
+
+    @property
+    def int8_rotation(self) -> int:
+        """the LTX_I8_* mask of the rotating kinds"""
+        out = C.c_ubyte(0)
+        _check(lib.ltx_dit_get_int8_rotation(self._h, C.byref(out)))
+        return out.value
 
     # ---- INT8 Q K^T self-attention (include/ltxhip_int8_attn.h): handle state, independent of the int8 linears
     def set_int8_attention(self, on=True, block_flags: Optional[Sequence] = None):
@@ -2659,6 +2684,30 @@ class ops:
                                            C.c_int64(rows_per_batch), _ptr(q), _ptr(sc), _stream()))
         return q, sc
 
+    # ---- the rotated quantise passes (include/ltxhip_int8_rot.h)
+    @staticmethod
+    def hadamard_quant_rows_i8(x, out_scale=1.0):
+        """x [rows, D] bf16 (any row stride, unit column stride), D a power of two -> (q int8 [rows, D] of H x, scale f32 [rows] =
+        (amax / 127) * out_scale)"""
+        if x.dim() != 2 or x.stride(1) != 1:
+            x = x.contiguous()
+        rows, D = x.shape
+        q = torch.empty(rows, D, dtype=torch.int8, device=x.device)
+        sc = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _check(lib.ltx_op_hadamard_quant_rows_i8(_ptr(x), C.c_int64(rows), D, x.stride(0) if rows > 1 else D, C.c_float(out_scale), _ptr(q), _ptr(sc), _stream()))
+        return q, sc
+
+    @staticmethod
+    def rownorm_hadamard_quant_i8(h, shift, scale, rows_per_batch, eps=1e-6):
+        """q, row_scale of H n, n the modulated RMS norm of h [rows, D] bf16; shift / scale f32 [groups, mod_stride]"""
+        rows, D = h.shape
+        h = h.contiguous()
+        q = torch.empty(rows, D, dtype=torch.int8, device=h.device)
+        sc = torch.empty(rows, dtype=torch.float32, device=h.device)
+        _check(lib.ltx_op_rownorm_hadamard_quant_i8(_ptr(h), C.c_int64(rows), D, D, C.c_float(eps), _ptr(shift), _ptr(scale), shift.stride(0),
+                                                    C.c_int64(rows_per_batch), _ptr(q), _ptr(sc), _stream()))
+        return q, sc
+
     @staticmethod
     def gemm_i8(a_q, a_scale, w_q, w_scale, bias=None, epi=0, resid=None, gate=None, rows_per_batch=1, seg_width=0, tile=-1):
         """y bf16 = epi((float(a_q w_q^T) * a_scale[m]) * w_scale[n] + bias); seg_width: N / seg_width dense [M, seg_width] matrices;
@@ -3066,7 +3115,8 @@ def prof_report(kind: int):
 
 PROF_KERNELS = ("gemm_kernel (128 x 128)", "gemm_big_kernel", "gemm_p8_kernel", "conv_halo_kernel", "gemm_asm_kernel (32x32x16)", "gemm_asm16_kernel", "gemm_ring_kernel",
                 "gemm_i8_kernel", "quant_rows_i8_kernel", "rownorm_quant_i8_kernel",      # (the last two are timed in class 4, the row norms)
-                "gemm_w8_kernel")
+                "gemm_w8_kernel",
+                "hadamard_quant_rows_i8_kernel", "rownorm_hadamard_quant_i8_kernel")      # (class 4 like their plain siblings)
 
 
 def prof_report_kernel(kind: int, kernel: int):

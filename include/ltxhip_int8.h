@@ -29,8 +29,8 @@
  * handle has set.
  *
  * Out of scope: attn2 (to_q, to_out, the text k / v), proj_in / proj_out, the VAE and T5; the row maximum of ff2's input as a
- * by-product of ff1's epilogue; static activation scales; outlier rotation; loading pre-quantised checkpoints; measured plans for
- * gemm_i8 (its tile is a shape rule) and split K.
+ * by-product of ff1's epilogue; static activation scales; loading pre-quantised checkpoints; measured plans for
+ * gemm_i8 (its tile is a shape rule) and split K.  Outlier rotation is ltxhip_int8_rot.h's.
  * Conventions are those of ltxhip.h (device pointers unless marked HOST, 0 = success, ltx_last_error). */
 #ifndef LTXHIP_INT8_H
 #define LTXHIP_INT8_H

@@ -238,6 +238,20 @@ impl HipDit {
         check(unsafe { sys::ltx_dit_set_int8_linears(self.h, p, mask, std::ptr::null_mut()) })
     }
 
+    /// Rotate the activations and weight copies of the kinds in `mask` (`sys::LTX_I8_*`) by a Hadamard matrix before they are
+    /// quantised (include/ltxhip_int8_rot.h), wherever `set_int8_linears` runs them in int8; either call may come first.  Mask 0
+    /// clears it.  A bf16 model whose inner dimension is a power of two, 128 ..= 4096.
+    pub fn set_int8_rotation(&mut self, mask: u8) -> Result<()> {
+        check(unsafe { sys::ltx_dit_set_int8_rotation(self.h, mask, std::ptr::null_mut()) })
+    }
+
+    /// The `sys::LTX_I8_*` mask of the rotating kinds.
+    pub fn int8_rotation(&self) -> Result<u8> {
+        let mut out = 0u8;
+        check(unsafe { sys::ltx_dit_get_int8_rotation(self.h, &mut out) })?;
+        Ok(out)
+    }
+
     /// The `sys::LTX_F8_*` mask of every block: the linears that stayed in fp8 (E4M3 sources of a bf16 handle, include/ltxhip_fp8.h).
     pub fn fp8_linears(&self) -> Result<Vec<u8>> {
         let mut out = vec![0u8; self.cfg.num_layers];

@@ -555,6 +555,17 @@ extern "C" {
     pub fn ltx_op_gemm_i8_raw(a_q: *const c_void, w_q: *const c_void, acc: *mut c_int, m: c_int, n: c_int, k: c_int, tile: c_int, stream: ltx_stream) -> c_int;
 }
 
+// ---- include/ltxhip_int8_rot.h: opt-in Hadamard rotation of the INT8 block linears (mask bits: LTX_I8_*) ----
+
+extern "C" {
+    pub fn ltx_dit_set_int8_rotation(m: *mut ltx_dit, mask: u8, stream: ltx_stream) -> c_int;
+    pub fn ltx_dit_get_int8_rotation(m: *const ltx_dit, mask_out: *mut u8) -> c_int;
+    pub fn ltx_op_hadamard_quant_rows_i8(x: *const c_void, rows: i64, d: c_int, ld: c_int, out_scale: c_float, q: *mut c_void, scale: *mut c_float,
+                                         stream: ltx_stream) -> c_int;
+    pub fn ltx_op_rownorm_hadamard_quant_i8(h: *const c_void, rows: i64, d: c_int, ld: c_int, eps: c_float, shift: *const c_float, scale: *const c_float,
+                                            mod_stride: c_int, rows_per_batch: i64, q: *mut c_void, row_scale: *mut c_float, stream: ltx_stream) -> c_int;
+}
+
 // ---- include/ltxhip_int8_attn.h: opt-in INT8 Q K^T self-attention on the int8 MFMA ----
 
 extern "C" {
